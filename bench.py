@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - self-play data generation throughput on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]            (N > 1: launched by torch.distributed.run)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]     (N > 1: launched by torch.distributed.run)
 
 Workload (BASELINE.json configs[2]): Gomoku 15x15, 800 simulations per move, 2048 concurrent self-play
 games per GPU, policy-value net = the reference's training config (ai/nn.py Net(15, patch 5, embed 512,
@@ -25,10 +25,15 @@ call); a world size that disagrees with --gpus is an error (non-zero exit), neve
 One JSON line on rank 0.  Extra objects:
   roofline      k_tree (PUCT scan + expand + backup), HBM-bound: algorithmic bytes per launch from the engine's
                 device counters / mean launch duration from HIP events on the launch stream
-  fp32_line     the same workload timed a second time IN THIS RUN on the fp32-accurate evaluator (the one that meets north_star's
-                1e-5 bar on visit-count policies); `parity.quoted` holds builder-run numbers read from profiles/, labelled as such
-  cpu_baseline  the oracle (CPU restatement of the reference algorithm, batch-1 fp32 net, eval cache) timed on
+  fp32_line     --full only: the same workload timed a second time IN THIS RUN on the fp32-accurate evaluator (the one that meets
+                north_star's 1e-5 bar on visit-count policies); `parity.quoted` holds builder-run numbers read from profiles/, labelled as such
+  cpu_baseline  --full only: the oracle (CPU restatement of the reference algorithm, batch-1 fp32 net, eval cache) timed on
                 this box's host cores on a bounded sample of the same workload
+A plain run (no --full) sets up, pre-rolls, warms up, times the --steps moves and prints the line; both objects above are null in it.
+
+--dump-outputs DIR writes the per-move records of the last timed move - what SelfPlayRunner hands its caller: pi (root visit
+policy), q, action, winner, done, one row per game slot - as DIR/<name>.npy in float64 (DIR/<name>_rank<r>.npy with several GPUs),
+after the timed window.  The inputs are seeded: the same arguments give the same records, so two builds can be compared.
 """
 import argparse
 import json
@@ -177,6 +182,28 @@ class StubRunner:
         pass
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(runner, out_dir, rank, world):
+    """--dump-outputs: the last move's records of every game slot of this rank (the pinned host buffers play_move() filled), float64.
+    Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the slots is written, with their indices as `slot`."""
+    import numpy as np
+    cols = {"pi": [h.h_pi for h in runner.halves], "q": [h.h_q for h in runner.halves], "action": [h.h_chosen for h in runner.halves],
+            "winner": [h.h_winner for h in runner.halves], "done": [h.h_done for h in runner.halves]}
+    out = {k: np.concatenate([t.numpy() for t in v]).astype(np.float64) for k, v in cols.items()}
+    n = len(out["q"])
+    row_bytes = sum(a[0].nbytes for a in out.values())
+    keep = (DUMP_LIMIT_BYTES // world) // (row_bytes + 8)
+    if n > keep:
+        slot = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        out = {k: a[slot] for k, a in out.items()}
+        out["slot"] = slot.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, f"{k}.npy" if world == 1 else f"{k}_rank{rank}.npy"), a)
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` outside torch.distributed.run: start the N ranks as a child job (the driver's own
     command line) before this process has touched the GPU, and exit with its code."""
@@ -194,7 +221,7 @@ def spawn_ranks(n, argv):
 
 
 def fp32_window(args, cfg, rank, local_rank, world, dist):
-    """The second timed window of the default run: the SAME workload on the hand-written fp32-accurate evaluator (csrc/azk_nnx.hip +
+    """The second timed window of a --full run: the SAME workload on the hand-written fp32-accurate evaluator (csrc/azk_nnx.hip +
     k_embed_fold<EX>) - the evaluator whose 800-simulation visit-count policies equal the reference's float32 network's on every
     recorded position (tests/test_gpu_exact.py, asserted at north_star's 1e-5) - with its own untimed pre-roll, timed like the
     headline (barrier + synchronize on both sides, MAX over ranks).  Returns the object printed as `fp32_line`."""
@@ -293,9 +320,13 @@ def main():
     ap.add_argument("--virtual-loss", type=int, default=1, metavar="K",
                     help="OPT-IN, NOT the headline: K > 1 leaves in flight per game with a virtual loss on their paths (north_star's 'virtual-loss "
                          "expansion').  Changes search results (the reference's search is sequential), so the line is reported under its own metric key")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="wall-clock budget of the CPU baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the fp32-accurate evaluator's window (`fp32_line`) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed move's records (pi, q, action, winner, done per game slot) as DIR/<name>.npy, float64")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="with --full: wall-clock budget of the CPU baseline leg (0 = skip)")
     ap.add_argument("--fp32-steps", type=int, default=12,
-                    help="the default (bf16) run ends with a second timed window on the fp32-accurate evaluator (`fp32_line`): this many moves (0 = skip)")
+                    help="with --full, the default (bf16) run ends with a second timed window on the fp32-accurate evaluator (`fp32_line`): this many moves (0 = skip)")
     ap.add_argument("--fp32-warmup", type=int, default=4, help="untimed moves of the fp32 window after its own pre-roll")
     ap.add_argument("--net", default="main", choices=["main", "compare"],
                     help="main (default): main.py:134's network, Net(patch 5, embed 512, heads 8, depth 1) - the metric's config.  compare: SIDE LINE on "
@@ -316,6 +347,10 @@ def main():
                     help="with --train-step: every n-th move the trained weights are promoted into the self-play evaluator (main.py:55-59: "
                          "load_state_dict + MCTS.cache.clear()), in place - the captured step graphs keep replaying; 0 = never")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.stub_engine or args.async_moves):
+        ap.error("--dump-outputs needs the lock-step runner (the asynchronous runner and the stub keep no per-move records)")
     if args.nn_path is None:
         args.nn_path = "clsfold"
 
@@ -486,10 +521,12 @@ def main():
     from shard import reduce_measurement
     dt_max, (plies_all, fin_window, finp_window, sims_all, leaves_all) = reduce_measurement(
         dt, [plies, fin - fin0, finp - finp0, c["sims"], c["leaves_evaluated"]], dist if world > 1 else None, rdev)
+    if args.dump_outputs:
+        dump_outputs(runner, args.dump_outputs, rank, world)
 
-    # ---- second timed window of the default run: the same workload on the fp32-accurate evaluator (north_star's 1e-5 parity bar) ----
+    # ---- --full: second timed window, the same workload on the fp32-accurate evaluator (north_star's 1e-5 parity bar) ----
     fp32 = None
-    if (not stub and args.nn_dtype == "bf16" and args.fp32_steps > 0 and args.nn_path == "clsfold" and not args.async_moves
+    if (args.full and not stub and args.nn_dtype == "bf16" and args.fp32_steps > 0 and args.nn_path == "clsfold" and not args.async_moves
             and args.virtual_loss <= 1 and not args.train_step and args.split == 1 and not args.no_graph and not args.budget_stepping):
         n_split_, spg_, lps_ = runner.n_split, runner.steps_per_graph, runner.leaves_per_step
         for h in runner.halves:
@@ -695,7 +732,7 @@ def main():
             "mean_plies_per_game": mean_plies, "game_length_source": src, "games_finished_in_window": fin_window,
             "plies_in_window": plies_all, "counters_rank0": c, "roofline": dominant, "roofline_puct": roof, "kernel_rooflines": kernels,
         }
-        # measured IN THIS RUN: the fp32-accurate evaluator's own timed window (None when a side-line flag is set or --fp32-steps 0)
+        # measured IN THIS RUN: the fp32-accurate evaluator's own timed window (None without --full, when a side-line flag is set or --fp32-steps 0)
         out["fp32_line"] = fp32
         out["consistency"] = {"headline_window_s": dt_max, "fp32_window_s": fp32["seconds"] if fp32 else 0.0,
                               "timed_windows_sum_s": dt_max + (fp32["seconds"] if fp32 else 0.0),
@@ -733,7 +770,7 @@ def main():
                                  "note": "promotion (main.py:55-59) = trained weights -> the self-play evaluator's device buffers, refreshed IN PLACE "
                                          "(folded constants and packed fragments recomputed on the device, same addresses: the captured step graphs "
                                          "are not re-captured) + eval-cache clear; its wall time is inside the timed window"}
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.sims, args.cpu_seconds, mean_plies)
             out["gpu_over_cpu"] = games_per_s / out["cpu_baseline"]["value"]
         else:

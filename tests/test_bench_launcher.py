@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import pytest
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
@@ -47,6 +48,31 @@ def test_world_size_mismatch_is_an_error():
     assert r.returncode != 0 and "refusing" in r.stderr
     r = _run(["--gpus", "1"], env={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29999"})
     assert r.returncode != 0
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_same_records_twice(tmp_path):
+    """A plain run (no --full) times exactly --steps moves, measures nothing beside the headline, and --dump-outputs writes the last
+    timed move's records; the inputs are seeded, so a second run with the same arguments writes the same bytes."""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--games", "128", "--sims", "48", "--preroll-cheap", "2", "--preroll-full", "1",
+            "--steps-per-graph", "8", "--cache-entries", "256"]
+    lines = []
+    for d in ("a", "b"):
+        e = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+        r = subprocess.run([sys.executable, BENCH] + args + ["--dump-outputs", str(tmp_path / d)], env=e, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(_line(r))
+    for l in lines:
+        assert l["steps"] == 2 and l["ms_per_step"] > 0 and l["fp32_line"] is None and l["cpu_baseline"] is None
+    shapes = {"pi": (128, 225), "q": (128,), "action": (128,), "winner": (128,), "done": (128,)}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f"{k}.npy" for k in shapes)
+    for k, shape in shapes.items():
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.shape == shape and a.dtype == np.float64
+        assert a.tobytes() == b.tobytes(), k
+    pi = np.load(tmp_path / "a" / "pi.npy")
+    assert np.isfinite(pi).all() and pi.max() > 0 and (np.load(tmp_path / "a" / "action.npy") >= 0).any()
 
 
 def _agree_worker(rank, world, port, q):

@@ -5,7 +5,7 @@ the search results, measured against the reference's own fp32 arithmetic on the 
 north_star asks for visit-count policies within 1e-5 at a fixed seed.  That bar is met - exactly, delta = 0 - whenever the
 evaluator's outputs are the reference's (fixture evaluators everywhere else in the suite; the fp32 network paths here).  The
 bf16 evaluator moves logits by <= 1e-2, which changes a handful of visits in a few positions: the bound asserted for it is
-the measured one with margin, stated in the test, and bench.py prints an fp32-evaluator line next to the bf16 one."""
+the measured one with margin, stated in the test, and bench.py --full prints an fp32-evaluator line next to the bf16 one."""
 import numpy as np
 import pytest
 import torch

@@ -10,7 +10,7 @@ d=json.loads(open('$O/$name.json').read().strip().splitlines()[-1])
 print(round(d['value'],1), d['unit'], round(d['ms_per_step'],2), 'ms/step', round(d['sims_per_sec']/1e6,2), 'M sims/s', ('fp32_line %.1f games/s %.2f ms' % (d['fp32_line']['games_per_sec'], d['fp32_line']['ms_per_step'])) if d.get('fp32_line') else '')")"; }
 timeout -k 10 700 python3 -m pytest tests -m gpu -q > $O/gputests.log 2>&1 || { tail -20 $O/gputests.log; exit 1; }
 tail -1 $O/gputests.log
-run bench_default python3 bench.py
+run bench_default python3 bench.py --full
 run bench_tail_wide_registers python3 bench.py --tail-wide registers --steps 20 --warmup 5 --cpu-seconds 0 --fp32-steps 0
 run bench_fp32 python3 bench.py --nn-dtype fp32 --steps 40 --warmup 10 --cpu-seconds 0
 run bench_fp32_tail_wide_registers python3 bench.py --nn-dtype fp32 --tail-wide registers --steps 20 --warmup 5 --cpu-seconds 0

@@ -11,6 +11,8 @@ fixture here comes from importing its modules and calling its functions:
   ai/mcts.py MCTS.mcts + ai/node.py + utils.py (search)            -> search.npz
   <Game>.self_play + train.save_data_to_buffer (whole games)       -> games.npz
   ai/nn.py Net (small config, committed weights)                   -> nn_small.npz
+  ai/nn.py Net (main.py's two configs, seed 0) on edge boards      -> nn_edges.npz
+  MCTS.mcts driven by the seed-0 Net (800 sims, 92 positions)       -> nn_search15.npz
 
 Import hygiene: `import games` would create <reference>/logs/*.log through
 utils.get_game_logger at class-definition time (utils.py:71-90).  We neutralise the
@@ -541,6 +543,178 @@ def gen_nn_depth2():
 
 
 # =================================================================================
+# 4b. the real network (seed 0) inside the reference's own search, and on boards where the fold kernels can go wrong
+# =================================================================================
+def golden_positions_15():
+    """(game, cells int8 [225], to_move, move_count) of every recorded ply of the 15x15 games in games.npz, in file order
+    (tools/measure_nn_parity.golden_positions yields the same positions)."""
+    import json
+    z = np.load(os.path.join(HERE, "games.npz"))
+    out = []
+    for m in json.loads(bytes(z["meta_json"]).decode()):
+        if m["size"] != 15:
+            continue
+        cells = z[f"g{m['game']}_board_cells"]
+        for ply in range(len(cells)):
+            out.append((m["game"], cells[ply].astype(np.int8).reshape(-1), ply & 1, ply))
+    return out
+
+
+def seed0_net():
+    torch.manual_seed(0)
+    return RefNet(15, patch_size=5, embed_dim=512, action_dim=225, num_heads=8, depth=1, channels=2, dropout=0.1).eval()
+
+
+def board_of_cells(cells):
+    """The reference's 2x15x15 game board (plane p = player p's stones) of an int8 cell vector."""
+    b = np.zeros((2, 15, 15), np.float32)
+    b[0].reshape(-1)[cells == 1] = 1
+    b[1].reshape(-1)[cells == 2] = 1
+    return b
+
+
+def gen_nn_search15():
+    """MCTS.mcts(seed-0 Net(15, 5, 512, 225, 8, 1), board, root, Gomoku, 800, dirichlet=True) from each of the 92 positions of
+    the recorded 15x15 games; position i's Dirichlet draw is row i of RandomState(7).dirichlet([0.03] * 225, size=92) (stored at the
+    root children's cells only: the full rows are 160 KB of incompressible doubles, and the seed regenerates them)."""
+    import json
+    set_gomoku(15)
+    positions = golden_positions_15()
+    G = len(positions)
+    noise = np.random.RandomState(7).dirichlet([0.03] * 225, size=G)
+    net = seed0_net()
+    cells_k, visit_k, value_k, prior_k, noise_k, off = [], [], [], [], [], [0]
+    root_logits = np.zeros((G, 225), np.float32)
+    root_v = np.zeros(G, np.float32)
+    meta = []
+    orig_dir = np.random.dirichlet
+    for i, (game, cells, to_move, ply) in enumerate(positions):
+        board = board_of_cells(cells)
+        calls = []
+
+        def fixed_dir(alpha, size=None):
+            assert size is None and len(alpha) == 225
+            calls.append(1)
+            return noise[i].copy()
+        MCTS.cache.clear()
+        MCTS.matched = 0
+        MCTS.mcts_count = 0
+        root = Node(None, None, to_move, ply)
+        before = board.copy()
+        np.random.dirichlet = fixed_dir
+        t0 = time.time()
+        try:
+            with torch.no_grad():
+                MCTS.mcts(net, board, root, GMK, 800, True)
+        finally:
+            np.random.dirichlet = orig_dir
+        dt = time.time() - t0
+        assert len(calls) == 1 and np.array_equal(before, board)
+        with torch.no_grad():
+            lg, v = net(torch.from_numpy(GMK.get_canonical_board(board, to_move)).unsqueeze(0))
+        root_logits[i], root_v[i] = lg[0].numpy(), v.reshape(-1)[0].item()
+        cells_k += [cell_idx(GMK, c.prevAction) for c in root.children]
+        visit_k += [c.visit for c in root.children]
+        value_k += [float(c.value) for c in root.children]
+        prior_k += [float(c.prior) for c in root.children]
+        noise_k += [noise[i][cell_idx(GMK, c.prevAction)] for c in root.children]
+        off.append(len(cells_k))
+        meta.append(dict(position=i, game=game, ply=ply, to_move=to_move, root_visit=int(root.visit), root_value=float(root.value),
+                         n_children=len(root.children), matched=int(MCTS.matched), mcts_count=int(MCTS.mcts_count)))
+        print("nn_search15", meta[-1], "ref_seconds", round(dt, 2), flush=True)     # printed, not stored: the file is reproducible byte for byte
+    return dict(cells=np.stack([p[1] for p in positions]), to_move=np.array([p[2] for p in positions], np.int8),
+                move_count=np.array([p[3] for p in positions], np.int16),
+                child_off=np.array(off, np.int32), child_cell=np.array(cells_k, np.int16),
+                child_visit=np.array(visit_k, np.int16), child_value=np.array(value_k, np.float64),
+                child_prior=np.array(prior_k, np.float64), child_noise=np.array(noise_k, np.float64), root_logits=root_logits, root_value=root_v,
+                torch_threads=np.array(torch.get_num_threads()),
+                meta_json=np.frombuffer(json.dumps(meta).encode(), np.uint8))
+
+
+def edge_boards():
+    """Canonical 2x15x15 boards (plane 0 = side to move) where the compacted fold kernels do their least common work:
+    the conv padding, border tokens, dense and one-colour boards, and a few real positions.  Returns (boards, names)."""
+    rng = np.random.RandomState(2024)
+    bs, names = [], []
+
+    def add(name, p0=(), p1=()):
+        b = np.zeros((2, 15, 15), np.float32)
+        for r, c in p0:
+            b[0, r, c] = 1
+        for r, c in p1:
+            b[1, r, c] = 1
+        assert not (b[0] * b[1]).any(), name
+        bs.append(b)
+        names.append(name)
+
+    def rand_cells(n, pool=None):
+        pool = np.arange(225) if pool is None else np.asarray(pool)
+        return [divmod(int(x), 15) for x in rng.choice(pool, size=n, replace=False)]
+
+    add("empty")
+    for rc in [(0, 0), (0, 14), (14, 0), (14, 14), (0, 7), (7, 0), (7, 14), (14, 7)]:
+        add(f"own_{rc[0]}_{rc[1]}", p0=[rc])
+        add(f"opp_{rc[0]}_{rc[1]}", p1=[rc])
+    row = rng.randint(2, size=15)
+    add("row14", p0=[(14, c) for c in range(15) if row[c]], p1=[(14, c) for c in range(15) if not row[c]])
+    col = rng.randint(2, size=15)
+    add("col14", p0=[(r, 14) for r in range(15) if col[r]], p1=[(r, 14) for r in range(15) if not col[r]])
+    for r0, c0 in [(10, 10), (5, 5)]:
+        patch = [(r0 + i, c0 + j) for i in range(5) for j in range(5)]
+        add(f"patch_{r0}_{c0}", p0=patch[0::2], p1=patch[1::2])
+    ring = [(r, c) for r in range(15) for c in range(15) if r in (0, 14) or c in (0, 14)]
+    add("ring", p0=ring[0::2], p1=ring[1::2])
+    border = [r * 15 + c for r, c in ring]
+    for k in range(2):
+        cs = rand_cells(20, border)
+        add(f"border20_{k}", p0=cs[:10], p1=cs[10:])
+    for n in (40, 120):
+        cs = rand_cells(n)
+        add(f"own_only_{n}", p0=cs)
+        cs = rand_cells(n)
+        add(f"opp_only_{n}", p1=cs)
+    all_rc = [(r, c) for r in range(15) for c in range(15)]
+    add("checker", p0=[rc for rc in all_rc if (rc[0] + rc[1]) % 2 == 0], p1=[rc for rc in all_rc if (rc[0] + rc[1]) % 2])
+    add("checker_inv_224", p0=[rc for rc in all_rc if (rc[0] + rc[1]) % 2 and rc != (7, 7)],
+        p1=[rc for rc in all_rc if (rc[0] + rc[1]) % 2 == 0 and rc != (7, 7)])
+    add("stripes", p0=[rc for rc in all_rc if rc[0] % 2 == 0], p1=[rc for rc in all_rc if rc[0] % 2])
+    for n in (100, 150, 200, 224):
+        for k in range(2):
+            cs = rand_cells(n)
+            add(f"random_{n}_{k}", p0=cs[: (n + 1) // 2], p1=cs[(n + 1) // 2:])
+    for hole in [(0, 0), (14, 14)]:
+        cs = [rc for rc in all_rc if rc != hole]
+        perm = rng.permutation(len(cs))
+        add(f"full_but_{hole[0]}_{hole[1]}", p0=[cs[j] for j in perm[:112]], p1=[cs[j] for j in perm[112:]])
+    positions = golden_positions_15()
+    for i in (1, 10, 30, 60, 67, 91):
+        _, cells, to_move, ply = positions[i]
+        b = GMK.get_canonical_board(board_of_cells(cells), to_move)
+        bs.append(np.ascontiguousarray(b, np.float32))
+        names.append(f"position_{i}")
+    return np.stack(bs), names
+
+
+def gen_nn_edges():
+    """The seed-0 depth-1 D = 512 network and main.py:186-188's depth-2 D = 256 network on edge_boards(): one batched CPU
+    forward each."""
+    import json
+    x, names = edge_boards()
+    out = {"x": x, "names_json": np.frombuffer(json.dumps(names).encode(), np.uint8)}
+    with torch.no_grad():
+        lg, v = seed0_net()(torch.from_numpy(x))
+    out["d1_logits"], out["d1_value"] = lg.numpy(), v.numpy().reshape(-1)
+    torch.manual_seed(0)
+    net2 = RefNet(dropout=0.1, img_size=15, patch_size=5, embed_dim=256, action_dim=225, num_heads=8, depth=2, channels=2).eval()
+    with torch.no_grad():
+        lg, v = net2(torch.from_numpy(x))
+    out["d2_logits"], out["d2_value"] = lg.numpy(), v.numpy().reshape(-1)
+    out["torch_threads"] = np.array(torch.get_num_threads())
+    print("nn_edges", len(names), "boards")
+    return out
+
+
+# =================================================================================
 # 5. train step (train.py:85-123): loss, L2 quirk, Adam - small net, dropout 0 (deterministic)
 # =================================================================================
 def gen_train(dropout=0.0, torch_seed_for_masks=None):
@@ -590,7 +764,7 @@ def gen_train(dropout=0.0, torch_seed_for_masks=None):
 
 
 def main():
-    which = sys.argv[1:] or ["rules", "search", "games", "compete", "nn", "nn_depth2", "train", "train_dropout"]
+    which = sys.argv[1:] or ["rules", "search", "games", "compete", "nn", "nn_depth2", "nn_search15", "nn_edges", "train", "train_dropout"]
     print("python", sys.version.split()[0], "numpy", np.__version__, "torch", torch.__version__,
           "cpus", os.cpu_count(), "torch threads", torch.get_num_threads())
     if "rules" in which:
@@ -614,6 +788,10 @@ def main():
         np.savez_compressed(os.path.join(HERE, "nn_small.npz"), **gen_nn_small())
     if "nn_depth2" in which:
         np.savez_compressed(os.path.join(HERE, "nn_depth2.npz"), **gen_nn_depth2())
+    if "nn_search15" in which:
+        np.savez_compressed(os.path.join(HERE, "nn_search15.npz"), **gen_nn_search15())
+    if "nn_edges" in which:
+        np.savez_compressed(os.path.join(HERE, "nn_edges.npz"), **gen_nn_edges())
     if "train" in which:
         np.savez_compressed(os.path.join(HERE, "train_small.npz"), **gen_train())
     if "train_dropout" in which:

@@ -39,8 +39,9 @@ def test_benched_evaluator_against_reference_known_answers():
 def test_search_policies_fp32_exact_and_bf16_bounded():
     """800-simulation searches from all 92 recorded positions of the reference's 15x15 games, same Dirichlet noise:
       fp32 'cls' vs fp32 'full' (same function, different summation order): pi identical to the last visit (the 1e-5 bar);
-      bf16 'clsfold' vs fp32 'full': measured 88 / 92 positions identical (round 2's conv-form embedding kernel: 86), max |delta pi| 3.8e-3 (3 visits of 799), mean total
-      variation 1.4e-4, no position changes its most-visited move.  Asserted with margin: >= 70 % identical, max |delta pi|
+      bf16 'clsfold' vs fp32 'full': measured 87 / 92 positions identical (round 2's conv-form embedding kernel: 86; round 3: 88), max |delta pi| 2.5e-3
+      (2 visits of 799; round 3: 3.8e-3), mean total variation 9.5e-5, no position changes its most-visited move.  Asserted with margin: >= 85
+      identical (the measured count - 2), max |delta pi|
       <= 2e-2, mean TV <= 1e-3, most-visited move changed in <= 5 % of the positions.  And the bf16 search is deterministic."""
     import sys, os
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
@@ -60,7 +61,7 @@ def test_search_policies_fp32_exact_and_bf16_bounded():
     identical = int((d.max(1) == 0).sum())
     print(f"bf16 clsfold vs fp32 full: {identical}/{G} identical, max |dpi| {d.max():.2e}, mean TV {0.5 * d.sum(1).mean():.2e}, "
           f"argmax changed {(pi16.argmax(1) != ref_pi.argmax(1)).mean():.3f}")
-    assert identical >= 0.7 * G
+    assert identical >= 85
     assert d.max() <= 2e-2 and 0.5 * d.sum(1).mean() <= 1e-3
     assert (pi16.argmax(1) != ref_pi.argmax(1)).mean() <= 0.05
     again, _ = search_pis(net16, "bfloat16", positions, 800, noise)

@@ -5,7 +5,8 @@ reference's fp32 network?  (north_star: "within 1e-5 on visi
      the seed-0 network in (a) fp32 'full' (the reference's own arithmetic), (b) fp32 'cls' (same function, different
      summation order: the sensitivity floor), (c) fp32 'clsfold' (the hand-written fp32-accurate kernels, csrc/azk_nnx.hip),
      (d) bf16 'clsfold' (the benched path): max |delta pi|, total variation, share of
-     positions whose most-visited move changes.
+     positions whose most-visited move changes - against (a) ('search_vs_fp32_full') and against the reference's own searches
+     with the same network and noise (tests/golden/nn_search15.npz, 'search_vs_reference').
 usage: measure_nn_parity.py [n_sims]      -> one JSON line"""
 import json
 import os
@@ -32,6 +33,20 @@ def golden_positions():
         for ply in range(len(cells)):
             out.append((cells[ply].astype(np.int8).reshape(-1), ply & 1, ply))
     return out
+
+
+def reference_pi():
+    """The reference's own 800-simulation pi (child visits / their sum) from each golden_positions() position with the seed-0 network
+    and RandomState(7)'s noise rows (tests/golden/nn_search15.npz): float64 [92, 225]."""
+    z = load_golden("nn_search15.npz")
+    pos = golden_positions()
+    assert len(pos) == len(z["cells"]) and all(np.array_equal(p[0], c) for p, c in zip(pos, z["cells"]))
+    pi = np.zeros((len(pos), 225))
+    off = z["child_off"]
+    for i in range(len(pos)):
+        cell, visit = z["child_cell"][off[i]:off[i + 1]], z["child_visit"][off[i]:off[i + 1]].astype(np.float64)
+        pi[i, cell] = visit / visit.sum()
+    return pi
 
 
 def search_pis(net, leaf_dtype, positions, n_sims, noise):
@@ -95,15 +110,21 @@ def main():
     again = search_pis(nets["bf16_clsfold"], "bfloat16", positions, n_sims, noise)
     ref_pi, ref_q = pis["fp32_full"]
 
-    def dev(name):
+    def dev(name, against=None):
         pi, q = pis[name]
-        d = np.abs(pi - ref_pi)
-        return {"max_abs_dpi": float(d.max()), "mean_over_positions_of_max_abs_dpi": float(d.max(1).mean()),
-                "tv_mean": float(0.5 * d.sum(1).mean()), "tv_max": float(0.5 * d.sum(1).max()),
-                "argmax_changed_share": float((pi.argmax(1) != ref_pi.argmax(1)).mean()),
-                "positions_with_identical_pi": int((d.max(1) == 0).sum()), "max_abs_dq": float(np.abs(q - ref_q).max())}
+        rp = ref_pi if against is None else against
+        d = np.abs(pi - rp)
+        out = {"max_abs_dpi": float(d.max()), "mean_over_positions_of_max_abs_dpi": float(d.max(1).mean()),
+               "tv_mean": float(0.5 * d.sum(1).mean()), "tv_max": float(0.5 * d.sum(1).max()),
+               "argmax_changed_share": float((pi.argmax(1) != rp.argmax(1)).mean()),
+               "positions_with_identical_pi": int((d.max(1) == 0).sum())}
+        if against is None:
+            out["max_abs_dq"] = float(np.abs(q - ref_q).max())
+        return out
+    ref_run = reference_pi() if n_sims == 800 else None          # the reference's own searches (800 simulations)
     out = {"n_sims": n_sims, "positions": G, "kat_vs_reference_seed0": kat, "clsfold_vs_fp32_full_on_256_boards": wide, "fp32_clsfold_vs_fp32_full_on_256_boards": wide_x,
            "search_vs_fp32_full": {"fp32_cls": dev("fp32_cls"), "fp32_clsfold": dev("fp32_clsfold"), "bf16_clsfold": dev("bf16_clsfold")},
+           "search_vs_reference": None if ref_run is None else {k: dev(k, ref_run) for k in pis},
            "bf16_clsfold_rerun_identical": bool(np.array_equal(again[0], pis["bf16_clsfold"][0]))}
     print(json.dumps(out))
 

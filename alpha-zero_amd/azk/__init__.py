@@ -47,7 +47,7 @@ class Config(C.Structure):
     _fields_ = [("game", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("n_games", C.c_int32),
                 ("max_sims", C.c_int32), ("leaf_dtype", C.c_int32), ("device", C.c_int32),
                 ("arena_nodes", C.c_int32), ("cache_entries", C.c_int32), ("cache_shared", C.c_int32), ("leaves_per_step", C.c_int32),
-                ("reserved", C.c_int32 * 5)]
+                ("tree_reuse", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class LeafSource(C.Structure):
@@ -129,10 +129,10 @@ class AsyncConfig(C.Structure):
 
 class Counters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("sims", "edges_scanned", "trace_nodes", "edges_created",
-                                          "leaves_evaluated", "terminal_sims", "moves_played", "cache_hits")] + [("reserved", C.c_int64 * 8)]
+                                          "leaves_evaluated", "terminal_sims", "moves_played", "cache_hits", "roots_reused", "nodes_carried")] + [("reserved", C.c_int64 * 6)]
 
     def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_[:8]}
+        return {n: int(getattr(self, n)) for n, _ in self._fields_[:10]}
 
 
 def build(force=False, verbose=False):
@@ -272,7 +272,7 @@ class Engine:
     """G concurrent games + their search trees resident on one GPU (one engine per process / GPU)."""
 
     def __init__(self, game, n_games, max_sims, size=None, device=0, leaf_dtype="float32", arena_nodes=0, cache_entries=0,
-                 cache_shared=False, leaves_per_step=1):
+                 cache_shared=False, leaves_per_step=1, tree_reuse=0):
         torch = _torch()
         self.torch = torch
         self.L = lib()
@@ -287,6 +287,10 @@ class Engine:
         # OPT-IN virtual-loss expansion: K leaves in flight per game (changes search results; 1 = the reference's sequential search)
         self.K = max(1, int(leaves_per_step))
         cfg.leaves_per_step = self.K
+        # OPT-IN tree reuse across moves (changes search results): 1 = carry (n_sims new simulations on the carried subtree), 2 = top-up
+        # (only as many as bring the root back to n_sims visits; budget stepping only).  0 = a fresh root every move, the reference's search
+        self.tree_reuse = int(tree_reuse)
+        cfg.tree_reuse = self.tree_reuse
         cfg.leaf_dtype = LEAF_BF16 if leaf_dtype in ("bfloat16", "bf16", torch.bfloat16) else LEAF_F32
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
@@ -546,7 +550,7 @@ class Engine:
         return dict(cell=cells[:n].copy(), visit=visits[:n].astype(np.int64), value=values[:n].copy(), prior=priors[:n].copy())
 
     def export_tree(self, game, cap=None):
-        cap = cap or (1 + self.max_sims * self.rows * self.cols)
+        cap = cap or (1 + (2 if self.tree_reuse == 1 else 1) * self.max_sims * self.rows * self.cols)   # (a carry engine's default arena is twice the size)
         depth = np.empty(cap, np.int32); cell = np.empty(cap, np.int32); visit = np.empty(cap, np.int32)
         value = np.empty(cap, np.float64); prior = np.empty(cap, np.float64)
         n = self._chk(self.L.azk_export_tree(self.h, int(game), cap, _np(depth), _np(cell), _np(visit), _np(value), _np(prior), _stream()))

@@ -18,7 +18,7 @@
 
 namespace {
 
-enum { CNT_SIMS = 0, CNT_SCANNED, CNT_TRACE, CNT_CREATED, CNT_LEAVES, CNT_TERMINAL, CNT_MOVES, CNT_CACHE_HITS, CNT_N };
+enum { CNT_SIMS = 0, CNT_SCANNED, CNT_TRACE, CNT_CREATED, CNT_LEAVES, CNT_TERMINAL, CNT_MOVES, CNT_CACHE_HITS, CNT_REUSED, CNT_CARRIED, CNT_N };
 
 struct __attribute__((aligned(16))) NodeH { int N; float P; uint32_t meta; int fc; };
 typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // four consecutive floats of a row that is only 4-byte aligned (A = 225: 900-byte rows)
@@ -75,6 +75,16 @@ struct Dev {               // device view of the engine, passed to kernels by va
     int *err;              // sticky error word
     int ablate;            // debug only (AZK_TREE_ABLATE): timing experiments that break parity on purpose
     long long *dbg;        // debug only: [G][8] cycle stamps per phase when ablate & 16
+};
+
+// tree reuse across moves (azk_config.tree_reuse, opt-in; all null / 0 otherwise).  Its own argument of the few kernels that need it:
+// Dev - and with it the kernel-argument offsets and instruction stream of k_tree - is that of an engine without the feature
+struct ReuseDev {
+    int mode;              // 0 off, 1 carry, 2 top-up
+    int words;             // 64-bit words of one game's mark bitmap: ceil(cap / 64)
+    int *chosen_node;      // [G] arena index of the child k_advance played (the next search's root), -1 = start from a fresh root
+    unsigned long long *bits;   // [G][words] k_reroot scratch: bit i = node i belongs to the kept subtree
+    unsigned *pre;         // [G][words] k_reroot scratch: kept nodes below the word = new index of the word's first kept node
 };
 
 struct LdsView {
@@ -1003,10 +1013,7 @@ __device__ __forceinline__ void clear_leaf_slots(const Dev &d, int g) {
 }
 
 // Node(None, None, current_player, move_count) for every game (gomoku.py:134)
-__global__ void k_begin_search(Dev d) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= d.G) return;
-    if (g == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
+__device__ __forceinline__ void fresh_root_one(const Dev &d, int g) {
     drop_pending_cache_claim(d, g);
     const size_t base = (size_t)g * d.cap;
     d.H[base] = NodeH{0, 0.f, meta_pack(0xffff, 0), -1}; d.W[base] = 0.0;
@@ -1015,18 +1022,192 @@ __global__ void k_begin_search(Dev d) {
     d.sims_done[g] = 0;
 }
 
-__global__ void k_reset_games(Dev d, int first, int count) {
+__global__ void k_begin_search(Dev d) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= d.G) return;
+    if (g == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
+    fresh_root_one(d, g);
+}
+
+// ================================================================================================
+// Tree reuse across moves (azk_config.tree_reuse, opt-in): the search of the next move starts on the subtree under the child
+// that was played - the reference's MCTS.mcts(model, board, root, ...) (ai/mcts.py:11) handed `root = chosen_child;
+// root.parent = None` instead of a new Node (games/gomoku.py:134).  reroot_one moves that subtree to the front of the game's
+// arena IN PLACE (the arena pointers are baked into captured step graphs) and repairs the links.  One wave per game:
+//   mark   a child block is allocated after its parent exists, so first_child(node) > node: ONE ascending sweep over a bitmap
+//          of the arena finds the subtree - a marked, expanded node marks its child block, always at higher indices.  The sweep
+//          holds 64 bitmap words (4 096 nodes) in registers, skips empty words without touching memory, reads the 16-byte
+//          headers of a word's marked nodes in one load, and fetches the window again only after a mark that fell inside it.
+//   rank   new index of a kept node = number of kept nodes below it: a running popcount per bitmap word (rr_pre) + the bits
+//          below the node in its own word.  Order-preserving, so blocks stay contiguous, in list order, behind their parents.
+//   slide  kept records (NodeH + W) move to their rank in ascending order, four bitmap words per round trip; destination <=
+//          source for every node and a round's records are all in registers before its first store, so no record is overwritten
+//          before it was read.  first_child goes through the same rank computation.
+// Every loop is bounded by the game's arena_top; a link that does not point forward inside the arena ends in the sticky
+// error word and a fresh root.  n_sims: the simulations this search may still run (the arena rule's worst case, and the
+// top-up target).  The kept subtree is dropped for a fresh root when  kept + n_new * widest > cap  (include/azk.h).
+// ================================================================================================
+__device__ __forceinline__ unsigned long long rr_load64(const unsigned long long *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // past the vector L1: the words are updated by atomics
+}
+__device__ __forceinline__ unsigned long long rr_below(int bit) { return (1ull << bit) - 1ull; }
+// rank of node i among the kept nodes
+__device__ __forceinline__ int rr_rank(const unsigned long long *bm, const unsigned *pre, int i) {
+    const unsigned long long w = rr_load64(bm + (i >> 6));
+    const unsigned p = __hip_atomic_load(pre + (i >> 6), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return (int)p + __popcll(w & rr_below(i & 63));
+}
+
+__device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_sims) {
+    const int lane = azk_lane();
+    const GameDesc &gd = d.g;
+    const size_t base = (size_t)g * (size_t)d.cap;
+    const int T = uniform_i32(d.arena_top[g]);
+    unsigned long long *bm = r.bits + (size_t)g * r.words;
+    unsigned *pre = r.pre + (size_t)g * r.words;
+    bool keep = c > 0 && c < T && T <= d.cap && uniform_i32(d.done[g]) == 0;
+    bool bad = false;
+    NodeH hroot = NodeH{0, 0.f, 0u, -1};
+    if (keep) hroot = d.H[base + c];
+    const int root_fc = uniform_i32(hroot.fc), root_nch = uniform_i32(meta_nch(hroot.meta)), root_N = uniform_i32(hroot.N);
+    if (keep && root_fc < 0) keep = false;                        // the chosen child was never expanded (n_sims = 1)
+    const int n_new = r.mode == 2 ? max(1, n_sims - root_N) : n_sims;
+    const int w0 = c >> 6, w1 = (T - 1) >> 6;                     // bitmap words the subtree can touch
+    int kept = 0;
+    if (keep) {
+        for (int w = w0 + lane; w <= w1; w += AZK_WAVE) bm[w] = w == w0 ? 1ull << (c & 63) : 0ull;
+        __threadfence();
+        for (int wb = w0; wb <= w1 && !bad; wb += AZK_WAVE) {
+            unsigned long long wreg = wb + lane <= w1 ? rr_load64(bm + wb + lane) : 0ull;
+            for (int k = 0; k < AZK_WAVE && wb + k <= w1 && !bad; k++) {
+                unsigned long long seen = 0ull;
+                for (int round = 0; round <= AZK_WAVE; round++) {            // a round handles at least one new node of the word
+                    const unsigned long long word = azk_readlane_u64(wreg, k) & ~seen;
+                    if (word == 0ull) break;
+                    seen |= word;
+                    kept += __popcll(word);
+                    const int node = (wb + k) * AZK_WAVE + lane;
+                    const bool has = (word >> lane) & 1ull;
+                    const NodeH h = d.H[base + (has ? node : c)];
+                    const int hn = meta_nch(h.meta);
+                    const bool ex = has && h.fc >= 0;
+                    if (__ballot(ex && !(h.fc > node && hn >= 1 && hn <= T - h.fc)) != 0ull) { bad = true; break; }
+                    unsigned long long m = __ballot(ex);
+                    bool near = false;
+                    while (m != 0ull) {                                       // the child block of each expanded node, as whole-word masks
+                        const int l = __ffsll((long long)m) - 1;
+                        m &= m - 1ull;
+                        const int f = __builtin_amdgcn_readlane(h.fc, l), n = __builtin_amdgcn_readlane(hn, l);
+                        const int fw = f >> 6, lw = (f + n - 1) >> 6;
+                        for (int w = fw + lane; w <= lw; w += AZK_WAVE) {
+                            const int lo = max(f, w * 64) - w * 64, hi = min(f + n, w * 64 + 64) - w * 64;
+                            const unsigned long long mask = hi - lo == 64 ? ~0ull : rr_below(hi - lo) << lo;
+                            atomicOr(bm + w, mask);
+                        }
+                        near = near || fw < wb + AZK_WAVE;
+                    }
+                    if (!near) break;                                         // every new mark lies beyond this window
+                    __threadfence();
+                    wreg = wb + lane <= w1 ? rr_load64(bm + wb + lane) : 0ull;
+                }
+            }
+        }
+        __threadfence();
+    }
+    // the arena rule: the kept subtree plus the most this search can still allocate - one expansion per simulation, and no position
+    // below the root has more legal moves than min(max children, empty cells of the root position).  (The root's own child count is
+    // NOT such a bound: Gomoku's legal moves are the cells next to a stone, and their number grows along a line of play.)
+    const int widest = min(gd.kind == AZK_KIND_C4 ? gd.cols : gd.rc, gd.state_dim - uniform_i32(d.move_count[g]));
+    if (bad || !keep || (long long)kept + (long long)n_new * widest > (long long)d.cap) {
+        if (lane == 0) {
+            if (bad) atomicExch(d.err, AZK_ERR_STATE);
+            fresh_root_one(d, g);
+        }
+        return;
+    }
+    // rank: kept nodes below each word
+    int run = 0;
+    for (int wb = w0; wb <= w1; wb += AZK_WAVE) {
+        const unsigned long long word = wb + lane <= w1 ? rr_load64(bm + wb + lane) : 0ull;
+        int incl = __popcll(word);
+        const int own = incl;
+#pragma unroll
+        for (int off = 1; off < AZK_WAVE; off <<= 1) { const int o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+        if (wb + lane <= w1) pre[wb + lane] = (unsigned)(run + incl - own);
+        run += __shfl(incl, AZK_WAVE - 1);
+    }
+    __threadfence();
+    // slide
+    for (int wb = w0; wb <= w1; wb += AZK_WAVE) {
+        const unsigned long long wreg = wb + lane <= w1 ? rr_load64(bm + wb + lane) : 0ull;
+        const int preg = wb + lane <= w1 ? (int)__hip_atomic_load(pre + wb + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        for (int k0 = 0; k0 < AZK_WAVE && wb + k0 <= w1; k0 += 4) {
+            unsigned long long wd[4];
+            int pk[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) { wd[j] = azk_readlane_u64(wreg, k0 + j); pk[j] = __builtin_amdgcn_readlane(preg, k0 + j); }
+            if ((wd[0] | wd[1] | wd[2] | wd[3]) == 0ull) continue;
+            NodeH h[4];
+            double wv[4];
+            bool has[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {                                     // every record of the round, before any store
+                has[j] = (wd[j] >> lane) & 1ull;
+                const size_t src = base + (has[j] ? (wb + k0 + j) * AZK_WAVE + lane : c);
+                h[j] = d.H[src]; wv[j] = d.W[src];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) if (has[j] && h[j].fc >= 0) h[j].fc = rr_rank(bm, pre, h[j].fc);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (!has[j]) continue;
+                const int dst = pk[j] + __popcll(wd[j] & rr_below(lane));
+                if ((wb + k0 + j) * AZK_WAVE + lane == c) { h[j].P = 0.f; h[j].meta = meta_pack(0xffff, root_nch); }   // the root: no prevAction
+                d.H[base + dst] = h[j]; d.W[base + dst] = wv[j];
+            }
+        }
+    }
+    __threadfence();
+    azk_wave_sync();
+    // the root's children: float64 priors with this move's Dirichlet row (utils.py:24-25 on the stored float32 prior), else as they are
+    const int new_fc = rr_rank(bm, pre, root_fc);
+    if (d.noise != nullptr) {
+        for (int i = lane; i < root_nch; i += AZK_WAVE) {
+            const NodeH ch = d.H[base + new_fc + i];
+            d.rootP[(size_t)g * gd.rc + i] = (double)(0.75f * ch.P) + 0.25 * d.noise[(size_t)g * gd.action_dim + azk_action_idx(gd, meta_cell(ch.meta))];
+        }
+    }
+    if (lane == 0) {
+        drop_pending_cache_claim(d, g);
+        d.arena_top[g] = kept; d.root_f64[g] = d.noise != nullptr ? 1 : 0;
+        clear_leaf_slots(d, g);
+        d.sims_done[g] = r.mode == 2 ? n_sims - n_new : 0;
+        count_add(d, CNT_REUSED, g, 1);
+        count_add(d, CNT_CARRIED, g, kept);
+    }
+}
+
+// azk_begin_search on a reuse engine: re-root on the child k_advance recorded, or a fresh root where there is none
+__global__ __launch_bounds__(AZK_WAVE) void k_reroot(Dev d, ReuseDev r, int n_sims) {
+    const int g = blockIdx.x;
+    if (g == 0 && azk_lane() == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
+    const int c = uniform_i32(r.chosen_node[g]);
+    reroot_one(d, r, g, c, n_sims);
+    if (azk_lane() == 0) r.chosen_node[g] = -1;                   // one search per recorded move
+}
+
+__global__ void k_reset_games(Dev d, int first, int count, int *chosen_node) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count * d.rc_pad) return;
     const int g = first + t / d.rc_pad, i = t % d.rc_pad;
     d.cells[(size_t)g * d.rc_pad + i] = 0;
     if (i == 0) drop_pending_cache_claim(d, g);
-    if (i == 0) { d.to_move[g] = 0; d.move_count[g] = 0; d.done[g] = 0; d.winner[g] = -2; clear_leaf_slots(d, g); }
+    if (i == 0) { d.to_move[g] = 0; d.move_count[g] = 0; d.done[g] = 0; d.winner[g] = -2; clear_leaf_slots(d, g); if (chosen_node) chosen_node[g] = -1; }
 }
 
 // Continuous self-play: every finished game's slot restarts from Game() (empty board, player 0).
 // stats[0] += games recycled, stats[1] += plies those games lasted, stats[2..4] += wins of player 0 / player 1 / draws.
-__global__ void k_recycle(Dev d, long long *stats) {
+__global__ void k_recycle(Dev d, long long *stats, int *chosen_node) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.G || !d.done[g]) return;
     atomicAdd((unsigned long long *)&stats[0], 1ull);
@@ -1037,6 +1218,7 @@ __global__ void k_recycle(Dev d, long long *stats) {
     for (int i = 0; i < d.rc_pad; i++) d.cells[(size_t)g * d.rc_pad + i] = 0;
     d.to_move[g] = 0; d.move_count[g] = 0; d.done[g] = 0; d.winner[g] = -2;
     clear_leaf_slots(d, g);
+    if (chosen_node) chosen_node[g] = -1;
 }
 
 // utils.get_probablity_distribution_of_children (utils.py:46-55), root.value / root.visit (gomoku.py:140)
@@ -1151,7 +1333,7 @@ __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool
 }
 
 __global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *uniforms, int sample_until,
-                                                       int *chosen, int *winner_out, int *done_out) {
+                                                       int *chosen, int *winner_out, int *done_out, int *chosen_node) {
     const int g = blockIdx.x, lane = azk_lane();
     LdsView L = carve(d.g, d.path_cap, d.table_size);
     if (uniform_i32(d.done[g]) != 0) {
@@ -1159,11 +1341,22 @@ __global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *unifo
             if (chosen) chosen[g] = -1;
             if (winner_out) winner_out[g] = d.winner[g];
             if (done_out) done_out[g] = 1;
+            if (chosen_node) chosen_node[g] = -1;
         }
         return;
     }
     int win = -2, dn = 0, sum = 0;
     const int cellc = advance_one(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum);
+    if (chosen_node) {
+        // tree reuse: the arena index of the child that was played (a cell occurs once among a node's children)
+        const size_t base = (size_t)g * d.cap;
+        const int fc = uniform_i32(d.H[base].fc), nch = uniform_i32(meta_nch(d.H[base].meta));
+        int found = 0x7fffffff;
+        for (int i = lane; i < nch; i += AZK_WAVE) if (meta_cell(d.H[base + fc + i].meta) == cellc && i < found) found = i;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(found, off); found = o < found ? o : found; }
+        if (lane == 0) chosen_node[g] = (cellc >= 0 && dn == 0 && found != 0x7fffffff) ? fc + found : -1;
+    }
     if (cellc < 0) return;
     if (lane == 0) {
         if (chosen) chosen[g] = cellc;
@@ -1584,6 +1777,7 @@ struct azk_engine {
     bool multi = false;                  // budget stepping (azk_begin_search_budget): the MULTI instantiation of k_tree
     int budget_host[4] = {0, 1, 0, 0};
     int ticks_per_us = 100;              // constant-rate clock of wall_clock64()
+    ReuseDev ru;                         // tree reuse (cfg.tree_reuse); ru.mode == 0: off, every pointer null
     AsyncDev ad;                         // asynchronous self-play (azk_async_begin); ad.slot_moves == nullptr: not set up
     bool async_on = false;
     int async_recycle = 1;
@@ -1622,12 +1816,16 @@ int32_t azk_create(const azk_config *cfg, azk_engine **out) {
     Dev &d = e->d;
     memset(&d, 0, sizeof d);
     memset(&e->ad, 0, sizeof e->ad);
+    memset(&e->ru, 0, sizeof e->ru);
     auto fail = [&](int code, const std::string &msg) { g_create_error = msg; azk_destroy(e); return code; };
     std::string gerr;
     if (!make_game(cfg->game, cfg->rows, cfg->cols, &d.g, &gerr)) return fail(AZK_ERR_ARG, gerr);
     if (cfg->n_games < 1 || cfg->max_sims < 1) return fail(AZK_ERR_ARG, "n_games and max_sims must be >= 1");
     if (cfg->leaf_dtype != AZK_LEAF_F32 && cfg->leaf_dtype != AZK_LEAF_BF16) return fail(AZK_ERR_ARG, "bad leaf_dtype");
     if (cfg->leaves_per_step < 0 || cfg->leaves_per_step > 64) return fail(AZK_ERR_ARG, "leaves_per_step must be 0..64");
+    const int tree_reuse = cfg->tree_reuse;
+    if (tree_reuse < 0 || tree_reuse > 2) return fail(AZK_ERR_ARG, "tree_reuse must be 0 (off), 1 (carry) or 2 (top-up)");
+    if (tree_reuse != 0 && cfg->leaves_per_step > 1) return fail(AZK_ERR_ARG, "tree_reuse does not combine with leaves_per_step > 1 (virtual loss)");
     if (cfg->cache_entries < 0 || (cfg->cache_entries & (cfg->cache_entries - 1)) != 0) return fail(AZK_ERR_ARG, "cache_entries must be 0 or a power of two");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
@@ -1637,7 +1835,9 @@ int32_t azk_create(const azk_config *cfg, azk_engine **out) {
     { int khz = 0; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, cfg->device) == hipSuccess && khz >= 1000) e->ticks_per_us = khz / 1000; }
     const GameDesc &g = d.g;
     const int maxch = g.kind == AZK_CONNECT4 ? g.cols : g.rc;
-    long long cap = cfg->arena_nodes > 0 ? cfg->arena_nodes : 1 + (long long)cfg->max_sims * maxch;
+    // carry mode: the root's visits grow beyond max_sims from move to move, so the default arena holds a kept subtree of max_sims
+    // expansions plus the max_sims new ones (the arena rule of include/azk.h drops a larger subtree)
+    long long cap = cfg->arena_nodes > 0 ? cfg->arena_nodes : 1 + (long long)(tree_reuse == 1 ? 2 : 1) * cfg->max_sims * maxch;
     if (cap > 0x7ffffff0LL) return fail(AZK_ERR_ARG, "arena too large");
     d.G = cfg->n_games; d.cap = (int)cap; d.path_cap = g.state_dim + 2; d.rc_pad = up16(g.rc);
     d.leaf_dtype = cfg->leaf_dtype; d.table_size = table_size_for(g);
@@ -1651,6 +1851,11 @@ int32_t azk_create(const azk_config *cfg, azk_engine **out) {
     DA(d.cells, G * d.rc_pad); DA(d.to_move, G); DA(d.move_count, G); DA(d.done, G); DA(d.winner, G);
     DA(d.H, nodes); DA(d.W, nodes);
     DA(d.rootP, G * g.rc); DA(d.root_f64, G); DA(d.arena_top, G);
+    e->ru.mode = tree_reuse;
+    if (tree_reuse) {
+        e->ru.words = (d.cap + 63) / 64;
+        DA(e->ru.chosen_node, G); DA(e->ru.bits, G * (size_t)e->ru.words); DA(e->ru.pre, G * (size_t)e->ru.words);
+    }
     d.K = cfg->leaves_per_step > 1 ? cfg->leaves_per_step : 1;
     const size_t GV = G * (size_t)d.K;                            // pending-leaf slots
     DA(d.leaf_node, GV); DA(d.leaf_depth, GV); DA(d.leaf_nmoves, GV); DA(d.leaf_slot, GV); DA(d.to_move_v, GV);
@@ -1690,7 +1895,7 @@ int32_t azk_create(const azk_config *cfg, azk_engine **out) {
     }
     (void)hipMemset(d.dbg, 0, sizeof(long long) * G * 8);
     (void)hipMemset(d.leaf_node, 0xff, sizeof(int) * GV);
-    k_reset_games<<<(unsigned)((G * d.rc_pad + 255) / 256), 256>>>(d, 0, d.G);
+    k_reset_games<<<(unsigned)((G * d.rc_pad + 255) / 256), 256>>>(d, 0, d.G, e->ru.chosen_node);
     k_begin_search<<<(unsigned)((G + 255) / 256), 256>>>(d);
     s = hipDeviceSynchronize();
     if (s != hipSuccess) return fail(AZK_ERR_HIP, std::string("init kernels: ") + hipGetErrorString(s));
@@ -1717,7 +1922,7 @@ int32_t azk_geometry(const azk_engine *e, int32_t *planes, int32_t *rows, int32_
 int32_t azk_reset_games(azk_engine *e, int32_t first, int32_t count, void *stream) {
     if (!e || first < 0 || count < 0 || first + count > e->d.G) { if (e) e->err = "azk_reset_games: bad range"; return AZK_ERR_ARG; }
     if (count == 0) return AZK_OK;
-    k_reset_games<<<(unsigned)(((size_t)count * e->d.rc_pad + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d, first, count);
+    k_reset_games<<<(unsigned)(((size_t)count * e->d.rc_pad + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d, first, count, e->ru.chosen_node);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -1743,6 +1948,7 @@ int32_t azk_set_positions(azk_engine *e, int32_t first, int32_t count, const int
     HIPCHK(e, hipMemcpyAsync(d.move_count + first, move_count_host, sizeof(int) * count, hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemcpyAsync(d.done + first, zeros.data(), sizeof(int) * count, hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemcpyAsync(d.winner + first, win.data(), sizeof(int) * count, hipMemcpyHostToDevice, st));
+    if (e->ru.chosen_node) HIPCHK(e, hipMemsetAsync(e->ru.chosen_node + first, 0xff, sizeof(int) * count, st));   // a new position: its search starts from a fresh root
     HIPCHK(e, hipStreamSynchronize(st));   // host staging buffers go out of scope
     return AZK_OK;
 }
@@ -1750,8 +1956,10 @@ int32_t azk_set_positions(azk_engine *e, int32_t first, int32_t count, const int
 int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
     e->d.noise = noise_dev; e->d.noise_sel = nullptr;
+    if (e->ru.mode == 2) { e->err = "azk_begin_search: top-up tree reuse needs the budget (azk_begin_search_budget)"; return AZK_ERR_STATE; }
     e->multi = false;
-    k_begin_search<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d);
+    if (e->ru.mode) k_reroot<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d, e->ru, e->cfg.max_sims);
+    else k_begin_search<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -1767,7 +1975,8 @@ int32_t azk_begin_search_budget(azk_engine *e, const double *noise_dev, int32_t 
         HIPCHK(e, hipMemcpyAsync(e->d.budget, e->budget_host, sizeof e->budget_host, hipMemcpyHostToDevice, (hipStream_t)stream));
         HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     }
-    k_begin_search<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d);
+    if (e->ru.mode) k_reroot<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d, e->ru, n_sims);
+    else k_begin_search<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -1778,6 +1987,7 @@ int32_t azk_async_begin(azk_engine *e, const azk_async_config *c, void *stream) 
         if (e) e->err = "azk_async_begin: bad argument";
         return AZK_ERR_ARG;
     }
+    if (e->ru.mode) { e->err = "azk_async_begin: the asynchronous movers do not re-root (tree_reuse engines use the lock-step drivers)"; return AZK_ERR_STATE; }
     if (c->record_capacity < 0 || (c->record_capacity > 0 && (!c->rec_meta_dev || !c->rec_q_dev || !c->rec_pi_dev))) { e->err = "azk_async_begin: record ring pointers missing"; return AZK_ERR_ARG; }
     Dev &d = e->d;
     if (d.K > 1) { e->err = "azk_async_begin: asynchronous moves run the sequential search (leaves_per_step = 1)"; return AZK_ERR_ARG; }
@@ -2039,7 +2249,7 @@ int32_t azk_clear_cache(azk_engine *e, void *stream) {
 
 int32_t azk_recycle_finished(azk_engine *e, int64_t *stats_dev, void *stream) {
     if (!e || !stats_dev) return AZK_ERR_ARG;
-    k_recycle<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d, (long long *)stats_dev);
+    k_recycle<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d, (long long *)stats_dev, e->ru.chosen_node);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -2055,7 +2265,7 @@ int32_t azk_advance(azk_engine *e, const double *uniforms_dev, int32_t sample_un
                     int32_t *winner_dev, int32_t *done_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
     k_advance<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, uniforms_dev, sample_until_move,
-                                                                         chosen_cell_dev, winner_dev, done_dev);
+                                                                         chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -2164,6 +2374,7 @@ int32_t azk_get_counters(azk_engine *e, azk_counters *out, void *stream) {
     out->sims = h[CNT_SIMS]; out->edges_scanned = h[CNT_SCANNED]; out->trace_nodes = h[CNT_TRACE];
     out->edges_created = h[CNT_CREATED]; out->leaves_evaluated = h[CNT_LEAVES]; out->terminal_sims = h[CNT_TERMINAL];
     out->moves_played = h[CNT_MOVES]; out->cache_hits = h[CNT_CACHE_HITS];
+    out->roots_reused = h[CNT_REUSED]; out->nodes_carried = h[CNT_CARRIED];
     return AZK_OK;
 }
 

@@ -42,7 +42,7 @@ class SelfPlayResult:
 def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
                     alpha=0.03, noise_fn=None, uniform_fn=None, device=0, leaf_dtype="float32", engine=None,
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
-                    budget_stepping=False, leaves_per_step=1):
+                    budget_stepping=False, leaves_per_step=1, tree_reuse=0):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -52,14 +52,16 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     (that is how parity tests inject the reference's recorded np.random draws).
     An evaluator of None plays vanilla MCTS (random rollouts on the device, mcts.py:57-79) - for a whole game
     (self_play(None, n): greedy moves, tictactoe.py:117 / gomoku.py:146) or for one side of an (ev0, ev1) pair
-    (test.compare(Game, None, model, ...), main.py:76).  vanilla_rng: uint32 [G, 625] MT19937 states (default: one
+    (test.compare(Game, None, model, ...), main.py:76).  tree_reuse (OPT-IN, changes search results; azk.h azk_config.tree_reuse): 1 = every
+    search after a game's first starts on the subtree under the move that was played and runs n_sims more simulations, 2 = only as
+    many as bring the root back to n_sims visits (driven by the simulation budget).  vanilla_rng: uint32 [G, 625] MT19937 states (default: one
     np.random.RandomState per global game index derived from `seed`).
     """
     import torch
     max_sims = max(n_sims) if isinstance(n_sims, (tuple, list)) else n_sims
     eng = engine or Engine(game, n_games, max_sims, size=size, device=device, leaf_dtype=leaf_dtype, cache_entries=cache_entries,
-                           cache_shared=cache_shared, leaves_per_step=leaves_per_step)
-    budget_stepping = budget_stepping or eng.K > 1          # virtual-loss engines are driven by the simulation budget
+                           cache_shared=cache_shared, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse)
+    budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2   # virtual-loss and top-up engines are driven by the simulation budget
     assert eng.G == n_games
     G, A = eng.G, eng.action_dim
     eng.reset_games()
@@ -197,14 +199,17 @@ class SelfPlayRunner:
                  alpha=0.03, device=0, leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None,
                  use_graph=False, n_split=1, replay=None, cache_entries=0, cache_shared=False, budget_stepping=False, per_launch=8,
                  steps_per_graph=32,
-                 leaves_per_step=1):
+                 leaves_per_step=1, tree_reuse=0):
         import torch
         self.replay = replay
         self.torch = torch
         # leaves_per_step > 1: OPT-IN virtual-loss expansion (K leaves in flight per game; changes search results); it is driven
         # by the simulation budget, like budget stepping
         self.leaves_per_step = max(1, int(leaves_per_step))
-        self.budget_stepping, self.per_launch = (budget_stepping or self.leaves_per_step > 1) and use_graph, per_launch
+        # tree_reuse: OPT-IN tree reuse across moves (azk.h azk_config.tree_reuse; changes search results): 1 = carry, 2 = top-up.  Top-up
+        # stops a game at n_sims root visits through the simulation budget, so it turns budget stepping on (eager runner: Engine.search_budget)
+        self.tree_reuse = int(tree_reuse)
+        self.budget_stepping, self.per_launch = (budget_stepping or self.leaves_per_step > 1 or self.tree_reuse == 2) and use_graph, per_launch
         assert self.leaves_per_step == 1 or use_graph, "virtual-loss mode runs on the graph runner"
         self.launches = 0               # simulation-step launches issued (per game group) since construction
         self.use_graph = use_graph
@@ -214,7 +219,8 @@ class SelfPlayRunner:
         self.n_split = n_split if use_graph else 1
         per = n_games // self.n_split
         self.halves = [_Half(torch, Engine(game, per, n_sims, size=size, device=device, leaf_dtype=leaf_dtype,
-                                           cache_entries=cache_entries, cache_shared=cache_shared, leaves_per_step=self.leaves_per_step), dirichlet)
+                                           cache_entries=cache_entries, cache_shared=cache_shared, leaves_per_step=self.leaves_per_step,
+                                           tree_reuse=self.tree_reuse), dirichlet)
                        for _ in range(self.n_split)]
         self.eng = self.halves[0].eng
         self.G = n_games
@@ -265,6 +271,9 @@ class SelfPlayRunner:
     def search(self, noise):
         """Eager stepping (host sync per simulation, n_leaf-sized evaluator batches); optional k_tree event timing."""
         e, torch, kt = self.eng, self.torch, self.kernel_timer
+        if self.tree_reuse == 2:
+            e.search_budget(self.evaluator, self.n_sims, noise if self.dirichlet else None, self.per_launch)
+            return
         e.begin_search(noise)
         logits = values = None
         for s in range(self.n_sims):
@@ -482,8 +491,11 @@ class AsyncSelfPlayRunner:
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
-                 per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0):
+                 per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0):
         import torch
+        if tree_reuse:
+            raise ValueError("AsyncSelfPlayRunner does not re-root: the asynchronous movers start a game's next search inside the move kernel "
+                             "(azk_async_begin refuses a tree_reuse engine); use SelfPlayRunner(tree_reuse=...)")
         self.torch, self.replay, self.evaluator = torch, replay, evaluator
         self.eng = Engine(game, n_games, n_sims, size=size, device=device, leaf_dtype=leaf_dtype, cache_entries=cache_entries, cache_shared=cache_shared)
         e = self.eng

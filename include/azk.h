@@ -70,7 +70,26 @@ typedef struct {
                               * selection leaves a visit and a lost game on its path until the leaf's value is backed up, so the
                               * next selections of the same game go elsewhere; the evaluator batch holds up to n_games * K boards.
                               * Drive it with azk_begin_search_budget (n_sims completed simulations per game). */
-    int32_t reserved[5];
+    int32_t tree_reuse;    /* 0: every search starts from a fresh root (games/gomoku.py:134; parity mode, the default).
+                            * 1 / 2 (OPT-IN, changes search results): tree reuse across moves - the search that follows azk_advance starts
+                            * on the subtree under the child that was played, i.e. the reference's own MCTS.mcts (ai/mcts.py:11-60) handed
+                            * `root = chosen_child; root.parent = None` with its visits, values and priors; with Dirichlet noise the new
+                            * root's children get (double)(0.75f * prior) + 0.25 * noise of this move's row, exactly as a freshly expanded
+                            * noisy root does.  azk_begin_search(_budget) moves the subtree to the front of the game's arena (k_reroot).
+                            *   1 carry : the full n_sims new simulations on top of the carried statistics (a deeper search per move);
+                            *   2 top-up: only max(1, n_sims - root.visit) new simulations, so the root ends at n_sims visits again;
+                            *             needs azk_begin_search_budget.
+                            * A game starts from a fresh root instead - today's behaviour, bit for bit - when the played child was never
+                            * expanded, when the game was reset, recycled or given a position since its last search, or when the ARENA RULE
+                            * refuses:  kept_nodes + n_new * widest <= nodes per game  must hold, with n_new the most simulations the search may
+                            * still run (the budget's; max_sims for azk_begin_search) and widest = min(max_children, empty cells of the root
+                            * position), a bound on the legal moves of every position below the root - the most a search can allocate, so
+                            * AZK_ERR_ARENA_FULL cannot come from a re-rooted search.  (The new root's own child count is no such bound:
+                            * Gomoku's legal moves are the cells next to a stone and grow along a line of play.)  With arena_nodes = 0 a carry engine allocates
+                            * 1 + 2 * max_sims * max_children nodes per game (TWICE the default: about 17 GB instead of 9 GB at 2 048 games
+                            * x 800 simulations of 15x15 Gomoku) and drops a subtree of more than about max_sims expansions; top-up fits
+                            * the default arena.  Not with leaves_per_step > 1 (AZK_ERR_ARG) nor azk_async_begin (AZK_ERR_STATE). */
+    int32_t reserved[4];
 } azk_config;
 
 /* device-side work counters; sums over all games since the last azk_reset_counters */
@@ -83,7 +102,9 @@ typedef struct {
     int64_t terminal_sims;    /* simulations that ended in mcts.py:25-32 */
     int64_t moves_played;
     int64_t cache_hits;       /* MCTS.matched (mcts.py:9,44): leaves served by the eval cache; leaves_evaluated counts the misses */
-    int64_t reserved[8];
+    int64_t roots_reused;     /* tree reuse: searches that began on a carried subtree (the others began on a fresh root) */
+    int64_t nodes_carried;    /* tree reuse: nodes of those subtrees */
+    int64_t reserved[6];
 } azk_counters;
 
 int32_t azk_abi_version(void);
@@ -105,7 +126,7 @@ int32_t azk_set_positions(azk_engine *e, int32_t first, int32_t count, const int
                           const int32_t *to_move_host, const int32_t *move_count_host, void *stream);
 
 /* ---- one search = Node(None, None, player, move_count) + MCTS.mcts(...) (gomoku.py:134-136) ---- */
-/* Fresh root for every game.  noise_dev: float64 [G][A] Dirichlet draws (utils.py:24) or NULL for
+/* Fresh root for every game (a tree_reuse engine: the carried subtree of every game that has one, see azk_config).  noise_dev: float64 [G][A] Dirichlet draws (utils.py:24) or NULL for
  * dirichlet=False.  The pointer is read by later steps: keep it alive until the search ends. */
 int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream);
 
@@ -209,7 +230,8 @@ int32_t azk_root_children(azk_engine *e, int32_t game, int32_t cap, int32_t *cel
 int32_t azk_export_tree(azk_engine *e, int32_t game, int32_t cap, int32_t *depth_host, int32_t *cell_host,
                         int32_t *visit_host, double *value_host, double *prior_host, void *stream);
 
-/* Move selection + state advance for all active games (gomoku.py:143-162):
+/* Move selection + state advance for all active games (gomoku.py:143-162; a tree_reuse engine also notes the played child as the
+ * next search's root - forgotten again by azk_reset_games, azk_set_positions, azk_recycle_finished and for finished games):
  *   game g samples ~ visits when move_count[g] < sample_until_move (Node.sample_child, node.py:83-93:
  *   legacy np.random.choice == searchsorted(cumsum(pi)/sum, u, 'right') with u = uniforms_dev[g]),
  *   else takes the first child with the most visits (Node.max_visit_child, node.py:76-81);

@@ -16,9 +16,6 @@ _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 LIB_PATH = os.path.join(_HERE, "libazk.so")
 
 ABI_VERSION = 4           # include/azk.h AZK_ABI_VERSION the structure layouts below were written for
-GAME_ID = {"tictactoe": 0, "connect4": 1, "gomoku": 2}
-LEAF_F32, LEAF_BF16 = 0, 1
-EMBED_POOL_COMPACT_MAX_SLOTS = 65279       # AZK_EMBED_POOL_COMPACT_MAX_SLOTS (include/azk.h)
 
 # every symbol include/azk.h declares (checked by tests/test_abi.py against the header text)
 SYMBOLS = [
@@ -43,96 +40,13 @@ class AzkError(RuntimeError):
     pass
 
 
-class Config(C.Structure):
-    _fields_ = [("game", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("n_games", C.c_int32),
-                ("max_sims", C.c_int32), ("leaf_dtype", C.c_int32), ("device", C.c_int32),
-                ("arena_nodes", C.c_int32), ("cache_entries", C.c_int32), ("cache_shared", C.c_int32), ("leaves_per_step", C.c_int32),
-                ("tree_reuse", C.c_int32), ("reserved", C.c_int32 * 4)]
-
-
-class LeafSource(C.Structure):
-    """azk_leaf_source (include/azk.h): where azk_nn_embed_pool_leaves finds the pending leaves of an engine."""
-    _fields_ = [("leaf_flag", C.c_void_p), ("leaf_cells", C.c_void_p), ("to_move", C.c_void_p), ("leaf_depth", C.c_void_p),
-                ("leaf_slot", C.c_void_p), ("n_leaf", C.c_void_p), ("n_games", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
-                ("rc", C.c_int32), ("rc_pad", C.c_int32), ("planes", C.c_int32), ("flag_bytes", C.c_int32), ("cache_stamp", C.c_void_p)]
-
-
-class EmbedPoolConsts(C.Structure):
-    """azk_embed_pool_consts (include/azk.h): the per-token tables of the compacting embedding + pooling kernel."""
-    _fields_ = [("wt_frag", C.c_void_p), ("cpos_tok", C.c_void_p), ("score_tok", C.c_void_p), ("wconst_tok", C.c_void_p),
-                ("xnconst_tok", C.c_void_p), ("z_all", C.c_void_p), ("l_all", C.c_void_p), ("score_msum", C.c_void_p),
-                ("score_ref", C.c_void_p), ("num_heads", C.c_int32), ("ksize", C.c_int32), ("kp", C.c_int32),
-                ("embed_dim", C.c_int32), ("ln_eps", C.c_float), ("work_stats", C.c_void_p)]
-
-
-class EmbedFoldConsts(C.Structure):
-    """azk_embed_fold_consts (include/azk.h): tables of the patch-pooling embedding kernel."""
-    _fields_ = [("g_frag", C.c_void_p), ("e_frag", C.c_void_p), ("u2_tok", C.c_void_p), ("score_tok", C.c_void_p),
-                ("wconst_tok", C.c_void_p), ("l_all", C.c_void_p), ("score_ref", C.c_void_p), ("inv_scales", C.c_void_p),
-                ("num_heads", C.c_int32), ("ksize", C.c_int32), ("embed_dim", C.c_int32), ("ln_eps", C.c_float),
-                ("work_stats", C.c_void_p)]
-
-
-class TailGemm(C.Structure):
-    """azk_tail_gemm (include/azk.h): one link of the cls-row tail."""
-    _fields_ = [("a_bf16", C.c_void_p), ("lda", C.c_int32), ("a_batch_stride", C.c_int32), ("w_packed", C.c_void_p),
-                ("m", C.c_int32), ("n_out", C.c_int32), ("k", C.c_int32), ("nbatch", C.c_int32), ("n_valid", C.c_void_p),
-                ("bias", C.c_void_p), ("layernorm_a", C.c_int32), ("epilogue", C.c_int32), ("ln_eps", C.c_float),
-                ("a_stats", C.c_void_p), ("a_stats_groups", C.c_int32), ("stats_out", C.c_void_p),
-                ("out_bf16", C.c_void_p), ("ldo", C.c_int32), ("resid_bf16", C.c_void_p), ("ldr", C.c_int32),
-                ("logits_out", C.c_void_p), ("values_out", C.c_void_p), ("action_dim", C.c_int32), ("a_col_sums", C.c_void_p)]
-
-
-class GemmTok(C.Structure):
-    """azk_gemm_tok (include/azk.h): the LDS-staged GEMM of the full-token transformer block."""
-    _fields_ = [("a_bf16", C.c_void_p), ("lda", C.c_int32), ("w_packed", C.c_void_p), ("m", C.c_int32), ("n_out", C.c_int32), ("k", C.c_int32),
-                ("n_valid", C.c_void_p), ("bias", C.c_void_p), ("epilogue", C.c_int32), ("out", C.c_void_p), ("ldo", C.c_int32),
-                ("resid_bf16", C.c_void_p), ("ldr", C.c_int32)]
-
-
-class EmbedPoolXConsts(C.Structure):
-    """azk_embed_pool_x_consts (include/azk.h): tables of the fp32-accurate embedding + pooling kernel."""
-    _fields_ = [("wt_frag", C.c_void_p), ("cpos_tok", C.c_void_p), ("score_tok", C.c_void_p), ("wconst_tok", C.c_void_p),
-                ("xnconst_tok", C.c_void_p), ("z_all", C.c_void_p), ("l_all", C.c_void_p), ("score_msum", C.c_void_p),
-                ("score_ref", C.c_void_p), ("num_heads", C.c_int32), ("ksize", C.c_int32), ("kp", C.c_int32),
-                ("embed_dim", C.c_int32), ("ln_eps", C.c_float), ("wt_scale", C.c_float), ("work_stats", C.c_void_p),
-                ("wconst_h16_tok", C.c_void_p), ("pool_scale", C.c_float)]
-
-
-class GemmX(C.Structure):
-    """azk_gemm_x (include/azk.h): one link of the cls-row tail in float32."""
-    _fields_ = [("a_f32", C.c_void_p), ("lda", C.c_int32), ("a_batch_stride", C.c_int32), ("w_packed", C.c_void_p),
-                ("m", C.c_int32), ("n_out", C.c_int32), ("k", C.c_int32), ("nbatch", C.c_int32), ("n_valid", C.c_void_p),
-                ("bias", C.c_void_p), ("layernorm_a", C.c_int32), ("epilogue", C.c_int32), ("ln_eps", C.c_float),
-                ("a_stats", C.c_void_p), ("stats_out", C.c_void_p), ("out_f32", C.c_void_p), ("ldo", C.c_int32),
-                ("resid_f32", C.c_void_p), ("ldr", C.c_int32), ("logits_out", C.c_void_p), ("values_out", C.c_void_p),
-                ("action_dim", C.c_int32)]
-
-
-class GemmH(C.Structure):
-    """azk_gemm_h (include/azk.h): one link of the cls-row tail on fp16 (hi, lo) operand planes."""
-    _fields_ = [("a_hi", C.c_void_p), ("a_lo", C.c_void_p), ("a_f32", C.c_void_p), ("lda", C.c_int32), ("a_batch_stride", C.c_int32),
-                ("w_packed", C.c_void_p), ("m", C.c_int32), ("n_out", C.c_int32), ("k", C.c_int32), ("nbatch", C.c_int32),
-                ("n_valid", C.c_void_p), ("bias", C.c_void_p), ("col_sums", C.c_void_p), ("layernorm_a", C.c_int32), ("epilogue", C.c_int32),
-                ("ln_eps", C.c_float), ("a_scale", C.c_float), ("w_scale", C.c_float), ("a_stats", C.c_void_p), ("stats_out", C.c_void_p),
-                ("out_hi", C.c_void_p), ("out_lo", C.c_void_p), ("out_f32", C.c_void_p), ("ldo", C.c_int32), ("resid_f32", C.c_void_p),
-                ("ldr", C.c_int32), ("logits_out", C.c_void_p), ("values_out", C.c_void_p), ("action_dim", C.c_int32), ("overflow_flag", C.c_void_p)]
-
-
-class AsyncConfig(C.Structure):
-    """azk_async_config (include/azk.h)."""
-    _fields_ = [("n_sims", C.c_int32), ("max_sims_per_launch", C.c_int32), ("sample_until_move", C.c_int32), ("dirichlet", C.c_int32),
-                ("recycle", C.c_int32), ("young_launch_us", C.c_int32), ("seed", C.c_uint64), ("first_global_game", C.c_int64), ("alpha", C.c_double),
-                ("stats_dev", C.c_void_p), ("record_capacity", C.c_int64), ("rec_meta_dev", C.c_void_p), ("rec_q_dev", C.c_void_p),
-                ("rec_pi_dev", C.c_void_p)]
-
-
-class Counters(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("sims", "edges_scanned", "trace_nodes", "edges_created",
-                                          "leaves_evaluated", "terminal_sims", "moves_played", "cache_hits", "roots_reused", "nodes_carried")] + [("reserved", C.c_int64 * 6)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_[:10]}
+from . import structs  # noqa: E402
+from .structs import (EMBED_FOLD_MAX_SLOTS, EMBED_FOLD_ROW, EMBED_POOL_COMPACT_MAX_SLOTS, GAME_ID, LEAF_BF16, LEAF_F32,  # noqa: E402,F401
+                      AsyncConfig, Config, Counters, EmbedFoldConsts, EmbedPoolConsts, EmbedPoolXConsts, GemmH, GemmTok, GemmX,
+                      LeafSource, TailGemm)
+from .packing import (GEMM_H_A_SCALE, GEMM_H_W_SCALE, pack_linear_weight, pack_linear_weight128, pack_linear_weight_h,  # noqa: E402,F401
+                      pack_linear_weight_x, packed_weight_col_sums, split_fp16)
+from .replay import DeviceReplay  # noqa: E402,F401
 
 
 def build(force=False, verbose=False):
@@ -141,7 +55,7 @@ def build(force=False, verbose=False):
     srcs.append(os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "azk.h"))
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
-    cmd = ["make", "-C", _CSRC] + (["-B"] if force else [])
+    cmd = ["make", "-C", _CSRC, "-j8"] + (["-B"] if force else [])      # one object per kernel family: they compile side by side
     r = subprocess.run(cmd, capture_output=not verbose, text=True)
     if r.returncode != 0:
         raise AzkError("building libazk.so failed:\n" + (r.stdout or "") + (r.stderr or ""))
@@ -163,87 +77,11 @@ def lib():
     # one, so torch is imported before libazk.so is mapped and the soname resolves to the copy already loaded.
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, u64, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double
-    L.azk_abi_version.restype = i32
+    L.azk_abi_version.restype = C.c_int32
     if L.azk_abi_version() != ABI_VERSION:
         raise AzkError(f"{LIB_PATH} speaks ABI version {L.azk_abi_version()}, this binding was written for {ABI_VERSION} "
                        "(include/azk.h AZK_ABI_VERSION): rebuild with __graft_entry__.build()")
-    L.azk_last_error.restype = C.c_char_p
-    L.azk_last_error.argtypes = [vp]
-    L.azk_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
-    L.azk_destroy.argtypes = [vp]
-    L.azk_destroy.restype = None
-    L.azk_geometry.argtypes = [vp] + [C.POINTER(i32)] * 5
-    L.azk_reset_games.argtypes = [vp, i32, i32, vp]
-    L.azk_set_positions.argtypes = [vp, i32, i32, vp, vp, vp, vp]
-    L.azk_begin_search.argtypes = [vp, vp, vp]
-    L.azk_step_select.argtypes = [vp, vp, vp, vp]
-    L.azk_step_expand_backup.argtypes = [vp, vp, vp, vp]
-    L.azk_step.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.azk_root_stats.argtypes = [vp, vp, vp, vp, vp]
-    L.azk_root_children.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
-    L.azk_export_tree.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
-    L.azk_advance.argtypes = [vp, vp, i32, vp, vp, vp, vp]
-    L.azk_get_positions.argtypes = [vp, vp, vp, vp, vp]
-    L.azk_get_counters.argtypes = [vp, C.POINTER(Counters), vp]
-    L.azk_reset_counters.argtypes = [vp, vp]
-    L.azk_clear_cache.argtypes = [vp, vp]
-    L.azk_emit_finished.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
-    L.azk_debug_stamps.argtypes = [vp, vp]
-    L.azk_check_device_error.argtypes = [vp, vp]
-    L.azk_gen_noise.argtypes = [vp, u64, i64, i32, f64, vp, vp, vp]
-    for name in ("azk_rules_legal_moves",):
-        getattr(L, name).argtypes = [i32, i32, i32, vp, i32, vp, vp, vp]
-    L.azk_rules_legal_mask.argtypes = [i32, i32, i32, vp, i32, vp, vp]
-    L.azk_rules_apply_move.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, vp]
-    L.azk_rules_undo_move.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp]
-    L.azk_rules_check_winner.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, vp]
-    L.azk_rules_canonical.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp]
-    L.azk_softmax_rows.argtypes = [vp, i32, i32, vp, vp]
-    L.azk_step_tree.argtypes = [vp, vp, vp, vp]
-    L.azk_vanilla_set_rng.argtypes = [vp, i32, i32, vp, vp]
-    L.azk_vanilla_get_rng.argtypes = [vp, i32, i32, vp, vp]
-    L.azk_vanilla_search.argtypes = [vp, i32, vp]
-    L.azk_step_gather.argtypes = [vp, vp, vp, vp]
-    L.azk_recycle_finished.argtypes = [vp, vp, vp]
-    L.azk_nn_patch_embed_scores.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.c_float, vp, vp]
-    L.azk_nn_embed_pool.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.c_float, vp, vp]
-    L.azk_leaf_source_of.argtypes = [vp, vp, C.POINTER(LeafSource)]
-    L.azk_nn_embed_pool_leaves.argtypes = [C.POINTER(LeafSource), vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.c_float, vp]
-    L.azk_nn_embed_pool_compact.argtypes = [vp, i32, C.POINTER(EmbedPoolConsts), vp, i32, i32, i32, i32, vp, vp, vp]
-    L.azk_nn_embed_pool_compact_leaves.argtypes = [C.POINTER(LeafSource), C.POINTER(EmbedPoolConsts), vp, vp, vp]
-    L.azk_nn_embed_fold.argtypes = [vp, i32, C.POINTER(EmbedFoldConsts), vp, i32, i32, i32, i32, vp, vp, vp]
-    L.azk_nn_embed_fold_leaves.argtypes = [C.POINTER(LeafSource), C.POINTER(EmbedFoldConsts), vp, vp, vp]
-    L.azk_nnx_embed_fold.argtypes = [vp, i32, C.POINTER(EmbedFoldConsts), vp, i32, i32, i32, i32, vp, vp, vp]
-    L.azk_nnx_embed_fold_leaves.argtypes = [C.POINTER(LeafSource), C.POINTER(EmbedFoldConsts), vp, vp, vp]
-    L.azk_begin_search_budget.argtypes = [vp, vp, i32, i32, vp]
-    L.azk_search_unfinished.argtypes = [vp, vp, vp]
-    L.azk_nn_tail_gemm.argtypes = [C.POINTER(TailGemm), vp]
-    L.azk_nn_tail_gemm_lds.argtypes = [C.POINTER(TailGemm), vp]
-    L.azk_nn_gemm_tok.argtypes = [C.POINTER(GemmTok), vp]
-    L.azk_nn_attention_tok.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-    L.azk_nnx_embed_pool.argtypes = [vp, i32, C.POINTER(EmbedPoolXConsts), vp, i32, i32, i32, i32, vp, vp, vp]
-    L.azk_nnx_embed_pool_leaves.argtypes = [C.POINTER(LeafSource), C.POINTER(EmbedPoolXConsts), vp, vp, vp]
-    L.azk_nnx_gemm.argtypes = [C.POINTER(GemmX), vp]
-    L.azk_nnx_gemm_h.argtypes = [C.POINTER(GemmH), vp]
-    L.azk_nnx_gemm_h_lds.argtypes = [C.POINTER(GemmH), vp]
-    L.azk_async_begin.argtypes = [vp, C.POINTER(AsyncConfig), vp]
-    L.azk_async_step.argtypes = [vp, vp, vp, i32, vp]
-    L.azk_async_set_budget.argtypes = [vp, i32, i32, vp]
-    L.azk_async_drain.argtypes = [vp, vp, vp, vp, i64, vp, vp]
-    L.azk_nn_ln_heads.argtypes = [vp, vp, vp, C.c_float, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    L.azk_nn_gemm_rows.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.azk_nn_layernorm_sum.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, vp, vp]
-    L.azk_nn_heads_finalize_sum.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp]
-    L.azk_nn_layernorm_rows.argtypes = [vp, vp, vp, C.c_float, vp, vp, i32, i32, vp, vp]
-    L.azk_nn_heads_finalize.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
-    L.azk_nn_cls_pool.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
-    L.azk_nn_cls_attention.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp]
-    L.azk_nn_patch_embed.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.c_float, vp]
-    for name in SYMBOLS:
-        f = getattr(L, name)
-        if name not in ("azk_last_error", "azk_destroy"):
-            f.restype = i32
+    structs.declare(L, SYMBOLS)
     _LIB = L
     return L
 
@@ -266,6 +104,11 @@ def _p(t):
 
 def _np(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _ok(rc, name):
+    if rc != 0:
+        raise AzkError(f"{name} failed ({rc})")
 
 
 class Engine:
@@ -664,8 +507,7 @@ def nn_patch_embed(boards, wt, cpos, ln_w, ln_b, rows, cols, ksize, embed_dim, w
     xh = torch.empty((n, T, embed_dim), dtype=torch.bfloat16, device=boards.device) if want_xhat else None
     rc = lib().azk_nn_patch_embed(_p(boards), 1 if boards.dtype == torch.float32 else 0, _p(wt), _p(cpos), _p(ln_w), _p(ln_b),
                                   _p(x), _p(xh), n, C, rows, cols, ksize, wt.shape[1], embed_dim, float(eps), _stream())
-    if rc != 0:
-        raise AzkError(f"azk_nn_patch_embed failed ({rc})")
+    _ok(rc, "azk_nn_patch_embed")
     return x, xh
 
 
@@ -679,8 +521,7 @@ def nn_cls_attention(xhat, m, c, num_heads):
     m = m.to(torch.float32).contiguous(); c = c.to(torch.float32).contiguous()
     z = torch.empty((n, num_heads, D), dtype=torch.bfloat16, device=xhat.device)
     rc = lib().azk_nn_cls_attention(_p(xhat), _p(m), _p(c), per_board, _p(z), n, T, D, num_heads, _stream())
-    if rc != 0:
-        raise AzkError(f"azk_nn_cls_attention failed ({rc})")
+    _ok(rc, "azk_nn_cls_attention")
     return z
 
 
@@ -707,13 +548,11 @@ def nn_embed_scores_pool(boards, wt_ext, cpos, score_cpos, score_msum, c, rows, 
     if timers is not None:
         timers[0].stop()
         timers[1].start()
-    if rc != 0:
-        raise AzkError(f"azk_nn_patch_embed_scores failed ({rc})")
+    _ok(rc, "azk_nn_patch_embed_scores")
     rc = L.azk_nn_cls_pool(_p(xh), _p(sc), _p(c), _p(z), n, T, embed_dim, num_heads, _p(count), _stream())
     if timers is not None:
         timers[1].stop()
-    if rc != 0:
-        raise AzkError(f"azk_nn_cls_pool failed ({rc})")
+    _ok(rc, "azk_nn_cls_pool")
     return z
 
 
@@ -736,8 +575,7 @@ def nn_embed_pool(boards, wt_ext, cpos_frag, score_frag, score_msum, score_ref, 
     rc = fn(*args)
     if timers is not None:
         timers[0].stop()
-    if rc != 0:
-        raise AzkError(f"azk_nn_embed_pool failed ({rc})")
+    _ok(rc, "azk_nn_embed_pool")
     return z
 
 
@@ -755,12 +593,50 @@ def nn_embed_pool_leaves(src, wt_ext, cpos_frag, score_frag, score_msum, score_r
     rc = fn(*args)
     if timers is not None:
         timers[0].stop()
-    if rc != 0:
-        raise AzkError(f"azk_nn_embed_pool_leaves failed ({rc})")
+    _ok(rc, "azk_nn_embed_pool_leaves")
     return z
 
 
-class EmbedPoolTables:
+class _Tables:
+    """Base of the three table holders: self.t (dict of device tensors, kept alive) and self.c (their ctypes descriptor)."""
+    work_stats = None
+
+    def enable_work_stats(self):
+        """Device counters [boards evaluated, 16-token tiles evaluated] (int64 [2]), bumped by every launch from now on."""
+        if self.work_stats is None:
+            self.work_stats = _torch().zeros(2, dtype=_torch().int64, device=self.t["score_tok"].device)
+            self.c.work_stats = self.work_stats.data_ptr()
+        return self.work_stats
+
+
+def _embed(symbol, dtype, width, tables, sched, timers, boards=None, rows=0, cols=0, count=None, src=None, exact=False):
+    """The call every compacting embedding kernel shares (azk_nn_embed_pool_compact, azk_nn_embed_fold, azk_nnx_embed_fold,
+    azk_nnx_embed_pool and their _leaves forms): boards [n, C, R, Cc] bf16 / f32, or an engine's pending leaves (src: LeafSource),
+    -> rows [n or slots, H, width] of `dtype`.  exact: the tables must be the float32-accurate ones."""
+    torch = _torch()
+    assert not exact or tables.exact
+    if src is None:
+        assert boards.is_cuda and boards.is_contiguous() and boards.dtype in (torch.bfloat16, torch.float32)
+        assert rows * cols + 1 == tables.tokens and sched.dtype == torch.int32 and sched.numel() >= 2
+        n, Cc = boards.shape[0], boards.shape[1]
+        out = torch.empty((n, tables.num_heads, width), dtype=getattr(torch, dtype), device=boards.device)
+        args = (_p(boards), 1 if boards.dtype == torch.float32 else 0, C.byref(tables.c), _p(out), n, Cc, rows, cols, _p(count), _p(sched), _stream())
+    else:
+        symbol += "_leaves"
+        assert src.rows * src.cols + 1 == tables.tokens and sched.dtype == torch.int32 and sched.numel() >= 2
+        out = torch.empty((src.n_games, tables.num_heads, width), dtype=getattr(torch, dtype), device=sched.device)
+        args = (C.byref(src), C.byref(tables.c), _p(out), _p(sched), _stream())
+    fn = getattr(lib(), symbol)
+    if timers is not None:          # everything is marshalled already: the events bracket the launch alone
+        timers[0].start()
+    rc = fn(*args)
+    if timers is not None:
+        timers[0].stop()
+    _ok(rc, symbol)
+    return out
+
+
+class EmbedPoolTables(_Tables):
     """The tables of azk_nn_embed_pool_compact, kept alive together with their ctypes descriptor.
     t: dict of CUDA tensors (wt_ext bf16 [D+16, kp]; cpos_tok f32 [T+1, D]; score_tok, wconst_tok f32 [T+1, 16]; xnconst_tok bf16
     [T+1, D]; z_all f32 [4, 8, 64, 4]; l_all, score_msum, score_ref f32 [16])."""
@@ -787,14 +663,6 @@ class EmbedPoolTables:
         self.c = EmbedPoolConsts(*[self.t[k].data_ptr() for k in ("wt_frag", "cpos_tok", "score_tok", "wconst_tok", "xnconst_tok", "z_all",
                                                                  "l_all", "score_msum", "score_ref")],
                                  num_heads, ksize, self.t["wt_ext"].shape[1], embed_dim, float(eps), None)
-        self.work_stats = None
-
-    def enable_work_stats(self):
-        """Device counters [boards evaluated, 16-token tiles evaluated] (int64 [2]), bumped by every launch from now on."""
-        if self.work_stats is None:
-            self.work_stats = _torch().zeros(2, dtype=_torch().int64, device=self.t["cpos_tok"].device)
-            self.c.work_stats = self.work_stats.data_ptr()
-        return self.work_stats
 
 
 def new_sched(device):
@@ -804,45 +672,15 @@ def new_sched(device):
 
 def nn_embed_pool_compact(boards, tables, rows, cols, sched, count=None, timers=None):
     """azk_nn_embed_pool_compact: boards [n, C, R, Cc] bf16 / f32 -> z bf16 [n, H, D], evaluating only the tokens a stone can reach."""
-    torch = _torch()
-    assert boards.is_cuda and boards.is_contiguous() and boards.dtype in (torch.bfloat16, torch.float32)
-    assert rows * cols + 1 == tables.tokens and sched.dtype == torch.int32 and sched.numel() >= 2
-    n, Cc = boards.shape[0], boards.shape[1]
-    z = torch.empty((n, tables.num_heads, tables.embed_dim), dtype=torch.bfloat16, device=boards.device)
-    fn = lib().azk_nn_embed_pool_compact
-    args = (_p(boards), 1 if boards.dtype == torch.float32 else 0, C.byref(tables.c), _p(z), n, Cc, rows, cols, _p(count), _p(sched), _stream())
-    if timers is not None:
-        timers[0].start()
-    rc = fn(*args)
-    if timers is not None:
-        timers[0].stop()
-    if rc != 0:
-        raise AzkError(f"azk_nn_embed_pool_compact failed ({rc})")
-    return z
+    return _embed("azk_nn_embed_pool_compact", "bfloat16", tables.embed_dim, tables, sched, timers, boards, rows, cols, count)
 
 
 def nn_embed_pool_compact_leaves(src, tables, sched, timers=None):
     """azk_nn_embed_pool_compact over an engine's pending leaves (LeafSource): z bf16 [G, H, D], rows [0, n_leaf) valid."""
-    torch = _torch()
-    assert src.rows * src.cols + 1 == tables.tokens and sched.dtype == torch.int32 and sched.numel() >= 2
-    z = torch.empty((src.n_games, tables.num_heads, tables.embed_dim), dtype=torch.bfloat16, device=sched.device)
-    fn = lib().azk_nn_embed_pool_compact_leaves
-    args = (C.byref(src), C.byref(tables.c), _p(z), _p(sched), _stream())
-    if timers is not None:
-        timers[0].start()
-    rc = fn(*args)
-    if timers is not None:
-        timers[0].stop()
-    if rc != 0:
-        raise AzkError(f"azk_nn_embed_pool_compact_leaves failed ({rc})")
-    return z
+    return _embed("azk_nn_embed_pool_compact", "bfloat16", tables.embed_dim, tables, sched, timers, src=src)
 
 
-EMBED_FOLD_ROW = 384        # include/azk.h AZK_EMBED_FOLD_ROW
-EMBED_FOLD_MAX_SLOTS = 8192 # include/azk.h AZK_EMBED_FOLD_MAX_SLOTS: pending-leaf slots azk_nn_embed_fold_leaves ranks in LDS
-
-
-class EmbedFoldTables:
+class EmbedFoldTables(_Tables):
     """Tables of azk_nn_embed_fold and the weight of the batched GEMM that follows it, from PolicyValueNet.fold_u's float64 operands
     (r: G [64, 64], ext [64, 16], U2 [T, 64], nt [T], sct [T, H], Dtab [T, 512], M [512, 64], rstdc [T], ref [H], wc [T, H], uall [512],
     lall [H]); kept alive with the ctypes descriptor.  `weight`: H blocks of [64][EMBED_FOLD_ROW] in azk_nn_tail_gemm's packing."""
@@ -910,81 +748,26 @@ class EmbedFoldTables:
         self.tokens, self.num_heads, self.embed_dim = T, H, D
         self.c = EmbedFoldConsts(*[t[k].data_ptr() for k in ("g_frag", "e_frag", "u2_tok", "score_tok", "wconst_tok", "l_all", "score_ref",
                                                              "inv_scales")], H, ksize, D, float(eps), None)
-        self.work_stats = None
-
-    def enable_work_stats(self):
-        if self.work_stats is None:
-            self.work_stats = _torch().zeros(2, dtype=_torch().int64, device=self.t["u2_tok"].device)
-            self.c.work_stats = self.work_stats.data_ptr()
-        return self.work_stats
 
 
 def nn_embed_fold(boards, tables, rows, cols, sched, count=None, timers=None):
     """azk_nn_embed_fold: boards [n, C, R, Cc] bf16 / f32 -> bf16 [n, H, EMBED_FOLD_ROW] (token weights / L, 1 / L, pooled patch / L)."""
-    torch = _torch()
-    assert boards.is_cuda and boards.is_contiguous() and boards.dtype in (torch.bfloat16, torch.float32)
-    assert rows * cols + 1 == tables.tokens and sched.dtype == torch.int32 and sched.numel() >= 2
-    n, Cc = boards.shape[0], boards.shape[1]
-    out = torch.empty((n, tables.num_heads, EMBED_FOLD_ROW), dtype=torch.bfloat16, device=boards.device)
-    args = (_p(boards), 1 if boards.dtype == torch.float32 else 0, C.byref(tables.c), _p(out), n, Cc, rows, cols, _p(count), _p(sched), _stream())
-    if timers is not None:
-        timers[0].start()
-    rc = lib().azk_nn_embed_fold(*args)
-    if timers is not None:
-        timers[0].stop()
-    if rc != 0:
-        raise AzkError(f"azk_nn_embed_fold failed ({rc})")
-    return out
+    return _embed("azk_nn_embed_fold", "bfloat16", EMBED_FOLD_ROW, tables, sched, timers, boards, rows, cols, count)
 
 
 def nn_embed_fold_leaves(src, tables, sched, timers=None):
     """azk_nn_embed_fold over an engine's pending leaves (LeafSource): bf16 [G, H, EMBED_FOLD_ROW], rows [0, n_leaf) valid."""
-    torch = _torch()
-    assert src.rows * src.cols + 1 == tables.tokens and sched.dtype == torch.int32 and sched.numel() >= 2
-    out = torch.empty((src.n_games, tables.num_heads, EMBED_FOLD_ROW), dtype=torch.bfloat16, device=sched.device)
-    args = (C.byref(src), C.byref(tables.c), _p(out), _p(sched), _stream())
-    if timers is not None:
-        timers[0].start()
-    rc = lib().azk_nn_embed_fold_leaves(*args)
-    if timers is not None:
-        timers[0].stop()
-    if rc != 0:
-        raise AzkError(f"azk_nn_embed_fold_leaves failed ({rc})")
-    return out
+    return _embed("azk_nn_embed_fold", "bfloat16", EMBED_FOLD_ROW, tables, sched, timers, src=src)
 
 
 def nnx_embed_fold(boards, tables, rows, cols, sched, count=None, timers=None):
     """azk_nnx_embed_fold: boards [n, C, R, Cc] bf16 / f32 -> float32 [n, H, EMBED_FOLD_ROW] (token weights / L, 1 / L, pooled patch / L)."""
-    torch = _torch()
-    assert tables.exact and boards.is_cuda and boards.is_contiguous() and boards.dtype in (torch.bfloat16, torch.float32)
-    assert rows * cols + 1 == tables.tokens and sched.dtype == torch.int32 and sched.numel() >= 2
-    n, Cc = boards.shape[0], boards.shape[1]
-    out = torch.empty((n, tables.num_heads, EMBED_FOLD_ROW), dtype=torch.float32, device=boards.device)
-    args = (_p(boards), 1 if boards.dtype == torch.float32 else 0, C.byref(tables.c), _p(out), n, Cc, rows, cols, _p(count), _p(sched), _stream())
-    if timers is not None:
-        timers[0].start()
-    rc = lib().azk_nnx_embed_fold(*args)
-    if timers is not None:
-        timers[0].stop()
-    if rc != 0:
-        raise AzkError(f"azk_nnx_embed_fold failed ({rc})")
-    return out
+    return _embed("azk_nnx_embed_fold", "float32", EMBED_FOLD_ROW, tables, sched, timers, boards, rows, cols, count, exact=True)
 
 
 def nnx_embed_fold_leaves(src, tables, sched, timers=None):
     """azk_nnx_embed_fold over an engine's pending leaves (LeafSource): float32 [G, H, EMBED_FOLD_ROW], rows [0, n_leaf) valid."""
-    torch = _torch()
-    assert tables.exact and src.rows * src.cols + 1 == tables.tokens and sched.dtype == torch.int32 and sched.numel() >= 2
-    out = torch.empty((src.n_games, tables.num_heads, EMBED_FOLD_ROW), dtype=torch.float32, device=sched.device)
-    args = (C.byref(src), C.byref(tables.c), _p(out), _p(sched), _stream())
-    if timers is not None:
-        timers[0].start()
-    rc = lib().azk_nnx_embed_fold_leaves(*args)
-    if timers is not None:
-        timers[0].stop()
-    if rc != 0:
-        raise AzkError(f"azk_nnx_embed_fold_leaves failed ({rc})")
-    return out
+    return _embed("azk_nnx_embed_fold", "float32", EMBED_FOLD_ROW, tables, sched, timers, src=src, exact=True)
 
 
 TAIL_BF16, TAIL_GELU, TAIL_RESID, TAIL_HEADS = 0, 1, 2, 3
@@ -1028,16 +811,6 @@ def nn_tail_gemm(a, w_packed, n_out, k, epilogue=TAIL_BF16, nbatch=1, a_batch_st
 TOK_BF16, TOK_GELU, TOK_RESID, TOK_F32 = 0, 1, 2, 4
 
 
-def pack_linear_weight128(w):
-    """pack_linear_weight with the output dimension padded (zero rows) to a multiple of 128: the operand of nn_gemm_tok."""
-    torch = _torch()
-    n_out, k = w.shape
-    npad = (n_out + 127) // 128 * 128
-    wp = torch.zeros(npad, k, dtype=torch.float32, device=w.device)
-    wp[:n_out] = w.float()
-    return pack_linear_weight(wp)
-
-
 def nn_gemm_tok(a, w_packed, n_out, epilogue=TOK_BF16, bias=None, out=None, resid=None, count=None):
     """out[m][n_out] = a[m][k] W^T (+ bias) through an epilogue (azk_nn_gemm_tok, csrc/azk_block.hip).  a: bf16 [m, k] (row stride
     a.stride(0)); w_packed: pack_linear_weight128(W); n_out: the padded output width (a multiple of 128); out: bf16 (float32 for
@@ -1059,8 +832,7 @@ def nn_gemm_tok(a, w_packed, n_out, epilogue=TOK_BF16, bias=None, out=None, resi
         assert resid.dtype == torch.bfloat16 and resid.stride(1) == 1
         d.resid_bf16, d.ldr = resid.data_ptr(), resid.stride(0)
     rc = lib().azk_nn_gemm_tok(C.byref(d), _stream())
-    if rc != 0:
-        raise AzkError(f"azk_nn_gemm_tok failed ({rc})")
+    _ok(rc, "azk_nn_gemm_tok")
     return out
 
 
@@ -1072,101 +844,8 @@ def nn_attention_tok(qkv, n_boards, tokens, embed_dim, num_heads, out=None, coun
         out = torch.empty((n_boards * tokens, embed_dim), dtype=torch.bfloat16, device=qkv.device)
     assert out.is_contiguous() and out.dtype == torch.bfloat16
     rc = lib().azk_nn_attention_tok(_p(qkv), _p(out), int(n_boards), int(tokens), int(embed_dim), int(num_heads), _p(count), _stream())
-    if rc != 0:
-        raise AzkError(f"azk_nn_attention_tok failed ({rc})")
+    _ok(rc, "azk_nn_attention_tok")
     return out
-
-
-def packed_weight_col_sums(w_packed, n_out, k):
-    """Column sums sum_k W[j][k] of a pack_linear_weight() tensor's bf16 values (float64 sum, rounded once): the
-    a_col_sums operand of azk_nn_tail_gemm_lds (LayerNorm applied in the epilogue)."""
-    torch = _torch()
-    npad = (n_out + 63) // 64 * 64
-    # [g, s, c, l4, l15, i] -> [g, l15, c, s, l4, i]: column 64 g + 4 l15 + c, k = 32 s + 8 l4 + i
-    w = w_packed.view(npad // 64, k // 32, 4, 4, 16, 8).permute(0, 4, 2, 1, 3, 5).reshape(npad, k)
-    return w.double().sum(1).float().contiguous()
-
-
-class _ReplayUnpickler(__import__("pickle").Unpickler):
-    """pickle.Unpickler limited to the globals of replay_buffer.py's file format (replay_buffer.py:37-65)."""
-    _ALLOWED = {("collections", "deque"), ("numpy", "ndarray"), ("numpy", "dtype"),
-                ("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
-                ("numpy.core.multiarray", "scalar"), ("numpy._core.multiarray", "scalar"),
-                ("numpy.core.numeric", "_frombuffer"), ("numpy._core.numeric", "_frombuffer")}
-
-    def find_class(self, module, name):
-        if (module, name) in self._ALLOWED:
-            return super().find_class(module, name)
-        import pickle
-        raise pickle.UnpicklingError(f"replay file refers to {module}.{name}: not part of the replay format, refused")
-
-
-class DeviceReplay:
-    """HBM-resident ring of (state, pi, z) tuples: the device form of replay_buffer.ReplayBuffer (deque(maxlen),
-    replay_buffer.py:7-13).  Filled by Engine.emit_finished; `sample` draws uniformly without replacement
-    (replay_buffer.py:15-25) and returns float32 CUDA tensors ready for the training step."""
-
-    def __init__(self, capacity, planes, rows, cols, action_dim, device=0):
-        torch = _torch()
-        self.torch, self.capacity = torch, int(capacity)
-        dev = torch.device("cuda", device) if isinstance(device, int) else device
-        self.states = torch.zeros((capacity, planes, rows, cols), dtype=torch.float32, device=dev)
-        self.pis = torch.zeros((capacity, action_dim), dtype=torch.float64, device=dev)
-        self.zs = torch.zeros(capacity, dtype=torch.float32, device=dev)
-        self.cursor = torch.zeros(1, dtype=torch.int64, device=dev)
-
-    def size(self):
-        return min(int(self.cursor.item()), self.capacity)
-
-    def sample(self, batch_size):
-        n = self.size()
-        if batch_size > n:          # np.random.choice(len, batch_size, replace=False) raises the same way (replay_buffer.py:16)
-            raise ValueError(f"cannot sample {batch_size} tuples without replacement from a ring holding {n}")
-        idx = self.torch.randperm(n, device=self.states.device)[:batch_size]
-        return self.states[idx], self.pis[idx].float(), self.zs[idx][:, None]
-
-    # ---- interchange with the reference's host-side ReplayBuffer (replay_buffer.py) ------------------------------
-    def add(self, state, policy_distribution, reward):
-        """ReplayBuffer.add (replay_buffer.py:12): append one tuple from the host (reward: float or [float])."""
-        torch = self.torch
-        i = int(self.cursor.item()) % self.capacity
-        self.states[i] = torch.as_tensor(np.asarray(state, np.float32))
-        self.pis[i] = torch.as_tensor(np.asarray(policy_distribution, np.float64))
-        self.zs[i] = float(np.asarray(reward, np.float32).reshape(-1)[0])
-        self.cursor += 1
-
-    def to_reference_deque(self):
-        """The ring as the reference keeps it: deque(maxlen=capacity) of (state float32 [F,R,C], pi float64 [A], [z]) tuples,
-        oldest first (train.save_data_to_buffer's element format, train.py:30-49)."""
-        from collections import deque
-        n, cur = self.size(), int(self.cursor.item())
-        order = [(cur - n + j) % self.capacity for j in range(n)]
-        s, p, z = self.states.cpu().numpy(), self.pis.cpu().numpy(), self.zs.cpu().numpy()
-        return deque(((s[i].copy(), p[i].copy(), [float(z[i])]) for i in order), maxlen=self.capacity)
-
-    def save_pickle(self, filename):
-        """ReplayBuffer.save_pickle's file format (replay_buffer.py:37-54): pickle.dump of the deque."""
-        import os, pickle
-        folder = os.path.dirname(filename)
-        if folder:
-            os.makedirs(folder, exist_ok=True)
-        with open(filename, "wb") as fh:
-            pickle.dump(self.to_reference_deque(), fh)
-
-    def load_pickle(self, filename):
-        """Refill the ring from a file in that format (one this class or the reference's ReplayBuffer wrote).  The file is
-        read by a restricted unpickler that can only build what the format holds - a deque of (ndarray, ndarray, list of
-        float) - and refuses every other global, so a crafted file cannot run code."""
-        with open(filename, "rb") as fh:
-            items = list(_ReplayUnpickler(fh).load())[-self.capacity:]
-        self.cursor.zero_()
-        if items:
-            torch = self.torch
-            n = len(items)
-            self.states[:n] = torch.as_tensor(np.stack([np.asarray(t[0], np.float32) for t in items]))
-            self.pis[:n] = torch.as_tensor(np.stack([np.asarray(t[1], np.float64) for t in items]))
-            self.zs[:n] = torch.as_tensor(np.array([float(np.asarray(t[2], np.float32).reshape(-1)[0]) for t in items], np.float32))
-            self.cursor += n
 
 
 def nn_heads_finalize(heads, action_dim, logits_out, values_out, count=None):
@@ -1175,8 +854,7 @@ def nn_heads_finalize(heads, action_dim, logits_out, values_out, count=None):
     assert heads.dtype == torch.bfloat16 and heads.is_contiguous() and logits_out.dtype == torch.float32 and values_out.dtype == torch.float32
     rc = lib().azk_nn_heads_finalize(_p(heads), heads.shape[1], int(action_dim), heads.shape[0], _p(logits_out), _p(values_out),
                                      _p(count), _stream())
-    if rc != 0:
-        raise AzkError(f"azk_nn_heads_finalize failed ({rc})")
+    _ok(rc, "azk_nn_heads_finalize")
 
 
 def nn_layernorm_rows(x, w, b, eps=1e-5, add_bias=None, count=None):
@@ -1185,8 +863,7 @@ def nn_layernorm_rows(x, w, b, eps=1e-5, add_bias=None, count=None):
     assert x.dtype == torch.bfloat16 and x.is_contiguous() and w.dtype == torch.float32 and b.dtype == torch.float32
     y = torch.empty_like(x)
     rc = lib().azk_nn_layernorm_rows(_p(x), _p(w), _p(b), float(eps), _p(y), _p(add_bias), x.shape[0], x.shape[1], _p(count), _stream())
-    if rc != 0:
-        raise AzkError(f"azk_nn_layernorm_rows failed ({rc})")
+    _ok(rc, "azk_nn_layernorm_rows")
     return y
 
 
@@ -1206,19 +883,6 @@ def mt_state_to_numpy(words, template=None):
     return ("MT19937", np.asarray(words[:624], np.uint32), int(words[624]), t[3], t[4])
 
 
-def pack_linear_weight(w):
-    """nn.Linear weight [n_out, k] (any float dtype, any device) -> bf16 tensor in azk_nn_gemm_rows' fragment order
-    (n_out padded with zero rows to a multiple of 64; k must be a multiple of 32)."""
-    torch = _torch()
-    n_out, k = w.shape
-    assert k % 32 == 0
-    npad = (n_out + 63) // 64 * 64
-    wp = torch.zeros(npad, k, dtype=torch.float32, device=w.device)
-    wp[:n_out] = w.float()
-    # [g, l15, c, s, l4, i] -> [g, s, c, l4, l15, i]
-    return wp.view(npad // 64, 16, 4, k // 32, 4, 8).permute(0, 3, 2, 4, 1, 5).contiguous().to(torch.bfloat16)
-
-
 def nn_gemm_rows(a, w_packed, n_out, ksplit=1, partials=None, bias=None, gelu_out=None, count=None):
     """a bf16 [m, k] (row stride = a.stride(0)) times a packed weight: float32 partial planes [ksplit, m, n_out] or
     bf16 GELU(a W^T + bias)."""
@@ -1227,24 +891,21 @@ def nn_gemm_rows(a, w_packed, n_out, ksplit=1, partials=None, bias=None, gelu_ou
     m, k = a.shape
     rc = lib().azk_nn_gemm_rows(_p(a), a.stride(0), _p(w_packed), m, int(n_out), k, int(ksplit), _p(partials), _p(bias), _p(gelu_out),
                                 _p(count), _stream())
-    if rc != 0:
-        raise AzkError(f"azk_nn_gemm_rows failed ({rc})")
+    _ok(rc, "azk_nn_gemm_rows")
 
 
 def nn_layernorm_sum(partials, w, b, y, bias=None, resid=None, add_bias=None, x_out=None, eps=1e-5, count=None):
     nsplit, m, d = partials.shape
     rc = lib().azk_nn_layernorm_sum(_p(partials), nsplit, m, _p(bias), _p(resid), _p(w), _p(b), float(eps), _p(y), _p(add_bias), _p(x_out),
                                     y.shape[0], d, _p(count), _stream())
-    if rc != 0:
-        raise AzkError(f"azk_nn_layernorm_sum failed ({rc})")
+    _ok(rc, "azk_nn_layernorm_sum")
 
 
 def nn_heads_finalize_sum(partials, bias, action_dim, logits_out, values_out, count=None):
     nsplit, m, ld = partials.shape
     rc = lib().azk_nn_heads_finalize_sum(_p(partials), nsplit, m, ld, _p(bias), int(action_dim), logits_out.shape[0], _p(logits_out),
                                          _p(values_out), _p(count), _stream())
-    if rc != 0:
-        raise AzkError(f"azk_nn_heads_finalize_sum failed ({rc})")
+    _ok(rc, "azk_nn_heads_finalize_sum")
 
 
 def nn_ln_heads(x, ln_w, ln_b, w_packed, bias, action_dim, logits_out, values_out, eps=1e-5, count=None):
@@ -1254,21 +915,11 @@ def nn_ln_heads(x, ln_w, ln_b, w_packed, bias, action_dim, logits_out, values_ou
     n, d = x.shape
     rc = lib().azk_nn_ln_heads(_p(x), _p(ln_w), _p(ln_b), float(eps), _p(w_packed), _p(bias), n, d, bias.numel(), int(action_dim),
                                _p(logits_out), _p(values_out), _p(count), _stream())
-    if rc != 0:
-        raise AzkError(f"azk_nn_ln_heads failed ({rc})")
+    _ok(rc, "azk_nn_ln_heads")
 
 
 # ---- fp32-accurate network path (csrc/azk_nnx.hip) ----------------------------------------------------------------------
-def split_fp16(x64, scale):
-    """float64 tensor -> (hi, lo) fp16 tensors with (hi + lo) / scale = x to 22 significant bits (two round-to-nearest steps)."""
-    torch = _torch()
-    xs = x64.double() * float(scale)
-    hi = xs.to(torch.float16)
-    lo = (xs - hi.double()).to(torch.float16)
-    return hi, lo
-
-
-class EmbedPoolXTables:
+class EmbedPoolXTables(_Tables):
     """Tables of azk_nnx_embed_pool, kept alive with their ctypes descriptor.  t: dict of CUDA tensors - wt_ext float64 [D+16, kp] (conv
     weight, folded score rows, mean row); cpos_tok, xnconst_tok f32 [T+1, D]; score_tok, wconst_tok f32 [T+1, 16]; z_all f32 [16, D]
     (head-major, converted to accumulator order here); l_all, score_msum, score_ref f32 [16]."""
@@ -1317,59 +968,16 @@ class EmbedPoolXTables:
                                                                   "l_all", "score_msum", "score_ref")],
                                   num_heads, ksize, kp, embed_dim, float(eps), float(self.WT_SCALE), None,
                                   self.t["wconst_h16"].data_ptr(), float(self.pool_scale))
-        self.work_stats = None
-
-    def enable_work_stats(self):
-        if self.work_stats is None:
-            self.work_stats = _torch().zeros(2, dtype=_torch().int64, device=self.t["cpos_tok"].device)
-            self.c.work_stats = self.work_stats.data_ptr()
-        return self.work_stats
 
 
 def nnx_embed_pool(boards, tables, rows, cols, sched, count=None, timers=None):
     """azk_nnx_embed_pool: boards [n, C, R, Cc] bf16 / f32 (values 0 / 1) -> z float32 [n, H, 512]."""
-    torch = _torch()
-    assert boards.is_cuda and boards.is_contiguous() and boards.dtype in (torch.bfloat16, torch.float32)
-    assert rows * cols + 1 == tables.tokens and sched.dtype == torch.int32 and sched.numel() >= 2
-    n, Cc = boards.shape[0], boards.shape[1]
-    z = torch.empty((n, tables.num_heads, tables.embed_dim), dtype=torch.float32, device=boards.device)
-    args = (_p(boards), 1 if boards.dtype == torch.float32 else 0, C.byref(tables.c), _p(z), n, Cc, rows, cols, _p(count), _p(sched), _stream())
-    if timers is not None:
-        timers[0].start()
-    rc = lib().azk_nnx_embed_pool(*args)
-    if timers is not None:
-        timers[0].stop()
-    if rc != 0:
-        raise AzkError(f"azk_nnx_embed_pool failed ({rc})")
-    return z
+    return _embed("azk_nnx_embed_pool", "float32", tables.embed_dim, tables, sched, timers, boards, rows, cols, count)
 
 
 def nnx_embed_pool_leaves(src, tables, sched, timers=None):
     """azk_nnx_embed_pool over an engine's pending leaves (LeafSource): z float32 [slots, H, 512], rows [0, n_leaf) valid."""
-    torch = _torch()
-    assert src.rows * src.cols + 1 == tables.tokens and sched.dtype == torch.int32 and sched.numel() >= 2
-    z = torch.empty((src.n_games, tables.num_heads, tables.embed_dim), dtype=torch.float32, device=sched.device)
-    args = (C.byref(src), C.byref(tables.c), _p(z), _p(sched), _stream())
-    if timers is not None:
-        timers[0].start()
-    rc = lib().azk_nnx_embed_pool_leaves(*args)
-    if timers is not None:
-        timers[0].stop()
-    if rc != 0:
-        raise AzkError(f"azk_nnx_embed_pool_leaves failed ({rc})")
-    return z
-
-
-def pack_linear_weight_x(w):
-    """nn.Linear weight [n_out, k] -> float32 tensor in azk_nnx_gemm's fragment order (n_out padded with zero rows to a multiple of 64)."""
-    torch = _torch()
-    n_out, k = w.shape
-    assert k % 16 == 0
-    npad = (n_out + 63) // 64 * 64
-    wp = torch.zeros(npad, k, dtype=torch.float32, device=w.device)
-    wp[:n_out] = w.float()
-    # [g, l15, c, s, l4, i] -> [g, s, c, l4, l15, i]
-    return wp.view(npad // 64, 16, 4, k // 16, 4, 4).permute(0, 3, 2, 4, 1, 5).contiguous()
+    return _embed("azk_nnx_embed_pool", "float32", tables.embed_dim, tables, sched, timers, src=src)
 
 
 def nnx_gemm(a, w_packed, n_out, k, epilogue=TAIL_BF16, nbatch=1, a_batch_stride=0, bias=None, out=None, resid=None,
@@ -1395,29 +1003,7 @@ def nnx_gemm(a, w_packed, n_out, k, epilogue=TAIL_BF16, nbatch=1, a_batch_stride
     if logits is not None:
         d.logits_out, d.values_out, d.action_dim = logits.data_ptr(), values.data_ptr(), int(action_dim)
     rc = lib().azk_nnx_gemm(C.byref(d), _stream())
-    if rc != 0:
-        raise AzkError(f"azk_nnx_gemm failed ({rc})")
-
-
-GEMM_H_A_SCALE, GEMM_H_W_SCALE = 16.0, 256.0      # activations x 16, weights x 256 before the fp16 (hi, lo) split (azk_nnx_gemm_h)
-
-
-def pack_linear_weight_h(w):
-    """nn.Linear weight [n_out, k] (float64 / float32) -> (fp16 planes in azk_nnx_gemm_h's fragment order
-    [n_out/64][k/32][4][2][64][8], float32 col_sums [n_out padded] = sum_k of the RECONSTRUCTED weights)."""
-    torch = _torch()
-    n_out, k = w.shape
-    assert k % 32 == 0
-    npad = (n_out + 63) // 64 * 64
-    wp = torch.zeros(npad, k, dtype=torch.float64, device=w.device)
-    wp[:n_out] = w.double()
-    assert float(wp.abs().max()) * GEMM_H_W_SCALE < 60000.0
-    hi, lo = split_fp16(wp, GEMM_H_W_SCALE)
-    # [g, l15, c, s, l4, i] -> [g, s, c, plane, l4, l15, i]
-    f = lambda t: t.view(npad // 64, 16, 4, k // 32, 4, 8).permute(0, 3, 2, 4, 1, 5)
-    packed = torch.stack([f(hi), f(lo)], dim=3).contiguous()
-    csum = ((hi.double() + lo.double()) / GEMM_H_W_SCALE).sum(1).float().contiguous()
-    return packed, csum
+    _ok(rc, "azk_nnx_gemm")
 
 
 def nnx_gemm_h(a, w_packed, n_out, k, epilogue=TAIL_BF16, nbatch=1, a_batch_stride=0, bias=None, col_sums=None, out=None, out_f32=None,

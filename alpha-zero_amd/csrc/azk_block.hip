@@ -1,5 +1,5 @@
 // azk_block.hip - the FULL-TOKEN transformer block of the policy-value network (ai/nn.py:38-61) for networks deeper than one block:
-// every block but the last runs over all T = R C + 1 tokens of every board (the last block only feeds the cls row: azk_nn.hip).
+// every block but the last runs over all T = R C + 1 tokens of every board (the last block only feeds the cls row: azk_embed_tok.hip k_cls_attn).
 //   x -> LayerNorm1 (azk_nn_layernorm_rows) -> QKV = LN1(x) Wi^T + bi (azk_nn_gemm_tok) -> softmax(Q K^T / sqrt(dh)) V per board and
 //   head (azk_nn_attention_tok) -> x += O Wo^T + bo (gemm, residual epilogue) -> LayerNorm2 -> GELU(. W0^T + b0) (gemm, GELU epilogue)
 //   -> x += . W3^T + b3 (gemm, residual epilogue)
@@ -16,13 +16,14 @@
 
 #include "azk.h"
 #include "azk_launch.h"
+#include "azk_nn_common.h"
 #include "azk_tail_common.h"
 
 namespace {
 
+using namespace azk_nn;
 using namespace azk_tail;
 
-template <int N> __device__ __forceinline__ void wait_vmcnt_c() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 __device__ __forceinline__ void wait_vmcnt(int n) {          // (wave-uniform n: a scalar branch tree)
     switch (n) {
 #define AZK_W(N_) case N_: wait_vmcnt_c<N_>(); break;
@@ -31,13 +32,6 @@ __device__ __forceinline__ void wait_vmcnt(int n) {          // (wave-uniform n:
 #undef AZK_W
         default: wait_vmcnt_c<0>(); break;
     }
-}
-
-// one LDS-DMA piece (see azk_tail.hip glds16: inline assembly so that the compiler does not drain it in front of every ds_read)
-__device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
 struct GemmTokArgs {

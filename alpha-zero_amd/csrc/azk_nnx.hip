@@ -24,31 +24,11 @@
 
 #include "azk.h"
 #include "azk_launch.h"
+#include "azk_nn_common.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-// Sum over the 16 lanes of a DPP row (lanes sharing lane>>4), result in every lane
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
-
-// exp(x) for x <= ~80 with float32 accuracy: x log2(e) carried as hi + lo (the plain product loses |x| ulps of the argument,
-// 5e-6 relative at x = -80), v_exp_f32 on hi, first-order correction for lo.
-__device__ __forceinline__ float exp_acc(float x) {
-    const float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.92596299112661746e-8f;
-    const float hi = x * L2E_HI;
-    const float lo = __builtin_fmaf(x, L2E_HI, -hi) + x * L2E_LO;
-    const float r = __builtin_amdgcn_exp2f(hi);
-    return __builtin_fmaf(r, lo * 0.693147180559945309f, r);
-}
+using namespace azk_nn;
 
 // =====================================================================================================
 // k_embed_pool_x
@@ -837,16 +817,6 @@ struct GemmHArgs {
     float *logits, *values; int action_dim;
     int *oflow;                                  // optional sticky flag: a plane value left fp16's range
 };
-
-// nn.GELU (erf form), erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7: 3e-7 on a hidden activation, below this path's 22-bit
-// operands) - a dozen instructions; erff costs fifty, and the wide link's epilogue runs it on 32 values per lane
-__device__ __forceinline__ float gelu_as(float x) {
-    const float z = fabsf(x) * 0.70710678118654752f;
-    const float t = 1.0f / (1.0f + 0.3275911f * z);
-    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    const float erf_abs = 1.0f - poly * __expf(-z * z);
-    return 0.5f * x * (1.0f + copysignf(erf_abs, x));
-}
 
 template <int EPI, int LNA, int AIN, int NWK, int KW>      // AIN 1: float32 A, split on the fly
 __global__ __launch_bounds__(256, 1) void k_gemm_h(GemmHArgs a) {

@@ -24,13 +24,14 @@
 
 #include "azk.h"
 #include "azk_launch.h"
+#include "azk_nn_common.h"
 #include "azk_tail_common.h"
 
 namespace {
 
+using namespace azk_nn;
 using namespace azk_tail;
 
-template <int N> __device__ __forceinline__ void wait_vmcnt_c() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 // (the count is a compile-time constant after unrolling; the asm immediate wants an integer constant expression)
 __device__ __forceinline__ void wait_vmcnt(int n) {
     switch (n) {
@@ -40,16 +41,6 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
 #undef AZK_W
         default: wait_vmcnt_c<0>(); break;
     }
-}
-
-// One LDS-DMA piece: 64 lanes x 16 bytes from per-lane global addresses to 1 KiB of LDS at the wave-uniform byte address lds_dst.
-// As inline assembly on purpose: hipcc treats the builtin form as a pending LDS write and drains it with s_waitcnt vmcnt(0) in front of
-// the next ds_read - every stage of the ring would be waited for at once.  The statement saves and restores M0 (the destination base);
-// the loads are invisible to the compiler's own counters, so every wait for them below is explicit.
-__device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
 // One tiling of a link.  WM x WN x WK waves; a wave owns 16 RT rows x 64 columns (RT A fragments, four B fragments per 32-wide
@@ -69,8 +60,6 @@ struct TailTiling {
     static_assert(NS >= 2 && NS - 1 <= KT && (NS - 1) * LPS <= 24, "ring depth");
     static_assert(WK == 1 || (WK - 1) * WM * WN * NCH * RT * 4096 <= NS * SB, "the split-K partials reuse the stage ring");
 };
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
 // The main loop shared by both operand forms: stages the block's activation rows (planes A0, A1) and weight groups through the ring
 // and returns the wave's chains in accs.  row0: first row of the block; g0: its first 64-column weight group.
@@ -358,15 +347,6 @@ struct HArgs {
     const float *stats_in; float *stats_out;
     int *oflow;
 };
-
-// nn.GELU (erf form), erf by Abramowitz & Stegun 7.1.26 - k_gemm_h's expression (a true division, not the reciprocal instruction)
-__device__ __forceinline__ float gelu_as(float x) {
-    const float z = fabsf(x) * 0.70710678118654752f;
-    const float t = 1.0f / (1.0f + 0.3275911f * z);
-    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    const float erf_abs = 1.0f - poly * __expf(-z * z);
-    return 0.5f * x * (1.0f + copysignf(erf_abs, x));
-}
 
 template <class T, int LNA, int EPI, bool AZK_XCD_ROWS>
 __device__ __forceinline__ void gemm_h_lds_body(const HArgs &a, const int nvalid, char *const lds) {

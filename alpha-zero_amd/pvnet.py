@@ -13,7 +13,7 @@ Evaluation paths (all compute the SAME function: logits [n,A], value [n] in (-1,
   "cls"   the last block only produces what is consumed: K,V for all tokens, Q / out-proj / MLP for the
           cls row alone (x[:,0] is the only row the heads read, nn.py:80-83).  0.254 GFLOP/board.
   "clsfold" as "cls", with the cls query folded through Wk and the value projection applied after the
-          softmax-weighted token sum, so K and V are never formed (csrc/azk_nn.hip): 0.022 GFLOP/board,
+          softmax-weighted token sum, so K and V are never formed (csrc/azk_embed_tok.hip; later forms: azk_embed_conv.hip, azk_nn.hip): 0.022 GFLOP/board,
           one streaming pass over LayerNorm1(tokens).  GPU + bf16 only.
 Rectangular boards (Connect4 6x7) get rows*cols+1 tokens; the reference's Net is square-only
 (nn.py:26-28), so that case has no reference numerics ("parity unpinned - build-defined").
@@ -155,6 +155,10 @@ class PolicyValueNet:
         self.chain_tail = False         # set by _prepare_folded when azk_nn_tail_gemm covers this configuration
         self.use_chain_tail = True
         self.use_lds_tail = True          # the two wide links of the chain tail LDS-staged (csrc/azk_tail.hip); False: k_tail_gemm for all five
+        self.use_hip_blocks = True      # the full-token blocks (and the cls path outside the benchmark shape) on csrc/azk_block.hip when prepared
+        self.exact_tail = "f32"         # float32 network: "h16" once _prepare_exact_tables has built the fp16 (hi, lo) planes of the tail
+        self._exact_overflow = None     # sticky device flag of the fp16-plane tail (check_exact_range)
+        self._tail_timer = None         # the tail timer while a sampled step is being timed (tail_fast)
         self._tail_ws = {}              # workspaces of the tail chain, one per board source, sized for the largest batch seen
         self._tail_ws_retired = []      # outgrown workspaces, kept alive (captured graphs may hold their addresses)
         self._compact = None            # azk.EmbedPoolTables when the compacting kernel covers this configuration (static softmax reference)
@@ -452,7 +456,7 @@ class PolicyValueNet:
         """The fp32-accurate folded cls path: boards (or the engine's pending leaves) -> z float32 [n, H, D] -> logits, tanh(value)."""
         import azk
         cfg, e = self.cfg, self._exact
-        if (e.get("foldu") is not None and self.use_fold_u and getattr(self, "exact_tail", "f32") == "h16"
+        if (e.get("foldu") is not None and self.use_fold_u and self.exact_tail == "h16"
                 and (self.leaf_source is None or self.leaf_source.n_games <= azk.EMBED_FOLD_MAX_SLOTS)):
             # the token rows are never formed (k_embed_fold<EX>): float32 rows of token weights / L, 1 / L, pooled patch / L per head
             if self.leaf_source is not None:
@@ -491,7 +495,7 @@ class PolicyValueNet:
                       st1=torch.empty((rows, D // 64, 2), **f32), st2=torch.empty((rows, D // 64, 2), **f32))
             self._tail_ws[key] = ws
         pl = lambda k_: (ws[k_][0, :n], ws[k_][1, :n])
-        if getattr(self, "_exact_overflow", None) is None or self._exact_overflow.device != dev:
+        if self._exact_overflow is None or self._exact_overflow.device != dev:
             self._exact_overflow = torch.zeros(1, dtype=torch.int32, device=dev)      # sticky: an activation left the fp16 planes' range (check_exact_range)
         of = self._exact_overflow
         G = lambda *a_, **k_: azk.nnx_gemm_h(*a_, overflow=of, **k_)
@@ -501,7 +505,7 @@ class PolicyValueNet:
         else:
             self._launch(G, z.view(n, H * D), e["WvH"], D // H, D, azk.TAIL_BF16, nbatch=H, a_batch_stride=D, out=pl("u"), count=cnt)
         self._launch(G, pl("u"), e["WoH"], D, D, azk.TAIL_BF16, bias=e["bias1"], out=pl("x1"), out_f32=ws["x1f"][:n], stats_out=ws["st1"][:n], count=cnt)
-        lds = getattr(self, "use_lds_tail", True)        # the two wide links LDS-staged (azk_nnx_gemm_h_lds, csrc/azk_tail.hip): same chains, same epilogue
+        lds = self.use_lds_tail        # the two wide links LDS-staged (azk_nnx_gemm_h_lds, csrc/azk_tail.hip): same chains, same epilogue
         self._launch(G, pl("x1"), e["W0GH"], 4 * D, D, azk.TAIL_GELU, bias=e["b0G"], col_sums=e["W0GH_csum"], out=pl("hh"), a_stats=ws["st1"][:n], count=cnt, lds=lds)
         self._launch(G, pl("hh"), e["W3H"], D, 4 * D, azk.TAIL_RESID, bias=e["b3"], resid=ws["x1f"][:n], out=pl("x2"), stats_out=ws["st2"][:n], count=cnt, lds=lds)
         if self.out_buffers is not None:
@@ -516,7 +520,7 @@ class PolicyValueNet:
     def check_exact_range(self):
         """The fp32-accurate tail hands its activations from link to link as fp16 (hi, lo) planes of x * 16: |x| >= 4094 does not fit.  The
         kernels set a sticky device flag when that happens (the outputs are then meaningless); this raises if it ever did.  Synchronises."""
-        f = getattr(self, "_exact_overflow", None)
+        f = self._exact_overflow
         if f is not None and int(f.item()) != 0:
             raise FloatingPointError("fp32-accurate tail: an activation left the range of its fp16 (hi, lo) planes (|x| >= 4094): use the torch "
                                      "float32 forward (path='cls') for this network")
@@ -525,7 +529,7 @@ class PolicyValueNet:
         """The cls-row tail as five float32 launches (csrc/azk_nnx.hip k_gemm_x), each honouring the device-side live count
         (nn.py:54-60, 78-83 for the row the heads read)."""
         import azk
-        if getattr(self, "exact_tail", "f32") == "h16":
+        if self.exact_tail == "h16":
             return self.tail_exact_h(z)
         cfg, e = self.cfg, self._exact
         n, A, D, H = z.shape[0], cfg.action_dim, cfg.embed_dim, cfg.num_heads
@@ -554,7 +558,7 @@ class PolicyValueNet:
         return lb, (vb if self.out_buffers is not None else vb[:, None])
 
     def _prepare_folded(self):
-        """Operands of the folded cls-row attention of the LAST block (csrc/azk_nn.hip k_cls_attn):
+        """Operands of the folded cls-row attention of the LAST block (csrc/azk_embed_tok.hip k_cls_attn):
         scores[h][t] = xhat_t . m_h + c_h with m_h = scale * Wk_h^T q_h, c_h = scale * q_h . bk_h; head output =
         Wv_h (sum_t a[h][t] xhat_t) + bv_h.  For depth 1 the cls query is input independent (x[:,0] = cls + pos[0]),
         so m and c are constants of the weights."""
@@ -695,7 +699,7 @@ class PolicyValueNet:
         self._fold = f
 
     def _prepare_compact(self, f, hp, sc, ms, ref):
-        """Tables of azk_nn_embed_pool_compact (csrc/azk_nn.hip k_embed_pool_c): a token whose patch is empty is a constant of
+        """Tables of azk_nn_embed_pool_compact (csrc/azk_embed_conv.hip k_embed_pool_c): a token whose patch is empty is a constant of
         the weights - x_t = cpos[t] - so with the static softmax reference its weight wc_t[h] = exp(s_t[h] - ref[h]) and its
         normalised row xnc_t are precomputed, together with their sums over ALL tokens (z_all, l_all); the kernel evaluates
         only the tokens a stone can reach and swaps their constant contribution for the real one.  The statistics follow the
@@ -873,7 +877,7 @@ class PolicyValueNet:
         else:
             self._launch(azk.nn_tail_gemm, z.view(n, H * D), f["WvHP"], D // H, D, azk.TAIL_BF16, nbatch=H, a_batch_stride=D, out=ws["u"], count=cnt)
         self._launch(azk.nn_tail_gemm, ws["u"], f["WoP"], D, D, azk.TAIL_BF16, bias=f["bias1_f"], out=ws["x1"], stats_out=ws["st1"], count=cnt)
-        lds = getattr(self, "use_lds_tail", True)        # the two wide links LDS-staged (csrc/azk_tail.hip) or whole-K-in-registers (k_tail_gemm)
+        lds = self.use_lds_tail        # the two wide links LDS-staged (csrc/azk_tail.hip) or whole-K-in-registers (k_tail_gemm)
         self._launch(azk.nn_tail_gemm, ws["x1"], f["W0GP"], 4 * D, D, azk.TAIL_GELU, bias=f["b0G_f"], out=ws["hh"], a_stats=ws["st1"], count=cnt,
                      col_sums=f["W0GP_csum"] if lds else None, lds=lds)
         self._launch(azk.nn_tail_gemm, ws["hh"], f["W3P"], D, 4 * D, azk.TAIL_RESID, bias=f["b3_f"], resid=ws["x1"], out=ws["x2"], stats_out=ws["st2"], count=cnt,
@@ -893,7 +897,7 @@ class PolicyValueNet:
         kt = self.kernel_timers[-1] if self.kernel_timers is not None and len(self.kernel_timers) >= (2 if self.fused_embed_pool else 3) else None
         self._tail_timer = kt                        # the hand-written chains bracket EACH launch with its own event pair (the host-side gap
         try:                                         # between two eager launches is longer than these kernels: one pair around all five would time the host)
-            if kt is None or z.dtype == torch.float32 or (getattr(self, "chain_tail", False) and self.use_chain_tail):
+            if kt is None or self.tail_choice(z) in ("exact", "chain"):
                 return self._tail_fast(z)
             kt.start()
             out = self._tail_fast(z)
@@ -904,20 +908,28 @@ class PolicyValueNet:
 
     def _launch(self, fn, *args, **kw):
         """One tail launch, bracketed by the tail timer's own event pair when a sampled step is being timed."""
-        kt = getattr(self, "_tail_timer", None)
+        kt = self._tail_timer
         if kt is not None:
             kt.start()
         fn(*args, **kw)
         if kt is not None:
             kt.stop()
 
-    def _tail_fast(self, z):
+    def tail_choice(self, z):
+        """Which tail runs behind the pooled rows z: "exact" (float32 rows), "chain" (azk_nn_tail_gemm links), "hip" (azk_nn_gemm_rows)
+        or "library" (hipBLASLt GEMMs between the hand-written row kernels).  The first two time each of their launches themselves."""
         if z.dtype == torch.float32:
-            return self.tail_exact(z)
-        if getattr(self, "chain_tail", False) and self.use_chain_tail:
-            return self.tail_chain(z)
+            return "exact"
+        if self.chain_tail and self.use_chain_tail:
+            return "chain"
         if self.hip_tail and self.use_hip_tail:
-            return self.tail_hip(z)
+            return "hip"
+        return "library"
+
+    def _tail_fast(self, z):
+        choice = self.tail_choice(z)
+        if choice != "library":
+            return {"exact": self.tail_exact, "chain": self.tail_chain, "hip": self.tail_hip}[choice](z)
         w, cfg, f = self.w, self.cfg, self._fold
         n, A = z.shape[0], cfg.action_dim
         import azk
@@ -995,7 +1007,7 @@ class PolicyValueNet:
         return t + w["embedding.pos_embedding"]                                # nn.py:35
 
     def embed_hip(self, x, want_x, want_xhat):
-        """(tokens, LayerNorm_block0(tokens)) from the hand-written im2col + MFMA kernel (csrc/azk_nn.hip)."""
+        """(tokens, LayerNorm_block0(tokens)) from the hand-written im2col + MFMA kernel (csrc/azk_embed_tok.hip)."""
         import azk
         h, cfg = self._hip, self.cfg
         if x.dtype not in (torch.bfloat16, torch.float32):
@@ -1086,6 +1098,22 @@ class PolicyValueNet:
         value = torch.tanh(F.linear(x0, self.w["value_head.weight"], self.w["value_head.bias"]))   # nn.py:82-83
         return logits.float(), value.float()
 
+    def embed_choice(self):
+        """Which embedding kernel a depth-1 'clsfold' forward (4 or 8 heads) runs: "fold" (k_embed_fold), "compact" (k_embed_pool_c),
+        "fused-leaves" / "fused" (k_embed_pool from the engine's pending leaves / from a board batch) or "two-kernel" (k_embed with
+        the score columns + k_cls_pool).  The first that applies, in this order."""
+        import azk
+        src = self.leaf_source
+        if (self._foldu is not None and self.use_fold_u and self.chain_tail and self.use_chain_tail
+                and (src is None or src.n_games <= azk.EMBED_FOLD_MAX_SLOTS)):
+            return "fold"
+        compact_ok = src is None or src.n_games <= azk.EMBED_POOL_COMPACT_MAX_SLOTS
+        if self.fused_embed_pool and self._compact is not None and self.use_compact and compact_ok:
+            return "compact"
+        if self.fused_embed_pool:
+            return "fused-leaves" if src is not None else "fused"
+        return "two-kernel"
+
     @torch.no_grad()
     def forward(self, x, path=None):
         return self.forward_impl(x, path)
@@ -1107,7 +1135,7 @@ class PolicyValueNet:
             if self._fold is None:
                 raise RuntimeError("path 'clsfold' needs the HIP kernels (CUDA, bf16, supported embed_dim/heads)")
             last = depth - 1
-            if (depth == 1 and not self.chain_tail and getattr(self, "_blocks", None) is not None and getattr(self, "use_hip_blocks", True)
+            if (depth == 1 and not self.chain_tail and self._blocks is not None and self.use_hip_blocks
                     and x.is_cuda and self.leaf_source is None):
                 return self.forward_blocks_hip(x)             # depth 1 outside the benchmark shape (e.g. D = 256): no library GEMM in the tail either
             if depth == 1:
@@ -1116,43 +1144,36 @@ class PolicyValueNet:
                 if self.cfg.num_heads in (4, 8):
                     if x.dtype not in (torch.bfloat16, torch.float32):
                         x = x.float()
-                    compact_ok = self.leaf_source is None or self.leaf_source.n_games <= azk.EMBED_POOL_COMPACT_MAX_SLOTS
-                    if (self._foldu is not None and self.use_fold_u and self.chain_tail and self.use_chain_tail
-                            and (self.leaf_source is None or self.leaf_source.n_games <= azk.EMBED_FOLD_MAX_SLOTS)):
+                    src, kt = self.leaf_source, self.kernel_timers
+                    bkw = dict(count=self.live_count, timers=kt)          # the forms that read a board batch honour the live count
+                    choice = self.embed_choice()
+                    if choice == "fold":
                         # the token rows are never formed: per head the token weights, 1 / L and the pooled patch (k_embed_fold);
                         # the tail's first GEMM turns them into the value-projected row
-                        if self.leaf_source is not None:
-                            z = azk.nn_embed_fold_leaves(self.leaf_source, self._foldu, self._sched_for(self.leaf_source), timers=self.kernel_timers)
-                        else:
-                            z = azk.nn_embed_fold(x.contiguous(), self._foldu, self.cfg.rows, self.cfg.cols, self._sched_for(None),
-                                                  count=self.live_count, timers=self.kernel_timers)
-                    elif self.fused_embed_pool and self._compact is not None and self.use_compact and compact_ok:
+                        z = (azk.nn_embed_fold_leaves(src, self._foldu, self._sched_for(src), timers=kt) if src is not None else
+                             azk.nn_embed_fold(x.contiguous(), self._foldu, self.cfg.rows, self.cfg.cols, self._sched_for(None), **bkw))
+                    elif choice == "compact":
                         # only the tokens a stone can reach are evaluated (k_embed_pool_c); boards pulled from a device queue
-                        if self.leaf_source is not None:
-                            z = azk.nn_embed_pool_compact_leaves(self.leaf_source, self._compact, self._sched_for(self.leaf_source),
-                                                                 timers=self.kernel_timers)
-                        else:
-                            z = azk.nn_embed_pool_compact(x.contiguous(), self._compact, self.cfg.rows, self.cfg.cols, self._sched_for(None),
-                                                          count=self.live_count, timers=self.kernel_timers)
-                    elif self.fused_embed_pool and self.leaf_source is not None:
+                        z = (azk.nn_embed_pool_compact_leaves(src, self._compact, self._sched_for(src), timers=kt) if src is not None else
+                             azk.nn_embed_pool_compact(x.contiguous(), self._compact, self.cfg.rows, self.cfg.cols, self._sched_for(None), **bkw))
+                    elif choice == "fused-leaves":
                         # boards straight from the engine's pending leaves (no compaction launch, no evaluator batch)
-                        z = azk.nn_embed_pool_leaves(self.leaf_source, f["wt_ext"], f["cpos_frag"], f["score_frag"], f["score_msum"],
-                                                     f["score_ref"], self.cfg.patch_size, self.cfg.embed_dim, self.cfg.num_heads,
-                                                     timers=self.kernel_timers)
-                    elif self.fused_embed_pool:
+                        z = azk.nn_embed_pool_leaves(src, f["wt_ext"], f["cpos_frag"], f["score_frag"], f["score_msum"],
+                                                     f["score_ref"], self.cfg.patch_size, self.cfg.embed_dim, self.cfg.num_heads, timers=kt)
+                    elif choice == "fused":
                         # one launch: the normalised tokens never reach HBM (azk_nn_embed_pool)
                         z = azk.nn_embed_pool(x.contiguous(), f["wt_ext"], f["cpos_frag"], f["score_frag"], f["score_msum"],
                                               f["score_ref"], self.cfg.rows, self.cfg.cols, self.cfg.patch_size, self.cfg.embed_dim,
-                                              self.cfg.num_heads, count=self.live_count, timers=self.kernel_timers)
+                                              self.cfg.num_heads, **bkw)
                     else:
                         z = azk.nn_embed_scores_pool(x.contiguous(), f["wt_ext"], hp["cpos"], f["score_cpos"], f["score_msum"], f["c_n"],
                                                      self.cfg.rows, self.cfg.cols, self.cfg.patch_size, self.cfg.embed_dim,
-                                                     self.cfg.num_heads, count=self.live_count, timers=self.kernel_timers)
+                                                     self.cfg.num_heads, **bkw)
                     return self.tail_fast(z)
                 x0 = hp["cpos"][0].to(self.dtype).expand(x.shape[0], -1)
                 _, xhat = self.embed_hip(x, want_x=False, want_xhat=True)
             else:
-                if getattr(self, "_blocks", None) is not None and getattr(self, "use_hip_blocks", True) and x.is_cuda:
+                if self._blocks is not None and self.use_hip_blocks and x.is_cuda:
                     return self.forward_blocks_hip(x)
                 t = self.embed(x)
                 for i in range(last):

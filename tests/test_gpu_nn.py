@@ -1,4 +1,4 @@
-"""GPU tests of the hand-written embedding kernel (csrc/azk_nn.hip) and the bf16 evaluator paths.
+"""GPU tests of the hand-written embedding kernel (csrc/azk_embed_tok.hip; the later generations and the tail: azk_embed_conv.hip, azk_nn.hip, azk_rows.hip) and the bf16 evaluator paths.
 Numerics reference = the same op in plain PyTorch fp32 (tolerances are bf16-level and stated per test)."""
 import numpy as np
 import pytest

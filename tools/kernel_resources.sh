@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-kernel register / LDS / scratch use as the compiler reports it (device-only assembly; no GPU needed).
-#   tools/kernel_resources.sh azk_nn.hip|azk_engine.hip [name pattern]
+#   tools/kernel_resources.sh azk_nn.hip|azk_embed_conv.hip|azk_nnx.hip|...|azk_engine.hip [name pattern]      (any file of csrc/)
 cd "$(dirname "$0")/../alpha-zero_amd/csrc" || exit 1
 src=${1:-azk_nn.hip}
 extra="-fno-slp-vectorize"; [ "$src" = azk_engine.hip ] && extra="-ffp-contract=off"

@@ -122,7 +122,7 @@ class Engine:
         self.game = game
         cfg = Config()
         cfg.game = GAME_ID[game]
-        cfg.rows = cfg.cols = int(size or 0)
+        cfg.rows, cfg.cols = (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (int(size or 0), int(size or 0))   # (rows, cols) or one side
         cfg.n_games, cfg.max_sims, cfg.device, cfg.arena_nodes = int(n_games), int(max_sims), int(device), int(arena_nodes)
         cfg.cache_entries = int(cache_entries)
         cfg.cache_shared = 1 if (cache_shared and cache_entries) else 0      # one table for all games (the reference's process-global MCTS.cache)

@@ -1,5 +1,5 @@
 // azk_device.h - device-side building blocks shared by the engine and the stateless rule kernels.
-// gfx950 only: 64-lane wavefronts; one wavefront (= one 64-thread workgroup) owns one game/board.
+// gfx950 only: 64-lane wavefronts; one wavefront owns one game/board (the plain k_tree adds a second wave per game, see below).
 // Reference lines cited as file:line relative to the reference root.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,10 +26,12 @@ __device__ __forceinline__ int azk_lane() { return threadIdx.x & 63; }
 
 __device__ __forceinline__ int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// ---- single-wave workgroups: ordering without waiting -------------------------------------------
-// Every kernel built on this header runs one 64-lane wave per workgroup.  The LDS executes a wave's instructions in issue
+// ---- ordering inside one wave, without waiting ---------------------------------------------------
+// Every kernel built on this header runs one 64-lane wave per workgroup, except the plain (lock-step) k_tree: two waves per game
+// with separate roles, separate LDS regions and exactly ONE s_barrier between them (the hand-off, azk_engine.hip).  Every function
+// of this header is run by ONE wave on LDS that only that wave touches.  The LDS executes a wave's instructions in issue
 // order, so "lane A writes, lane B reads" needs no s_waitcnt between the two - only that the compiler keeps their order.
-// (__syncthreads() in a single-wave workgroup is already barrier-free, but it still drains the LDS queue: one full round trip.)
+// (__syncthreads() must not be used here: in the two-wave workgroup it is a real barrier, which the other wave never meets.)
 __device__ __forceinline__ void azk_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -224,10 +226,10 @@ struct MoveScratch {
 //   Connect4   connect4.py:44-53    per column with an empty top cell: (lowest empty row, col)
 //   Gomoku     gomoku.py:93-106     empty 8-neighbours of any stone as list(set(...)): CPython set
 //                                   iteration order; centre cell when there is no candidate.
-// All lanes must call this (it synchronises the single-wave workgroup).
+// All lanes of the calling wave must call this.
 struct AzkNoHook { __device__ __forceinline__ void operator()() const {} };
 
-// The two small games (all lanes must call; synchronises the single-wave workgroup).
+// The two small games (all lanes of the calling wave must call).
 __device__ __forceinline__ int azk_valid_moves_small(const uint8_t *b, const GameDesc &g, int16_t *moves) {
     const int lane = azk_lane();
     int n = 0;
@@ -239,7 +241,7 @@ __device__ __forceinline__ int azk_valid_moves_small(const uint8_t *b, const Gam
             if (emp) moves[n + __popcll(m & ((1ull << lane) - 1ull))] = (int16_t)i;
             n += __popcll(m);
         }
-        __syncthreads();
+        azk_wave_sync();
         return n;
     }
     int cell = -1;                                                    // Connect4
@@ -249,7 +251,7 @@ __device__ __forceinline__ int azk_valid_moves_small(const uint8_t *b, const Gam
     }
     unsigned long long m = __ballot(cell >= 0);
     if (cell >= 0) moves[__popcll(m & ((1ull << lane) - 1ull))] = (int16_t)cell;
-    __syncthreads();
+    azk_wave_sync();
     return __popcll(m);
 }
 
@@ -261,7 +263,7 @@ __device__ int azk_valid_moves_gomoku(const uint8_t *b, const GameDesc &g, int16
     const int lane = azk_lane();
     int n = 0;
     // ---- Gomoku ----
-    // The workgroup is ONE wave: LDS instructions of a wave execute in issue order, so a write followed by another lane's read
+    // ONE wave runs this on scratch of its own: LDS instructions of a wave execute in issue order, so a write followed by another lane's read
     // needs no wait between them, only a compiler-level fence (azk_wave_sync).  Every wait in this function is a data wait.
     const int R = g.rows, C = g.cols, rc = g.rc;
     const int nwords = (rc * 8 + 31) >> 5;

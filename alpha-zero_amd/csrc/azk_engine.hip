@@ -1,5 +1,5 @@
 // azk_engine.hip - batched self-play engine for MI355X (gfx950): tree + board-rule kernels and the C ABI
-// declared in include/azk.h.  One 64-lane wavefront (one 64-thread workgroup) owns one game; the tree is
+// declared in include/azk.h.  One 64-lane wavefront owns one game (the plain k_tree gives it a helper wave); the tree is
 // a structure-of-arrays arena in HBM whose child blocks are contiguous, so a PUCT scan is a coalesced read
 // of the N / W / P columns; per-wave scratch (board, path, move list, emulated CPython set) lives in LDS.
 // Built with -ffp-contract=off: every float result is the same sequence of IEEE operations the oracle runs.
@@ -95,12 +95,14 @@ struct LdsView {
     int *cnt;
     double *cdf;
     MoveScratch ms;
+    uint8_t *board1;       // two-wave k_tree: the expanding wave's board (the pending leaf's cells)
+    int *ho;               // two-wave k_tree: hand-off words, see HO_*
 };
 
 __host__ __device__ inline int up16(int x) { return (x + 15) & ~15; }
 
 __host__ __device__ inline int lds_layout(const GameDesc &g, int path_cap, int table_size, int *off) {
-    // offsets (bytes) of: board, path, moves, e, cnt, cdf, bits, pref, ord, tabA, tabB, claim
+    // offsets (bytes) of: board, path, moves, e, cnt, cdf, bits, pref, ord, tabA, tabB, claim, board1, hand-off words
     int o = 0;
     off[0] = o; o += up16(g.rc);
     off[1] = o; o += up16(path_cap * 4);
@@ -116,12 +118,14 @@ __host__ __device__ inline int lds_layout(const GameDesc &g, int path_cap, int t
     off[9] = o; o += up16(table_size * 2);
     off[10] = o; o += up16(table_size * 2);
     off[11] = o; o += up16(table_size * 4);
+    off[12] = o; o += up16(g.rc);
+    off[13] = o; o += 32;
     return o;
 }
 
 extern __shared__ __attribute__((aligned(16))) unsigned char azk_smem[];
 
-__device__ __forceinline__ LdsView carve_at(const int *off, int table_size) {
+__device__ __forceinline__ LdsView carve_at(const int *off, int table_size, int rc) {
     LdsView L;
     L.board = azk_smem + off[0];
     L.path = (int *)(azk_smem + off[1]);
@@ -136,11 +140,15 @@ __device__ __forceinline__ LdsView carve_at(const int *off, int table_size) {
     L.ms.tabB = (uint16_t *)(azk_smem + off[10]);
     L.ms.claim = (uint32_t *)(azk_smem + off[11]);
     L.ms.table_size = table_size;
+    // (the last two regions follow `claim`; Dev carries the twelve offsets it always did, so no kernel's argument layout moves)
+    const int o12 = off[11] + up16(table_size * 4);
+    L.board1 = azk_smem + o12;
+    L.ho = (int *)(azk_smem + o12 + up16(rc));
     return L;
 }
 
 __device__ __forceinline__ LdsView carve(const GameDesc &g, int path_cap, int table_size) {
-    int off[12];
+    int off[14];
     lds_layout(g, path_cap, table_size, off);
     LdsView L;
     L.board = azk_smem + off[0];
@@ -156,6 +164,8 @@ __device__ __forceinline__ LdsView carve(const GameDesc &g, int path_cap, int ta
     L.ms.tabB = (uint16_t *)(azk_smem + off[10]);
     L.ms.claim = (uint32_t *)(azk_smem + off[11]);
     L.ms.table_size = table_size;
+    L.board1 = azk_smem + off[12];
+    L.ho = (int *)(azk_smem + off[13]);
     return L;
 }
 
@@ -179,6 +189,176 @@ __device__ __forceinline__ void backup_path(const Dev &d, size_t base, const int
     }
 }
 
+// Four consecutive floats of a row of A floats, one 16-byte access.  first = row_first(wanted, A): the lane at the row's end takes the
+// row's last four (overlapping its neighbour).  Rows of fewer than four floats (boards of 1-3 cells) go component by component.
+__device__ __forceinline__ int row_first(int wanted, int A) { return max(min(wanted, A - 4), 0); }
+__device__ __forceinline__ f32x4_a4 row_load4(const float *row, int first, int A) {
+    if (A >= 4) return *(const f32x4_a4 *)(row + first);
+    f32x4_a4 v;
+#pragma unroll
+    for (int c = 0; c < 4; c++) v[c] = row[min(first + c, A - 1)];
+    return v;
+}
+__device__ __forceinline__ void row_store4(float *row, int first, int A, f32x4_a4 v) {
+    if (A >= 4) { *(f32x4_a4 *)(row + first) = v; return; }
+#pragma unroll
+    for (int c = 0; c < 4; c++) if (first + c < A) row[first + c] = v[c];
+}
+
+enum { HO_OK = 0, HO_FC, HO_NV, HO_ROOTF64, HO_END_LO, HO_END_HI };   // hand-off words (wave 1 -> wave 0); END: wave 1's clock at the barrier (DBG records)
+
+// Wave 1 of a two-wave k_tree: mcts.py:46-60 for the leaf the previous launch selected, without Node.backup (wave 0's).  It reads the
+// pending-leaf record (wave 0 rewrites it only behind the barrier), builds the leaf's move list from leaf_cells when the selection
+// left none (leaf_nmoves = -1; a list left by a MULTI launch, >= 0, is taken from leaf_moves), and creates the children.  The
+// arithmetic and its order are those of the one-wave expansion.  Always posts the hand-off words; the caller executes the barrier.
+template <bool DBG, int KSL>
+__device__ __forceinline__ void tree_expand_wave(const Dev &d, const LdsView &L, const float *__restrict__ logits, const float *__restrict__ values, int ablate) {
+    const int g = blockIdx.x, vi = g * d.K, lane = azk_lane();        // (slot 0 of the game, as in wave 0)
+    const GameDesc &gd = d.g;
+    const int A = gd.action_dim, rc = gd.rc;
+    const size_t base = (size_t)g * (size_t)d.cap;
+    const bool shared = d.cache_entries && d.cache_shared;
+    const bool wrec = DBG && (ablate & 8192) != 0;
+    // first round trip: the record's words (lane k fetches word k), the leaf's key and its cells
+    const int *up = d.leaf_node + vi;
+    up = lane == 1 ? d.leaf_slot + vi : up;
+    up = lane == 2 ? d.leaf_depth + vi : up;
+    up = lane == 3 ? d.leaf_nmoves + vi : up;
+    up = lane == 4 ? d.arena_top + g : up;
+    up = (lane == 5 && d.cache_entries) ? d.leaf_cache + vi : up;
+    up = (lane == 6 && shared) ? (const int *)d.cache_stamp : up;
+    const int uw = *up;
+    unsigned long long e_key = 0ull;
+    if (shared) e_key = d.leaf_key[(size_t)vi * d.key_words + min(lane, d.key_words - 1)];
+    constexpr int NCW = (KSL * AZK_WAVE / 4 + AZK_WAVE - 1) / AZK_WAVE;
+    const int ncw = d.rc_pad >> 2;
+    uint32_t cw[NCW];
+    {
+        const uint32_t *lw = (const uint32_t *)(d.leaf_cells + (size_t)vi * d.rc_pad);
+#pragma unroll
+        for (int q = 0; q < NCW; q++) cw[q] = lw[min(lane + AZK_WAVE * q, ncw - 1)];
+    }
+    const int node = __builtin_amdgcn_readlane(uw, 0);
+    int ok = 0, fc = -1, nv = 0, rootf64 = 0;
+    if (node >= 0) {
+        const bool xst = (ablate & 1024) != 0;                  // debug only: cycle stamps of the expansion's sub-phases
+        long long x0 = 0, x1 = 0, x2 = 0, x3 = 0, x4 = 0;
+        if (xst) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); x0 = clock64(); }
+        const int slot = __builtin_amdgcn_readlane(uw, 1);
+        const int depth = __builtin_amdgcn_readlane(uw, 2);
+        nv = __builtin_amdgcn_readlane(uw, 3);
+        const int centry = d.cache_entries ? __builtin_amdgcn_readlane(uw, 5) : -1;
+        const unsigned cstamp = shared ? (unsigned)__builtin_amdgcn_readlane(uw, 6) : 0u;
+        const bool hit = d.cache_entries && centry >= 0;
+        const size_t crow = shared ? (size_t)(hit ? centry : -(centry + 1)) : ((size_t)g * d.cache_entries + (hit ? centry : -(centry + 1)));
+        const float *lg = hit ? (shared ? d.hit_logits + (size_t)vi * A : d.cache_logits + crow * A) : logits + (size_t)slot * A;
+        unsigned claim_now = 0u;
+        if (shared && !hit) claim_now = __hip_atomic_load(d.cache_claim + crow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // second round trip, issued before the move list is built and landing under it: logits (a lane takes FOUR consecutive ones per
+        // load: actions 4 lane .. 4 lane + 3 of each block of 256), value, the node's header; a list left in leaf_moves comes along
+        constexpr int NV4 = (KSL * AZK_WAVE + 255) / 256;
+        int la[NV4];                                              // first action of the lane's group
+        bool lact[NV4];
+        f32x4_a4 lgv[NV4];
+#pragma unroll
+        for (int q = 0; q < NV4; q++) {
+            lact[q] = 256 * q + 4 * lane < A;
+            la[q] = row_first(256 * q + 4 * lane, A);
+            lgv[q] = row_load4(lg, la[q], A);
+        }
+        const float vraw = hit ? (shared ? d.hit_value[vi] : d.cache_value[crow]) : values[slot];
+        const uint32_t node_meta = d.H[base + node].meta;
+#pragma unroll
+        for (int q = 0; q < NCW; q++) { const int i = lane + AZK_WAVE * q; if (i < ncw) ((uint32_t *)L.board1)[i] = cw[q]; }
+        if (nv >= 0) {
+            for (int i = lane; i < nv; i += AZK_WAVE) L.moves[i] = d.leaf_moves[(size_t)vi * rc + i];
+        }
+        azk_wave_sync();
+        if (nv < 0) {                                                 // mcts.py:34, moved from the selection to the expansion
+            if (ablate & 4) { nv = 1; if (lane == 0) L.moves[0] = (int16_t)(gd.rc / 2); azk_wave_sync(); }
+            else if (gd.kind == AZK_KIND_GOMOKU)
+                nv = azk_valid_moves_gomoku<KSL>(L.board1, gd, L.moves, L.ms, (ablate & 8) != 0, (ablate & 32) ? d.dbg + (size_t)g * 8 : nullptr);
+            else nv = azk_valid_moves_small(L.board1, gd, L.moves);
+        }
+        nv = uniform_i32(nv);
+        int e_mv[KSL];
+#pragma unroll
+        for (int k4 = 0; k4 < KSL; k4++) { const int i = lane + AZK_WAVE * k4; e_mv[k4] = L.moves[i < nv ? i : 0]; }
+        const bool mix = depth == 0 && d.noise != nullptr;        // mcts.py:42-43,52-53
+        double nzv[KSL] = {};
+        if (mix) {
+#pragma unroll
+            for (int k4 = 0; k4 < KSL; k4++) nzv[k4] = d.noise[(size_t)g * A + azk_action_idx(gd, e_mv[k4])];
+        }
+        bool cache_write = d.cache_entries && !hit;               // MCTS.cache[board_key] = (...)  (mcts.py:51)
+        if (shared && !hit) {
+            // one writer per entry and launch: the claim word moves to this launch's stamp by compare-and-swap; an entry
+            // already claimed in this launch (by any game) is left alone.  The round trip hides under the softmax below.
+            const unsigned cur = (unsigned)uniform_i32((int)claim_now);
+            unsigned got = cur;
+            if (cur != cstamp && lane == 0) got = atomicCAS(d.cache_claim + crow, cur, cstamp);
+            cache_write = cur != cstamp && (unsigned)uniform_i32((int)got) == cur;
+            if (cache_write && lane < d.key_words) d.cache_key[crow * d.key_words + lane] = e_key;
+        }
+        if (xst) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); x1 = clock64(); }
+        // float32 softmax, no max subtraction (mcts.py:48-49)
+#pragma unroll
+        for (int q = 0; q < NV4; q++) {
+            if (256 * q >= A) break;
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const float ev = (ablate & 1) ? 1.0f : azk_exp_det(lgv[q][c]);
+                if (lact[q] && la[q] + c < A) L.e[la[q] + c] = ev;
+            }
+        }
+        azk_wave_sync();
+        if (cache_write) {
+            // (behind the exponentials: by now every logit is in its register, and the stores go out back to back)
+#pragma unroll
+            for (int q = 0; q < NV4; q++) if (lact[q]) row_store4(d.cache_logits + crow * A, la[q], A, lgv[q]);
+            if (lane == 0) d.cache_value[crow] = vraw;
+        }
+        if (xst) x2 = clock64();
+        const float s = azk_pairwise_sum(L.e, A);
+        if (xst) x3 = clock64();
+        fc = __builtin_amdgcn_readlane(uw, 4);
+        const bool fits = fc + nv <= d.cap;
+        if (fits) {
+#pragma unroll
+            for (int k4 = 0; k4 < KSL; k4++) {                    // Node.expand (node.py:50-59)
+                const int i = lane + AZK_WAVE * k4;
+                if (i >= nv) break;
+                const int cell = e_mv[k4];
+                const int a = azk_action_idx(gd, cell);
+                const float p = L.e[a] / s;
+                const size_t idx = base + fc + i;
+                d.H[idx] = NodeH{0, p, meta_pack(cell, 0), -1}; d.W[idx] = 0.0;
+                if (mix) d.rootP[(size_t)g * rc + i] = (double)(0.75f * p) + 0.25 * nzv[k4];   // utils.py:24-25
+            }
+            if (lane == 0) {
+                d.H[base + node].fc = fc;
+                d.H[base + node].meta = (node_meta & 0xffff0000u) | (uint32_t)nv;
+                d.arena_top[g] = fc + nv;
+                if (depth == 0) d.root_f64[g] = mix ? 1 : 0;
+                count_add(d, CNT_CREATED, g, nv);
+            }
+            ok = 1; rootf64 = mix ? 1 : 0;
+        } else if (lane == 0) {
+            atomicExch(d.err, AZK_ERR_ARENA_FULL);
+        }
+        if (xst && lane == 0) {
+            x4 = clock64();
+            long long *qq = d.dbg + (size_t)g * 8;
+            qq[1] += x1 - x0; qq[2] += x2 - x1; qq[3] += x3 - x2; qq[4] += x4 - x3; qq[6] += 1;
+        }
+    }
+    if (wrec) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the record's clock: behind the last store, like the barrier)
+    if (lane == 0) {
+        L.ho[HO_OK] = ok; L.ho[HO_FC] = fc; L.ho[HO_NV] = nv; L.ho[HO_ROOTF64] = rootf64;
+        if (wrec) { const unsigned long long te = (unsigned long long)clock64(); L.ho[HO_END_LO] = (int)(unsigned)te; L.ho[HO_END_HI] = (int)(unsigned)(te >> 32); }
+    }
+}
+
 // ================================================================================================
 // k_tree<EXPAND, SELECT>: one simulation step for every game.
 //   EXPAND: mcts.py:46-60 for the leaf selected by the previous step (softmax, noise, expand, backup)
@@ -195,8 +375,22 @@ __device__ __forceinline__ void backup_path(const Dev &d, size_t base, const int
 // KSL: cells (and actions) per lane the kernel is compiled for - 4 covers boards of up to 256 cells (every shipped game), 7 the rest
 // (make_game allows 400).  A compile-time bound: the per-lane load sequences, their registers and the move generator's cell groups are
 // unrolled to it, and a 15 x 15 board does not pay for three empty groups in each of them.
+//
+// TWO WAVES PER GAME (every instantiation with MULTI = false; the MULTI ones stay one wave and build the move list at the leaf):
+//   wave 0  the game's critical chain: entry loads, Node.backup of the previous leaf along its path (path, depth and value only), the
+//           walk, the terminal test, the eval-cache probe and the leaf's record.  It builds no move list: leaf_nmoves = -1 means
+//           "build it from leaf_cells at expansion".
+//   wave 1  everything else about the previous leaf, beside wave 0's memory round trips: its move list (from leaf_cells, on a board and
+//           scratch of its own), softmax, eval-cache write, root noise, the children, the node's fc / child count, arena_top, root_f64.
+// The hand-off is ONE s_barrier, executed exactly once by each wave on every path (idle or finished game, no pending leaf, terminal
+// leaf, full arena): wave 1 behind its last store (vmcnt(0)) and the hand-off words in LDS; wave 0 when its walk arrives at the
+// previous leaf's node - whose fc and child count it then takes from the hand-off words, never from the header its parent's scan brought
+// along - or, if the walk goes elsewhere, before the first store to the pending-leaf record that wave 1 reads (leaf_cells, leaf_cache,
+// leaf_key, hit_logits ...), at the latest before it ends.  Both waves share a CU and its L1: workgroup scope is enough.  Nothing
+// waits on memory.
+
 template <bool EXPAND, bool SELECT, bool DBG, bool MULTI = false, int KSL = 7>
-__global__ __launch_bounds__(AZK_WAVE) void k_tree(Dev dd, const float *__restrict__ logits, const float *__restrict__ values) {
+__global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd, const float *__restrict__ logits, const float *__restrict__ values) {
     const Dev &d = dd;
     const int ablate = DBG ? dd.ablate : 0;
     const int g = blockIdx.x;
@@ -204,11 +398,34 @@ __global__ __launch_bounds__(AZK_WAVE) void k_tree(Dev dd, const float *__restri
     const GameDesc &gd = d.g;
     const int A = gd.action_dim, rc = gd.rc;
     const size_t base = (size_t)g * (size_t)d.cap;
-    LdsView L = carve_at(d.lds_off, d.table_size);
-    const bool wrec = DBG && (ablate & 8192) != 0;      // debug only: ONE record per wave and launch (overwritten), for the distribution of wave times
+    LdsView L = carve_at(d.lds_off, d.table_size, d.g.rc);
+    const bool wrec = DBG && (ablate & 8192) != 0;      // debug only: ONE record per game and launch (overwritten), for the distribution of wave times
     const bool stamp = (ablate & 16) != 0 || wrec;
     long long t0 = stamp ? clock64() : 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
-    int rec_type = -1, rec_depth = 0, rec_nv = 0, rec_env = 0;   // wrec: -1 idle game, 0 terminal leaf, 1 eval-cache hit, 2 leaf for the evaluator
+    constexpr bool TWO = !MULTI;
+    if constexpr (TWO) {
+        if (uniform_i32((int)(threadIdx.x >> 6)) != 0) {             // wave-uniform: the role split is a scalar branch
+            if constexpr (EXPAND) tree_expand_wave<DBG, KSL>(d, L, logits, values, ablate);
+            // every store above has been acknowledged and the hand-off words are in LDS before the barrier (the workgroup-scope
+            // release alone leaves vmcnt open on this target: one CU's vector memory operations are performed in issue order)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_s_barrier();
+            return;
+        }
+    }
+    bool joined = false;                                             // wave 0 has executed its barrier
+    int prev_leaf_done = -1;                                         // >= 0: leaf_node still names the leaf wave 1 expands (cleared at the end unless a new leaf was written)
+    int bar_phase = 0, prev_leaf_rec = -1;                           // wrec: where wave 0 met the barrier (1 walk, 2 before the leaf writes, 3 at its end)
+    long long bar_wait = 0, w1_end = 0;                              // wrec: cycles wave 0 spent at the barrier; wave 1's clock at its own
+    auto join = [&](int phase) {                                     // wave 0's one barrier; behind it the hand-off words are wave 1's
+        const long long ta = wrec ? clock64() : 0;
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if (wrec) { bar_wait += clock64() - ta; bar_phase = phase; }
+        joined = true;
+    };
+    int rec_type = -1, rec_depth = 0, rec_env = 0;   // wrec: -1 idle game, 0 terminal leaf, 1 eval-cache hit, 2 leaf for the evaluator
     int done_sims = MULTI ? d.sims_done[g] : 0;
     const int sim_target = MULTI ? d.budget[0] : 0, max_iter = MULTI ? d.budget[1] : 1;
     // a launch lasts as long as its slowest wave: a game whose simulation needed no evaluator starts another one only while the launch is
@@ -268,13 +485,13 @@ __global__ __launch_bounds__(AZK_WAVE) void k_tree(Dev dd, const float *__restri
         r_meta = SELECT ? d.H[base].meta : 0u;
     }
     unsigned long long e_key = 0ull;
-    if (EXPAND && shared) e_key = d.leaf_key[(size_t)vi * d.key_words + min(lane, d.key_words - 1)];
+    if (EXPAND && MULTI && shared) e_key = d.leaf_key[(size_t)vi * d.key_words + min(lane, d.key_words - 1)];
     // (every per-lane load below is UNCONDITIONAL with a clamped index: a load under a lane predicate - `lane < n ? p[lane] : 0` -
     //  is compiled as a branch around the load plus a wait for its result right behind it, and the eighteen loads of this entry
     //  sequence then cost one memory round trip EACH instead of one together)
     const int e_path = EXPAND ? d.path[(size_t)vi * d.path_cap + min(lane, d.path_cap - 1)] : 0;     // trace nodes 0..63 (deeper ones: below)
     int e_mv[KSL] = {};
-    if (EXPAND) {
+    if (EXPAND && MULTI) {                                   // (two-wave kernels: the list belongs to wave 1)
 #pragma unroll
         for (int k4 = 0; k4 < KSL; k4++) e_mv[k4] = d.leaf_moves[(size_t)vi * rc + min(lane + AZK_WAVE * k4, rc - 1)];
     }
@@ -298,10 +515,48 @@ __global__ __launch_bounds__(AZK_WAVE) void k_tree(Dev dd, const float *__restri
         r_meta = (uint32_t)__builtin_amdgcn_readlane(uw, 13);
     }
 
-    if (EXPAND) {
+    const int prev_leaf = (EXPAND && TWO) ? uniform_i32(e_node) : -1;   // the node wave 1 is expanding (-1: none)
+    prev_leaf_done = prev_leaf;
+    if (wrec) prev_leaf_rec = prev_leaf;
+    int prev_crow = -1;                                      // shared eval cache: the entry wave 1 may be rewriting in this launch
+    if constexpr (EXPAND && TWO) {
+        // wave 0's share of mcts.py:46-60: Node.backup of the previous leaf - the path, the depth and the value, nothing else
+        const int node = prev_leaf;
+        if (node >= 0) {
+            const int slot = uniform_i32(e_slot);
+            const int depth = uniform_i32(e_depth);
+            const int centry = d.cache_entries ? uniform_i32(e_centry) : -1;
+            const bool hit = d.cache_entries && centry >= 0;
+            const size_t crow = shared ? (size_t)(hit ? centry : -(centry + 1)) : ((size_t)g * d.cache_entries + (hit ? centry : -(centry + 1)));
+            if (shared && !hit) prev_crow = -(centry + 1);
+            const bool shortpath = depth < AZK_WAVE;
+            // (unconditional, the lanes beyond the path read the root: a load under a lane predicate is followed by a wait for it)
+            const int bnode = (shortpath && lane <= depth) ? e_path : 0;
+            const int bN = d.H[base + bnode].N;
+            const double bW = d.W[base + bnode];
+            const float vraw = hit ? (shared ? d.hit_value[vi] : d.cache_value[crow]) : values[slot];
+            const double v = -(double)vraw;                          // mcts.py:56
+            if (shortpath) {                                          // Node.backup (node.py:62-74) on the operands fetched above
+                const int nN = bN + 1;
+                const double nW = bW + (((depth - lane) & 1) ? -v : v);
+                if (lane <= depth) {
+                    d.H[base + e_path].N = nN;
+                    d.W[base + e_path] = nW;
+                }
+            } else {
+                backup_path(d, base, d.path + (size_t)vi * d.path_cap, depth, v, false);
+            }
+            r_N += 1;                                                 // the root is trace node 0 of every simulation
+            if (lane == 0) count_add(d, CNT_TRACE, g, depth + 1);
+            // (leaf_node = -1 waits until the barrier is behind this wave: wave 1 reads the word at ITS entry)
+        }
+        azk_wave_sync();   // this wave's tree writes are visible to its own SELECT reads below
+    }
+    if constexpr (EXPAND && MULTI) {
         const int node = uniform_i32(e_node);
-        if (MULTI && node >= 0 && !(d.cache_entries && uniform_i32(e_centry) >= 0) && ((!vl && it > 0) || logits == nullptr)) {
-            if (lane == 0) atomicExch(d.err, AZK_ERR_STATE);          // a pending evaluation without its logits: caller error
+        if (MULTI && node >= 0 && (uniform_i32(e_nv) < 0 ||          // a leaf of the two-wave kernels: its move list was never built
+                                   (!(d.cache_entries && uniform_i32(e_centry) >= 0) && ((!vl && it > 0) || logits == nullptr)))) {
+            if (lane == 0) atomicExch(d.err, AZK_ERR_STATE);          // ... or a pending evaluation without its logits: caller error
             break;
         }
         if (node >= 0) {
@@ -458,9 +713,19 @@ __global__ __launch_bounds__(AZK_WAVE) void k_tree(Dev dd, const float *__restri
         int Np = uniform_i32(r_N);
         uint32_t nmeta = (uint32_t)uniform_i32((int)r_meta);
         int node_cell = -1;
-        const bool root_f64 = uniform_i32(s_rootf64) != 0;
+        bool root_f64 = uniform_i32(s_rootf64) != 0;
         long long seg_a = 0, seg_b = 0, seg_c = 0, seg_d = 0, seg_t = 0;      // debug only (ablate & 64)
         for (;;) {                                                    // mcts.py:20-23
+            if (TWO && EXPAND && node == prev_leaf && !joined) {
+                // the walk stands on the node wave 1 is expanding (the root: at once): the one barrier, then the node's children from
+                // the hand-off words - the header in registers was loaded while wave 1 may have been writing it.  A full arena leaves
+                // the node a leaf (HO_OK = 0: nothing was written, the header stands).
+                join(1);
+                if (uniform_i32(L.ho[HO_OK])) {
+                    fc = uniform_i32(L.ho[HO_FC]); nmeta = (nmeta & 0xffff0000u) | (uint32_t)uniform_i32(L.ho[HO_NV]);
+                    if (node == 0) root_f64 = uniform_i32(L.ho[HO_ROOTF64]) != 0;
+                }
+            }
             const int nch = meta_nch(nmeta);
             if (nch <= 0 || (ablate & 2)) break;
             if (ablate & 64) seg_t = clock64();
@@ -628,6 +893,53 @@ __global__ __launch_bounds__(AZK_WAVE) void k_tree(Dev dd, const float *__restri
         }
         const int node_player = (root_player + depth) & 1;
         const int node_mc = root_mc + depth;
+        // ---- eval-cache probe (mcts.py:37-44: key = canonical board bytes), issued early and looked at late: the table sits in HBM, and
+        //      its round trips (claim word + key + row, then the claim word again for a hit) pass under other work instead of behind
+        //      it.  MULTI: issued behind the terminal test, passes under the move generation.  Two-wave kernels: no move generation
+        //      follows, so the loads go out in FRONT of the terminal test, which covers their first round trip (a terminal leaf then
+        //      fetches a cache row for nothing).  key = ballots of "own stone" / "opponent stone" over the cells (own = the side to
+        //      move at the leaf)
+        bool cached = false;
+        int entry = 0;
+        unsigned long long mykey = 0ull, kw = 0ull;
+        unsigned c1v = 0u, c2v = 0u;
+        constexpr int NV4P = (KSL * AZK_WAVE + 255) / 256;           // the cached row, four consecutive logits per lane and load (as at the expansion)
+        f32x4_a4 row[NV4P] = {};
+        float vv = 0.f;
+        bool maybe_hit = false;                                       // shared table: key and claim word say "hit" - the second claim read decides
+        const int KW = d.key_words;
+        auto probe_issue = [&]() {
+            if (!d.cache_entries) return;
+            const int half = KW >> 1;
+            unsigned long long h = 0x9E3779B97F4A7C15ull;
+            for (int q = 0; q < half; q++) {
+                const int c = q * AZK_WAVE + lane;
+                const uint8_t code = c < rc ? L.board[c] : (uint8_t)0;
+                unsigned long long own = __ballot((code >> node_player) & 1);
+                const unsigned long long opp = __ballot((code >> (node_player ^ 1)) & 1);
+                if (q == half - 1) own |= (unsigned long long)node_player << 63;   // side to move (3-plane games; cell 63 of the last word is never a cell)
+                if (lane == q) mykey = own;
+                if (lane == half + q) mykey = opp;
+                h = (h ^ own) * 0xFF51AFD7ED558CCDull; h ^= h >> 29;
+                h = (h ^ opp) * 0xC4CEB9FE1A85EC53ull; h ^= h >> 32;
+            }
+            if (shared) {
+                entry = (int)(h & d.cache_mask);
+                // the claim word, the key and the entry's row (fetched on speculation: most probes miss, a row is 900 bytes) together
+                c1v = __hip_atomic_load(d.cache_claim + entry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                kw = d.cache_key[(size_t)entry * KW + min(lane, KW - 1)];
+#pragma unroll
+                for (int q = 0; q < NV4P; q++) {
+                    if constexpr (TWO) row[q] = row_load4(d.cache_logits + (size_t)entry * A, row_first(256 * q + 4 * lane, A), A);
+                    else row[q] = *(const f32x4_a4 *)(d.cache_logits + (size_t)entry * A + min(256 * q + 4 * lane, A - 4));
+                }
+                vv = d.cache_value[entry];
+            } else {
+                entry = (int)(h & (unsigned long long)(d.cache_entries - 1));
+                kw = d.cache_key[((size_t)g * d.cache_entries + entry) * KW + min(lane, KW - 1)];
+            }
+        };
+        if (TWO) probe_issue();
         int term = -1;
         if (depth > 0) {                                              // mcts.py:25-32 (root is never tested)
             const int w = azk_check_winner(L.board, gd, 1 - node_player, node_cell);
@@ -651,46 +963,7 @@ __global__ __launch_bounds__(AZK_WAVE) void k_tree(Dev dd, const float *__restri
             break;
         }
         if (stamp) t3 = clock64();
-        // ---- eval-cache probe (mcts.py:37-44: key = canonical board bytes), ISSUED HERE and looked at after the legal moves: the
-        //      table sits in HBM, and its round trips (claim word + key + row, then the claim word again for a hit) pass under the
-        //      move generation instead of behind it.  key = ballots of "own stone" / "opponent stone" over the cells (own = the
-        //      side to move at the leaf)
-        bool cached = false;
-        int entry = 0;
-        unsigned long long mykey = 0ull, kw = 0ull;
-        unsigned c1v = 0u, c2v = 0u;
-        constexpr int NV4P = (KSL * AZK_WAVE + 255) / 256;           // the cached row, four consecutive logits per lane and load (as at the expansion)
-        f32x4_a4 row[NV4P] = {};
-        float vv = 0.f;
-        bool maybe_hit = false;                                       // shared table: key and claim word say "hit" - the second claim read decides
-        const int KW = d.key_words;
-        if (d.cache_entries) {
-            const int half = KW >> 1;
-            unsigned long long h = 0x9E3779B97F4A7C15ull;
-            for (int q = 0; q < half; q++) {
-                const int c = q * AZK_WAVE + lane;
-                const uint8_t code = c < rc ? L.board[c] : (uint8_t)0;
-                unsigned long long own = __ballot((code >> node_player) & 1);
-                const unsigned long long opp = __ballot((code >> (node_player ^ 1)) & 1);
-                if (q == half - 1) own |= (unsigned long long)node_player << 63;   // side to move (3-plane games; cell 63 of the last word is never a cell)
-                if (lane == q) mykey = own;
-                if (lane == half + q) mykey = opp;
-                h = (h ^ own) * 0xFF51AFD7ED558CCDull; h ^= h >> 29;
-                h = (h ^ opp) * 0xC4CEB9FE1A85EC53ull; h ^= h >> 32;
-            }
-            if (shared) {
-                entry = (int)(h & d.cache_mask);
-                // the claim word, the key and the entry's row (fetched on speculation: most probes miss, a row is 900 bytes) together
-                c1v = __hip_atomic_load(d.cache_claim + entry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                kw = d.cache_key[(size_t)entry * KW + min(lane, KW - 1)];
-#pragma unroll
-                for (int q = 0; q < NV4P; q++) row[q] = *(const f32x4_a4 *)(d.cache_logits + (size_t)entry * A + min(256 * q + 4 * lane, A - 4));
-                vv = d.cache_value[entry];
-            } else {
-                entry = (int)(h & (unsigned long long)(d.cache_entries - 1));
-                kw = d.cache_key[((size_t)g * d.cache_entries + entry) * KW + min(lane, KW - 1)];
-            }
-        }
+        if (MULTI) probe_issue();
         // called by the move generator once its first phase is behind it (a few thousand cycles after the loads above went out):
         // the copy of the row is in registers before the claim word is read again
         auto probe_mid = [&]() {
@@ -699,25 +972,34 @@ __global__ __launch_bounds__(AZK_WAVE) void k_tree(Dev dd, const float *__restri
             const unsigned c1 = (unsigned)uniform_i32((int)c1v);
             const bool same = lane < KW ? kw == mykey : true;
             maybe_hit = c1 != 0u && c1 < cstamp && __ballot(!same) == 0ull;   // written in an earlier launch (complete and visible), same position
+            // the entry wave 1 claims in this launch for the previous leaf: in one wave the claim came first and the probe saw this
+            // launch's stamp there - never a hit, whichever wave gets to the claim word first
+            if (TWO && entry == prev_crow) maybe_hit = false;
             if (maybe_hit) c2v = __hip_atomic_load(d.cache_claim + entry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         };
         // (the second claim read is consumed inside each branch: a load still in flight where the branches meet makes the compiler
         //  wait for it wherever its register is reused - here that was the head of the Gomoku move generation, in front of
         //  everything the probe is meant to pass under)
-        int nv;
+        int nv = -1;                                                  // two-wave kernels: "list not built" (mcts.py:34 runs at expansion, on wave 1)
         unsigned c2 = 0u;
-        if (ablate & 4) { nv = 1; if (lane == 0) L.moves[0] = (int16_t)(gd.rc / 2); __syncthreads(); probe_mid(); c2 = (unsigned)uniform_i32((int)c2v); }
+        if constexpr (TWO) { probe_mid(); c2 = (unsigned)uniform_i32((int)c2v); }
         else if (gd.kind == AZK_KIND_GOMOKU) {                         // mcts.py:34
-            nv = azk_valid_moves_gomoku<KSL>(L.board, gd, L.moves, L.ms, (ablate & 8) != 0, (ablate & 32) ? d.dbg + (size_t)g * 8 : nullptr, probe_mid);
+            nv = azk_valid_moves_gomoku<KSL>(L.board, gd, L.moves, L.ms, false, nullptr, probe_mid);
             c2 = (unsigned)uniform_i32((int)c2v);
         } else { probe_mid(); c2 = (unsigned)uniform_i32((int)c2v); nv = azk_valid_moves_small(L.board, gd, L.moves); }
         if (stamp) t4 = clock64();
+        // everything below rewrites the pending-leaf record that wave 1 reads for the previous leaf: behind the barrier
+        if (TWO && !joined) join(2);
+        prev_leaf_done = -1;                                          // (leaf_node gets the new leaf below)
         if (d.cache_entries) {
             if (shared) {
                 if (maybe_hit && c2 == (unsigned)uniform_i32((int)c1v)) {   // nobody started rewriting the entry meanwhile: the copy is whole
                     cached = true;
 #pragma unroll
-                    for (int q = 0; q < NV4P; q++) if (256 * q + 4 * lane < A) *(f32x4_a4 *)(d.hit_logits + (size_t)vi * A + min(256 * q + 4 * lane, A - 4)) = row[q];
+                    for (int q = 0; q < NV4P; q++) if (256 * q + 4 * lane < A) {
+                        if constexpr (TWO) row_store4(d.hit_logits + (size_t)vi * A, row_first(256 * q + 4 * lane, A), A, row[q]);
+                        else *(f32x4_a4 *)(d.hit_logits + (size_t)vi * A + min(256 * q + 4 * lane, A - 4)) = row[q];
+                    }
                     if (lane == 0) d.hit_value[vi] = vv;
                 }
                 if (!cached && lane < KW) d.leaf_key[(size_t)vi * KW + lane] = mykey;      // written into the table at expansion
@@ -729,7 +1011,7 @@ __global__ __launch_bounds__(AZK_WAVE) void k_tree(Dev dd, const float *__restri
             }
             if (lane == 0) d.leaf_cache[vi] = cached ? entry : -(entry + 1);
         }
-        for (int i = lane; i < nv; i += AZK_WAVE) d.leaf_moves[(size_t)vi * rc + i] = L.moves[i];
+        if (MULTI) for (int i = lane; i < nv; i += AZK_WAVE) d.leaf_moves[(size_t)vi * rc + i] = L.moves[i];
         {
             uint32_t *lw = (uint32_t *)(d.leaf_cells + (size_t)vi * d.rc_pad);
 #pragma unroll
@@ -747,7 +1029,7 @@ __global__ __launch_bounds__(AZK_WAVE) void k_tree(Dev dd, const float *__restri
             d.leaf_flag[vi] = cached ? 0 : (uint8_t)(1 + min(7, node_mc / 6));
             if (cached) count_add(d, CNT_CACHE_HITS, g, 1);
             count_add(d, CNT_LEAVES, g, cached ? 0 : 1);
-            if (wrec) { rec_type = cached ? 1 : 2; rec_nv = nv; }
+            if (wrec) rec_type = cached ? 1 : 2;
             if (stamp && !wrec) {
                 long long *q = d.dbg + (size_t)g * 8;
                 const long long tend = clock64();
@@ -761,22 +1043,33 @@ __global__ __launch_bounds__(AZK_WAVE) void k_tree(Dev dd, const float *__restri
     break;
     }
     if (MULTI && lane0 == 0) d.sims_done[g] = done_sims;
+    if (TWO && !joined) join(3);                                  // (idle or finished game, terminal leaf, expand-only launch: the walk never got there)
+    if (TWO && EXPAND && prev_leaf_done >= 0 && lane0 == 0) d.leaf_node[g * d.K] = -1;   // the previous leaf is expanded and no new one took its place
     if (wrec) {
+        // the game's record: wave 0's phases, the cycles it spent at the barrier (in whichever phase it met it; q[7] includes them) and
+        // wave 1's clock at its barrier relative to wave 0's start (0: wave 1 had nothing to expand)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the wave's own stores are out: the record covers its whole life
         if (lane0 == 0) {
             long long *q = d.dbg + (size_t)g * 8;
             const long long tend = clock64();
             if (rec_type < 0) { t1 = t2 = t3 = t4 = tend; }
-            q[0] = t1 - t0; q[1] = t2 - t1; q[2] = t3 - t2; q[3] = t4 - t3; q[4] = tend - t4; q[5] = rec_depth;
-            q[6] = (long long)(rec_type + 1) | ((long long)rec_nv << 8) | ((long long)rec_env << 20); q[7] = tend - t0;
+            if (EXPAND && prev_leaf_rec >= 0) {
+                rec_env = L.ho[HO_OK] ? L.ho[HO_NV] : 0;
+                w1_end = (long long)(((unsigned long long)(unsigned)L.ho[HO_END_HI] << 32) | (unsigned)L.ho[HO_END_LO]);
+            }
+            const long long w1 = (prev_leaf_rec >= 0 && w1_end > t0) ? w1_end - t0 : 0;
+            q[0] = t1 - t0; q[1] = t2 - t1; q[2] = t3 - t2; q[3] = t4 - t3; q[4] = tend - t4;
+            q[5] = (long long)rec_depth | (bar_wait << 16) | ((long long)bar_phase << 56);
+            q[6] = (long long)(rec_type + 1) | ((long long)rec_env << 20) | (w1 << 32); q[7] = tend - t0;
         }
     }
 }
 
 // launch: the instantiation compiled for this engine's cells-per-lane bound
 #define AZK_LAUNCH_TREE(E_, S_, D_, M_, ARGS_) do { \
-        if (d.g.rc <= 4 * AZK_WAVE && d.g.action_dim <= 4 * AZK_WAVE) k_tree<E_, S_, D_, M_, 4><<<d.G, AZK_WAVE, d.lds_bytes, st>>> ARGS_; \
-        else k_tree<E_, S_, D_, M_, 7><<<d.G, AZK_WAVE, d.lds_bytes, st>>> ARGS_; } while (0)
+        const int nthr_ = (M_) ? AZK_WAVE : 2 * AZK_WAVE;              /* plain kernels: two waves per game */ \
+        if (d.g.rc <= 4 * AZK_WAVE && d.g.action_dim <= 4 * AZK_WAVE) k_tree<E_, S_, D_, M_, 4><<<d.G, nthr_, d.lds_bytes, st>>> ARGS_; \
+        else k_tree<E_, S_, D_, M_, 7><<<d.G, nthr_, d.lds_bytes, st>>> ARGS_; } while (0)
 
 // Leaf compaction: slot = number of leaf games with a lower index (deterministic order); writes the
 // canonical board (gomoku.py:34-40; 3-plane: mcts.py:126-137) of each leaf into the evaluator batch.

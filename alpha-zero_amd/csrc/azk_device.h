@@ -28,7 +28,7 @@ __device__ __forceinline__ int uniform_i32(int v) { return __builtin_amdgcn_read
 
 // ---- ordering inside one wave, without waiting ---------------------------------------------------
 // Every kernel built on this header runs one 64-lane wave per workgroup, except the plain (lock-step) k_tree: two waves per game
-// with separate roles, separate LDS regions and exactly ONE s_barrier between them (the hand-off, azk_engine.hip).  Every function
+// with separate roles, separate LDS regions and exactly ONE s_barrier between them (the hand-off, azk_tree.hip).  Every function
 // of this header is run by ONE wave on LDS that only that wave touches.  The LDS executes a wave's instructions in issue
 // order, so "lane A writes, lane B reads" needs no s_waitcnt between the two - only that the compiler keeps their order.
 // (__syncthreads() must not be used here: in the two-wave workgroup it is a real barrier, which the other wave never meets.)

@@ -1,0 +1,278 @@
+// azk_engine_int.h - what more than one engine file needs (azk_tree.hip, azk_vanilla.hip, azk_moves.hip, azk_rules.hip and the
+// kernel-free azk_engine.hip): the device view of the engine and its LDS layout, the node-record helpers, the host
+// struct behind the opaque azk_engine, and the few host symbols that cross files.  Not part of the ABI (include/azk.h).  A __device__
+// function is here only if kernels of two files call it.
+// The device types stay in an UNNAMED namespace although struct azk_engine, a global type, has members of them (every file includes
+// this one definition, so the layouts cannot drift apart): Dev is a parameter of nearly every engine kernel, and as long as it is
+// `(anonymous namespace)::Dev` each kernel keeps the mangled name tools/compare_kernel_isa.py compares builds by.  A named namespace
+// would be the cleaner form and renames every engine kernel at once - a commit of its own.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <hip/hip_bf16.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <string>
+#include <vector>
+
+#include "azk.h"
+#include "azk_device.h"
+
+namespace {
+
+enum { CNT_SIMS = 0, CNT_SCANNED, CNT_TRACE, CNT_CREATED, CNT_LEAVES, CNT_TERMINAL, CNT_MOVES, CNT_CACHE_HITS, CNT_REUSED, CNT_CARRIED, CNT_N };
+
+struct __attribute__((aligned(16))) NodeH { int N; float P; uint32_t meta; int fc; };
+
+struct Dev {               // device view of the engine, passed to kernels by value
+    GameDesc g;
+    int G, cap, path_cap, rc_pad, leaf_dtype, table_size, lds_bytes;
+    int lds_off[12];       // lds_layout()'s offsets, computed once on the host (k_tree reads them instead of redoing the arithmetic in every wave)
+    int K;                 // leaves in flight per game (virtual-loss mode, opt-in; 1 = the reference's sequential search).  Every
+                           // pending-leaf array below is [G * K], slot v = g * K + k
+    // game state
+    uint8_t *cells;        // [G][rc_pad]  cell codes (1 = player 0, 2 = player 1)
+    int *to_move, *move_count, *done, *winner;   // [G]
+    // tree arena, [G][cap] each (ai/node.py:21-40 as columns)
+    NodeH *H;              // per node, ONE 16-byte record: Node.visit N, Node.prior P (float32 softmax entry), meta = (Node.prevAction as
+                           // r*cols+c) << 16 | len(Node.children) (cell 0xFFFF = root), fc = index of children[0] in this game's arena
+                           // (-1 = not expanded): a PUCT candidate costs one 16-byte load + W instead of five column loads
+    double *W;             // Node.value (running sum)
+    double *rootP;         // [G][rc] float64 root priors after Dirichlet mixing (utils.py:24-25), by child position
+    int *root_f64;         // [G] root children use rootP (float64 UCB) instead of P (float32 UCB)
+    int *arena_top;        // [G] bump allocator
+    // pending leaf of the current simulation
+    int *leaf_node, *leaf_depth, *leaf_nmoves, *leaf_slot;   // [G]
+    int *path;             // [G][path_cap]
+    uint8_t *leaf_cells;   // [G][rc_pad] board at the leaf
+    int16_t *leaf_moves;   // [G][rc] valid moves at the leaf, reference list order
+    uint8_t *leaf_flag;    // [G * K] 1 = this slot contributes a leaf to the evaluator batch this step
+    int *to_move_v;        // [G * K] to_move of the slot's game (K > 1: what the leaf hand-off kernels index by slot)
+    const double *noise;   // [G][A] or nullptr (asynchronous moves: [G][2][A], see noise_sel)
+    const long long *noise_sel;   // asynchronous moves: [G] the slot's move counter - its low bit selects the row of the game's CURRENT search; else nullptr
+    // eval cache (MCTS.cache, ai/mcts.py:7,38-51): per-game direct-mapped table keyed by the exact canonical position
+    int cache_entries, key_words;          // entries per game (power of two, 0 = off); 64-bit words per key
+    unsigned long long *cache_key;         // [G][E][key_words] own-stone bit plane, opponent bit plane (+ side bit)
+    float *cache_logits;                   // [G][E][A] the evaluator's logits row
+    float *cache_value;                    // [G][E]
+    int *leaf_cache;                       // [G] >= 0: pending leaf was a cache hit (entry index); < 0: miss, insert at -(x)-1
+    // shared mode (one table for every game of the engine, like the reference's process-global MCTS.cache): entries are written
+    // at EXPANSION by whichever game wins the entry's claim word for the current launch stamp, and read at selection only when
+    // their claim stamp is older than the current launch (the kernel boundary is the only cross-CU ordering relied on); a hit is
+    // copied into the game's own buffers at once, because another game may overwrite the entry before this game expands
+    int cache_shared;
+    unsigned long long cache_mask;         // shared: entries - 1 (entries = the largest power of two <= G * cache_entries)
+    unsigned *cache_claim;                 // shared: [entries] launch stamp of the entry's last write, 0 = never written
+    unsigned *cache_stamp;                 // shared: [1] stamp of the current launch (bumped by the leaf hand-off kernels)
+    unsigned long long *leaf_key;          // shared: [G][key_words] key of the pending (missed) leaf
+    float *hit_logits, *hit_value;         // shared: [G][A], [G] private copy of a hit
+    int16_t *traj_action;  // [G][state_dim] cell played at each ply of the current game (square boards only, else null)
+    double *traj_pi;       // [G][state_dim][A] visit distribution recorded at each ply
+    long long *emit_base;  // [G] first tuple index (64-bit: the stream never wraps) of a game being emitted, -1 = not emitting
+    int *sims_done;        // [G] simulations of the current search already run (budget stepping, azk_begin_search_budget)
+    int *budget;           // [4] simulations per search, most simulations per game and launch, launch age (wall-clock ticks) up to which a
+                           //     game may start another simulation (0: no limit), reserved
+    long long *counters;   // [CNT_N][G]
+    int *err;              // sticky error word
+    int ablate;            // debug only (AZK_TREE_ABLATE): timing experiments that break parity on purpose
+    long long *dbg;        // debug only: [G][8] cycle stamps per phase when ablate & 16
+};
+
+// tree reuse across moves (azk_config.tree_reuse, opt-in; all null / 0 otherwise).  Its own argument of the few kernels that need it:
+// Dev - and with it the kernel-argument offsets and instruction stream of k_tree - is that of an engine without the feature
+struct ReuseDev {
+    int mode;              // 0 off, 1 carry, 2 top-up
+    int words;             // 64-bit words of one game's mark bitmap: ceil(cap / 64)
+    int *chosen_node;      // [G] arena index of the child k_advance played (the next search's root), -1 = start from a fresh root
+    unsigned long long *bits;   // [G][words] k_reroot scratch: bit i = node i belongs to the kept subtree
+    unsigned *pre;         // [G][words] k_reroot scratch: kept nodes below the word = new index of the word's first kept node
+};
+
+struct LdsView {
+    uint8_t *board;
+    int *path;
+    int16_t *moves;
+    float *e;
+    int *cnt;
+    double *cdf;
+    MoveScratch ms;
+    uint8_t *board1;       // two-wave k_tree: the expanding wave's board (the pending leaf's cells)
+    int *ho;               // two-wave k_tree: hand-off words, see HO_*
+};
+
+__host__ __device__ inline int up16(int x) { return (x + 15) & ~15; }
+
+__host__ __device__ inline int lds_layout(const GameDesc &g, int path_cap, int table_size, int *off) {
+    // offsets (bytes) of: board, path, moves, e, cnt, cdf, bits, pref, ord, tabA, tabB, claim, board1, hand-off words
+    int o = 0;
+    off[0] = o; o += up16(g.rc);
+    off[1] = o; o += up16(path_cap * 4);
+    off[2] = o; o += up16(g.rc * 2);
+    int ea = g.action_dim > g.rc ? g.action_dim : g.rc;
+    off[3] = o; o += up16(ea * 4);
+    off[4] = o; o += up16(ea * 4);
+    off[5] = o; o += up16(ea * 8);
+    int nwords = (g.rc * 8 + 31) >> 5;
+    off[6] = o; o += up16((nwords > (table_size >> 5) + 2 ? nwords : (table_size >> 5) + 2) * 4);   // key bitmap, later the set table's occupancy bitmap
+    off[7] = o; o += up16(nwords * 2);
+    off[8] = o; o += up16(g.rc * 2);
+    off[9] = o; o += up16(table_size * 2);
+    off[10] = o; o += up16(table_size * 2);
+    off[11] = o; o += up16(table_size * 4);
+    off[12] = o; o += up16(g.rc);
+    off[13] = o; o += 32;
+    return o;
+}
+
+extern __shared__ __attribute__((aligned(16))) unsigned char azk_smem[];
+
+__device__ __forceinline__ LdsView carve_at(const int *off, int table_size, int rc) {
+    LdsView L;
+    L.board = azk_smem + off[0];
+    L.path = (int *)(azk_smem + off[1]);
+    L.moves = (int16_t *)(azk_smem + off[2]);
+    L.e = (float *)(azk_smem + off[3]);
+    L.cnt = (int *)(azk_smem + off[4]);
+    L.cdf = (double *)(azk_smem + off[5]);
+    L.ms.bits = (uint32_t *)(azk_smem + off[6]);
+    L.ms.pref = (uint16_t *)(azk_smem + off[7]);
+    L.ms.ord = (int16_t *)(azk_smem + off[8]);
+    L.ms.tabA = (uint16_t *)(azk_smem + off[9]);
+    L.ms.tabB = (uint16_t *)(azk_smem + off[10]);
+    L.ms.claim = (uint32_t *)(azk_smem + off[11]);
+    L.ms.table_size = table_size;
+    // (the last two regions follow `claim`; Dev carries the twelve offsets it always did, so no kernel's argument layout moves)
+    const int o12 = off[11] + up16(table_size * 4);
+    L.board1 = azk_smem + o12;
+    L.ho = (int *)(azk_smem + o12 + up16(rc));
+    return L;
+}
+
+__device__ __forceinline__ LdsView carve(const GameDesc &g, int path_cap, int table_size) {
+    int off[14];
+    lds_layout(g, path_cap, table_size, off);
+    LdsView L;
+    L.board = azk_smem + off[0];
+    L.path = (int *)(azk_smem + off[1]);
+    L.moves = (int16_t *)(azk_smem + off[2]);
+    L.e = (float *)(azk_smem + off[3]);
+    L.cnt = (int *)(azk_smem + off[4]);
+    L.cdf = (double *)(azk_smem + off[5]);
+    L.ms.bits = (uint32_t *)(azk_smem + off[6]);
+    L.ms.pref = (uint16_t *)(azk_smem + off[7]);
+    L.ms.ord = (int16_t *)(azk_smem + off[8]);
+    L.ms.tabA = (uint16_t *)(azk_smem + off[9]);
+    L.ms.tabB = (uint16_t *)(azk_smem + off[10]);
+    L.ms.claim = (uint32_t *)(azk_smem + off[11]);
+    L.ms.table_size = table_size;
+    L.board1 = azk_smem + off[12];
+    L.ho = (int *)(azk_smem + off[13]);
+    return L;
+}
+
+__device__ __forceinline__ uint32_t meta_pack(int cell, int nch) { return ((uint32_t)(cell & 0xffff) << 16) | (uint32_t)nch; }
+__device__ __forceinline__ int meta_cell(uint32_t m) { return (int)(m >> 16); }
+__device__ __forceinline__ int meta_nch(uint32_t m) { return (int)(m & 0xffffu); }
+
+// device counters: fire-and-forget atomics (no load -> add -> store round trip on the simulation's critical path)
+__device__ __forceinline__ void count_add(const Dev &d, int which, int g, long long v) {
+    atomicAdd((unsigned long long *)&d.counters[(size_t)which * d.G + g], (unsigned long long)v);
+}
+
+// Node.backup (node.py:62-74): the node at trace index i gets value * (-1)^(depth - i); lanes take one node each.
+__device__ __forceinline__ void backup_path(const Dev &d, size_t base, const int *path, int depth, double value, bool undo_virtual_loss = false) {
+    for (int i = azk_lane(); i <= depth; i += AZK_WAVE) {
+        int nd = path[i];
+        double sv = ((depth - i) & 1) ? -value : value;
+        if (undo_virtual_loss) { d.W[base + nd] = (d.W[base + nd] + sv) + 1.0; continue; }      // the visit was counted at selection (same association as the short-path form)
+        d.H[base + nd].N += 1;
+        d.W[base + nd] += sv;
+    }
+}
+
+// asynchronous self-play (azk_async_begin): the movers' own kernel argument, see azk_moves.hip
+struct AsyncDev {
+    int n_sims, sample_until, dirichlet;
+    unsigned long long seed;
+    long long first_game;
+    double alpha;
+    long long *slot_moves;     // [G] moves this slot has played since azk_async_begin (all its games): the RNG's move key
+    double *noise;             // [G][2][A] engine-owned: row (k & 1) of game g is the Dirichlet row of its search with move key k, for the
+                               //   current key (slot_moves[g]) and the next one - generated a whole search ahead of its use
+    int *noise_key;            // [G] the highest move key whose row exists
+    int *todo_list, *todo_count;   // games that moved since the last drain: their row for key slot_moves[g] + 1 is due (k_noise_ahead)
+    long long *stats;          // caller's int64 [16]: games, plies, wins 0 / 1, draws, moves, record cursor, searches begun
+    long long rec_cap;
+    int *rec_meta; double *rec_q; double *rec_pi;
+    int *fin_list, *fin_count; // games found finished by the drain
+};
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+inline bool make_game(int kind, int rows, int cols, GameDesc *g, std::string *err) {
+    memset(g, 0, sizeof *g);
+    g->kind = kind;
+    if (kind == AZK_TICTACTOE) { rows = 3; cols = 3; g->planes = 3; g->win_len = 3; g->action_dim = 9; }
+    else if (kind == AZK_CONNECT4) { rows = 6; cols = 7; g->planes = 3; g->win_len = 4; g->action_dim = 7; }
+    else if (kind == AZK_GOMOKU) {
+        // (<= 30 columns: azk_valid_moves_gomoku shifts the board's bit string by up to cols + 1 inside 64-bit words)
+        if (rows < 1 || cols < 1 || rows * cols > 400 || cols > 30) { *err = "gomoku board must have 1..400 cells and at most 30 columns"; return false; }
+        g->planes = 2; g->win_len = 5; g->action_dim = rows * cols;
+    } else { *err = "unknown game id"; return false; }
+    g->rows = rows; g->cols = cols; g->rc = rows * cols; g->state_dim = rows * cols;
+    g->inv_cols = (65536u + (unsigned)cols - 1u) / (unsigned)cols;
+    return true;
+}
+
+inline int table_size_for(const GameDesc &g) { return g.rc < 307 ? 512 : 2048; }   // CPython set growth: 8 -> 32 -> 128 -> 512 -> 2048
+
+}  // namespace
+
+struct azk_engine {
+    Dev d;
+    azk_config cfg;
+    std::string err;
+    std::vector<void *> allocs;
+    long long *counter_sums = nullptr;   // device [CNT_N]
+    int *n_leaf_scratch = nullptr;
+    void *leaf_scratch = nullptr;        // used when the caller passes no leaf buffer
+    uint32_t *vanilla_rng = nullptr;     // [G][625] MT19937 key + position (vanilla mode), allocated on first use
+    double *lntab = nullptr;             // [lntab_n] math.log(N), from the host libm (the reference's math.log)
+    int lntab_n = 0;
+    bool multi = false;                  // budget stepping (azk_begin_search_budget): the MULTI instantiation of k_tree
+    int budget_host[4] = {0, 1, 0, 0};
+    int ticks_per_us = 100;              // constant-rate clock of wall_clock64()
+    ReuseDev ru;                         // tree reuse (cfg.tree_reuse); ru.mode == 0: off, every pointer null
+    AsyncDev ad;                         // asynchronous self-play (azk_async_begin); ad.slot_moves == nullptr: not set up
+    bool async_on = false;
+    int async_recycle = 1;
+};
+
+#define HIPCHK(e, call)                                                                 \
+    do {                                                                                \
+        hipError_t _s = (call);                                                         \
+        if (_s != hipSuccess) {                                                         \
+            (e)->err = std::string(#call) + ": " + hipGetErrorString(_s);              \
+            return AZK_ERR_HIP;                                                         \
+        }                                                                               \
+    } while (0)
+
+template <typename T>
+static hipError_t dalloc(azk_engine *e, T **p, size_t count) {
+    void *q = nullptr;
+    hipError_t s = hipMalloc(&q, count * sizeof(T) + 64);
+    if (s != hipSuccess) return s;
+    e->allocs.push_back(q);
+    *p = (T *)q;
+    return hipSuccess;
+}
+
+// host symbols that cross engine files: hidden, not in include/azk.h
+#define AZK_INTERNAL __attribute__((visibility("hidden")))
+extern AZK_INTERNAL thread_local std::string azk_create_error;   // azk_last_error(nullptr): written by azk_create and the stateless rule calls (azk_engine.hip)
+// the k_tree instantiation for this engine and step (azk_tree.hip)
+AZK_INTERNAL int32_t azk_launch_tree(azk_engine *e, bool expand, bool select, bool multi, const float *logits, const float *values, hipStream_t st);
+// azk_create's last step: every game empty, every tree a fresh root (azk_moves.hip)
+AZK_INTERNAL int32_t azk_init_games(azk_engine *e);

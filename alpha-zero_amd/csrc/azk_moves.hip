@@ -1,0 +1,862 @@
+// azk_moves.hip - everything of the batched self-play engine that happens between searches: a search begins (fresh root, or the
+// re-rooted subtree of the played child), root statistics, the move, games reset and recycled, (state, pi, z) emission, the Philox
+// noise rows, counters, and the asynchronous movers that do all of it per game inside the step; the kernels and the C ABI calls
+// that launch them (include/azk.h).  Built with -ffp-contract=off like every engine file.
+#include "azk_engine_int.h"
+
+namespace {
+
+// A leaf that missed the eval cache claims its entry's key at selection and fills logits/value at expansion; if the search
+// is abandoned in between (new search, reset, recycle) the half-written entry must not survive.
+__device__ __forceinline__ void drop_pending_cache_claim(const Dev &d, int g) {
+    for (int k = 0; k < d.K; k++) {
+        const int v = g * d.K + k;
+        if (d.cache_entries && !d.cache_shared && d.leaf_node[v] >= 0 && d.leaf_cache[v] < 0) {      // (shared mode claims nothing at selection)
+            unsigned long long *kp = d.cache_key + ((size_t)g * d.cache_entries + (size_t)(-(d.leaf_cache[v] + 1))) * d.key_words;
+            for (int w = 0; w < d.key_words; w++) kp[w] = ~0ull;
+        }
+    }
+}
+
+// every pending-leaf slot of game g back to "nothing pending"
+__device__ __forceinline__ void clear_leaf_slots(const Dev &d, int g) {
+    for (int k = 0; k < d.K; k++) { d.leaf_node[g * d.K + k] = -1; d.leaf_flag[g * d.K + k] = 0; d.to_move_v[g * d.K + k] = d.to_move[g]; }
+}
+
+// Node(None, None, current_player, move_count) for every game (gomoku.py:134)
+__device__ __forceinline__ void fresh_root_one(const Dev &d, int g) {
+    drop_pending_cache_claim(d, g);
+    const size_t base = (size_t)g * d.cap;
+    d.H[base] = NodeH{0, 0.f, meta_pack(0xffff, 0), -1}; d.W[base] = 0.0;
+    d.arena_top[g] = 1; d.root_f64[g] = 0;
+    clear_leaf_slots(d, g);
+    d.sims_done[g] = 0;
+}
+
+__global__ void k_begin_search(Dev d) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= d.G) return;
+    if (g == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
+    fresh_root_one(d, g);
+}
+
+// ================================================================================================
+// Tree reuse across moves (azk_config.tree_reuse, opt-in): the search of the next move starts on the subtree under the child
+// that was played - the reference's MCTS.mcts(model, board, root, ...) (ai/mcts.py:11) handed `root = chosen_child;
+// root.parent = None` instead of a new Node (games/gomoku.py:134).  reroot_one moves that subtree to the front of the game's
+// arena IN PLACE (the arena pointers are baked into captured step graphs) and repairs the links.  One wave per game:
+//   mark   a child block is allocated after its parent exists, so first_child(node) > node: ONE ascending sweep over a bitmap
+//          of the arena finds the subtree - a marked, expanded node marks its child block, always at higher indices.  The sweep
+//          holds 64 bitmap words (4 096 nodes) in registers, skips empty words without touching memory, reads the 16-byte
+//          headers of a word's marked nodes in one load, and fetches the window again only after a mark that fell inside it.
+//   rank   new index of a kept node = number of kept nodes below it: a running popcount per bitmap word (rr_pre) + the bits
+//          below the node in its own word.  Order-preserving, so blocks stay contiguous, in list order, behind their parents.
+//   slide  kept records (NodeH + W) move to their rank in ascending order, four bitmap words per round trip; destination <=
+//          source for every node and a round's records are all in registers before its first store, so no record is overwritten
+//          before it was read.  first_child goes through the same rank computation.
+// Every loop is bounded by the game's arena_top; a link that does not point forward inside the arena ends in the sticky
+// error word and a fresh root.  n_sims: the simulations this search may still run (the arena rule's worst case, and the
+// top-up target).  The kept subtree is dropped for a fresh root when  kept + n_new * widest > cap  (include/azk.h).
+// ================================================================================================
+__device__ __forceinline__ unsigned long long rr_load64(const unsigned long long *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // past the vector L1: the words are updated by atomics
+}
+__device__ __forceinline__ unsigned long long rr_below(int bit) { return (1ull << bit) - 1ull; }
+// rank of node i among the kept nodes
+__device__ __forceinline__ int rr_rank(const unsigned long long *bm, const unsigned *pre, int i) {
+    const unsigned long long w = rr_load64(bm + (i >> 6));
+    const unsigned p = __hip_atomic_load(pre + (i >> 6), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return (int)p + __popcll(w & rr_below(i & 63));
+}
+
+__device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_sims) {
+    const int lane = azk_lane();
+    const GameDesc &gd = d.g;
+    const size_t base = (size_t)g * (size_t)d.cap;
+    const int T = uniform_i32(d.arena_top[g]);
+    unsigned long long *bm = r.bits + (size_t)g * r.words;
+    unsigned *pre = r.pre + (size_t)g * r.words;
+    bool keep = c > 0 && c < T && T <= d.cap && uniform_i32(d.done[g]) == 0;
+    bool bad = false;
+    NodeH hroot = NodeH{0, 0.f, 0u, -1};
+    if (keep) hroot = d.H[base + c];
+    const int root_fc = uniform_i32(hroot.fc), root_nch = uniform_i32(meta_nch(hroot.meta)), root_N = uniform_i32(hroot.N);
+    if (keep && root_fc < 0) keep = false;                        // the chosen child was never expanded (n_sims = 1)
+    const int n_new = r.mode == 2 ? max(1, n_sims - root_N) : n_sims;
+    const int w0 = c >> 6, w1 = (T - 1) >> 6;                     // bitmap words the subtree can touch
+    int kept = 0;
+    if (keep) {
+        for (int w = w0 + lane; w <= w1; w += AZK_WAVE) bm[w] = w == w0 ? 1ull << (c & 63) : 0ull;
+        __threadfence();
+        for (int wb = w0; wb <= w1 && !bad; wb += AZK_WAVE) {
+            unsigned long long wreg = wb + lane <= w1 ? rr_load64(bm + wb + lane) : 0ull;
+            for (int k = 0; k < AZK_WAVE && wb + k <= w1 && !bad; k++) {
+                unsigned long long seen = 0ull;
+                for (int round = 0; round <= AZK_WAVE; round++) {            // a round handles at least one new node of the word
+                    const unsigned long long word = azk_readlane_u64(wreg, k) & ~seen;
+                    if (word == 0ull) break;
+                    seen |= word;
+                    kept += __popcll(word);
+                    const int node = (wb + k) * AZK_WAVE + lane;
+                    const bool has = (word >> lane) & 1ull;
+                    const NodeH h = d.H[base + (has ? node : c)];
+                    const int hn = meta_nch(h.meta);
+                    const bool ex = has && h.fc >= 0;
+                    if (__ballot(ex && !(h.fc > node && hn >= 1 && hn <= T - h.fc)) != 0ull) { bad = true; break; }
+                    unsigned long long m = __ballot(ex);
+                    bool near = false;
+                    while (m != 0ull) {                                       // the child block of each expanded node, as whole-word masks
+                        const int l = __ffsll((long long)m) - 1;
+                        m &= m - 1ull;
+                        const int f = __builtin_amdgcn_readlane(h.fc, l), n = __builtin_amdgcn_readlane(hn, l);
+                        const int fw = f >> 6, lw = (f + n - 1) >> 6;
+                        for (int w = fw + lane; w <= lw; w += AZK_WAVE) {
+                            const int lo = max(f, w * 64) - w * 64, hi = min(f + n, w * 64 + 64) - w * 64;
+                            const unsigned long long mask = hi - lo == 64 ? ~0ull : rr_below(hi - lo) << lo;
+                            atomicOr(bm + w, mask);
+                        }
+                        near = near || fw < wb + AZK_WAVE;
+                    }
+                    if (!near) break;                                         // every new mark lies beyond this window
+                    __threadfence();
+                    wreg = wb + lane <= w1 ? rr_load64(bm + wb + lane) : 0ull;
+                }
+            }
+        }
+        __threadfence();
+    }
+    // the arena rule: the kept subtree plus the most this search can still allocate - one expansion per simulation, and no position
+    // below the root has more legal moves than min(max children, empty cells of the root position).  (The root's own child count is
+    // NOT such a bound: Gomoku's legal moves are the cells next to a stone, and their number grows along a line of play.)
+    const int widest = min(gd.kind == AZK_KIND_C4 ? gd.cols : gd.rc, gd.state_dim - uniform_i32(d.move_count[g]));
+    if (bad || !keep || (long long)kept + (long long)n_new * widest > (long long)d.cap) {
+        if (lane == 0) {
+            if (bad) atomicExch(d.err, AZK_ERR_STATE);
+            fresh_root_one(d, g);
+        }
+        return;
+    }
+    // rank: kept nodes below each word
+    int run = 0;
+    for (int wb = w0; wb <= w1; wb += AZK_WAVE) {
+        const unsigned long long word = wb + lane <= w1 ? rr_load64(bm + wb + lane) : 0ull;
+        int incl = __popcll(word);
+        const int own = incl;
+#pragma unroll
+        for (int off = 1; off < AZK_WAVE; off <<= 1) { const int o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+        if (wb + lane <= w1) pre[wb + lane] = (unsigned)(run + incl - own);
+        run += __shfl(incl, AZK_WAVE - 1);
+    }
+    __threadfence();
+    // slide
+    for (int wb = w0; wb <= w1; wb += AZK_WAVE) {
+        const unsigned long long wreg = wb + lane <= w1 ? rr_load64(bm + wb + lane) : 0ull;
+        const int preg = wb + lane <= w1 ? (int)__hip_atomic_load(pre + wb + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        for (int k0 = 0; k0 < AZK_WAVE && wb + k0 <= w1; k0 += 4) {
+            unsigned long long wd[4];
+            int pk[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) { wd[j] = azk_readlane_u64(wreg, k0 + j); pk[j] = __builtin_amdgcn_readlane(preg, k0 + j); }
+            if ((wd[0] | wd[1] | wd[2] | wd[3]) == 0ull) continue;
+            NodeH h[4];
+            double wv[4];
+            bool has[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {                                     // every record of the round, before any store
+                has[j] = (wd[j] >> lane) & 1ull;
+                const size_t src = base + (has[j] ? (wb + k0 + j) * AZK_WAVE + lane : c);
+                h[j] = d.H[src]; wv[j] = d.W[src];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) if (has[j] && h[j].fc >= 0) h[j].fc = rr_rank(bm, pre, h[j].fc);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (!has[j]) continue;
+                const int dst = pk[j] + __popcll(wd[j] & rr_below(lane));
+                if ((wb + k0 + j) * AZK_WAVE + lane == c) { h[j].P = 0.f; h[j].meta = meta_pack(0xffff, root_nch); }   // the root: no prevAction
+                d.H[base + dst] = h[j]; d.W[base + dst] = wv[j];
+            }
+        }
+    }
+    __threadfence();
+    azk_wave_sync();
+    // the root's children: float64 priors with this move's Dirichlet row (utils.py:24-25 on the stored float32 prior), else as they are
+    const int new_fc = rr_rank(bm, pre, root_fc);
+    if (d.noise != nullptr) {
+        for (int i = lane; i < root_nch; i += AZK_WAVE) {
+            const NodeH ch = d.H[base + new_fc + i];
+            d.rootP[(size_t)g * gd.rc + i] = (double)(0.75f * ch.P) + 0.25 * d.noise[(size_t)g * gd.action_dim + azk_action_idx(gd, meta_cell(ch.meta))];
+        }
+    }
+    if (lane == 0) {
+        drop_pending_cache_claim(d, g);
+        d.arena_top[g] = kept; d.root_f64[g] = d.noise != nullptr ? 1 : 0;
+        clear_leaf_slots(d, g);
+        d.sims_done[g] = r.mode == 2 ? n_sims - n_new : 0;
+        count_add(d, CNT_REUSED, g, 1);
+        count_add(d, CNT_CARRIED, g, kept);
+    }
+}
+
+// azk_begin_search on a reuse engine: re-root on the child k_advance recorded, or a fresh root where there is none
+__global__ __launch_bounds__(AZK_WAVE) void k_reroot(Dev d, ReuseDev r, int n_sims) {
+    const int g = blockIdx.x;
+    if (g == 0 && azk_lane() == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
+    const int c = uniform_i32(r.chosen_node[g]);
+    reroot_one(d, r, g, c, n_sims);
+    if (azk_lane() == 0) r.chosen_node[g] = -1;                   // one search per recorded move
+}
+
+__global__ void k_reset_games(Dev d, int first, int count, int *chosen_node) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count * d.rc_pad) return;
+    const int g = first + t / d.rc_pad, i = t % d.rc_pad;
+    d.cells[(size_t)g * d.rc_pad + i] = 0;
+    if (i == 0) drop_pending_cache_claim(d, g);
+    if (i == 0) { d.to_move[g] = 0; d.move_count[g] = 0; d.done[g] = 0; d.winner[g] = -2; clear_leaf_slots(d, g); if (chosen_node) chosen_node[g] = -1; }
+}
+
+// Continuous self-play: every finished game's slot restarts from Game() (empty board, player 0).
+// stats[0] += games recycled, stats[1] += plies those games lasted, stats[2..4] += wins of player 0 / player 1 / draws.
+__global__ void k_recycle(Dev d, long long *stats, int *chosen_node) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= d.G || !d.done[g]) return;
+    atomicAdd((unsigned long long *)&stats[0], 1ull);
+    atomicAdd((unsigned long long *)&stats[1], (unsigned long long)d.move_count[g]);
+    const int w = d.winner[g];
+    atomicAdd((unsigned long long *)&stats[w == 0 ? 2 : (w == 1 ? 3 : 4)], 1ull);
+    drop_pending_cache_claim(d, g);
+    for (int i = 0; i < d.rc_pad; i++) d.cells[(size_t)g * d.rc_pad + i] = 0;
+    d.to_move[g] = 0; d.move_count[g] = 0; d.done[g] = 0; d.winner[g] = -2;
+    clear_leaf_slots(d, g);
+    if (chosen_node) chosen_node[g] = -1;
+}
+
+// utils.get_probablity_distribution_of_children (utils.py:46-55), root.value / root.visit (gomoku.py:140)
+__global__ __launch_bounds__(AZK_WAVE) void k_root_stats(Dev d, double *pi, double *q, int *root_visit) {
+    const int g = blockIdx.x, lane = azk_lane();
+    const size_t base = (size_t)g * d.cap;
+    const int A = d.g.action_dim;
+    LdsView L = carve(d.g, d.path_cap, d.table_size);
+    const int fc = d.H[base].fc, nch = meta_nch(d.H[base].meta);
+    for (int a = lane; a < A; a += AZK_WAVE) L.cnt[a] = 0;
+    __syncthreads();
+    int sum = 0;
+    for (int i = lane; i < nch; i += AZK_WAVE) {
+        const int n = d.H[base + fc + i].N;
+        L.cnt[azk_action_idx(d.g, meta_cell(d.H[base + fc + i].meta))] = n;
+        sum += n;
+    }
+    sum = wave_sum_i32(sum);
+    __syncthreads();
+    if (pi) for (int a = lane; a < A; a += AZK_WAVE) pi[(size_t)g * A + a] = (double)L.cnt[a] / (double)sum;
+    if (lane == 0) {
+        if (q) q[g] = d.W[base] / (double)d.H[base].N;
+        if (root_visit) root_visit[g] = d.H[base].N;
+    }
+}
+
+// gomoku.py:143-162 for one game (one wave): choose (sample ~ visits | first max-visit child), record pi / the action in the
+// trajectory, make_move, check_winner, draw.  Returns the chosen cell (-1: state error, already reported); *win_out / *done_out as
+// k_advance's outputs; pi of the move is left in L.cnt / sum_out (visit counts per action and their sum).
+__device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool have_u, double u, int sample_until, int *win_out, int *done_out,
+                                           int *sum_out) {
+    const int lane = azk_lane();
+    const GameDesc &gd = d.g;
+    const size_t base = (size_t)g * d.cap;
+    const int A = gd.action_dim, rc = gd.rc;
+    const int fc = uniform_i32(d.H[base].fc), nch = uniform_i32(meta_nch(d.H[base].meta));
+    const int mc = uniform_i32(d.move_count[g]), mover = uniform_i32(d.to_move[g]);
+    for (int i = lane; i < rc; i += AZK_WAVE) L.board[i] = d.cells[(size_t)g * d.rc_pad + i];
+    for (int a = lane; a < A; a += AZK_WAVE) L.cnt[a] = 0;
+    __syncthreads();
+    int sum = 0;
+    for (int i = lane; i < nch; i += AZK_WAVE) {
+        const int n = d.H[base + fc + i].N;
+        L.cnt[azk_action_idx(gd, meta_cell(d.H[base + fc + i].meta))] = n;
+        sum += n;
+    }
+    sum = wave_sum_i32(sum);
+    __syncthreads();
+    *sum_out = sum;
+    int cellc = -1;
+    if (nch <= 0 || sum <= 0) {
+        if (lane == 0) atomicExch(d.err, AZK_ERR_STATE);
+        return -1;
+    }
+    if (have_u && mc < sample_until) {
+        // Node.sample_child (node.py:83-93) -> legacy np.random.choice(p=pi): cdf = cumsum(pi); cdf /= cdf[-1];
+        // index = searchsorted(cdf, u, side='right').  cumsum is sequential in float64.
+        if (lane == 0) {
+            double acc = 0.0;
+            for (int a = 0; a < A; a++) { acc += (double)L.cnt[a] / (double)sum; L.cdf[a] = acc; }
+            const double lastv = L.cdf[A - 1];
+            int lo = 0, hi = A;
+            while (lo < hi) { int mid = (lo + hi) >> 1; if (u < L.cdf[mid] / lastv) hi = mid; else lo = mid + 1; }
+            L.path[0] = lo < A ? lo : A - 1;                         // action drawn (path scratch: cnt[] is still needed)
+        }
+        __syncthreads();
+        const int act = L.path[0];
+        int found = 0x7fffffff;
+        for (int i = lane; i < nch; i += AZK_WAVE)
+            if (azk_action_idx(gd, meta_cell(d.H[base + fc + i].meta)) == act && i < found) found = i;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { int o = __shfl_xor(found, off); found = o < found ? o : found; }
+        cellc = found != 0x7fffffff ? meta_cell(d.H[base + fc + found].meta) : -1;
+    } else {
+        // Node.max_visit_child (node.py:76-81): first child with the most visits
+        int best = 0x7fffffff, bn = 0;
+        for (int i = lane; i < nch; i += AZK_WAVE) {
+            const int n = d.H[base + fc + i].N;
+            if (best == 0x7fffffff || n > bn) { bn = n; best = i; }
+        }
+        wave_argmax_first<int>(bn, best);
+        cellc = meta_cell(d.H[base + fc + uniform_i32(best)].meta);
+    }
+    cellc = uniform_i32(cellc);
+    if (cellc < 0) {
+        if (lane == 0) atomicExch(d.err, AZK_ERR_STATE);
+        return -1;
+    }
+    if (d.traj_pi != nullptr && mc < gd.state_dim) {               // gomoku.py:138-146: pi and the action of this ply
+        double *tp = d.traj_pi + ((size_t)g * gd.state_dim + mc) * A;
+        for (int a = lane; a < A; a += AZK_WAVE) tp[a] = (double)L.cnt[a] / (double)sum;
+        if (lane == 0) d.traj_action[(size_t)g * gd.state_dim + mc] = (int16_t)cellc;
+    }
+    if (lane == 0) {
+        if (gd.kind == AZK_KIND_C4) L.board[cellc] |= (uint8_t)(1 << mover);
+        else if (L.board[cellc] == 0) L.board[cellc] = (uint8_t)(1 << mover);
+    }
+    __syncthreads();
+    const int w = azk_check_winner(L.board, gd, mover, cellc);      // gomoku.py:150
+    int win = -2, dn = 0;
+    if (w != -1) { win = w; dn = 1; }
+    else if (mc + 1 == gd.state_dim) { win = -1; dn = 1; }
+    if (lane == 0) {
+        d.cells[(size_t)g * d.rc_pad + cellc] = L.board[cellc];
+        d.to_move[g] = 1 - mover;
+        d.move_count[g] = mc + 1;
+        d.winner[g] = win; d.done[g] = dn;
+        d.counters[(size_t)CNT_MOVES * d.G + g] += 1;
+    }
+    *win_out = win; *done_out = dn;
+    return cellc;
+}
+
+__global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *uniforms, int sample_until,
+                                                       int *chosen, int *winner_out, int *done_out, int *chosen_node) {
+    const int g = blockIdx.x, lane = azk_lane();
+    LdsView L = carve(d.g, d.path_cap, d.table_size);
+    if (uniform_i32(d.done[g]) != 0) {
+        if (lane == 0) {
+            if (chosen) chosen[g] = -1;
+            if (winner_out) winner_out[g] = d.winner[g];
+            if (done_out) done_out[g] = 1;
+            if (chosen_node) chosen_node[g] = -1;
+        }
+        return;
+    }
+    int win = -2, dn = 0, sum = 0;
+    const int cellc = advance_one(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum);
+    if (chosen_node) {
+        // tree reuse: the arena index of the child that was played (a cell occurs once among a node's children)
+        const size_t base = (size_t)g * d.cap;
+        const int fc = uniform_i32(d.H[base].fc), nch = uniform_i32(meta_nch(d.H[base].meta));
+        int found = 0x7fffffff;
+        for (int i = lane; i < nch; i += AZK_WAVE) if (meta_cell(d.H[base + fc + i].meta) == cellc && i < found) found = i;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(found, off); found = o < found ? o : found; }
+        if (lane == 0) chosen_node[g] = (cellc >= 0 && dn == 0 && found != 0x7fffffff) ? fc + found : -1;
+    }
+    if (cellc < 0) return;
+    if (lane == 0) {
+        if (chosen) chosen[g] = cellc;
+        if (winner_out) winner_out[g] = win;
+        if (done_out) done_out[g] = dn;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// (state, pi, z) emission: train.save_data_to_buffer (train.py:30-49) with rotate_data / flip_data (train.py:8-27).
+// Position i of a finished game (side to move = i & 1): z = +-1 by winner (0 for a draw), state = canonical board;
+// positions 0 and 1 once, the others 8 times in the order rot0, lr(rot0), tb(rot0), rot90, lr(rot90), tb(rot90),
+// rot180, rot270 (np.rot90 is counter-clockwise).  Tuple t of the stream lands in slot t % capacity (deque(maxlen)).
+// ------------------------------------------------------------------------------------------------
+__global__ void k_emit_alloc(Dev d, unsigned long long *cursor, long long *game_base_out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= d.G) return;
+    long long base = -1;                                          // the stream index stays 64-bit end to end (2^31 tuples = hours of self-play)
+    if (d.done[g] == 1) {
+        const int n = d.move_count[g];
+        const int tuples = n <= 2 ? n : 2 + 8 * (n - 2);
+        base = (long long)atomicAdd(cursor, (unsigned long long)tuples);
+    }
+    d.emit_base[g] = base;
+    if (game_base_out) game_base_out[g] = base;
+}
+
+__device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
+    // source cell (row-major) of output cell (i, j) under transform t of the reference's emission order
+    int si, sj;
+    switch (t) {
+        case 0: si = i; sj = j; break;                          // rot0
+        case 1: si = i; sj = N - 1 - j; break;                  // lr(rot0)
+        case 2: si = N - 1 - i; sj = j; break;                  // tb(rot0)
+        case 3: si = j; sj = N - 1 - i; break;                  // rot90 (ccw): out[i][j] = in[j][N-1-i]
+        case 4: si = N - 1 - j; sj = N - 1 - i; break;          // lr(rot90)
+        case 5: si = j; sj = i; break;                          // tb(rot90)
+        case 6: si = N - 1 - i; sj = N - 1 - j; break;          // rot180
+        default: si = N - 1 - j; sj = i; break;                 // rot270: out[i][j] = in[N-1-j][i]
+    }
+    return si * N + sj;
+}
+
+template <bool LIST>     // LIST: the grid walks a list of finished games (asynchronous drain) instead of covering all G
+__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(Dev d, float *states, double *pis, float *zs, long long capacity,
+                                                            const unsigned long long *cursor, const int *list, const int *n_list) {
+    const int S = d.g.state_dim, A = d.g.action_dim, rc = d.g.rc, F = d.g.planes, N = d.g.rows;
+    const int lane = azk_lane();
+    const int nb = LIST ? *n_list * S : (int)gridDim.x;
+    for (int blk = blockIdx.x; blk < nb; blk += gridDim.x) {
+    if (LIST && blk != (int)blockIdx.x) __syncthreads();
+    const int gi = blk / S, i = blk - gi * S;
+    const int g = LIST ? list[gi] : gi;
+    const long long base = d.emit_base[g];
+    if (base < 0 || i >= d.move_count[g]) continue;
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+    uint8_t *cells = sm;                                          // board before ply i
+    for (int c = lane; c < rc; c += AZK_WAVE) cells[c] = 0;
+    __syncthreads();
+    const int16_t *acts = d.traj_action + (size_t)g * S;
+    for (int j = lane; j < i; j += AZK_WAVE) cells[acts[j]] = (uint8_t)(1 << (j & 1));
+    __syncthreads();
+    const int side = i & 1, winner = d.winner[g];
+    const float z = winner == -1 ? 0.0f : (side == winner ? 1.0f : -1.0f);
+    const double *pi = d.traj_pi + ((size_t)g * S + i) * A;
+    const int ntr = i < 2 ? 1 : 8;
+    const long long first = base + (i < 2 ? i : 2 + 8 * (i - 2));
+    const long long stream_end = (long long)*cursor;              // after k_emit_alloc: one past the newest tuple of this call
+    for (int t = 0; t < ntr; t++) {
+        if (first + t < stream_end - capacity) continue;          // already pushed out of the ring by newer tuples (deque(maxlen))
+        const long long slot = (first + t) % capacity;
+        float *so = states + (size_t)slot * F * rc;
+        double *po = pis + (size_t)slot * A;
+        for (int e = lane; e < rc; e += AZK_WAVE) {
+            const int src = d4_source(t, e / N, e % N, N);
+            const uint8_t code = cells[src];
+            so[e] = (float)((code >> side) & 1);                    // canonical: own stones first (gomoku.py:34-40)
+            so[rc + e] = (float)((code >> (side ^ 1)) & 1);
+            if (F == 3) so[2 * rc + e] = (float)side;
+            po[e] = pi[src];                                        // square boards: action index == cell index
+        }
+        if (lane == 0) zs[slot] = z;
+    }
+    }
+}
+
+__global__ void k_emit_mark(Dev d) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < d.G && d.done[g] == 1 && d.emit_base[g] >= 0) d.done[g] = 2;      // emitted; recycle / later calls skip it
+}
+
+__global__ void k_sum_counters(const long long *counters, int G, long long *out) {
+    // one block per counter
+    __shared__ long long sm[256];
+    long long s = 0;
+    for (int i = threadIdx.x; i < G; i += blockDim.x) s += counters[(size_t)blockIdx.x * G + i];
+    sm[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) out[blockIdx.x] = sm[0];
+}
+
+// ------------------------------------------------------------------------------------------------
+// Counter-based RNG for the product path: Philox4x32-10 keyed by (seed), counter = (game, move, lane idx, draw).
+// Dirichlet(alpha) via Gamma(alpha) = Gamma(alpha + 1) * U^(1/alpha) (Marsaglia-Tsang for the shape > 1 part).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
+        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
+        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+__device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {     // uniform in (0, 1)
+    const unsigned long long x = (((unsigned long long)hi << 32) | lo) >> 11;
+    return ((double)x + 0.5) * (1.0 / 9007199254740992.0);
+}
+
+// the uniform of (seed, global game, move): np.random.choice's draw of that move
+__device__ __forceinline__ double noise_uniform(unsigned long long seed, unsigned long long gg, int move) {
+    uint32_t c[4] = {(uint32_t)gg, (uint32_t)(gg >> 32), (uint32_t)move, 0xFFFFFFFFu};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return (double)((((unsigned long long)c[0] << 32) | c[1]) >> 11) * (1.0 / 9007199254740992.0);   // [0,1)
+}
+
+// the Dirichlet(alpha) row of (seed, global game, move), by one wave; red: 64 doubles of LDS scratch
+__device__ __forceinline__ void noise_row(int A, unsigned long long seed, unsigned long long gg, int move, double alpha, double *row, double *red) {
+    const int lane = azk_lane();
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    double part = 0.0;
+    for (int a = lane; a < A; a += AZK_WAVE) {
+        const double d = alpha + 1.0 - 1.0 / 3.0, cc = 1.0 / sqrt(9.0 * d);
+        double gam = 0.0;
+        for (uint32_t it = 0; it < 64; it++) {
+            uint32_t c[4] = {(uint32_t)gg, (uint32_t)(gg >> 32) ^ ((uint32_t)a << 8), (uint32_t)move, it};
+            philox4x32_10(c, k0, k1);
+            uint32_t c2[4] = {(uint32_t)gg, (uint32_t)(gg >> 32) ^ ((uint32_t)a << 8), (uint32_t)move, it | 0x40000000u};
+            philox4x32_10(c2, k0, k1);
+            const double u1 = u53(c[0], c[1]), u2 = u53(c[2], c[3]), u3 = u53(c2[0], c2[1]), u4 = u53(c2[2], c2[3]);
+            const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+            const double t = 1.0 + cc * x;
+            if (t <= 0.0) continue;
+            const double v = t * t * t;
+            if (log(u3) < 0.5 * x * x + d - d * v + d * log(v)) { gam = d * v * pow(u4, 1.0 / alpha); break; }
+        }
+        row[a] = gam;
+        part += gam;
+    }
+    red[lane] = part;
+    __syncthreads();
+    for (int o = 32; o > 0; o >>= 1) { if (lane < o) red[lane] += red[lane + o]; __syncthreads(); }
+    const double tot = red[0];
+    for (int a = lane; a < A; a += AZK_WAVE) row[a] = tot > 0.0 ? row[a] / tot : 1.0 / (double)A;
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(AZK_WAVE) void k_gen_noise(int A, unsigned long long seed, long long first_game, int move,
+                                                         double alpha, double *noise, double *uniforms, long long row_stride) {
+    const int g = blockIdx.x, lane = azk_lane();
+    const unsigned long long gg = (unsigned long long)(first_game + g);
+    __shared__ double red[AZK_WAVE];
+    if (uniforms && lane == 0) uniforms[g] = noise_uniform(seed, gg, move);
+    if (!noise) return;
+    noise_row(A, seed, gg, move, alpha, noise + (size_t)g * (size_t)row_stride, red);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Asynchronous self-play (games/gomoku.py:132-162: a game moves as soon as ITS search is done).  After every tree launch
+// k_move_async looks at every game: one whose search is complete (its simulation budget used up, nothing pending) gets its move
+// - root statistics, pi into the trajectory, sampled / most-visited child, make_move, check_winner, a record into the device
+// ring - and, unless the game ended, its next search at once: fresh root, Dirichlet row of (seed, global game, the slot's move
+// counter).  Finished games wait for azk_async_drain ((state, pi, z) emission, statistics, restart), which the host runs every
+// few launches.  Random numbers are keyed by (seed, global game index, per-slot move counter): exactly the keys of the lock-step
+// driver, so a slot plays the same sequence of games move for move, whatever the timing.
+// ------------------------------------------------------------------------------------------------
+// Node(None, None, player, move_count) for one game (one wave).  The search's Dirichlet row is NOT made here: a row's key (seed, global
+// game, slot move counter) is known a whole search before its use, so the rows are generated one search ahead, off the step's chain
+// (k_noise_ahead in the drain) - in this function the Marsaglia-Tsang chain (float64 log / cos / pow, two Philox blocks per try) cost a
+// moving game's wave ~30 us inside a launch every other wave had left after 1 us.
+__device__ __forceinline__ void begin_search_one(const Dev &d, const AsyncDev &p, int g, double *red) {
+    const int lane = azk_lane();
+    if (lane == 0) {
+        drop_pending_cache_claim(d, g);
+        const size_t base = (size_t)g * d.cap;
+        d.H[base] = NodeH{0, 0.f, meta_pack(0xffff, 0), -1}; d.W[base] = 0.0;
+        d.arena_top[g] = 1; d.root_f64[g] = 0;
+        clear_leaf_slots(d, g);
+        d.sims_done[g] = 0;
+        atomicAdd((unsigned long long *)&p.stats[7], 1ull);
+    }
+    (void)red;
+}
+
+// drain: the Dirichlet rows that fell due since the last drain - for every game that moved, the row of the search AFTER the one it has
+// just begun (key slot_moves[g] + 1, into the buffer the finished search read from)
+__global__ __launch_bounds__(AZK_WAVE) void k_noise_ahead(Dev d, AsyncDev p) {
+    __shared__ double red[AZK_WAVE];
+    const int n = *p.todo_count, A = d.g.action_dim;
+    for (int f = blockIdx.x; f < n; f += gridDim.x) {
+        const int g = p.todo_list[f];
+        const int key = (int)p.slot_moves[g] + 1;
+        if (uniform_i32(p.noise_key[g]) >= key) continue;
+        noise_row(A, p.seed, (unsigned long long)(p.first_game + g), key, p.alpha, p.noise + ((size_t)g * 2 + (size_t)(key & 1)) * A, red);
+        if (azk_lane() == 0) p.noise_key[g] = key;
+        __syncthreads();
+    }
+}
+
+__global__ void k_fill_i32(int *p, int n, int v) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p) {
+    const int g = blockIdx.x, lane = azk_lane();
+    // one vector load for the three words that decide whether this game moves now (almost never: the wave then ends at once)
+    const int *up = d.done + g;
+    up = lane == 1 ? d.sims_done + g : up;
+    up = lane == 2 ? d.leaf_node + g : up;
+    up = lane == 3 ? d.budget : up;                                // (the simulation budget lives in device memory: azk_async_set_budget)
+    up = (lane == 4 && p.dirichlet) ? p.noise_key + g : up;
+    up = lane == 5 ? (const int *)(p.slot_moves + g) : up;         // (low word: a slot plays far fewer than 2^31 moves)
+    const int uw = *up;
+    if (__builtin_amdgcn_readlane(uw, 0) != 0 || __builtin_amdgcn_readlane(uw, 1) < __builtin_amdgcn_readlane(uw, 3) || __builtin_amdgcn_readlane(uw, 2) >= 0) return;
+    // the next search's Dirichlet row is made a search ahead (k_noise_ahead, every drain); a game whose whole search fitted between two
+    // drains (tiny budgets only) waits for it - a scheduling delay, the game's moves do not change
+    if (p.dirichlet && __builtin_amdgcn_readlane(uw, 4) < __builtin_amdgcn_readlane(uw, 5) + 1) return;
+    LdsView L = carve(d.g, d.path_cap, d.table_size);
+    const int A = d.g.action_dim;
+    const size_t base = (size_t)g * d.cap;
+    const long long mv = p.slot_moves[g];
+    const double q = d.W[base] / (double)d.H[base].N;                 // root.value / root.visit (gomoku.py:140), before the tree is reset
+    int win = -2, dn = 0, sum = 0;
+    const double u = noise_uniform(p.seed, (unsigned long long)(p.first_game + g), (int)mv);
+    const int cellc = advance_one(d, L, g, true, u, p.sample_until, &win, &dn, &sum);
+    if (cellc < 0) return;
+    if (p.rec_cap > 0) {                                           // the move's record: what the reference's self_play keeps per ply
+        long long slot = 0;
+        if (lane == 0) slot = (long long)(atomicAdd((unsigned long long *)&p.stats[6], 1ull) % (unsigned long long)p.rec_cap);
+        slot = ((long long)__builtin_amdgcn_readfirstlane((int)(slot >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)slot);
+        for (int a = lane; a < A; a += AZK_WAVE) p.rec_pi[(size_t)slot * A + a] = (double)L.cnt[a] / (double)sum;
+        if (lane == 0) {
+            p.rec_q[slot] = q;
+            int *m = p.rec_meta + (size_t)slot * 4;
+            m[0] = g; m[1] = (int)mv; m[2] = cellc; m[3] = win;
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {
+        p.slot_moves[g] = mv + 1;                                  // the NEW search's key: its row (mv + 1) & 1 has been waiting since the last move
+        atomicAdd((unsigned long long *)&p.stats[5], 1ull);
+        if (p.dirichlet) p.todo_list[atomicAdd(p.todo_count, 1)] = g;          // row mv + 2 is due
+    }
+    __syncthreads();
+    if (!dn) begin_search_one(d, p, g, L.cdf);
+}
+
+// drain, step 1: list the finished games (done == 1) - the emission and restart kernels work through the list only
+__global__ void k_async_list(Dev d, AsyncDev p) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < d.G && d.done[g] != 0) p.fin_list[atomicAdd(p.fin_count, 1)] = g;
+}
+
+// drain, step 3: statistics + Game() + the next search for every listed game
+__global__ __launch_bounds__(AZK_WAVE) void k_async_restart(Dev d, AsyncDev p, int recycle) {
+    const int lane = azk_lane();
+    LdsView L = carve(d.g, d.path_cap, d.table_size);
+    const int n = *p.fin_count;
+    for (int f = blockIdx.x; f < n; f += gridDim.x) {
+        const int g = p.fin_list[f];
+        if (uniform_i32(d.done[g]) == 3) continue;                 // already counted by an earlier drain (recycle off: the slot stays finished)
+        if (lane == 0) {
+            atomicAdd((unsigned long long *)&p.stats[0], 1ull);
+            atomicAdd((unsigned long long *)&p.stats[1], (unsigned long long)d.move_count[g]);
+            const int w = d.winner[g];
+            atomicAdd((unsigned long long *)&p.stats[w == 0 ? 2 : (w == 1 ? 3 : 4)], 1ull);
+        }
+        if (!recycle) { if (lane == 0) d.done[g] = 3; continue; }
+        for (int i = lane; i < d.rc_pad; i += AZK_WAVE) d.cells[(size_t)g * d.rc_pad + i] = 0;
+        if (lane == 0) { d.to_move[g] = 0; d.move_count[g] = 0; d.done[g] = 0; d.winner[g] = -2; }
+        __syncthreads();
+        begin_search_one(d, p, g, L.cdf);
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+int32_t azk_init_games(azk_engine *e) {
+    const Dev &d = e->d;
+    k_reset_games<<<(unsigned)(((size_t)d.G * d.rc_pad + 255) / 256), 256>>>(d, 0, d.G, e->ru.chosen_node);
+    k_begin_search<<<(unsigned)((d.G + 255) / 256), 256>>>(d);
+    HIPCHK(e, hipDeviceSynchronize());
+    return AZK_OK;
+}
+
+extern "C" {
+
+int32_t azk_reset_games(azk_engine *e, int32_t first, int32_t count, void *stream) {
+    if (!e || first < 0 || count < 0 || first + count > e->d.G) { if (e) e->err = "azk_reset_games: bad range"; return AZK_ERR_ARG; }
+    if (count == 0) return AZK_OK;
+    k_reset_games<<<(unsigned)(((size_t)count * e->d.rc_pad + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d, first, count, e->ru.chosen_node);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    e->d.noise = noise_dev; e->d.noise_sel = nullptr;
+    if (e->ru.mode == 2) { e->err = "azk_begin_search: top-up tree reuse needs the budget (azk_begin_search_budget)"; return AZK_ERR_STATE; }
+    e->multi = false;
+    if (e->ru.mode) k_reroot<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d, e->ru, e->cfg.max_sims);
+    else k_begin_search<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_begin_search_budget(azk_engine *e, const double *noise_dev, int32_t n_sims, int32_t max_sims_per_launch, void *stream) {
+    if (!e || n_sims < 1 || n_sims > e->cfg.max_sims || max_sims_per_launch < 1) { if (e) e->err = "azk_begin_search_budget: bad argument"; return AZK_ERR_ARG; }
+    e->d.noise = noise_dev; e->d.noise_sel = nullptr;
+    e->multi = true;
+    if (e->budget_host[0] != n_sims || e->budget_host[1] != (e->d.K > 1 ? e->d.K : max_sims_per_launch)) {
+        // the budget lives in device memory so that a captured step graph keeps working when it changes
+        e->budget_host[0] = n_sims; e->budget_host[1] = max_sims_per_launch; e->budget_host[2] = 0;
+        if (e->d.K > 1) e->budget_host[1] = e->d.K;               // virtual-loss mode: one iteration per slot
+        HIPCHK(e, hipMemcpyAsync(e->d.budget, e->budget_host, sizeof e->budget_host, hipMemcpyHostToDevice, (hipStream_t)stream));
+        HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
+    }
+    if (e->ru.mode) k_reroot<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d, e->ru, n_sims);
+    else k_begin_search<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+// ---- asynchronous self-play ---------------------------------------------------------------------------------------------
+int32_t azk_async_begin(azk_engine *e, const azk_async_config *c, void *stream) {
+    if (!e || !c || !c->stats_dev || c->n_sims < 1 || c->n_sims > e->cfg.max_sims || c->max_sims_per_launch < 1 || !(c->alpha > 0.0)) {
+        if (e) e->err = "azk_async_begin: bad argument";
+        return AZK_ERR_ARG;
+    }
+    if (e->ru.mode) { e->err = "azk_async_begin: the asynchronous movers do not re-root (tree_reuse engines use the lock-step drivers)"; return AZK_ERR_STATE; }
+    if (c->record_capacity < 0 || (c->record_capacity > 0 && (!c->rec_meta_dev || !c->rec_q_dev || !c->rec_pi_dev))) { e->err = "azk_async_begin: record ring pointers missing"; return AZK_ERR_ARG; }
+    Dev &d = e->d;
+    if (d.K > 1) { e->err = "azk_async_begin: asynchronous moves run the sequential search (leaves_per_step = 1)"; return AZK_ERR_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    AsyncDev &a = e->ad;
+    if (!a.slot_moves) {
+        HIPCHK(e, dalloc(e, &a.slot_moves, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &a.noise, (size_t)d.G * 2 * d.g.action_dim));
+        HIPCHK(e, dalloc(e, &a.noise_key, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &a.todo_list, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &a.todo_count, 1));
+        HIPCHK(e, dalloc(e, &a.fin_list, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &a.fin_count, 1));
+    }
+    a.n_sims = c->n_sims; a.sample_until = c->sample_until_move; a.dirichlet = c->dirichlet ? 1 : 0;
+    a.seed = c->seed; a.first_game = c->first_global_game; a.alpha = c->alpha;
+    a.stats = (long long *)c->stats_dev; a.rec_cap = c->record_capacity; a.rec_meta = c->rec_meta_dev; a.rec_q = c->rec_q_dev; a.rec_pi = c->rec_pi_dev;
+    e->async_recycle = c->recycle ? 1 : 0;
+    HIPCHK(e, hipMemsetAsync(a.slot_moves, 0, sizeof(long long) * (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(a.stats, 0, sizeof(long long) * 16, st));
+    // the simulation budget lives in device memory (a captured step graph keeps working when it changes)
+    e->budget_host[0] = c->n_sims; e->budget_host[1] = c->max_sims_per_launch;
+    e->budget_host[2] = c->young_launch_us > 0 ? c->young_launch_us * e->ticks_per_us : 0;
+    HIPCHK(e, hipMemcpyAsync(d.budget, e->budget_host, sizeof e->budget_host, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    d.noise = a.dirichlet ? a.noise : nullptr;
+    d.noise_sel = a.dirichlet ? a.slot_moves : nullptr;
+    e->multi = true;
+    e->async_on = true;
+    // first search of every game: fresh roots + the Dirichlet rows of move keys 0 (this search) and 1 (the next one)
+    k_begin_search<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d);
+    HIPCHK(e, hipMemsetAsync(a.todo_count, 0, sizeof(int), st));
+    if (a.dirichlet) {
+        const int A = d.g.action_dim;
+        k_gen_noise<<<d.G, AZK_WAVE, 0, st>>>(A, a.seed, a.first_game, 0, a.alpha, a.noise, nullptr, 2LL * A);
+        k_gen_noise<<<d.G, AZK_WAVE, 0, st>>>(A, a.seed, a.first_game, 1, a.alpha, a.noise + A, nullptr, 2LL * A);
+        k_fill_i32<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(a.noise_key, d.G, 1);
+    }
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *values_dev, int32_t phases, void *stream) {
+    if (!e || !e->async_on) { if (e) e->err = "azk_async_step: call azk_async_begin first"; return AZK_ERR_STATE; }
+    const Dev &d = e->d;
+    hipStream_t st = (hipStream_t)stream;
+    if (phases & 1) { const int32_t rc = azk_launch_tree(e, true, true, true, logits_dev, values_dev, st); if (rc != AZK_OK) return rc; }
+    if (phases & 2) k_move_async<<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_async_set_budget(azk_engine *e, int32_t n_sims, int32_t max_sims_per_launch, void *stream) {
+    if (!e || !e->async_on || n_sims < 1 || n_sims > e->cfg.max_sims || max_sims_per_launch < 1) { if (e) e->err = "azk_async_set_budget: bad argument"; return AZK_ERR_ARG; }
+    e->budget_host[0] = n_sims; e->budget_host[1] = max_sims_per_launch;
+    HIPCHK(e, hipMemcpyAsync(e->d.budget, e->budget_host, sizeof e->budget_host, hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_async_drain(azk_engine *e, float *states_dev, double *pis_dev, float *zs_dev, int64_t capacity, int64_t *cursor_dev, void *stream) {
+    if (!e || !e->async_on) { if (e) e->err = "azk_async_drain: call azk_async_begin first"; return AZK_ERR_STATE; }
+    const Dev &d = e->d;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(e, hipMemsetAsync(e->ad.fin_count, 0, sizeof(int), st));
+    k_async_list<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, e->ad);
+    if (states_dev) {
+        if (!pis_dev || !zs_dev || !cursor_dev || capacity < 1 || !d.traj_pi) { e->err = "azk_async_drain: bad replay arguments"; return AZK_ERR_ARG; }
+        k_emit_alloc<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, (unsigned long long *)cursor_dev, nullptr);
+        const int blocks = d.G * d.g.state_dim < 16384 ? d.G * d.g.state_dim : 16384;
+        k_emit_tuples<true><<<(unsigned)blocks, AZK_WAVE, up16(d.g.rc), st>>>(d, states_dev, pis_dev, zs_dev, (long long)capacity,
+                                                                            (const unsigned long long *)cursor_dev, e->ad.fin_list, e->ad.fin_count);
+        k_emit_mark<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d);
+    }
+    k_async_restart<<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->async_recycle);
+    if (e->ad.dirichlet) {                                        // the rows of the searches AFTER the ones begun since the last drain
+        k_noise_ahead<<<(unsigned)(d.G < 512 ? d.G : 512), AZK_WAVE, 0, st>>>(d, e->ad);
+        HIPCHK(e, hipMemsetAsync(e->ad.todo_count, 0, sizeof(int), st));
+    }
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_emit_finished(azk_engine *e, float *states_dev, double *pis_dev, float *zs_dev, int64_t capacity,
+                          int64_t *cursor_dev, int64_t *game_base_dev, void *stream) {
+    if (!e || !states_dev || !pis_dev || !zs_dev || !cursor_dev || capacity < 1) return AZK_ERR_ARG;
+    const Dev &d = e->d;
+    if (!d.traj_pi) { e->err = "azk_emit_finished: (state, pi, z) emission needs a square board with one action per cell"; return AZK_ERR_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    k_emit_alloc<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, (unsigned long long *)cursor_dev, (long long *)game_base_dev);
+    k_emit_tuples<false><<<(unsigned)(d.G * d.g.state_dim), AZK_WAVE, up16(d.g.rc), st>>>(d, states_dev, pis_dev, zs_dev, (long long)capacity,
+                                                                                         (const unsigned long long *)cursor_dev, nullptr, nullptr);
+    k_emit_mark<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_recycle_finished(azk_engine *e, int64_t *stats_dev, void *stream) {
+    if (!e || !stats_dev) return AZK_ERR_ARG;
+    k_recycle<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d, (long long *)stats_dev, e->ru.chosen_node);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_root_stats(azk_engine *e, double *pi_dev, double *q_dev, int32_t *root_visit_dev, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    k_root_stats<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, pi_dev, q_dev, root_visit_dev);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_advance(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t *chosen_cell_dev,
+                    int32_t *winner_dev, int32_t *done_dev, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    k_advance<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, uniforms_dev, sample_until_move,
+                                                                         chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_get_counters(azk_engine *e, azk_counters *out, void *stream) {
+    if (!e || !out) return AZK_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    k_sum_counters<<<CNT_N, 256, 0, st>>>(e->d.counters, e->d.G, e->counter_sums);
+    HIPCHK(e, hipGetLastError());
+    long long h[CNT_N];
+    HIPCHK(e, hipMemcpyAsync(h, e->counter_sums, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    memset(out, 0, sizeof *out);
+    out->sims = h[CNT_SIMS]; out->edges_scanned = h[CNT_SCANNED]; out->trace_nodes = h[CNT_TRACE];
+    out->edges_created = h[CNT_CREATED]; out->leaves_evaluated = h[CNT_LEAVES]; out->terminal_sims = h[CNT_TERMINAL];
+    out->moves_played = h[CNT_MOVES]; out->cache_hits = h[CNT_CACHE_HITS];
+    out->roots_reused = h[CNT_REUSED]; out->nodes_carried = h[CNT_CARRIED];
+    return AZK_OK;
+}
+
+int32_t azk_gen_noise(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double alpha,
+                      double *noise_dev, double *uniforms_dev, void *stream) {
+    if (!e || alpha <= 0.0) return AZK_ERR_ARG;
+    k_gen_noise<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d.g.action_dim, seed, first_global_game, move_index, alpha,
+                                                            noise_dev, uniforms_dev, (long long)e->d.g.action_dim);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+}  // extern "C"

@@ -557,7 +557,7 @@ int azo_mcts(const azo_game_t *g, azo_tree_t *t, float *board, int n_iter,
 }
 
 /* ---------------------------------------------------------------------------------------
- * Virtual-loss expansion: the engine's OPT-IN mode (azk_config.leaves_per_step = K > 1; csrc/azk_engine.hip
+ * Virtual-loss expansion: the engine's OPT-IN mode (azk_config.leaves_per_step = K > 1; csrc/azk_tree.hip
  * k_tree<.., MULTI> with K slots) restated sequentially.  NOT reference behaviour - ai/mcts.py:16-60 is strictly
  * sequential, north_star asks for "virtual-loss expansion" on top of it - so there is no reference output to pin
  * this function to: it pins the KERNEL to a plain sequential statement of the schedule, built from the pinned

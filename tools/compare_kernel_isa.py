@@ -5,7 +5,7 @@
     python3 tools/compare_kernel_isa.py OLD/libazk.so alpha-zero_amd/azk/libazk.so
 
 Each side is a build directory (every *.o in it) or a library.  Every code object bundled in them is extracted (one per translation
-unit: csrc/azk_engine.hip, azk_nn.hip, ...), every kernel is cut at its symbol's size (llvm-readelf -s: llvm-objdump -d goes on to
+unit: csrc/azk_search.hip, azk_moves.hip, azk_nn.hip, ...), every kernel is cut at its symbol's size (llvm-readelf -s: llvm-objdump -d goes on to
 disassemble a section's padding as if it were code) and the instruction text is compared symbol by symbol, whichever file the
 symbol lives in on either side (addresses and encodings left out; kernels in anonymous namespaces keep their mangled names when
 they move between files).  The 64-byte kernel descriptors (register counts, LDS size, ...) are compared too, less the code's own

@@ -32,7 +32,7 @@ SYMBOLS = [
     "azk_nn_embed_fold", "azk_nn_embed_fold_leaves", "azk_nnx_embed_fold", "azk_nnx_embed_fold_leaves",
     "azk_nn_tail_gemm", "azk_nn_tail_gemm_lds", "azk_nn_tail_lds_footprint", "azk_nn_embed_fold_grid", "azk_nn_gemm_tok", "azk_nn_attention_tok", "azk_begin_search_budget", "azk_search_unfinished",
     "azk_nnx_embed_pool", "azk_nnx_embed_pool_leaves", "azk_nnx_gemm", "azk_nnx_gemm_h", "azk_nnx_gemm_h_lds",
-    "azk_async_begin", "azk_async_step", "azk_async_drain", "azk_async_set_budget",
+    "azk_async_begin", "azk_async_step", "azk_async_drain", "azk_async_set_budget", "azk_async_begin_reuse",
 ]
 
 
@@ -308,8 +308,9 @@ class Engine:
 
     # ---- asynchronous self-play (azk_async_*) -----------------------------------------------------
     def async_begin(self, n_sims, per_launch, sample_until, seed, first_global_game, alpha=0.03, dirichlet=True, recycle=True, record_capacity=0,
-                    young_launch_us=0):
+                    young_launch_us=0, reroot=False):
         """Every game starts its first search; from now on azk_async_step moves each game as soon as its own search is done.
+        reroot=True (an engine with tree_reuse 1 | 2): azk_async_begin_reuse - a moved game is parked and re-rooted on the played child by the next drain.
         Returns (stats int64 [16] CUDA, records dict or None) - caller-visible tensors the engine writes (include/azk.h)."""
         torch = self.torch
         self.async_stats = torch.zeros(16, dtype=torch.int64, device=self.device)
@@ -326,7 +327,7 @@ class Engine:
         c.young_launch_us = int(young_launch_us)      # > 0: another simulation inside a launch only while the launch is younger than this
         if rec is not None:
             c.rec_meta_dev, c.rec_q_dev, c.rec_pi_dev = rec["meta"].data_ptr(), rec["q"].data_ptr(), rec["pi"].data_ptr()
-        self._chk(self.L.azk_async_begin(self.h, C.byref(c), _stream()))
+        self._chk((self.L.azk_async_begin_reuse if reroot else self.L.azk_async_begin)(self.h, C.byref(c), _stream()))
         return self.async_stats, rec
 
     def async_step(self, logits, values, phases=3):

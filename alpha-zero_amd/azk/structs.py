@@ -163,6 +163,7 @@ def declare(L, symbols):
     L.azk_nnx_gemm_h.argtypes = [C.POINTER(GemmH), vp]
     L.azk_nnx_gemm_h_lds.argtypes = [C.POINTER(GemmH), vp]
     L.azk_async_begin.argtypes = [vp, C.POINTER(AsyncConfig), vp]
+    L.azk_async_begin_reuse.argtypes = [vp, C.POINTER(AsyncConfig), vp]
     L.azk_async_step.argtypes = [vp, vp, vp, i32, vp]
     L.azk_async_set_budget.argtypes = [vp, i32, i32, vp]
     L.azk_async_drain.argtypes = [vp, vp, vp, vp, i64, vp, vp]

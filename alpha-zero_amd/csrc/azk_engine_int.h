@@ -206,6 +206,10 @@ struct AsyncDev {
     long long rec_cap;
     int *rec_meta; double *rec_q; double *rec_pi;
     int *fin_list, *fin_count; // games found finished by the drain
+    // re-rooting engines only (azk_async_begin_reuse; null otherwise)
+    int *parked;               // [G] 1 = the game has moved and waits for the drain to re-root it: the movers pass it by (its sims_done is the
+                               //   largest int, so k_tree idles it whatever the budget becomes); the played child is in ReuseDev.chosen_node
+    int *reroot_list, *reroot_count;   // the games parked since the last drain (k_reroot_list)
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -57,6 +57,7 @@ __global__ void k_begin_search(Dev d) {
 // Every loop is bounded by the game's arena_top; a link that does not point forward inside the arena ends in the sticky
 // error word and a fresh root.  n_sims: the simulations this search may still run (the arena rule's worst case, and the
 // top-up target).  The kept subtree is dropped for a fresh root when  kept + n_new * widest > cap  (include/azk.h).
+// noise: the game's Dirichlet row of this search, float64 [A], or null (the asynchronous engine keeps two rows per game).
 // ================================================================================================
 __device__ __forceinline__ unsigned long long rr_load64(const unsigned long long *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // past the vector L1: the words are updated by atomics
@@ -69,7 +70,7 @@ __device__ __forceinline__ int rr_rank(const unsigned long long *bm, const unsig
     return (int)p + __popcll(w & rr_below(i & 63));
 }
 
-__device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_sims) {
+__device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_sims, const double *noise) {
     const int lane = azk_lane();
     const GameDesc &gd = d.g;
     const size_t base = (size_t)g * (size_t)d.cap;
@@ -182,15 +183,15 @@ __device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_
     azk_wave_sync();
     // the root's children: float64 priors with this move's Dirichlet row (utils.py:24-25 on the stored float32 prior), else as they are
     const int new_fc = rr_rank(bm, pre, root_fc);
-    if (d.noise != nullptr) {
+    if (noise != nullptr) {
         for (int i = lane; i < root_nch; i += AZK_WAVE) {
             const NodeH ch = d.H[base + new_fc + i];
-            d.rootP[(size_t)g * gd.rc + i] = (double)(0.75f * ch.P) + 0.25 * d.noise[(size_t)g * gd.action_dim + azk_action_idx(gd, meta_cell(ch.meta))];
+            d.rootP[(size_t)g * gd.rc + i] = (double)(0.75f * ch.P) + 0.25 * noise[azk_action_idx(gd, meta_cell(ch.meta))];
         }
     }
     if (lane == 0) {
         drop_pending_cache_claim(d, g);
-        d.arena_top[g] = kept; d.root_f64[g] = d.noise != nullptr ? 1 : 0;
+        d.arena_top[g] = kept; d.root_f64[g] = noise != nullptr ? 1 : 0;
         clear_leaf_slots(d, g);
         d.sims_done[g] = r.mode == 2 ? n_sims - n_new : 0;
         count_add(d, CNT_REUSED, g, 1);
@@ -203,7 +204,7 @@ __global__ __launch_bounds__(AZK_WAVE) void k_reroot(Dev d, ReuseDev r, int n_si
     const int g = blockIdx.x;
     if (g == 0 && azk_lane() == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
     const int c = uniform_i32(r.chosen_node[g]);
-    reroot_one(d, r, g, c, n_sims);
+    reroot_one(d, r, g, c, n_sims, d.noise != nullptr ? d.noise + (size_t)g * d.g.action_dim : nullptr);
     if (azk_lane() == 0) r.chosen_node[g] = -1;                   // one search per recorded move
 }
 
@@ -343,6 +344,19 @@ __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool
     return cellc;
 }
 
+// tree reuse: the arena index of the root's child that holds cell `cellc` (a cell occurs once among a node's children), -1 = none.
+// One wave; the result is wave-uniform.  The move itself (advance_one) does not touch the tree, so this may follow it.
+__device__ __forceinline__ int played_child(const Dev &d, int g, int cellc) {
+    const int lane = azk_lane();
+    const size_t base = (size_t)g * d.cap;
+    const int fc = uniform_i32(d.H[base].fc), nch = uniform_i32(meta_nch(d.H[base].meta));
+    int found = 0x7fffffff;
+    for (int i = lane; i < nch; i += AZK_WAVE) if (meta_cell(d.H[base + fc + i].meta) == cellc && i < found) found = i;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(found, off); found = o < found ? o : found; }
+    return (cellc >= 0 && found != 0x7fffffff) ? fc + found : -1;
+}
+
 __global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *uniforms, int sample_until,
                                                        int *chosen, int *winner_out, int *done_out, int *chosen_node) {
     const int g = blockIdx.x, lane = azk_lane();
@@ -359,14 +373,8 @@ __global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *unifo
     int win = -2, dn = 0, sum = 0;
     const int cellc = advance_one(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum);
     if (chosen_node) {
-        // tree reuse: the arena index of the child that was played (a cell occurs once among a node's children)
-        const size_t base = (size_t)g * d.cap;
-        const int fc = uniform_i32(d.H[base].fc), nch = uniform_i32(meta_nch(d.H[base].meta));
-        int found = 0x7fffffff;
-        for (int i = lane; i < nch; i += AZK_WAVE) if (meta_cell(d.H[base + fc + i].meta) == cellc && i < found) found = i;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(found, off); found = o < found ? o : found; }
-        if (lane == 0) chosen_node[g] = (cellc >= 0 && dn == 0 && found != 0x7fffffff) ? fc + found : -1;
+        const int child = played_child(d, g, cellc);               // tree reuse: the next search's root
+        if (lane == 0) chosen_node[g] = dn == 0 ? child : -1;
     }
     if (cellc < 0) return;
     if (lane == 0) {
@@ -547,6 +555,11 @@ __global__ __launch_bounds__(AZK_WAVE) void k_gen_noise(int A, unsigned long lon
 // counter).  Finished games wait for azk_async_drain ((state, pi, z) emission, statistics, restart), which the host runs every
 // few launches.  Random numbers are keyed by (seed, global game index, per-slot move counter): exactly the keys of the lock-step
 // driver, so a slot plays the same sequence of games move for move, whatever the timing.
+// A re-rooting engine (azk_async_begin_reuse) does not begin the next search in the move kernel: re-rooting a large subtree is a
+// dependent chain of some hundred memory round trips for ONE wave, and every launch of the step chain would last that long.  The
+// move kernel notes the played child and PARKS the game - its parked word set, sims_done at the largest int so that k_tree idles it
+// whatever the budget becomes - on a list; the drain re-roots the listed games (k_reroot_list) and un-parks them.  The kernel
+// boundary is the only ordering relied on.
 // ------------------------------------------------------------------------------------------------
 // Node(None, None, player, move_count) for one game (one wave).  The search's Dirichlet row is NOT made here: a row's key (seed, global
 // game, slot move counter) is known a whole search before its use, so the rows are generated one search ahead, off the step's chain
@@ -586,7 +599,8 @@ __global__ void k_fill_i32(int *p, int n, int v) {
     if (i < n) p[i] = v;
 }
 
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p) {
+template <bool REROOT>   // REROOT: a re-rooting engine - the moved game is parked for the drain's k_reroot_list instead of beginning its search here
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, ReuseDev r) {
     const int g = blockIdx.x, lane = azk_lane();
     // one vector load for the three words that decide whether this game moves now (almost never: the wave then ends at once)
     const int *up = d.done + g;
@@ -595,7 +609,9 @@ __global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p) {
     up = lane == 3 ? d.budget : up;                                // (the simulation budget lives in device memory: azk_async_set_budget)
     up = (lane == 4 && p.dirichlet) ? p.noise_key + g : up;
     up = lane == 5 ? (const int *)(p.slot_moves + g) : up;         // (low word: a slot plays far fewer than 2^31 moves)
+    if (REROOT) up = lane == 6 ? p.parked + g : up;                // a parked game has moved already: its sims_done passes any budget
     const int uw = *up;
+    if (REROOT && __builtin_amdgcn_readlane(uw, 6) != 0) return;
     if (__builtin_amdgcn_readlane(uw, 0) != 0 || __builtin_amdgcn_readlane(uw, 1) < __builtin_amdgcn_readlane(uw, 3) || __builtin_amdgcn_readlane(uw, 2) >= 0) return;
     // the next search's Dirichlet row is made a search ahead (k_noise_ahead, every drain); a game whose whole search fitted between two
     // drains (tiny budgets only) waits for it - a scheduling delay, the game's moves do not change
@@ -627,7 +643,34 @@ __global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p) {
         if (p.dirichlet) p.todo_list[atomicAdd(p.todo_count, 1)] = g;          // row mv + 2 is due
     }
     __syncthreads();
-    if (!dn) begin_search_one(d, p, g, L.cdf);
+    if (REROOT) {
+        if (uniform_i32(dn)) return;                               // an ended game restarts from a fresh root in the drain, as ever
+        const int child = played_child(d, g, cellc);
+        if (lane == 0) {
+            r.chosen_node[g] = child;
+            d.sims_done[g] = 0x7fffffff;                           // no budget reaches this: k_tree and k_unfinished see a finished search
+            p.parked[g] = 1;
+            p.reroot_list[atomicAdd(p.reroot_count, 1)] = g;
+        }
+    } else if (!dn) begin_search_one(d, p, g, L.cdf);
+}
+
+// drain, step 4 (re-rooting engines): the next search of every game parked since the last drain - its subtree under the played child
+// moved to the front of the arena, or a fresh root where reroot_one refuses; one wave per game.  The Dirichlet row is the one of the
+// game's new key slot_moves[g] (the move kernel moved only once that row existed); k_noise_ahead, behind this kernel, writes the other.
+__global__ __launch_bounds__(AZK_WAVE) void k_reroot_list(Dev d, AsyncDev p, ReuseDev r) {
+    const int n = uniform_i32(*p.reroot_count), n_sims = uniform_i32(d.budget[0]), A = d.g.action_dim;
+    for (int f = blockIdx.x; f < n; f += gridDim.x) {
+        const int g = uniform_i32(p.reroot_list[f]);
+        const int c = uniform_i32(r.chosen_node[g]);
+        const double *row = p.dirichlet ? p.noise + ((size_t)g * 2 + (size_t)(uniform_i32((int)p.slot_moves[g]) & 1)) * A : nullptr;
+        reroot_one(d, r, g, c, n_sims, row);
+        if (azk_lane() == 0) {
+            r.chosen_node[g] = -1;                                 // one search per recorded move
+            p.parked[g] = 0;
+            atomicAdd((unsigned long long *)&p.stats[7], 1ull);
+        }
+    }
 }
 
 // drain, step 1: list the finished games (done == 1) - the emission and restart kernels work through the list only
@@ -708,12 +751,13 @@ int32_t azk_begin_search_budget(azk_engine *e, const double *noise_dev, int32_t 
 }
 
 // ---- asynchronous self-play ---------------------------------------------------------------------------------------------
-int32_t azk_async_begin(azk_engine *e, const azk_async_config *c, void *stream) {
+static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *stream, bool reuse) {
     if (!e || !c || !c->stats_dev || c->n_sims < 1 || c->n_sims > e->cfg.max_sims || c->max_sims_per_launch < 1 || !(c->alpha > 0.0)) {
         if (e) e->err = "azk_async_begin: bad argument";
         return AZK_ERR_ARG;
     }
-    if (e->ru.mode) { e->err = "azk_async_begin: the asynchronous movers do not re-root (tree_reuse engines use the lock-step drivers)"; return AZK_ERR_STATE; }
+    if (e->ru.mode && !reuse) { e->err = "azk_async_begin: a tree_reuse engine begins with azk_async_begin_reuse (games are parked and re-rooted in the drain)"; return AZK_ERR_STATE; }
+    if (!e->ru.mode && reuse) { e->err = "azk_async_begin_reuse: the engine was created with tree_reuse = 0 (use azk_async_begin)"; return AZK_ERR_STATE; }
     if (c->record_capacity < 0 || (c->record_capacity > 0 && (!c->rec_meta_dev || !c->rec_q_dev || !c->rec_pi_dev))) { e->err = "azk_async_begin: record ring pointers missing"; return AZK_ERR_ARG; }
     Dev &d = e->d;
     if (d.K > 1) { e->err = "azk_async_begin: asynchronous moves run the sequential search (leaves_per_step = 1)"; return AZK_ERR_ARG; }
@@ -728,12 +772,22 @@ int32_t azk_async_begin(azk_engine *e, const azk_async_config *c, void *stream) 
         HIPCHK(e, dalloc(e, &a.fin_list, (size_t)d.G));
         HIPCHK(e, dalloc(e, &a.fin_count, 1));
     }
+    if (reuse && !a.parked) {
+        HIPCHK(e, dalloc(e, &a.parked, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &a.reroot_list, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &a.reroot_count, 1));
+    }
     a.n_sims = c->n_sims; a.sample_until = c->sample_until_move; a.dirichlet = c->dirichlet ? 1 : 0;
     a.seed = c->seed; a.first_game = c->first_global_game; a.alpha = c->alpha;
     a.stats = (long long *)c->stats_dev; a.rec_cap = c->record_capacity; a.rec_meta = c->rec_meta_dev; a.rec_q = c->rec_q_dev; a.rec_pi = c->rec_pi_dev;
     e->async_recycle = c->recycle ? 1 : 0;
     HIPCHK(e, hipMemsetAsync(a.slot_moves, 0, sizeof(long long) * (size_t)d.G, st));
     HIPCHK(e, hipMemsetAsync(a.stats, 0, sizeof(long long) * 16, st));
+    if (reuse) {                                                  // nothing parked, no child noted: every game's first search starts from a fresh root
+        HIPCHK(e, hipMemsetAsync(a.parked, 0, sizeof(int) * (size_t)d.G, st));
+        HIPCHK(e, hipMemsetAsync(a.reroot_count, 0, sizeof(int), st));
+        HIPCHK(e, hipMemsetAsync(e->ru.chosen_node, 0xff, sizeof(int) * (size_t)d.G, st));
+    }
     // the simulation budget lives in device memory (a captured step graph keeps working when it changes)
     e->budget_host[0] = c->n_sims; e->budget_host[1] = c->max_sims_per_launch;
     e->budget_host[2] = c->young_launch_us > 0 ? c->young_launch_us * e->ticks_per_us : 0;
@@ -756,12 +810,19 @@ int32_t azk_async_begin(azk_engine *e, const azk_async_config *c, void *stream) 
     return AZK_OK;
 }
 
+int32_t azk_async_begin(azk_engine *e, const azk_async_config *c, void *stream) { return async_begin(e, c, stream, false); }
+
+int32_t azk_async_begin_reuse(azk_engine *e, const azk_async_config *c, void *stream) { return async_begin(e, c, stream, true); }
+
 int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *values_dev, int32_t phases, void *stream) {
     if (!e || !e->async_on) { if (e) e->err = "azk_async_step: call azk_async_begin first"; return AZK_ERR_STATE; }
     const Dev &d = e->d;
     hipStream_t st = (hipStream_t)stream;
     if (phases & 1) { const int32_t rc = azk_launch_tree(e, true, true, true, logits_dev, values_dev, st); if (rc != AZK_OK) return rc; }
-    if (phases & 2) k_move_async<<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad);
+    if (phases & 2) {
+        if (e->ru.mode) k_move_async<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru);
+        else k_move_async<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru);
+    }
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -789,6 +850,10 @@ int32_t azk_async_drain(azk_engine *e, float *states_dev, double *pis_dev, float
         k_emit_mark<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d);
     }
     k_async_restart<<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->async_recycle);
+    if (e->ru.mode) {                                             // the next search of every game that moved since the last drain
+        k_reroot_list<<<(unsigned)d.G, AZK_WAVE, 0, st>>>(d, e->ad, e->ru);
+        HIPCHK(e, hipMemsetAsync(e->ad.reroot_count, 0, sizeof(int), st));
+    }
     if (e->ad.dirichlet) {                                        // the rows of the searches AFTER the ones begun since the last drain
         k_noise_ahead<<<(unsigned)(d.G < 512 ? d.G : 512), AZK_WAVE, 0, st>>>(d, e->ad);
         HIPCHK(e, hipMemsetAsync(e->ad.todo_count, 0, sizeof(int), st));

@@ -487,17 +487,25 @@ class AsyncSelfPlayRunner:
     the statistics; it looks at them one replay late, so the GPU never waits for the host.
 
     play_move() keeps the lock-step runner's contract for its callers (bench.py): it returns once the batch has played G more
-    moves in total (one move per resident game on average) - G x n_sims simulations, the same work as one lock-step move."""
+    moves in total (one move per resident game on average) - G x n_sims simulations, the same work as one lock-step move.
+
+    reroot = 1 | 2 (OPT-IN tree reuse across moves, azk.h azk_config.tree_reuse: 1 carry, 2 top-up; arena_nodes as Engine's): the games
+    of SelfPlayRunner(tree_reuse=reroot).  The move kernel parks a moved game and the drain re-roots it on the played child, so a game
+    idles from its move to the next drain - about half of `steps_per_graph` steps."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
-                 per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0):
+                 per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0):
         import torch
         if tree_reuse:
-            raise ValueError("AsyncSelfPlayRunner does not re-root: the asynchronous movers start a game's next search inside the move kernel "
-                             "(azk_async_begin refuses a tree_reuse engine); use SelfPlayRunner(tree_reuse=...)")
+            raise ValueError("AsyncSelfPlayRunner takes tree reuse as reroot=1 (carry) or reroot=2 (top-up): the re-root runs in the drain "
+                             "(azk_async_begin_reuse), not where SelfPlayRunner(tree_reuse=...) has it")
+        if reroot not in (0, 1, 2):
+            raise ValueError(f"AsyncSelfPlayRunner: reroot must be 0 (off), 1 (carry) or 2 (top-up), not {reroot!r}")
+        self.reroot = int(reroot)
         self.torch, self.replay, self.evaluator = torch, replay, evaluator
-        self.eng = Engine(game, n_games, n_sims, size=size, device=device, leaf_dtype=leaf_dtype, cache_entries=cache_entries, cache_shared=cache_shared)
+        self.eng = Engine(game, n_games, n_sims, size=size, device=device, leaf_dtype=leaf_dtype, cache_entries=cache_entries, cache_shared=cache_shared,
+                          tree_reuse=self.reroot, arena_nodes=arena_nodes)
         e = self.eng
         self.G, self._n_sims, self.n_split, self.leaves_per_step = n_games, n_sims, 1, 1
         self.per_launch, self.steps_per_graph, self.use_graph = int(per_launch), max(1, int(steps_per_graph)), use_graph
@@ -508,7 +516,7 @@ class AsyncSelfPlayRunner:
         e.reset_games()
         cap = (4 * n_games if record_capacity is None else record_capacity) if (on_records is not None or record_capacity) else 0
         self.stats, self.records = e.async_begin(n_sims, self.per_launch, SAMPLE_UNTIL[game], seed, first_global_game, alpha, dirichlet, recycle, cap,
-                                                 young_launch_us=young_launch_us)
+                                                 young_launch_us=young_launch_us, reroot=bool(self.reroot))
         self.rec_cap, self.rec_read, self.copy_stream = cap, 0, None
         self.h_stats = [torch.zeros(16, dtype=torch.int64, pin_memory=True) for _ in range(2)]
         self.events = [None, None]

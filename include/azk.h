@@ -88,7 +88,8 @@ typedef struct {
                             * Gomoku's legal moves are the cells next to a stone and grow along a line of play.)  With arena_nodes = 0 a carry engine allocates
                             * 1 + 2 * max_sims * max_children nodes per game (TWICE the default: about 17 GB instead of 9 GB at 2 048 games
                             * x 800 simulations of 15x15 Gomoku) and drops a subtree of more than about max_sims expansions; top-up fits
-                            * the default arena.  Not with leaves_per_step > 1 (AZK_ERR_ARG) nor azk_async_begin (AZK_ERR_STATE). */
+                            * the default arena.  Not with leaves_per_step > 1 (AZK_ERR_ARG).  The asynchronous movers take such an engine through
+                            * azk_async_begin_reuse; azk_async_begin answers AZK_ERR_STATE. */
     int32_t reserved[4];
 } azk_config;
 
@@ -150,8 +151,16 @@ int32_t azk_search_unfinished(azk_engine *e, int32_t *count_host, void *stream);
  * states_dev = NULL to skip), statistics, and - with recycle - Game() + first search of the next game in the slot.
  * The random keys are those of the lock-step drivers (azk_gen_noise with move_index = the slot's move counter), so a slot plays the
  * same games move for move.  Both calls only enqueue kernels (capturable).
- *   stats_dev  int64 [16], zeroed by azk_async_begin: [0] games finished, [1] their plies, [2] wins of player 0, [3] of player 1,
- *              [4] draws, [5] moves played, [6] records written (ring cursor), [7] searches begun
+ * An engine created with tree_reuse = 1 | 2 begins with azk_async_begin_reuse and plays the games of the lock-step reuse drivers.  Its
+ * move kernel does not begin the moved game's next search: it notes the played child and PARKS the game - the tree launches and the
+ * movers pass a parked game by, whatever azk_async_set_budget does meanwhile - and the next search of a moved game begins at the
+ * FOLLOWING azk_async_drain, which re-roots every parked game on its noted child (carry / top-up and the fresh-root fallbacks exactly
+ * as azk_config.tree_reuse describes, with n_sims = the budget as it stands at that drain, and the Dirichlet row of the game's new
+ * move key mixed into the new root's children) and un-parks it.  A game idles from its move to that drain, so such an engine wants
+ * the drain often (a few steps apart); azk_counters.roots_reused / nodes_carried count as in the lock-step drivers.
+ *   stats_dev  int64 [16], zeroed by azk_async_begin(_reuse): [0] games finished, [1] their plies, [2] wins of player 0, [3] of player 1,
+ *              [4] draws, [5] moves played, [6] records written (ring cursor), [7] searches begun - by azk_async_begin's move kernel,
+ *              by the drain's restart of a finished game, and by the drain's re-root of a parked game (carried subtree or fallback)
  *   record ring (optional, record_capacity entries; entry r % capacity): rec_meta int32 [cap][4] = slot, the slot's move counter,
  *              chosen cell, winner (-2 running, -1 draw, 0 / 1); rec_q float64 [cap] = root.value / root.visit; rec_pi float64 [cap][A] */
 typedef struct azk_async_config {
@@ -167,6 +176,9 @@ typedef struct azk_async_config {
     double *rec_q_dev, *rec_pi_dev;
 } azk_async_config;
 int32_t azk_async_begin(azk_engine *e, const azk_async_config *cfg, void *stream);
+/* azk_async_begin for an engine created with tree_reuse = 1 | 2 (AZK_ERR_STATE on any other; azk_async_begin answers the same on such an
+ * engine).  azk_async_step, azk_async_drain and azk_async_set_budget serve both kinds. */
+int32_t azk_async_begin_reuse(azk_engine *e, const azk_async_config *cfg, void *stream);
 /* phases: bit 0 = the tree launch, bit 1 = the move kernel (3 = both; separately for per-kernel timing) */
 int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *values_dev, int32_t phases, void *stream);
 /* change the simulation budget of every later launch (it lives in device memory, so captured step graphs pick it up); synchronises */

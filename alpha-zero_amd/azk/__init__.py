@@ -33,6 +33,7 @@ SYMBOLS = [
     "azk_nn_tail_gemm", "azk_nn_tail_gemm_lds", "azk_nn_tail_lds_footprint", "azk_nn_embed_fold_grid", "azk_nn_gemm_tok", "azk_nn_attention_tok", "azk_begin_search_budget", "azk_search_unfinished",
     "azk_nnx_embed_pool", "azk_nnx_embed_pool_leaves", "azk_nnx_gemm", "azk_nnx_gemm_h", "azk_nnx_gemm_h_lds",
     "azk_async_begin", "azk_async_step", "azk_async_drain", "azk_async_set_budget", "azk_async_begin_reuse",
+    "azk_set_playout_cap", "azk_begin_search_capped", "azk_get_search_full", "azk_async_record_flags",
 ]
 
 
@@ -158,6 +159,7 @@ class Engine:
         self.winner = torch.zeros(self.G, dtype=torch.int32, device=dev)
         self.done = torch.zeros(self.G, dtype=torch.int32, device=dev)
         self._noise = None
+        self.playout_cap = None                     # (p_full, n_fast) once set_playout_cap has switched the option on
         self.cache_entries = int(cache_entries)
         # with the eval cache a step can have pending (cached) leaves to expand although no leaf went to the evaluator
         need = cache_entries or self.K > 1
@@ -206,14 +208,37 @@ class Engine:
         self._noise = noise     # keep alive for the whole search
         self._chk(self.L.azk_begin_search(self.h, _p(noise), _stream()))
 
-    def begin_search_budget(self, noise, n_sims, per_launch=8):
+    def set_playout_cap(self, p_full, n_fast, seed=0, first_global_game=0):
+        """OPT-IN playout-cap randomisation (azk_set_playout_cap): from now on every search is FULL (n_sims simulations) with probability
+        p_full and FAST (n_fast simulations) otherwise, by a coin keyed (seed, first_global_game + g, move key); only the plies of full
+        searches are emitted as (state, pi, z).  Searches then begin with begin_search_budget(..., move_index=...) (lock-step) or
+        async_begin (which keys the coins by its own seed / first game).  n_fast = 0 switches it off."""
+        self._chk(self.L.azk_set_playout_cap(self.h, float(p_full), int(n_fast), int(seed), int(first_global_game), _stream()))
+        self.playout_cap = (float(p_full), int(n_fast)) if int(n_fast) else None
+        if self.playout_cap and getattr(self, "_search_full", None) is None:
+            self._search_full = self.torch.ones(self.G, dtype=self.torch.uint8, device=self.device)
+
+    def search_full(self):
+        """uint8 CUDA tensor [G]: 1 = the game's current search is a full one (azk_get_search_full; valid until the next call)."""
+        if self.playout_cap is None:
+            raise AzkError("search_full: no playout cap is set (set_playout_cap)")
+        self._chk(self.L.azk_get_search_full(self.h, _p(self._search_full), _stream()))
+        return self._search_full
+
+    def begin_search_budget(self, noise, n_sims, per_launch=8, move_index=None):
         """begin_search + a simulation budget: afterwards every step lets a game run on inside the launch while its simulations
-        need no evaluator (terminal leaves, eval-cache hits); step until unfinished() == 0, then step_expand_backup once."""
+        need no evaluator (terminal leaves, eval-cache hits); step until unfinished() == 0, then step_expand_backup once.
+        With a playout cap set, move_index (the coin's move key: the noise row's move_index) is required."""
         if noise is not None:
             assert noise.dtype == self.torch.float64 and noise.is_cuda and noise.is_contiguous()
             assert tuple(noise.shape) == (self.G, self.action_dim)
         assert n_sims <= self.max_sims
         self._noise = noise
+        if self.playout_cap is not None:
+            if move_index is None:
+                raise AzkError("begin_search_budget: an engine with a playout cap needs move_index (the coin's move key)")
+            self._chk(self.L.azk_begin_search_capped(self.h, _p(noise), int(n_sims), int(per_launch), int(move_index), _stream()))
+            return
         self._chk(self.L.azk_begin_search_budget(self.h, _p(noise), int(n_sims), int(per_launch), _stream()))
 
     def unfinished(self):
@@ -280,12 +305,12 @@ class Engine:
         if logits is not None:
             self.step_expand_backup(logits, values)
 
-    def search_budget(self, evaluator, n_sims, noise=None, per_launch=8):
+    def search_budget(self, evaluator, n_sims, noise=None, per_launch=8, move_index=None):
         """The same search as `search` - bit-identical trees - with budget stepping: a game runs on inside a launch while its
         simulations need no evaluator, so n_sims simulations take about (share of simulations that miss the cache) * n_sims
         launches, each with a fuller evaluator batch.  Returns the number of launches."""
         torch = self.torch
-        self.begin_search_budget(noise, n_sims, per_launch)
+        self.begin_search_budget(noise, n_sims, per_launch, move_index)
         logits = values = None
         launches = 0
         while True:
@@ -319,6 +344,9 @@ class Engine:
             rec = dict(meta=torch.zeros((record_capacity, 4), dtype=torch.int32, device=self.device),
                        q=torch.zeros(record_capacity, dtype=torch.float64, device=self.device),
                        pi=torch.zeros((record_capacity, self.action_dim), dtype=torch.float64, device=self.device))
+            if self.playout_cap is not None:                  # the ring's kind column: 1 = the record's search was a full one
+                rec["full"] = torch.ones(record_capacity, dtype=torch.uint8, device=self.device)
+                self._chk(self.L.azk_async_record_flags(self.h, _p(rec["full"])))
         self.async_records = rec
         c = AsyncConfig()
         c.n_sims, c.max_sims_per_launch, c.sample_until_move = int(n_sims), int(per_launch), int(min(sample_until, 1 << 30))

@@ -167,6 +167,10 @@ def declare(L, symbols):
     L.azk_async_step.argtypes = [vp, vp, vp, i32, vp]
     L.azk_async_set_budget.argtypes = [vp, i32, i32, vp]
     L.azk_async_drain.argtypes = [vp, vp, vp, vp, i64, vp, vp]
+    L.azk_set_playout_cap.argtypes = [vp, f64, i32, u64, i64, vp]
+    L.azk_begin_search_capped.argtypes = [vp, vp, i32, i32, i32, vp]
+    L.azk_get_search_full.argtypes = [vp, vp, vp]
+    L.azk_async_record_flags.argtypes = [vp, vp]
     L.azk_nn_ln_heads.argtypes = [vp, vp, vp, C.c_float, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.azk_nn_gemm_rows.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.azk_nn_layernorm_sum.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, vp, vp]

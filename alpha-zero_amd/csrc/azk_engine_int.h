@@ -89,6 +89,20 @@ struct ReuseDev {
     unsigned *pre;         // [G][words] k_reroot scratch: kept nodes below the word = new index of the word's first kept node
 };
 
+// playout-cap randomisation (azk_set_playout_cap, opt-in; n_fast == 0 otherwise): a search is FULL (the budget's simulations) with probability
+// p_full and FAST (n_fast simulations) otherwise, by a coin keyed like the search's noise row.  Its own argument of the kernels that exist only
+// for it (k_*_cap in azk_moves.hip): Dev, AsyncDev and ReuseDev - and every kernel an engine without the option launches - stay as they were
+struct CapDev {
+    int n_fast;                // simulations of a fast search; 0 = off
+    double p_full;
+    unsigned long long seed;   // the coin's key: (seed, first_game + g, move key), azk_async_begin puts its own seed / first game here
+    long long first_game;
+    uint8_t *search_full;      // [G] kind of the game's current search: 1 full, 0 fast
+    uint8_t *traj_full;        // [G][state_dim] kind of the search behind each ply of the current game (null where traj_pi is)
+    uint8_t *rec_full;         // asynchronous record ring: [record_capacity] kind per record, or null
+    long long *stats;          // asynchronous movers: the caller's stats_dev ([8] full, [9] fast searches begun), else null
+};
+
 struct LdsView {
     uint8_t *board;
     int *path;
@@ -250,6 +264,7 @@ struct azk_engine {
     int ticks_per_us = 100;              // constant-rate clock of wall_clock64()
     ReuseDev ru;                         // tree reuse (cfg.tree_reuse); ru.mode == 0: off, every pointer null
     AsyncDev ad;                         // asynchronous self-play (azk_async_begin); ad.slot_moves == nullptr: not set up
+    CapDev cp = {};                      // playout-cap randomisation (azk_set_playout_cap); cp.n_fast == 0: off
     bool async_on = false;
     int async_recycle = 1;
 };

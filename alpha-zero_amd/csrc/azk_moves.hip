@@ -70,7 +70,9 @@ __device__ __forceinline__ int rr_rank(const unsigned long long *bm, const unsig
     return (int)p + __popcll(w & rr_below(i & 63));
 }
 
-__device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_sims, const double *noise) {
+// sims_base: what sims_done starts from before the top-up preset - 0, or budget - target under a playout cap (n_sims is then the game's
+// own target and the budget stops the game after n_new simulations).
+__device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_sims, const double *noise, int sims_base = 0) {
     const int lane = azk_lane();
     const GameDesc &gd = d.g;
     const size_t base = (size_t)g * (size_t)d.cap;
@@ -134,6 +136,7 @@ __device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_
         if (lane == 0) {
             if (bad) atomicExch(d.err, AZK_ERR_STATE);
             fresh_root_one(d, g);
+            if (sims_base != 0) d.sims_done[g] = sims_base;
         }
         return;
     }
@@ -193,7 +196,7 @@ __device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_
         drop_pending_cache_claim(d, g);
         d.arena_top[g] = kept; d.root_f64[g] = noise != nullptr ? 1 : 0;
         clear_leaf_slots(d, g);
-        d.sims_done[g] = r.mode == 2 ? n_sims - n_new : 0;
+        d.sims_done[g] = sims_base + (r.mode == 2 ? n_sims - n_new : 0);
         count_add(d, CNT_REUSED, g, 1);
         count_add(d, CNT_CARRIED, g, kept);
     }
@@ -357,8 +360,9 @@ __device__ __forceinline__ int played_child(const Dev &d, int g, int cellc) {
     return (cellc >= 0 && found != 0x7fffffff) ? fc + found : -1;
 }
 
-__global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *uniforms, int sample_until,
-                                                       int *chosen, int *winner_out, int *done_out, int *chosen_node) {
+template <bool CAP>      // CAP: playout-cap engines (k_advance_cap) - the ply's kind goes into traj_full beside its pi
+__device__ __forceinline__ void advance_body(Dev d, CapDev cp, const double *uniforms, int sample_until,
+                                             int *chosen, int *winner_out, int *done_out, int *chosen_node) {
     const int g = blockIdx.x, lane = azk_lane();
     LdsView L = carve(d.g, d.path_cap, d.table_size);
     if (uniform_i32(d.done[g]) != 0) {
@@ -371,7 +375,9 @@ __global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *unifo
         return;
     }
     int win = -2, dn = 0, sum = 0;
+    const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
     const int cellc = advance_one(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum);
+    if (CAP && cellc >= 0 && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = cp.search_full[g];
     if (chosen_node) {
         const int child = played_child(d, g, cellc);               // tree reuse: the next search's root
         if (lane == 0) chosen_node[g] = dn == 0 ? child : -1;
@@ -384,24 +390,38 @@ __global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *unifo
     }
 }
 
+__global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *uniforms, int sample_until,
+                                                       int *chosen, int *winner_out, int *done_out, int *chosen_node) {
+    advance_body<false>(d, CapDev{}, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
+}
+
 // ------------------------------------------------------------------------------------------------
 // (state, pi, z) emission: train.save_data_to_buffer (train.py:30-49) with rotate_data / flip_data (train.py:8-27).
 // Position i of a finished game (side to move = i & 1): z = +-1 by winner (0 for a draw), state = canonical board;
 // positions 0 and 1 once, the others 8 times in the order rot0, lr(rot0), tb(rot0), rot90, lr(rot90), tb(rot90),
 // rot180, rot270 (np.rot90 is counter-clockwise).  Tuple t of the stream lands in slot t % capacity (deque(maxlen)).
 // ------------------------------------------------------------------------------------------------
-__global__ void k_emit_alloc(Dev d, unsigned long long *cursor, long long *game_base_out) {
+// CAP (playout-cap engines, the k_*_cap kernels): only the plies of FULL searches are emitted - ply i's group (1 tuple for i < 2, else 8) sits at
+// the sum of the groups of the full plies before it; the board before ply i is rebuilt from every earlier ply, fast ones included.
+template <bool CAP>
+__device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full, unsigned long long *cursor, long long *game_base_out) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.G) return;
     long long base = -1;                                          // the stream index stays 64-bit end to end (2^31 tuples = hours of self-play)
     if (d.done[g] == 1) {
         const int n = d.move_count[g];
-        const int tuples = n <= 2 ? n : 2 + 8 * (n - 2);
+        int tuples = n <= 2 ? n : 2 + 8 * (n - 2);
+        if (CAP) {
+            tuples = 0;
+            for (int i = 0; i < n; i++) if (traj_full[(size_t)g * d.g.state_dim + i]) tuples += i < 2 ? 1 : 8;
+        }
         base = (long long)atomicAdd(cursor, (unsigned long long)tuples);
     }
     d.emit_base[g] = base;
     if (game_base_out) game_base_out[g] = base;
 }
+
+__global__ void k_emit_alloc(Dev d, unsigned long long *cursor, long long *game_base_out) { emit_alloc_body<false>(d, nullptr, cursor, game_base_out); }
 
 __device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
     // source cell (row-major) of output cell (i, j) under transform t of the reference's emission order
@@ -419,9 +439,9 @@ __device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
     return si * N + sj;
 }
 
-template <bool LIST>     // LIST: the grid walks a list of finished games (asynchronous drain) instead of covering all G
-__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(Dev d, float *states, double *pis, float *zs, long long capacity,
-                                                            const unsigned long long *cursor, const int *list, const int *n_list) {
+template <bool LIST, bool CAP>
+__device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full, float *states, double *pis, float *zs, long long capacity,
+                                                 const unsigned long long *cursor, const int *list, const int *n_list) {
     const int S = d.g.state_dim, A = d.g.action_dim, rc = d.g.rc, F = d.g.planes, N = d.g.rows;
     const int lane = azk_lane();
     const int nb = LIST ? *n_list * S : (int)gridDim.x;
@@ -431,6 +451,7 @@ __global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(Dev d, float *states, 
     const int g = LIST ? list[gi] : gi;
     const long long base = d.emit_base[g];
     if (base < 0 || i >= d.move_count[g]) continue;
+    if (CAP && traj_full[(size_t)g * S + i] == 0) continue;      // a fast ply: it chose the move, it is not trained on
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     uint8_t *cells = sm;                                          // board before ply i
     for (int c = lane; c < rc; c += AZK_WAVE) cells[c] = 0;
@@ -442,7 +463,12 @@ __global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(Dev d, float *states, 
     const float z = winner == -1 ? 0.0f : (side == winner ? 1.0f : -1.0f);
     const double *pi = d.traj_pi + ((size_t)g * S + i) * A;
     const int ntr = i < 2 ? 1 : 8;
-    const long long first = base + (i < 2 ? i : 2 + 8 * (i - 2));
+    long long first = base + (i < 2 ? i : 2 + 8 * (i - 2));
+    if (CAP) {                                                    // tuples of the full plies before this one
+        int before = 0;
+        for (int j = lane; j < i; j += AZK_WAVE) if (traj_full[(size_t)g * S + j]) before += j < 2 ? 1 : 8;
+        first = base + wave_sum_i32(before);
+    }
     const long long stream_end = (long long)*cursor;              // after k_emit_alloc: one past the newest tuple of this call
     for (int t = 0; t < ntr; t++) {
         if (first + t < stream_end - capacity) continue;          // already pushed out of the ring by newer tuples (deque(maxlen))
@@ -460,6 +486,12 @@ __global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(Dev d, float *states, 
         if (lane == 0) zs[slot] = z;
     }
     }
+}
+
+template <bool LIST>     // LIST: the grid walks a list of finished games (asynchronous drain) instead of covering all G
+__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(Dev d, float *states, double *pis, float *zs, long long capacity,
+                                                            const unsigned long long *cursor, const int *list, const int *n_list) {
+    emit_tuples_body<LIST, false>(d, nullptr, states, pis, zs, capacity, cursor, list, n_list);
 }
 
 __global__ void k_emit_mark(Dev d) {
@@ -599,8 +631,30 @@ __global__ void k_fill_i32(int *p, int n, int v) {
     if (i < n) p[i] = v;
 }
 
-template <bool REROOT>   // REROOT: a re-rooting engine - the moved game is parked for the drain's k_reroot_list instead of beginning its search here
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, ReuseDev r) {
+// the coin of playout-cap randomisation: is the search of (seed, global game, move key) a FULL one?  Philox word 3 = 0xFFFFFFFE is no other
+// draw's (noise_uniform: 0xFFFFFFFF; noise_row: it < 64 and it | 0x40000000), so every noise row and move uniform is what it was.
+__device__ __forceinline__ bool cap_coin(const CapDev &c, int g, int move) {
+    const unsigned long long gg = (unsigned long long)(c.first_game + g);
+    uint32_t w[4] = {(uint32_t)gg, (uint32_t)(gg >> 32), (uint32_t)move, 0xFFFFFFFEu};
+    philox4x32_10(w, (uint32_t)c.seed, (uint32_t)(c.seed >> 32));
+    const double u = (double)((((unsigned long long)w[0] << 32) | w[1]) >> 11) * (1.0 / 9007199254740992.0);   // [0,1), as noise_uniform
+    return u < c.p_full;
+}
+// simulations of a search of that kind under the budget as it stands (a fast search never exceeds the budget)
+__device__ __forceinline__ int cap_target(const CapDev &c, bool full, int budget) { return full ? budget : min(c.n_fast, budget); }
+
+// a fresh-root search has just begun for game g (one lane): flip its coin and preset sims_done so that budget stepping stops a fast
+// search after n_fast simulations - what top-up does with the carried visits
+__device__ __forceinline__ void cap_begin_fresh(const Dev &d, const CapDev &c, int g, int move, bool count) {
+    const int n = d.budget[0];
+    const bool full = cap_coin(c, g, move);
+    c.search_full[g] = full ? 1 : 0;
+    d.sims_done[g] = n - cap_target(c, full, n);
+    if (count && c.stats != nullptr) atomicAdd((unsigned long long *)&c.stats[full ? 8 : 9], 1ull);
+}
+
+template <bool REROOT, bool CAP>   // the body of k_move_async / k_move_async_cap
+__device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp) {
     const int g = blockIdx.x, lane = azk_lane();
     // one vector load for the three words that decide whether this game moves now (almost never: the wave then ends at once)
     const int *up = d.done + g;
@@ -623,8 +677,11 @@ __global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, Reus
     const double q = d.W[base] / (double)d.H[base].N;                 // root.value / root.visit (gomoku.py:140), before the tree is reset
     int win = -2, dn = 0, sum = 0;
     const double u = noise_uniform(p.seed, (unsigned long long)(p.first_game + g), (int)mv);
+    const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
+    const int kind = CAP ? uniform_i32((int)cp.search_full[g]) : 1;     // of the search that is complete
     const int cellc = advance_one(d, L, g, true, u, p.sample_until, &win, &dn, &sum);
     if (cellc < 0) return;
+    if (CAP && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = (uint8_t)kind;
     if (p.rec_cap > 0) {                                           // the move's record: what the reference's self_play keeps per ply
         long long slot = 0;
         if (lane == 0) slot = (long long)(atomicAdd((unsigned long long *)&p.stats[6], 1ull) % (unsigned long long)p.rec_cap);
@@ -634,6 +691,7 @@ __global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, Reus
             p.rec_q[slot] = q;
             int *m = p.rec_meta + (size_t)slot * 4;
             m[0] = g; m[1] = (int)mv; m[2] = cellc; m[3] = win;
+            if (CAP && cp.rec_full != nullptr) cp.rec_full[slot] = (uint8_t)kind;
         }
     }
     __syncthreads();
@@ -652,8 +710,14 @@ __global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, Reus
             p.parked[g] = 1;
             p.reroot_list[atomicAdd(p.reroot_count, 1)] = g;
         }
-    } else if (!dn) begin_search_one(d, p, g, L.cdf);
+    } else if (!dn) {
+        begin_search_one(d, p, g, L.cdf);
+        if (CAP && lane == 0) cap_begin_fresh(d, cp, g, (int)mv + 1, true);
+    }
 }
+
+template <bool REROOT>   // REROOT: a re-rooting engine - the moved game is parked for the drain's k_reroot_list instead of beginning its search here
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, ReuseDev r) { move_async_body<REROOT, false>(d, p, r, CapDev{}); }
 
 // drain, step 4 (re-rooting engines): the next search of every game parked since the last drain - its subtree under the played child
 // moved to the front of the arena, or a fresh root where reroot_one refuses; one wave per game.  The Dirichlet row is the one of the
@@ -680,7 +744,8 @@ __global__ void k_async_list(Dev d, AsyncDev p) {
 }
 
 // drain, step 3: statistics + Game() + the next search for every listed game
-__global__ __launch_bounds__(AZK_WAVE) void k_async_restart(Dev d, AsyncDev p, int recycle) {
+template <bool CAP>
+__device__ __forceinline__ void async_restart_body(Dev d, AsyncDev p, int recycle, CapDev cp) {
     const int lane = azk_lane();
     LdsView L = carve(d.g, d.path_cap, d.table_size);
     const int n = *p.fin_count;
@@ -698,9 +763,79 @@ __global__ __launch_bounds__(AZK_WAVE) void k_async_restart(Dev d, AsyncDev p, i
         if (lane == 0) { d.to_move[g] = 0; d.move_count[g] = 0; d.done[g] = 0; d.winner[g] = -2; }
         __syncthreads();
         begin_search_one(d, p, g, L.cdf);
+        if (CAP && lane == 0) cap_begin_fresh(d, cp, g, (int)p.slot_moves[g], true);
         __syncthreads();
     }
 }
+
+__global__ __launch_bounds__(AZK_WAVE) void k_async_restart(Dev d, AsyncDev p, int recycle) { async_restart_body<false>(d, p, recycle, CapDev{}); }
+
+// ------------------------------------------------------------------------------------------------
+// Playout-cap randomisation (azk_set_playout_cap, opt-in): the kernels a capped engine launches IN PLACE of their
+// namesakes.  Each is its namesake's body with CAP set, so an engine without the option runs the instruction streams it always ran.
+// A fast search is the same search with fewer simulations: sims_done starts at budget - n_fast and budget stepping (k_tree<MULTI>,
+// k_unfinished, the movers' "search complete" test) ends it after n_fast.  The root's Dirichlet mix lives in k_tree and stays on for
+// fast searches too.
+// ------------------------------------------------------------------------------------------------
+__global__ void k_begin_search_cap(Dev d, CapDev c, int move) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= d.G) return;
+    if (g == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
+    fresh_root_one(d, g);
+    cap_begin_fresh(d, c, g, move, false);
+}
+
+// azk_begin_search_capped on a reuse engine: the per-game target replaces n_sims in reroot_one
+__global__ __launch_bounds__(AZK_WAVE) void k_reroot_cap(Dev d, ReuseDev r, CapDev cp, int move) {
+    const int g = blockIdx.x;
+    if (g == 0 && azk_lane() == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
+    const int c = uniform_i32(r.chosen_node[g]), n_sims = uniform_i32(d.budget[0]);
+    const bool full = uniform_i32((int)cap_coin(cp, g, move)) != 0;
+    const int target = cap_target(cp, full, n_sims);
+    reroot_one(d, r, g, c, target, d.noise != nullptr ? d.noise + (size_t)g * d.g.action_dim : nullptr, n_sims - target);
+    if (azk_lane() == 0) { r.chosen_node[g] = -1; cp.search_full[g] = full ? 1 : 0; }
+}
+
+__global__ __launch_bounds__(AZK_WAVE) void k_advance_cap(Dev d, CapDev cp, const double *uniforms, int sample_until,
+                                                           int *chosen, int *winner_out, int *done_out, int *chosen_node) {
+    advance_body<true>(d, cp, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
+}
+
+__global__ void k_emit_alloc_cap(Dev d, CapDev cp, unsigned long long *cursor, long long *game_base_out) {
+    emit_alloc_body<true>(d, cp.traj_full, cursor, game_base_out);
+}
+
+template <bool LIST>
+__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples_cap(Dev d, CapDev cp, float *states, double *pis, float *zs, long long capacity,
+                                                                const unsigned long long *cursor, const int *list, const int *n_list) {
+    emit_tuples_body<LIST, true>(d, cp.traj_full, states, pis, zs, capacity, cursor, list, n_list);
+}
+
+template <bool REROOT>
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async_cap(Dev d, AsyncDev p, ReuseDev r, CapDev cp) { move_async_body<REROOT, true>(d, p, r, cp); }
+
+// k_reroot_list with the coin of the game's new move key deciding the search's target
+__global__ __launch_bounds__(AZK_WAVE) void k_reroot_list_cap(Dev d, AsyncDev p, ReuseDev r, CapDev cp) {
+    const int n = uniform_i32(*p.reroot_count), n_sims = uniform_i32(d.budget[0]), A = d.g.action_dim;
+    for (int f = blockIdx.x; f < n; f += gridDim.x) {
+        const int g = uniform_i32(p.reroot_list[f]);
+        const int c = uniform_i32(r.chosen_node[g]);
+        const int key = uniform_i32((int)p.slot_moves[g]);
+        const double *row = p.dirichlet ? p.noise + ((size_t)g * 2 + (size_t)(key & 1)) * A : nullptr;
+        const bool full = uniform_i32((int)cap_coin(cp, g, key)) != 0;
+        const int target = cap_target(cp, full, n_sims);
+        reroot_one(d, r, g, c, target, row, n_sims - target);
+        if (azk_lane() == 0) {
+            r.chosen_node[g] = -1;                                 // one search per recorded move
+            p.parked[g] = 0;
+            atomicAdd((unsigned long long *)&p.stats[7], 1ull);
+            cp.search_full[g] = full ? 1 : 0;
+            if (cp.stats != nullptr) atomicAdd((unsigned long long *)&cp.stats[full ? 8 : 9], 1ull);
+        }
+    }
+}
+
+__global__ __launch_bounds__(AZK_WAVE) void k_async_restart_cap(Dev d, AsyncDev p, int recycle, CapDev cp) { async_restart_body<true>(d, p, recycle, cp); }
 
 }  // namespace
 
@@ -724,6 +859,7 @@ int32_t azk_reset_games(azk_engine *e, int32_t first, int32_t count, void *strea
 
 int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
+    if (e->cp.n_fast) { e->err = "azk_begin_search: a playout cap is set - its searches begin with azk_begin_search_capped (budget + move index)"; return AZK_ERR_STATE; }
     e->d.noise = noise_dev; e->d.noise_sel = nullptr;
     if (e->ru.mode == 2) { e->err = "azk_begin_search: top-up tree reuse needs the budget (azk_begin_search_budget)"; return AZK_ERR_STATE; }
     e->multi = false;
@@ -733,8 +869,8 @@ int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream) {
     return AZK_OK;
 }
 
-int32_t azk_begin_search_budget(azk_engine *e, const double *noise_dev, int32_t n_sims, int32_t max_sims_per_launch, void *stream) {
-    if (!e || n_sims < 1 || n_sims > e->cfg.max_sims || max_sims_per_launch < 1) { if (e) e->err = "azk_begin_search_budget: bad argument"; return AZK_ERR_ARG; }
+// azk_begin_search_budget (move_index < 0) and azk_begin_search_capped
+static int32_t begin_budget(azk_engine *e, const double *noise_dev, int32_t n_sims, int32_t max_sims_per_launch, int32_t move_index, void *stream) {
     e->d.noise = noise_dev; e->d.noise_sel = nullptr;
     e->multi = true;
     if (e->budget_host[0] != n_sims || e->budget_host[1] != (e->d.K > 1 ? e->d.K : max_sims_per_launch)) {
@@ -744,9 +880,61 @@ int32_t azk_begin_search_budget(azk_engine *e, const double *noise_dev, int32_t 
         HIPCHK(e, hipMemcpyAsync(e->d.budget, e->budget_host, sizeof e->budget_host, hipMemcpyHostToDevice, (hipStream_t)stream));
         HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     }
-    if (e->ru.mode) k_reroot<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d, e->ru, n_sims);
+    if (move_index >= 0) {                                        // playout cap: the coin of (seed, global game, move_index) sets each game's target
+        if (e->ru.mode) k_reroot_cap<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d, e->ru, e->cp, move_index);
+        else k_begin_search_cap<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d, e->cp, move_index);
+    } else if (e->ru.mode) k_reroot<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d, e->ru, n_sims);
     else k_begin_search<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d);
     HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_begin_search_budget(azk_engine *e, const double *noise_dev, int32_t n_sims, int32_t max_sims_per_launch, void *stream) {
+    if (!e || n_sims < 1 || n_sims > e->cfg.max_sims || max_sims_per_launch < 1) { if (e) e->err = "azk_begin_search_budget: bad argument"; return AZK_ERR_ARG; }
+    if (e->cp.n_fast) { e->err = "azk_begin_search_budget: a playout cap is set - its searches begin with azk_begin_search_capped (the coin needs the move index)"; return AZK_ERR_STATE; }
+    return begin_budget(e, noise_dev, n_sims, max_sims_per_launch, -1, stream);
+}
+
+// ---- playout-cap randomisation ---------------------------------------------------------------------------------------------
+int32_t azk_set_playout_cap(azk_engine *e, double p_full, int32_t n_fast, uint64_t seed, int64_t first_global_game, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_playout_cap: set the cap before azk_async_begin"; return AZK_ERR_STATE; }
+    if (n_fast == 0) { e->cp.n_fast = 0; return AZK_OK; }         // off: the engine launches what it launched before
+    if (!(p_full >= 0.0 && p_full <= 1.0)) { e->err = "azk_set_playout_cap: p_full must lie in [0, 1]"; return AZK_ERR_ARG; }
+    if (n_fast < 1 || n_fast > e->cfg.max_sims) { e->err = "azk_set_playout_cap: n_fast must lie in [1, max_sims]"; return AZK_ERR_ARG; }
+    if (e->d.K > 1) { e->err = "azk_set_playout_cap: a playout cap does not combine with leaves_per_step > 1 (virtual loss counts completed simulations differently)"; return AZK_ERR_ARG; }
+    const Dev &d = e->d;
+    CapDev &c = e->cp;
+    if (!c.search_full) {
+        HIPCHK(e, dalloc(e, &c.search_full, (size_t)d.G));
+        if (d.traj_pi) HIPCHK(e, dalloc(e, &c.traj_full, (size_t)d.G * d.g.state_dim));
+    }
+    HIPCHK(e, hipMemsetAsync(c.search_full, 1, (size_t)d.G, (hipStream_t)stream));
+    if (c.traj_full) HIPCHK(e, hipMemsetAsync(c.traj_full, 1, (size_t)d.G * d.g.state_dim, (hipStream_t)stream));
+    c.p_full = p_full; c.seed = seed; c.first_game = first_global_game; c.stats = nullptr; c.rec_full = nullptr;
+    c.n_fast = n_fast;
+    return AZK_OK;
+}
+
+int32_t azk_begin_search_capped(azk_engine *e, const double *noise_dev, int32_t n_sims, int32_t max_sims_per_launch, int32_t move_index, void *stream) {
+    if (!e || n_sims < 1 || n_sims > e->cfg.max_sims || max_sims_per_launch < 1 || move_index < 0) { if (e) e->err = "azk_begin_search_capped: bad argument"; return AZK_ERR_ARG; }
+    if (!e->cp.n_fast) { e->err = "azk_begin_search_capped: no playout cap is set (azk_set_playout_cap)"; return AZK_ERR_STATE; }
+    if (e->cp.n_fast > n_sims) { e->err = "azk_begin_search_capped: n_fast exceeds n_sims"; return AZK_ERR_ARG; }
+    return begin_budget(e, noise_dev, n_sims, max_sims_per_launch, move_index, stream);
+}
+
+int32_t azk_get_search_full(azk_engine *e, uint8_t *full_dev, void *stream) {
+    if (!e || !full_dev) return AZK_ERR_ARG;
+    if (!e->cp.n_fast) { e->err = "azk_get_search_full: no playout cap is set (azk_set_playout_cap)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(full_dev, e->cp.search_full, (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_async_record_flags(azk_engine *e, uint8_t *rec_full_dev) {
+    if (!e) return AZK_ERR_ARG;
+    if (!e->cp.n_fast) { e->err = "azk_async_record_flags: no playout cap is set (azk_set_playout_cap)"; return AZK_ERR_STATE; }
+    if (e->async_on) { e->err = "azk_async_record_flags: call it before azk_async_begin"; return AZK_ERR_STATE; }
+    e->cp.rec_full = rec_full_dev;
     return AZK_OK;
 }
 
@@ -759,6 +947,7 @@ static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *strea
     if (e->ru.mode && !reuse) { e->err = "azk_async_begin: a tree_reuse engine begins with azk_async_begin_reuse (games are parked and re-rooted in the drain)"; return AZK_ERR_STATE; }
     if (!e->ru.mode && reuse) { e->err = "azk_async_begin_reuse: the engine was created with tree_reuse = 0 (use azk_async_begin)"; return AZK_ERR_STATE; }
     if (c->record_capacity < 0 || (c->record_capacity > 0 && (!c->rec_meta_dev || !c->rec_q_dev || !c->rec_pi_dev))) { e->err = "azk_async_begin: record ring pointers missing"; return AZK_ERR_ARG; }
+    if (e->cp.n_fast > c->n_sims) { e->err = "azk_async_begin: the playout cap's n_fast exceeds n_sims"; return AZK_ERR_ARG; }
     Dev &d = e->d;
     if (d.K > 1) { e->err = "azk_async_begin: asynchronous moves run the sequential search (leaves_per_step = 1)"; return AZK_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
@@ -798,7 +987,10 @@ static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *strea
     e->multi = true;
     e->async_on = true;
     // first search of every game: fresh roots + the Dirichlet rows of move keys 0 (this search) and 1 (the next one)
-    k_begin_search<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d);
+    if (e->cp.n_fast) {                                           // the coins share the noise rows' key: this run's seed and first game
+        e->cp.seed = a.seed; e->cp.first_game = a.first_game; e->cp.stats = a.stats;
+        k_begin_search_cap<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, e->cp, 0);
+    } else k_begin_search<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d);
     HIPCHK(e, hipMemsetAsync(a.todo_count, 0, sizeof(int), st));
     if (a.dirichlet) {
         const int A = d.g.action_dim;
@@ -820,7 +1012,10 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
     hipStream_t st = (hipStream_t)stream;
     if (phases & 1) { const int32_t rc = azk_launch_tree(e, true, true, true, logits_dev, values_dev, st); if (rc != AZK_OK) return rc; }
     if (phases & 2) {
-        if (e->ru.mode) k_move_async<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru);
+        if (e->cp.n_fast) {
+            if (e->ru.mode) k_move_async_cap<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp);
+            else k_move_async_cap<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp);
+        } else if (e->ru.mode) k_move_async<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru);
         else k_move_async<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru);
     }
     HIPCHK(e, hipGetLastError());
@@ -843,15 +1038,23 @@ int32_t azk_async_drain(azk_engine *e, float *states_dev, double *pis_dev, float
     k_async_list<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, e->ad);
     if (states_dev) {
         if (!pis_dev || !zs_dev || !cursor_dev || capacity < 1 || !d.traj_pi) { e->err = "azk_async_drain: bad replay arguments"; return AZK_ERR_ARG; }
-        k_emit_alloc<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, (unsigned long long *)cursor_dev, nullptr);
         const int blocks = d.G * d.g.state_dim < 16384 ? d.G * d.g.state_dim : 16384;
+        if (e->cp.n_fast) {
+            k_emit_alloc_cap<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, e->cp, (unsigned long long *)cursor_dev, nullptr);
+            k_emit_tuples_cap<true><<<(unsigned)blocks, AZK_WAVE, up16(d.g.rc), st>>>(d, e->cp, states_dev, pis_dev, zs_dev, (long long)capacity,
+                                                                                    (const unsigned long long *)cursor_dev, e->ad.fin_list, e->ad.fin_count);
+        } else {
+        k_emit_alloc<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, (unsigned long long *)cursor_dev, nullptr);
         k_emit_tuples<true><<<(unsigned)blocks, AZK_WAVE, up16(d.g.rc), st>>>(d, states_dev, pis_dev, zs_dev, (long long)capacity,
                                                                             (const unsigned long long *)cursor_dev, e->ad.fin_list, e->ad.fin_count);
+        }
         k_emit_mark<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d);
     }
-    k_async_restart<<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->async_recycle);
+    if (e->cp.n_fast) k_async_restart_cap<<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->async_recycle, e->cp);
+    else k_async_restart<<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->async_recycle);
     if (e->ru.mode) {                                             // the next search of every game that moved since the last drain
-        k_reroot_list<<<(unsigned)d.G, AZK_WAVE, 0, st>>>(d, e->ad, e->ru);
+        if (e->cp.n_fast) k_reroot_list_cap<<<(unsigned)d.G, AZK_WAVE, 0, st>>>(d, e->ad, e->ru, e->cp);
+        else k_reroot_list<<<(unsigned)d.G, AZK_WAVE, 0, st>>>(d, e->ad, e->ru);
         HIPCHK(e, hipMemsetAsync(e->ad.reroot_count, 0, sizeof(int), st));
     }
     if (e->ad.dirichlet) {                                        // the rows of the searches AFTER the ones begun since the last drain
@@ -868,9 +1071,15 @@ int32_t azk_emit_finished(azk_engine *e, float *states_dev, double *pis_dev, flo
     const Dev &d = e->d;
     if (!d.traj_pi) { e->err = "azk_emit_finished: (state, pi, z) emission needs a square board with one action per cell"; return AZK_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
+    if (e->cp.n_fast) {                                           // playout cap: the plies of full searches only
+        k_emit_alloc_cap<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, e->cp, (unsigned long long *)cursor_dev, (long long *)game_base_dev);
+        k_emit_tuples_cap<false><<<(unsigned)(d.G * d.g.state_dim), AZK_WAVE, up16(d.g.rc), st>>>(d, e->cp, states_dev, pis_dev, zs_dev, (long long)capacity,
+                                                                                                 (const unsigned long long *)cursor_dev, nullptr, nullptr);
+    } else {
     k_emit_alloc<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, (unsigned long long *)cursor_dev, (long long *)game_base_dev);
     k_emit_tuples<false><<<(unsigned)(d.G * d.g.state_dim), AZK_WAVE, up16(d.g.rc), st>>>(d, states_dev, pis_dev, zs_dev, (long long)capacity,
                                                                                          (const unsigned long long *)cursor_dev, nullptr, nullptr);
+    }
     k_emit_mark<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
@@ -893,7 +1102,9 @@ int32_t azk_root_stats(azk_engine *e, double *pi_dev, double *q_dev, int32_t *ro
 int32_t azk_advance(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t *chosen_cell_dev,
                     int32_t *winner_dev, int32_t *done_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
-    k_advance<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, uniforms_dev, sample_until_move,
+    if (e->cp.n_fast) k_advance_cap<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, uniforms_dev, sample_until_move,
+                                                                                               chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
+    else k_advance<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, uniforms_dev, sample_until_move,
                                                                          chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;

@@ -27,11 +27,33 @@ def cells_to_board(cells, planes, rows, cols, side_to_move):
     return b
 
 
+def check_playout_cap(playout_cap, n_sims, leaves_per_step=1):
+    """playout_cap = (p_full, n_fast) -> (float, int), or None for off.  OPT-IN playout-cap randomisation (include/azk.h azk_set_playout_cap;
+    DESIGN section 18): a search is FULL (n_sims simulations) with probability p_full, else FAST (n_fast simulations); only full plies are
+    trained on.  Raises ValueError for what the engine refuses too: p_full outside [0, 1], n_fast outside [1, n_sims], virtual loss."""
+    if playout_cap is None:
+        return None
+    try:
+        p_full, n_fast = playout_cap
+        p_full, n_fast = float(p_full), int(n_fast)
+    except (TypeError, ValueError):
+        raise ValueError(f"playout_cap must be (p_full, n_fast), not {playout_cap!r}")
+    if not 0.0 <= p_full <= 1.0:                                  # (NaN fails both comparisons)
+        raise ValueError(f"playout_cap: p_full must lie in [0, 1], not {p_full!r}")
+    low = min(n_sims) if isinstance(n_sims, (tuple, list)) else n_sims
+    if not 1 <= n_fast <= low:
+        raise ValueError(f"playout_cap: n_fast must lie in [1, n_sims = {low}], not {n_fast!r}")
+    if int(leaves_per_step) > 1:
+        raise ValueError("playout_cap does not combine with leaves_per_step > 1 (virtual loss counts completed simulations differently)")
+    return p_full, n_fast
+
+
 class SelfPlayResult:
-    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base")
+    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base", "full")
 
     def __init__(self):
         self.boards, self.actions, self.pis, self.qs, self.winner, self.cells = [], [(-1, -1)], [], [], None, []
+        self.full = []               # per ply: was its search a full one (always True without playout_cap); only those plies are trained on
         self.replay_base = None      # first tuple index in the DeviceReplay stream (when a replay ring is attached)
 
     def as_reference_tuple(self):
@@ -42,7 +64,7 @@ class SelfPlayResult:
 def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
                     alpha=0.03, noise_fn=None, uniform_fn=None, device=0, leaf_dtype="float32", engine=None,
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
-                    budget_stepping=False, leaves_per_step=1, tree_reuse=0):
+                    budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -55,13 +77,20 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     (test.compare(Game, None, model, ...), main.py:76).  tree_reuse (OPT-IN, changes search results; azk.h azk_config.tree_reuse): 1 = every
     search after a game's first starts on the subtree under the move that was played and runs n_sims more simulations, 2 = only as
     many as bring the root back to n_sims visits (driven by the simulation budget).  vanilla_rng: uint32 [G, 625] MT19937 states (default: one
-    np.random.RandomState per global game index derived from `seed`).
+    np.random.RandomState per global game index derived from `seed`).  playout_cap = (p_full, n_fast) (OPT-IN, check_playout_cap): per ply a
+    coin keyed (seed, global game, move) makes the search full or fast; SelfPlayResult.full records it and a replay ring gets the full plies only.
     """
     import torch
+    cap = check_playout_cap(playout_cap, n_sims, leaves_per_step)
+    if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
+        raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
     max_sims = max(n_sims) if isinstance(n_sims, (tuple, list)) else n_sims
     eng = engine or Engine(game, n_games, max_sims, size=size, device=device, leaf_dtype=leaf_dtype, cache_entries=cache_entries,
                            cache_shared=cache_shared, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse)
-    budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2   # virtual-loss and top-up engines are driven by the simulation budget
+    if cap is not None:
+        eng.set_playout_cap(cap[0], cap[1], seed, first_global_game)
+    # virtual-loss, top-up and capped engines are driven by the simulation budget
+    budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
     assert eng.G == n_games
     G, A = eng.G, eng.action_dim
     eng.reset_games()
@@ -94,9 +123,10 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         if ev is None:
             eng.vanilla_search(ns, chunk=vanilla_chunk)
         elif budget_stepping:
-            eng.search_budget(ev, ns, noise if dirichlet else None)
+            eng.search_budget(ev, ns, noise if dirichlet else None, move_index=move)
         else:
             eng.search(ev, ns, noise if dirichlet else None)
+        full_h = eng.search_full().cpu().numpy() if eng.playout_cap is not None else None
         pi, q, _ = eng.root_stats()
         cells_before, to_move, _ = eng.get_positions()
         chosen, winner, done = eng.advance(uni, su)
@@ -108,6 +138,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
             r.boards.append(cells_to_board(cells_before[g], eng.planes, eng.rows, eng.cols, to_move[g]))
             r.pis.append(pi_h[g].copy())
             r.qs.append(float(q_h[g]))
+            r.full.append(True if full_h is None else bool(full_h[g]))
             c = int(chosen_h[g])
             r.cells.append(c)
             r.actions.append((c // eng.cols, c % eng.cols))
@@ -140,6 +171,7 @@ class _Half:
         self.h_winner = torch.zeros(e.G, dtype=torch.int32, **pin)
         self.h_done = torch.zeros(e.G, dtype=torch.int32, **pin)
         self.h_stats = torch.zeros(8, dtype=torch.int64, **pin)
+        self.h_full = torch.ones(e.G, dtype=torch.uint8, **pin)      # playout cap: kind of each slot's search (1 = full); all ones without
         # static buffers so a captured step graph always sees the same addresses
         self.noise_buf = torch.zeros((e.G, e.action_dim), dtype=torch.float64, device=e.device) if dirichlet else None
         self.logits_buf = torch.zeros((e.slots, e.action_dim), dtype=torch.float32, device=e.device)
@@ -193,14 +225,20 @@ class SelfPlayRunner:
     of the other.  Groups are independent games, so this changes no result.
 
     RNG key = (seed, first_global_game + slot, move counter): results do not depend on the sharding.
+
+    playout_cap = (p_full, n_fast) (OPT-IN, check_playout_cap): every search is full or fast by a coin of the same key; the searches run under
+    the simulation budget (as tree_reuse=2), `record_full` (uint8 [group size], valid inside on_records) tells the kind of each record, and
+    the replay ring gets the plies of full searches only.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
                  alpha=0.03, device=0, leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None,
                  use_graph=False, n_split=1, replay=None, cache_entries=0, cache_shared=False, budget_stepping=False, per_launch=8,
                  steps_per_graph=32,
-                 leaves_per_step=1, tree_reuse=0):
+                 leaves_per_step=1, tree_reuse=0, playout_cap=None):
         import torch
+        self.playout_cap = check_playout_cap(playout_cap, n_sims, leaves_per_step)
+        self.record_full = None
         self.replay = replay
         self.torch = torch
         # leaves_per_step > 1: OPT-IN virtual-loss expansion (K leaves in flight per game; changes search results); it is driven
@@ -209,7 +247,8 @@ class SelfPlayRunner:
         # tree_reuse: OPT-IN tree reuse across moves (azk.h azk_config.tree_reuse; changes search results): 1 = carry, 2 = top-up.  Top-up
         # stops a game at n_sims root visits through the simulation budget, so it turns budget stepping on (eager runner: Engine.search_budget)
         self.tree_reuse = int(tree_reuse)
-        self.budget_stepping, self.per_launch = (budget_stepping or self.leaves_per_step > 1 or self.tree_reuse == 2) and use_graph, per_launch
+        self.budget_stepping = (budget_stepping or self.leaves_per_step > 1 or self.tree_reuse == 2 or self.playout_cap is not None) and use_graph
+        self.per_launch = per_launch
         assert self.leaves_per_step == 1 or use_graph, "virtual-loss mode runs on the graph runner"
         self.launches = 0               # simulation-step launches issued (per game group) since construction
         self.use_graph = use_graph
@@ -232,8 +271,10 @@ class SelfPlayRunner:
         self.streams = concurrent_streams(torch, self.eng.device, self.n_split) if self.n_split > 1 else []
         self.move_idx = 0
         self.plies_played = 0
-        for h in self.halves:
+        for i, h in enumerate(self.halves):
             h.eng.reset_games()
+            if self.playout_cap is not None:
+                h.eng.set_playout_cap(self.playout_cap[0], self.playout_cap[1], seed, first_global_game + i * per)
 
     # ---- one move for every slot -------------------------------------------------------------------------
     def play_move(self):
@@ -249,6 +290,8 @@ class SelfPlayRunner:
             self.search(self.halves[0].noise_buf)
         for h in self.halves:
             e = h.eng
+            if self.playout_cap is not None:
+                h.h_full.copy_(e.search_full(), non_blocking=True)
             pi, q, _ = e.root_stats()
             h.h_pi.copy_(pi, non_blocking=True)
             h.h_q.copy_(q, non_blocking=True)
@@ -265,14 +308,15 @@ class SelfPlayRunner:
         for i, h in enumerate(self.halves):
             self.plies_played += int((h.h_chosen >= 0).sum())
             if self.on_records is not None:
+                self.record_full = h.h_full
                 self.on_records(self.move_idx, i * per, h.h_pi, h.h_q, h.h_chosen, h.h_winner, h.h_done)
         self.move_idx += 1
 
     def search(self, noise):
         """Eager stepping (host sync per simulation, n_leaf-sized evaluator batches); optional k_tree event timing."""
         e, torch, kt = self.eng, self.torch, self.kernel_timer
-        if self.tree_reuse == 2:
-            e.search_budget(self.evaluator, self.n_sims, noise if self.dirichlet else None, self.per_launch)
+        if self.tree_reuse == 2 or self.playout_cap is not None:
+            e.search_budget(self.evaluator, self.n_sims, noise if self.dirichlet else None, self.per_launch, move_index=self.move_idx)
             return
         e.begin_search(noise)
         logits = values = None
@@ -362,7 +406,7 @@ class SelfPlayRunner:
         torch = self.torch
         for h in self.halves:
             if self.budget_stepping:
-                h.eng.begin_search_budget(h.noise_buf, self.n_sims, self.per_launch)
+                h.eng.begin_search_budget(h.noise_buf, self.n_sims, self.per_launch, move_index=self.move_idx)
             else:
                 h.eng.begin_search(h.noise_buf)
         cur = torch.cuda.current_stream()
@@ -430,7 +474,8 @@ class SelfPlayRunner:
         else:
             # no game can finish before its budget's worth of cache misses: a first stretch without looking, then a look (one
             # 4-byte read-back) every few launches
-            s, first = done, max(done, int(0.36 * self.n_sims / self.leaves_per_step))
+            longest = self.playout_cap[1] if self.playout_cap is not None and self.playout_cap[0] == 0.0 else self.n_sims   # (all searches fast)
+            s, first = done, max(done, int(0.36 * longest / self.leaves_per_step))
             while True:
                 stop = first if s < first else s + 8
                 while s < stop:
@@ -491,12 +536,18 @@ class AsyncSelfPlayRunner:
 
     reroot = 1 | 2 (OPT-IN tree reuse across moves, azk.h azk_config.tree_reuse: 1 carry, 2 top-up; arena_nodes as Engine's): the games
     of SelfPlayRunner(tree_reuse=reroot).  The move kernel parks a moved game and the drain re-roots it on the played child, so a game
-    idles from its move to the next drain - about half of `steps_per_graph` steps."""
+    idles from its move to the next drain - about half of `steps_per_graph` steps.
+
+    playout_cap = (p_full, n_fast) (OPT-IN, check_playout_cap; with any reroot): the games of SelfPlayRunner(playout_cap=...), slot for slot.
+    `record_full` (uint8 numpy, one per record, valid inside on_records) tells each record's kind; searches_full / searches_fast count them."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
-                 per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0):
+                 per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
+                 playout_cap=None):
         import torch
+        self.playout_cap = check_playout_cap(playout_cap, n_sims)
+        self.record_full = None
         if tree_reuse:
             raise ValueError("AsyncSelfPlayRunner takes tree reuse as reroot=1 (carry) or reroot=2 (top-up): the re-root runs in the drain "
                              "(azk_async_begin_reuse), not where SelfPlayRunner(tree_reuse=...) has it")
@@ -514,6 +565,8 @@ class AsyncSelfPlayRunner:
         self.h = self.halves[0]
         self.leaf_source_ok = True
         e.reset_games()
+        if self.playout_cap is not None:
+            e.set_playout_cap(self.playout_cap[0], self.playout_cap[1], seed, first_global_game)
         cap = (4 * n_games if record_capacity is None else record_capacity) if (on_records is not None or record_capacity) else 0
         self.stats, self.records = e.async_begin(n_sims, self.per_launch, SAMPLE_UNTIL[game], seed, first_global_game, alpha, dirichlet, recycle, cap,
                                                  young_launch_us=young_launch_us, reroot=bool(self.reroot))
@@ -633,6 +686,8 @@ class AsyncSelfPlayRunner:
         with self.torch.cuda.stream(self.copy_stream):
             idx = self.torch.arange(self.rec_read, cursor, device=self.eng.device) % self.rec_cap
             meta, q, pi = self.records["meta"][idx].cpu().numpy(), self.records["q"][idx].cpu().numpy(), self.records["pi"][idx].cpu().numpy()
+            if "full" in self.records:
+                self.record_full = self.records["full"][idx].cpu().numpy()
         self.rec_read = cursor
         self.on_records(meta, q, pi)
 
@@ -666,6 +721,15 @@ class AsyncSelfPlayRunner:
     @property
     def finished_plies(self):
         return int(self._seen[1])
+
+    @property
+    def searches_full(self):
+        """Full / fast searches among the searches begun (stats [8] / [9]; both 0 without playout_cap)."""
+        return int(self._seen[8])
+
+    @property
+    def searches_fast(self):
+        return int(self._seen[9])
 
     def counters(self):
         return self.eng.counters()

@@ -29,15 +29,18 @@ def flip_data(board, policy, mode="lr"):
     return np.flip(board, axis=1), np.flipud(p).reshape(-1)
 
 
-def save_data_to_buffer(Game, buffer, data):
+def save_data_to_buffer(Game, buffer, data, full=None):
     """train.py:30-49: z = +reward for the winner's positions, -reward for the loser's; canonical boards; positions 0 and 1
-    once, every later position with its 8 dihedral images in the reference's order."""
+    once, every later position with its 8 dihedral images in the reference's order.  full (playout cap, SelfPlayResult.full): one flag
+    per position; the positions of fast searches are left out, the others keep the group they would have had."""
     boards, actions, policies, qs, winner, reward = data
     current = 0
     for i in range(len(boards)):
         target = [reward] if current == winner else [-reward]
         canon = Game.get_canonical_board(boards[i], current)
         current = 1 - current
+        if full is not None and not full[i]:
+            continue
         if i < 2:
             buffer.add(canon, policies[i], target)
             continue
@@ -50,14 +53,17 @@ def save_data_to_buffer(Game, buffer, data):
                     buffer.add(fb, fp, target)
 
 
-def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed=None, batched=True):
+def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed=None, batched=True, playout_cap=None):
     """train.py:54-83: `iterations` self-play games of Game with `model` into `buffer`; returns [first, second, draw] counts.
     batched=False plays the games one after the other through Game().self_play and save_data_to_buffer exactly as the
     reference does (global np.random stream: a seeded caller gets the reference's buffer); the default plays them as one
-    engine batch with the engine's own counter-based RNG."""
+    engine batch with the engine's own counter-based RNG.  playout_cap = (p_full, n_fast) (OPT-IN, batched only; selfplay.check_playout_cap):
+    fast searches choose their move and are not stored, in a DeviceReplay and in a host buffer alike."""
     from azk import DeviceReplay
     from selfplay import self_play_batch
     if not batched:
+        if playout_cap is not None:
+            raise ValueError("collect_data: playout_cap needs the batched engine (batched=True)")
         results = [0, 0, 0]
         for _ in range(iterations):
             game = Game()
@@ -70,13 +76,13 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     on_device = isinstance(buffer, DeviceReplay)
     leaf_dtype = "bfloat16" if getattr(model, "dtype", None) is not None and str(model.dtype).endswith("bfloat16") else "float32"
     res = self_play_batch(Game.engine_name, model, iterations, mcts_iter, size=Game._size(), seed=seed, leaf_dtype=leaf_dtype,
-                          replay=buffer if on_device else None)
+                          replay=buffer if on_device else None, playout_cap=playout_cap)
     results = [0, 0, 0]
     for r in res:
         results[2 if r.winner == -1 else r.winner] += 1
         if not on_device:
             reward = 0 if r.winner == -1 else 1
-            save_data_to_buffer(Game, buffer, (r.boards, r.actions, r.pis, r.qs, r.winner, reward))
+            save_data_to_buffer(Game, buffer, (r.boards, r.actions, r.pis, r.qs, r.winner, reward), full=r.full if playout_cap is not None else None)
         if display:
             Game.display_board(r.boards[-1])
     return results

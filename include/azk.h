@@ -161,6 +161,7 @@ int32_t azk_search_unfinished(azk_engine *e, int32_t *count_host, void *stream);
  *   stats_dev  int64 [16], zeroed by azk_async_begin(_reuse): [0] games finished, [1] their plies, [2] wins of player 0, [3] of player 1,
  *              [4] draws, [5] moves played, [6] records written (ring cursor), [7] searches begun - by azk_async_begin's move kernel,
  *              by the drain's restart of a finished game, and by the drain's re-root of a parked game (carried subtree or fallback)
+ *              [8] / [9] with a playout cap (azk_set_playout_cap): full / fast searches among those of [7]
  *   record ring (optional, record_capacity entries; entry r % capacity): rec_meta int32 [cap][4] = slot, the slot's move counter,
  *              chosen cell, winner (-2 running, -1 draw, 0 / 1); rec_q float64 [cap] = root.value / root.visit; rec_pi float64 [cap][A] */
 typedef struct azk_async_config {
@@ -184,6 +185,38 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
 /* change the simulation budget of every later launch (it lives in device memory, so captured step graphs pick it up); synchronises */
 int32_t azk_async_set_budget(azk_engine *e, int32_t n_sims, int32_t max_sims_per_launch, void *stream);
 int32_t azk_async_drain(azk_engine *e, float *states_dev, double *pis_dev, float *zs_dev, int64_t capacity, int64_t *cursor_dev, void *stream);
+
+/* ---- playout-cap randomisation (OPT-IN; off, the engine is what it was bit for bit).  The data-generation scheme of KataGo (Wu 2019,
+ * section 3.1): each search is FULL - the budget's n_sims simulations, exactly the search the engine runs without the option - with
+ * probability p_full, and FAST - n_fast simulations - otherwise.  A fast search only chooses the move: its ply is left out of the
+ * (state, pi, z) emission (azk_emit_finished, azk_async_drain), so every pi that is trained on comes from a full search, while games
+ * finish several times sooner.
+ *   the coin   one per search, drawn where the search begins, keyed like the search's Dirichlet row: Philox4x32-10, counter
+ *              {global game lo, global game hi, move key, 0xFFFFFFFE}, key (seed lo, seed hi), u = ((c0 << 32 | c1) >> 11) * 2^-53, full iff
+ *              u < p_full.  Word 3 = 0xFFFFFFFE belongs to no other draw (azk_gen_noise's uniform has 0xFFFFFFFF, its rows it < 64 and
+ *              it | 0x40000000): every noise row and move uniform is unchanged, and the coins do not depend on how games are sharded.
+ *              p_full = 1: every search full; p_full = 0: every search fast.
+ *   fast       the same search with fewer simulations: the game's completed-simulation count starts at budget - n_fast (the budget as it
+ *              stands when the search begins; a budget below n_fast runs the budget), and budget stepping ends the search after n_fast.
+ *              Dirichlet noise, eval cache, move selection, q and the records are those of any search.  DEVIATION from KataGo: fast
+ *              searches keep the configured root noise (the mix is part of the tree kernel, which this option leaves untouched).
+ *   tree_reuse the per-game target (n_sims full, n_fast fast) takes n_sims' place: carry runs target more simulations, top-up
+ *              max(1, target - carried root visits); the arena rule uses the same count.
+ *   emission   a game reserves the sum over its full plies of (ply < 2 ? 1 : 8) tuples; ply i's group lands at the sum over the full
+ *              plies before it, each group as azk_emit_finished describes (boards rebuilt from ALL earlier plies).  A game without a
+ *              full ply emits nothing and is marked and recycled as usual.
+ * azk_set_playout_cap: 0 <= p_full <= 1, 1 <= n_fast <= max_sims, not with leaves_per_step > 1, else AZK_ERR_ARG; n_fast = 0 switches the
+ * option off.  Call it before azk_async_begin(_reuse) (which then uses ITS seed and first_global_game for the coins, move key = the
+ * slot's move counter, and counts stats_dev[8] full / [9] fast searches begun, where it counts [7]); AZK_ERR_ARG there when n_fast > n_sims.
+ * Lock-step drivers begin every search with azk_begin_search_capped (azk_begin_search_budget + the move key; azk_begin_search and
+ * azk_begin_search_budget answer AZK_ERR_STATE while a cap is set) and step as after azk_begin_search_budget.
+ * azk_get_search_full: uint8 [G] into device memory, 1 = the game's current search is full (asynchronous copy on the stream).
+ * azk_async_record_flags (optional, before azk_async_begin): a uint8 [record_capacity] column of the record ring, entry r % capacity = 1
+ * when record r's search was full. */
+int32_t azk_set_playout_cap(azk_engine *e, double p_full, int32_t n_fast, uint64_t seed, int64_t first_global_game, void *stream);
+int32_t azk_begin_search_capped(azk_engine *e, const double *noise_dev, int32_t n_sims, int32_t max_sims_per_launch, int32_t move_index, void *stream);
+int32_t azk_get_search_full(azk_engine *e, uint8_t *full_dev, void *stream);
+int32_t azk_async_record_flags(azk_engine *e, uint8_t *rec_full_dev);
 
 /* One simulation per active game (ai/mcts.py:16-60), split around the evaluator:
  *   azk_step_select   - mcts.py:18-37: PUCT walk (node.py:42-47, utils.py:29-44), make_move along the

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 LIB_PATH = os.path.join(_HERE, "libazk.so")
 
-ABI_VERSION = 4           # include/azk.h AZK_ABI_VERSION the structure layouts below were written for
+ABI_VERSION = 5           # include/azk.h AZK_ABI_VERSION the structure layouts below were written for
 
 # every symbol include/azk.h declares (checked by tests/test_abi.py against the header text)
 SYMBOLS = [
@@ -27,11 +27,11 @@ SYMBOLS = [
     "azk_rules_check_winner", "azk_rules_canonical", "azk_softmax_rows",
     "azk_step_tree", "azk_step_gather", "azk_recycle_finished", "azk_nn_patch_embed", "azk_nn_cls_attention", "azk_nn_patch_embed_scores", "azk_nn_cls_pool", "azk_debug_stamps", "azk_debug_stamps_raw", "azk_emit_finished", "azk_clear_cache", "azk_nn_heads_finalize", "azk_nn_layernorm_rows",
     "azk_vanilla_set_rng", "azk_vanilla_get_rng", "azk_vanilla_search", "azk_nn_embed_pool",
-    "azk_nn_gemm_rows", "azk_nn_layernorm_sum", "azk_nn_heads_finalize_sum", "azk_nn_ln_heads",
+    "azk_nn_ln_heads",
     "azk_leaf_source_of", "azk_nn_embed_pool_leaves", "azk_nn_embed_pool_compact", "azk_nn_embed_pool_compact_leaves",
     "azk_nn_embed_fold", "azk_nn_embed_fold_leaves", "azk_nnx_embed_fold", "azk_nnx_embed_fold_leaves",
     "azk_nn_tail_gemm", "azk_nn_tail_gemm_lds", "azk_nn_tail_lds_footprint", "azk_nn_embed_fold_grid", "azk_nn_gemm_tok", "azk_nn_attention_tok", "azk_begin_search_budget", "azk_search_unfinished",
-    "azk_nnx_embed_pool", "azk_nnx_embed_pool_leaves", "azk_nnx_gemm", "azk_nnx_gemm_h", "azk_nnx_gemm_h_lds",
+    "azk_nnx_embed_pool", "azk_nnx_embed_pool_leaves", "azk_nnx_gemm_h", "azk_nnx_gemm_h_lds",
     "azk_async_begin", "azk_async_step", "azk_async_drain", "azk_async_set_budget", "azk_async_begin_reuse",
     "azk_set_playout_cap", "azk_begin_search_capped", "azk_get_search_full", "azk_async_record_flags",
 ]
@@ -43,10 +43,10 @@ class AzkError(RuntimeError):
 
 from . import structs  # noqa: E402
 from .structs import (EMBED_FOLD_MAX_SLOTS, EMBED_FOLD_ROW, EMBED_POOL_COMPACT_MAX_SLOTS, GAME_ID, LEAF_BF16, LEAF_F32,  # noqa: E402,F401
-                      AsyncConfig, Config, Counters, EmbedFoldConsts, EmbedPoolConsts, EmbedPoolXConsts, GemmH, GemmTok, GemmX,
+                      AsyncConfig, Config, Counters, EmbedFoldConsts, EmbedPoolConsts, EmbedPoolXConsts, GemmH, GemmTok,
                       LeafSource, TailGemm)
 from .packing import (GEMM_H_A_SCALE, GEMM_H_W_SCALE, pack_linear_weight, pack_linear_weight128, pack_linear_weight_h,  # noqa: E402,F401
-                      pack_linear_weight_x, packed_weight_col_sums, split_fp16)
+                      packed_weight_col_sums, split_fp16)
 from .replay import DeviceReplay  # noqa: E402,F401
 
 
@@ -912,37 +912,12 @@ def mt_state_to_numpy(words, template=None):
     return ("MT19937", np.asarray(words[:624], np.uint32), int(words[624]), t[3], t[4])
 
 
-def nn_gemm_rows(a, w_packed, n_out, ksplit=1, partials=None, bias=None, gelu_out=None, count=None):
-    """a bf16 [m, k] (row stride = a.stride(0)) times a packed weight: float32 partial planes [ksplit, m, n_out] or
-    bf16 GELU(a W^T + bias)."""
-    torch = _torch()
-    assert a.dtype == torch.bfloat16 and a.stride(1) == 1
-    m, k = a.shape
-    rc = lib().azk_nn_gemm_rows(_p(a), a.stride(0), _p(w_packed), m, int(n_out), k, int(ksplit), _p(partials), _p(bias), _p(gelu_out),
-                                _p(count), _stream())
-    _ok(rc, "azk_nn_gemm_rows")
-
-
-def nn_layernorm_sum(partials, w, b, y, bias=None, resid=None, add_bias=None, x_out=None, eps=1e-5, count=None):
-    nsplit, m, d = partials.shape
-    rc = lib().azk_nn_layernorm_sum(_p(partials), nsplit, m, _p(bias), _p(resid), _p(w), _p(b), float(eps), _p(y), _p(add_bias), _p(x_out),
-                                    y.shape[0], d, _p(count), _stream())
-    _ok(rc, "azk_nn_layernorm_sum")
-
-
-def nn_heads_finalize_sum(partials, bias, action_dim, logits_out, values_out, count=None):
-    nsplit, m, ld = partials.shape
-    rc = lib().azk_nn_heads_finalize_sum(_p(partials), nsplit, m, ld, _p(bias), int(action_dim), logits_out.shape[0], _p(logits_out),
-                                         _p(values_out), _p(count), _stream())
-    _ok(rc, "azk_nn_heads_finalize_sum")
-
-
-def nn_ln_heads(x, ln_w, ln_b, w_packed, bias, action_dim, logits_out, values_out, eps=1e-5, count=None):
+def nn_ln_heads(x, w_packed, bias, action_dim, logits_out, values_out, eps=1e-5, count=None):
     """Final LayerNorm + merged policy/value head + finalize in one launch: x bf16 [n, D] -> logits f32 [n, A], values f32 [n]."""
     torch = _torch()
     assert x.dtype == torch.bfloat16 and x.is_contiguous()
     n, d = x.shape
-    rc = lib().azk_nn_ln_heads(_p(x), _p(ln_w), _p(ln_b), float(eps), _p(w_packed), _p(bias), n, d, bias.numel(), int(action_dim),
+    rc = lib().azk_nn_ln_heads(_p(x), float(eps), _p(w_packed), _p(bias), n, d, bias.numel(), int(action_dim),
                                _p(logits_out), _p(values_out), _p(count), _stream())
     _ok(rc, "azk_nn_ln_heads")
 
@@ -1007,32 +982,6 @@ def nnx_embed_pool(boards, tables, rows, cols, sched, count=None, timers=None):
 def nnx_embed_pool_leaves(src, tables, sched, timers=None):
     """azk_nnx_embed_pool over an engine's pending leaves (LeafSource): z float32 [slots, H, 512], rows [0, n_leaf) valid."""
     return _embed("azk_nnx_embed_pool", "float32", tables.embed_dim, tables, sched, timers, src=src)
-
-
-def nnx_gemm(a, w_packed, n_out, k, epilogue=TAIL_BF16, nbatch=1, a_batch_stride=0, bias=None, out=None, resid=None,
-             a_stats=None, stats_out=None, logits=None, values=None, action_dim=0, count=None, eps=1e-5):
-    """One link of the fp32 cls-row tail (azk_nnx_gemm): a float32 [m, lda] x packed float32 weights -> out float32 [m, nbatch * n_out]
-    (or logits / values for the heads epilogue).  epilogue: TAIL_BF16 (= plain) / TAIL_GELU / TAIL_RESID / TAIL_HEADS."""
-    torch = _torch()
-    assert a.dtype == torch.float32 and a.stride(1) == 1 and w_packed.dtype == torch.float32
-    d = GemmX()
-    d.a_f32, d.lda, d.a_batch_stride, d.w_packed = a.data_ptr(), a.stride(0), int(a_batch_stride), w_packed.data_ptr()
-    d.m, d.n_out, d.k, d.nbatch = a.shape[0], int(n_out), int(k), int(nbatch)
-    d.n_valid = count.data_ptr() if count is not None else None
-    d.bias = bias.data_ptr() if bias is not None else None
-    d.layernorm_a, d.epilogue, d.ln_eps = (1 if a_stats is not None else 0), int(epilogue), float(eps)
-    d.a_stats = a_stats.data_ptr() if a_stats is not None else None
-    d.stats_out = stats_out.data_ptr() if stats_out is not None else None
-    if out is not None:
-        assert out.dtype == torch.float32 and out.stride(1) == 1
-        d.out_f32, d.ldo = out.data_ptr(), out.stride(0)
-    if resid is not None:
-        assert resid.dtype == torch.float32 and resid.stride(1) == 1
-        d.resid_f32, d.ldr = resid.data_ptr(), resid.stride(0)
-    if logits is not None:
-        d.logits_out, d.values_out, d.action_dim = logits.data_ptr(), values.data_ptr(), int(action_dim)
-    rc = lib().azk_nnx_gemm(C.byref(d), _stream())
-    _ok(rc, "azk_nnx_gemm")
 
 
 def nnx_gemm_h(a, w_packed, n_out, k, epilogue=TAIL_BF16, nbatch=1, a_batch_stride=0, bias=None, col_sums=None, out=None, out_f32=None,

@@ -4,7 +4,7 @@ from ._rt import _torch
 
 
 def pack_linear_weight(w):
-    """nn.Linear weight [n_out, k] (any float dtype, any device) -> bf16 tensor in azk_nn_gemm_rows' fragment order
+    """nn.Linear weight [n_out, k] (any float dtype, any device) -> bf16 tensor in the MFMA B-fragment order of include/azk.h's cls-row tail section
     (n_out padded with zero rows to a multiple of 64; k must be a multiple of 32)."""
     torch = _torch()
     n_out, k = w.shape
@@ -43,18 +43,6 @@ def split_fp16(x64, scale):
     hi = xs.to(torch.float16)
     lo = (xs - hi.double()).to(torch.float16)
     return hi, lo
-
-
-def pack_linear_weight_x(w):
-    """nn.Linear weight [n_out, k] -> float32 tensor in azk_nnx_gemm's fragment order (n_out padded with zero rows to a multiple of 64)."""
-    torch = _torch()
-    n_out, k = w.shape
-    assert k % 16 == 0
-    npad = (n_out + 63) // 64 * 64
-    wp = torch.zeros(npad, k, dtype=torch.float32, device=w.device)
-    wp[:n_out] = w.float()
-    # [g, l15, c, s, l4, i] -> [g, s, c, l4, l15, i]
-    return wp.view(npad // 64, 16, 4, k // 16, 4, 4).permute(0, 3, 2, 4, 1, 5).contiguous()
 
 
 GEMM_H_A_SCALE, GEMM_H_W_SCALE = 16.0, 256.0      # activations x 16, weights x 256 before the fp16 (hi, lo) split (azk_nnx_gemm_h)

@@ -64,16 +64,6 @@ class EmbedPoolXConsts(C.Structure):
                 ("wconst_h16_tok", C.c_void_p), ("pool_scale", C.c_float)]
 
 
-class GemmX(C.Structure):
-    """azk_gemm_x (include/azk.h): one link of the cls-row tail in float32."""
-    _fields_ = [("a_f32", C.c_void_p), ("lda", C.c_int32), ("a_batch_stride", C.c_int32), ("w_packed", C.c_void_p),
-                ("m", C.c_int32), ("n_out", C.c_int32), ("k", C.c_int32), ("nbatch", C.c_int32), ("n_valid", C.c_void_p),
-                ("bias", C.c_void_p), ("layernorm_a", C.c_int32), ("epilogue", C.c_int32), ("ln_eps", C.c_float),
-                ("a_stats", C.c_void_p), ("stats_out", C.c_void_p), ("out_f32", C.c_void_p), ("ldo", C.c_int32),
-                ("resid_f32", C.c_void_p), ("ldr", C.c_int32), ("logits_out", C.c_void_p), ("values_out", C.c_void_p),
-                ("action_dim", C.c_int32)]
-
-
 class GemmH(C.Structure):
     """azk_gemm_h (include/azk.h): one link of the cls-row tail on fp16 (hi, lo) operand planes."""
     _fields_ = [("a_hi", C.c_void_p), ("a_lo", C.c_void_p), ("a_f32", C.c_void_p), ("lda", C.c_int32), ("a_batch_stride", C.c_int32),
@@ -159,7 +149,6 @@ def declare(L, symbols):
     L.azk_nn_attention_tok.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
     L.azk_nnx_embed_pool.argtypes = [vp, i32, C.POINTER(EmbedPoolXConsts), vp, i32, i32, i32, i32, vp, vp, vp]
     L.azk_nnx_embed_pool_leaves.argtypes = [C.POINTER(LeafSource), C.POINTER(EmbedPoolXConsts), vp, vp, vp]
-    L.azk_nnx_gemm.argtypes = [C.POINTER(GemmX), vp]
     L.azk_nnx_gemm_h.argtypes = [C.POINTER(GemmH), vp]
     L.azk_nnx_gemm_h_lds.argtypes = [C.POINTER(GemmH), vp]
     L.azk_async_begin.argtypes = [vp, C.POINTER(AsyncConfig), vp]
@@ -171,10 +160,7 @@ def declare(L, symbols):
     L.azk_begin_search_capped.argtypes = [vp, vp, i32, i32, i32, vp]
     L.azk_get_search_full.argtypes = [vp, vp, vp]
     L.azk_async_record_flags.argtypes = [vp, vp]
-    L.azk_nn_ln_heads.argtypes = [vp, vp, vp, C.c_float, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    L.azk_nn_gemm_rows.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.azk_nn_layernorm_sum.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, vp, vp]
-    L.azk_nn_heads_finalize_sum.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.azk_nn_ln_heads.argtypes = [vp, C.c_float, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.azk_nn_layernorm_rows.argtypes = [vp, vp, vp, C.c_float, vp, vp, i32, i32, vp, vp]
     L.azk_nn_heads_finalize.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     L.azk_nn_cls_pool.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]

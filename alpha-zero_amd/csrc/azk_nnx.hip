@@ -11,10 +11,10 @@
 //                    * LayerNorm statistics, normalisation, softmax weights (exp with an extended-precision argument): float32 VALU;
 //                    * weighted token sum Z += W^T Xn - Wc^T Xnc: both operands are run-time float32, so it runs on
 //                      v_mfma_f32_16x16x4_f32 (exact float32 fma chain), with both operands already in the accumulators' layout.
-//   k_gemm_x         the cls-row tail as float32 GEMMs on v_mfma_f32_16x16x4_f32: per-head value projection -> output projection
-//                    (+ row statistics) -> LayerNorm2 + MLP up + GELU (erff) -> MLP down + residual (+ row statistics) -> final
-//                    LayerNorm + merged heads + tanh.  LayerNorm as in k_tail_gemm: the producer's epilogue leaves per-row partial
-//                    (sum, sum of squares), the consumer normalises its A fragments on the fly; affines folded into the weights.
+//   k_gemm_h         the cls-row tail with every operand as two fp16 terms on v_mfma_f32_16x16x32_f16: per-head value projection ->
+//                    output projection (+ row statistics) -> LayerNorm2 + MLP up + GELU (erff) -> MLP down + residual (+ row
+//                    statistics) -> final LayerNorm + merged heads + tanh.  The producer's epilogue leaves per-row partial (sum, sum
+//                    of squares), the consumer applies LayerNorm in its epilogue; affines folded into the weights.
 // Everything the host folds (cls query through W_k, LayerNorm affines, softmax constants) is computed in float64 and rounded once.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -576,225 +576,15 @@ extern "C" int32_t azk_nnx_embed_pool_leaves(const azk_leaf_source *src, const a
 }
 
 // =====================================================================================================
-// k_gemm_x: one link of the cls-row tail in float32 on v_mfma_f32_16x16x4_f32 (exact float32 fma chains).
-//   C[m][nbatch * N] = op(A) W^T (+ bias) through the epilogues of k_tail_gemm, everything float32 in memory.
-//   Wave tile 32 rows x 64 columns (2 x 4 MFMA tiles); a lane's A operand of a 16-wide k-step is ONE 16-byte load (row lane&15,
-//   k = 16 s + 4 (lane>>4) .. +3: instruction i of the step takes component i, i.e. sums over k = 16 s + 4 g + i, g = 0..3), the
-//   weights come packed the same way: Wp[N/64][K/16][4][64 lanes] x float4, element [g][s][c][lane][i] = W[64 g + 4 (lane&15) + c][16 s + 4 (lane>>4) + i]
-//   (a lane's four accumulators of a row are four consecutive output columns: 16-byte stores).  The k loop streams 32 columns
-//   of K per iteration, the next iteration's twelve loads in flight under the current 64 MFMAs (2 048 cycles).
-//   NWK = 4: the four waves of a workgroup split K (the small GEMMs: enough waves to fill the chip, a quarter of the chain each),
-//   partial sums meet in LDS, wave 0 runs the epilogue.  NWK = 1: the four waves are a 2 x 2 block of wave tiles (shared A rows and
-//   weight fragments hit in L1).
-// =====================================================================================================
-namespace {
-
-struct GemmXArgs {
-    const float *A; int lda, a_batch;
-    const f32x4 *Wp; long long w_batch;          // f32x4 elements between batches
-    int M, N, nbatch;                            // N = output columns per batch (multiple of 64; of 128 for NWK = 1)
-    const int *count;
-    const float *bias;                           // [nbatch * N] or null
-    float *out; int ldo;
-    const float *resid; int ldr;
-    float ln_eps;
-    const float *stats_in;                       // AMODE 1: [M][8][2] partial (sum, sum of squares) of every A row (K = 512), left by the producer
-    float *stats_out;                            // optional: this GEMM's own partials [M][nbatch * N / 64][2]
-    float *logits, *values; int action_dim;
-};
-
-enum { X_EPI_PLAIN = 0, X_EPI_GELU = 1, X_EPI_RESID = 2, X_EPI_HEADS = 3 };
-
-template <int EPI, int AMODE, int NWK, int KW>      // KW = columns of K per wave (K = KW * NWK)
-__global__ __launch_bounds__(256, 1) void k_gemm_x(GemmXArgs a) {
-    constexpr int RT = 2, K = KW * NWK, S16 = K / 16, NCH = KW / 32;
-    __shared__ f32x4 kred[NWK > 1 ? (NWK - 1) * RT * 4 * 64 : 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, l4 = lane >> 4;
-    const int nvalid = a.count ? min(a.M, *a.count) : a.M;
-    const int wk = NWK > 1 ? wave : 0;
-    const int wr = NWK > 1 ? 0 : (wave >> 1), wc = NWK > 1 ? 0 : (wave & 1);
-    constexpr int WROWS = NWK > 1 ? 16 * RT : 32 * RT, WCOLS = NWK > 1 ? 64 : 128;
-    const int rtiles = (nvalid + WROWS - 1) / WROWS, ctiles = a.N / WCOLS;
-    const int nitems = rtiles * ctiles * a.nbatch;
-    for (int item = blockIdx.x; item < nitems; item += gridDim.x) {
-        if (NWK > 1 && item != (int)blockIdx.x) __syncthreads();      // wave 0 is done with the previous item's partial sums
-        const int ct = item % ctiles, r2 = item / ctiles, rt = r2 % rtiles, b = r2 / rtiles;
-        const int row0 = rt * WROWS + wr * 16 * RT, g = ct * (WCOLS / 64) + wc;
-        const float *ap[RT];
-#pragma unroll
-        for (int i = 0; i < RT; i++) ap[i] = a.A + (size_t)min(row0 + 16 * i + l15, a.M - 1) * a.lda + (size_t)b * a.a_batch + KW * wk + 4 * l4;
-        const f32x4 *bp = a.Wp + (size_t)b * a.w_batch + ((size_t)g * S16 + (size_t)(KW / 16) * wk) * 4 * 64 + lane;
-        f32x4 acc[RT][4];
-#pragma unroll
-        for (int i = 0; i < RT; i++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        f32x4 st[AMODE == 1 ? RT : 1];
-        if (AMODE == 1) {
-#pragma unroll
-            for (int i = 0; i < RT; i++) st[i] = *((const f32x4 *)(a.stats_in + (size_t)min(row0 + 16 * i + l15, a.M - 1) * 16) + l4);
-        }
-        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-        const int col0 = b * a.N + 64 * g + 4 * l15;
-        if (a.bias) bv = *(const f32x4 *)(a.bias + col0);
-        f32x4 af[2][RT][2], bf[2][2][4];                      // [buffer][row tile][k-step], [buffer][k-step][column tile]
-        auto fetch = [&](int buf, int ch) {
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-#pragma unroll
-                for (int i = 0; i < RT; i++) af[buf][i][s] = *(const f32x4 *)(ap[i] + 32 * ch + 16 * s);
-#pragma unroll
-                for (int c = 0; c < 4; c++) bf[buf][s][c] = bp[((2 * ch + s) * 4 + c) * 64];
-            }
-        };
-        fetch(0, 0);
-        float rstd[RT], shift[RT];
-        if (AMODE == 1) {                                     // the groups are added in a fixed order: deterministic, no atomics
-#pragma unroll
-            for (int i = 0; i < RT; i++) {
-                float s1 = st[i][0] + st[i][2], s2 = st[i][1] + st[i][3];
-                s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
-                s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-                const float mean = s1 * (1.0f / 512.0f);
-                rstd[i] = 1.0f / sqrtf(fmaxf(__builtin_fmaf(-mean, mean, s2 * (1.0f / 512.0f)), 0.f) + a.ln_eps);
-                shift[i] = -mean * rstd[i];
-            }
-        }
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++) {
-            const int cur = ch & 1;
-            if (ch + 1 < NCH) fetch(cur ^ 1, ch + 1);
-            __builtin_amdgcn_sched_barrier(0);                // the next iteration's loads are ISSUED here (left alone, hipcc sinks every load to
-                                                              // just before its first use and waits for it there: one exposed round trip per k-step)
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                if (AMODE == 1) {
-#pragma unroll
-                    for (int i = 0; i < RT; i++)
-#pragma unroll
-                        for (int e = 0; e < 4; e++) af[cur][i][s][e] = __builtin_fmaf(af[cur][i][s][e], rstd[i], shift[i]);
-                }
-#pragma unroll
-                for (int e = 0; e < 4; e++)
-#pragma unroll
-                    for (int i = 0; i < RT; i++)
-#pragma unroll
-                        for (int c = 0; c < 4; c++) acc[i][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[cur][i][s][e], bf[cur][s][c][e], acc[i][c], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (row0 >= nvalid) continue;                          // (uniform per wave tile; with NWK > 1 per workgroup)
-        if (NWK > 1) {
-            if (wave > 0) {
-#pragma unroll
-                for (int i = 0; i < RT; i++)
-#pragma unroll
-                    for (int c = 0; c < 4; c++) kred[((wave - 1) * RT * 4 + i * 4 + c) * 64 + lane] = acc[i][c];
-            }
-            __syncthreads();
-            if (wave > 0) continue;
-#pragma unroll
-            for (int w = 1; w < NWK; w++)
-#pragma unroll
-                for (int i = 0; i < RT; i++)
-#pragma unroll
-                    for (int c = 0; c < 4; c++) acc[i][c] += kred[((w - 1) * RT * 4 + i * 4 + c) * 64 + lane];
-        }
-        f32x4 rr[EPI == X_EPI_RESID ? RT : 1][4];
-        if (EPI == X_EPI_RESID) {
-#pragma unroll
-            for (int i = 0; i < RT; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) rr[i][j] = *(const f32x4 *)(a.resid + (size_t)min(row0 + 16 * i + 4 * l4 + j, a.M - 1) * a.ldr + col0);
-        }
-        if (EPI == X_EPI_HEADS) {                             // nn.py:82-83
-#pragma unroll
-            for (int i = 0; i < RT; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int row = row0 + 16 * i + 4 * l4 + j;
-#pragma unroll
-                    for (int c = 0; c < 4; c++) {
-                        const int col = col0 + c;
-                        const float x = acc[i][c][j] + bv[c];
-                        if (row < nvalid && col < a.action_dim) a.logits[(size_t)row * a.action_dim + col] = x;
-                        if (row < nvalid && col == a.action_dim) a.values[row] = tanhf(x);
-                    }
-                }
-        } else {
-            const int ngr = a.nbatch * (a.N >> 6), gr = b * (a.N >> 6) + g;
-#pragma unroll
-            for (int i = 0; i < RT; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    f32x4 v = {acc[i][0][j] + bv[0], acc[i][1][j] + bv[1], acc[i][2][j] + bv[2], acc[i][3][j] + bv[3]};
-                    if (EPI == X_EPI_GELU) {
-#pragma unroll
-                        for (int c = 0; c < 4; c++) v[c] = 0.5f * v[c] * (1.0f + erff(v[c] * 0.70710678118654752f));          // nn.GELU (erf form)
-                    }
-                    if (EPI == X_EPI_RESID) v += rr[i][j];
-                    const int row = row0 + 16 * i + 4 * l4 + j;
-                    if (row < nvalid) *(f32x4 *)(a.out + (size_t)row * a.ldo + col0) = v;
-                    if (a.stats_out) {
-                        const f32x2 ps = {row16_sum((v[0] + v[1]) + (v[2] + v[3])), row16_sum((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]))};
-                        if (l15 == 0 && row < nvalid) *(f32x2 *)(a.stats_out + ((size_t)row * ngr + gr) * 2) = ps;
-                    }
-                }
-        }
-    }
-}
-
-template <int EPI, int AMODE, int NWK, int KW>
-int launch_gemm_x(const GemmXArgs &a, hipStream_t st) {
-    constexpr int WROWS = NWK > 1 ? 32 : 64, WCOLS = NWK > 1 ? 64 : 128;
-    const long long items = (long long)((a.M + WROWS - 1) / WROWS) * (a.N / WCOLS) * a.nbatch;
-    const unsigned blocks = (unsigned)(items < 16384 ? items : 16384);
-    k_gemm_x<EPI, AMODE, NWK, KW><<<blocks, 256, 0, st>>>(a);
-    return hipGetLastError() == hipSuccess ? AZK_OK : AZK_ERR_HIP;
-}
-}  // namespace
-
-extern "C" int32_t azk_nnx_gemm(const azk_gemm_x *t, void *stream) {
-    if (!t || !t->a_f32 || !t->w_packed || t->m < 0 || t->n_out < 64 || (t->n_out & 63) || t->nbatch < 1) return AZK_ERR_ARG;
-    if ((t->k != 512 && t->k != 2048) || t->lda < t->k || (t->lda & 3) || (t->a_batch_stride & 3)) return AZK_ERR_ARG;
-    if (t->epilogue < 0 || t->epilogue > 3 || (t->layernorm_a && (t->k != 512 || !t->a_stats))) return AZK_ERR_ARG;
-    if (t->epilogue == X_EPI_HEADS ? (!t->logits_out || !t->values_out || t->action_dim + 1 > t->n_out * t->nbatch) : (!t->out_f32 || t->ldo < t->n_out * t->nbatch || (t->ldo & 3)))
-        return AZK_ERR_ARG;
-    if (t->epilogue == X_EPI_RESID && (!t->resid_f32 || (t->ldr & 3))) return AZK_ERR_ARG;
-    if (t->m == 0) return AZK_OK;
-    GemmXArgs a;
-    memset(&a, 0, sizeof a);
-    a.A = t->a_f32; a.lda = t->lda; a.a_batch = t->a_batch_stride; a.Wp = (const f32x4 *)t->w_packed;
-    a.w_batch = (long long)(t->n_out / 64) * (t->k / 16) * 4 * 64;
-    a.M = t->m; a.N = t->n_out; a.nbatch = t->nbatch; a.count = t->n_valid; a.bias = t->bias; a.out = t->out_f32; a.ldo = t->ldo;
-    a.resid = t->resid_f32; a.ldr = t->ldr; a.ln_eps = t->ln_eps; a.logits = t->logits_out; a.values = t->values_out;
-    a.action_dim = t->action_dim; a.stats_in = t->a_stats; a.stats_out = t->stats_out;
-    hipStream_t st = (hipStream_t)stream;
-    if (t->k == 2048) {
-        if (t->layernorm_a) return AZK_ERR_ARG;
-        if (t->epilogue == X_EPI_RESID) return launch_gemm_x<X_EPI_RESID, 0, 4, 512>(a, st);
-        if (t->epilogue == X_EPI_PLAIN) return launch_gemm_x<X_EPI_PLAIN, 0, 4, 512>(a, st);
-        return AZK_ERR_ARG;
-    }
-    const bool wide = t->n_out % 128 == 0 && t->n_out >= 1024;          // enough column groups to fill the chip without splitting K
-    if (t->layernorm_a) {
-        if (t->epilogue == X_EPI_GELU) return wide ? launch_gemm_x<X_EPI_GELU, 1, 1, 512>(a, st) : launch_gemm_x<X_EPI_GELU, 1, 4, 128>(a, st);
-        if (t->epilogue == X_EPI_HEADS) return launch_gemm_x<X_EPI_HEADS, 1, 4, 128>(a, st);
-        if (t->epilogue == X_EPI_PLAIN) return launch_gemm_x<X_EPI_PLAIN, 1, 4, 128>(a, st);
-        return AZK_ERR_ARG;
-    }
-    if (t->epilogue == X_EPI_PLAIN) return launch_gemm_x<X_EPI_PLAIN, 0, 4, 128>(a, st);
-    if (t->epilogue == X_EPI_GELU) return wide ? launch_gemm_x<X_EPI_GELU, 0, 1, 512>(a, st) : launch_gemm_x<X_EPI_GELU, 0, 4, 128>(a, st);
-    if (t->epilogue == X_EPI_RESID) return launch_gemm_x<X_EPI_RESID, 0, 4, 128>(a, st);
-    return launch_gemm_x<X_EPI_HEADS, 0, 4, 128>(a, st);
-}
-
-// =====================================================================================================
-// k_gemm_h: the same links on the fp16 matrix pipe with every operand carried as TWO fp16 terms (x S = hi + lo: 22 significant
-// bits, the products hi*hi + hi*lo + lo*hi exact in the float32 accumulator; the dropped lo*lo term is 2^-22 relative).
-//   v_mfma_f32_16x16x4_f32 runs at the float32 VECTOR rate: the two wide links of the tail are 32.8 k matrix-pipe cycles per wave
-//   on it (31 us each at the clock these loops hold).  Three v_mfma_f32_16x16x32_f16 per 32-wide k-step instead of eight f32
+// k_gemm_h: one link of the cls-row tail in float32 accuracy on the fp16 matrix pipe: C[m][nbatch * N] = op(A) W^T (+ bias) through
+// the epilogues of k_tail_gemm, every operand carried as TWO fp16 terms (x S = hi + lo: 22 significant bits, the products
+// hi*hi + hi*lo + lo*hi exact in the float32 accumulator; the dropped lo*lo term is 2^-22 relative).
+//   Why not the float32-input MFMA: v_mfma_f32_16x16x4_f32 runs at the float32 VECTOR rate, the two wide links of the tail are 32.8 k
+//   matrix-pipe cycles per wave on it (31 us each, measured).  Three v_mfma_f32_16x16x32_f16 per 32-wide k-step instead of eight f32
 //   instructions of twice the length is 5.3x less pipe time at the same operand bytes (4 B per element either way).
+//   Wave tile 32 rows x 64 columns (2 x 4 MFMA tiles).  NWK = 4: the four waves of a workgroup split K (the small GEMMs: enough waves
+//   to fill the chip, a quarter of the chain each), partial sums meet in LDS, wave 0 runs the epilogue.  NWK = 1: the four waves are
+//   a 2 x 2 block of wave tiles (shared A rows and weight fragments hit in L1).
 //   Activations travel between the links as (hi, lo) planes written by the PRODUCING epilogue (four VALU per element, once),
 //   scaled by 16; the first link reads the float32 z of k_embed_pool_x and splits on the fly (each element is read by one wave only).
 //   Weights: (hi, lo) planes of w x 256 in fragment order Wp[N/64][K/32][4][2][64 lanes][8].
@@ -802,6 +592,8 @@ extern "C" int32_t azk_nnx_gemm(const azk_gemm_x *t, void *stream) {
 //   producer's partial sums, as before) LN(x) W'^T = rstd (x W'^T - mean csum), csum[n] = sum_k W'[n][k] precomputed.
 // =====================================================================================================
 namespace {
+
+enum { X_EPI_PLAIN = 0, X_EPI_GELU = 1, X_EPI_RESID = 2, X_EPI_HEADS = 3 };
 
 struct GemmHArgs {
     const _Float16 *Ahi, *Alo; const float *Af32; int lda, a_batch;

@@ -146,17 +146,15 @@ class PolicyValueNet:
         self.fast_outputs = False   # True: logits may come back as a bf16 view (the caller converts while copying)
         self.last_value_pre_tanh = False
         self.out_buffers = None     # optional (logits f32 [n,A], values f32 [n]) the fast tail writes into directly
-        self.hip_tail = False           # set by _prepare_folded when the hand-written tail kernels cover this configuration
-        self.use_hip_tail = False       # True: the cls-row tail on azk_nn_gemm_rows (every launch honours the live count; measured
-                                        # 87 us vs 82 us for the hipBLASLt tail at 2048 rows / 1150 live, so the library GEMMs stay the default)
+        self.hip_tail = False           # set by _prepare_folded: the packed head weight of k_ln_heads (WhGP / bhG_f) exists and covers this width
         self.leaf_source = None         # azk.LeafSource of the engine being stepped: the fused kernel reads the pending leaves itself
-        self.fuse_ln_heads = True       # final LayerNorm + heads + finalize as one hand-written launch (needs hip_tail's packed weights)
+        self.fuse_ln_heads = True       # final LayerNorm + heads + finalize as one hand-written launch (needs hip_tail's packed head weight)
         self.fused_embed_pool = False   # set by _prepare_folded when azk_nn_embed_pool covers this configuration
         self.chain_tail = False         # set by _prepare_folded when azk_nn_tail_gemm covers this configuration
         self.use_chain_tail = True
         self.use_lds_tail = True          # the two wide links of the chain tail LDS-staged (csrc/azk_tail.hip); False: k_tail_gemm for all five
         self.use_hip_blocks = True      # the full-token blocks (and the cls path outside the benchmark shape) on csrc/azk_block.hip when prepared
-        self.exact_tail = "f32"         # float32 network: "h16" once _prepare_exact_tables has built the fp16 (hi, lo) planes of the tail
+        self.exact_tail = "f32"         # plain data, selects nothing: "h16" once _prepare_exact_tables has built `_exact`
         self._exact_overflow = None     # sticky device flag of the fp16-plane tail (check_exact_range)
         self._tail_timer = None         # the tail timer while a sampled step is being timed (tail_fast)
         self._tail_ws = {}              # workspaces of the tail chain, one per board source, sized for the largest batch seen
@@ -228,7 +226,7 @@ class PolicyValueNet:
         return self
 
     def exact_fold(self, dev=None):
-        """Operands of the fp32-accurate folded cls path (csrc/azk_nnx.hip: k_embed_pool_x, k_gemm_x) before packing: the same folds
+        """Operands of the fp32-accurate folded cls path (csrc/azk_nnx.hip: k_embed_pool_x, k_gemm_h) before packing: the same folds
         as _prepare_folded / _prepare_compact - cls query through W_k, LayerNorm affines into the consuming weights, constant-token
         softmax terms - carried out in FLOAT64 from the float32 master weights and rounded once.  Returns None when the
         configuration is not covered (depth 1, D = 512, 4 / 8 heads, <= 256 tokens, conv K <= 64, a static softmax reference
@@ -328,22 +326,19 @@ class PolicyValueNet:
         # link of the (hi, lo)-plane tail); tables in float64 from the master weights
         rf = self.fold_u()
         e["foldu"] = azk.EmbedFoldTables(rf, H, cfg.patch_size, cfg.embed_dim, self.device, exact=True) if rf is not None else None
-        e["WvX"] = torch.cat([azk.pack_linear_weight_x(r["Wvn"][h]).reshape(-1) for h in range(H)])
-        for k_ in ("Wo", "W0G", "W3", "WhG"):
-            e[k_ + "X"] = azk.pack_linear_weight_x(r[k_])
         for k_ in ("bias1", "b0G", "b3", "bhG"):
             e[k_] = r[k_]
-        # the same weights as fp16 (hi, lo) planes for the fp16-pipe tail (azk_nnx_gemm_h) + the column sums its LayerNorm epilogue needs
+        # the tail's weights as fp16 (hi, lo) planes (azk_nnx_gemm_h) + the column sums its LayerNorm epilogue needs
         wvh = [azk.pack_linear_weight_h(r["Wvn"][h]) for h in range(H)]
         e["WvH"] = torch.cat([w_.reshape(-1) for w_, _ in wvh])
         for k_ in ("Wo", "W0G", "W3", "WhG"):
             e[k_ + "H"], e[k_ + "H_csum"] = azk.pack_linear_weight_h(r[k_])
-        self.exact_tail = "h16"                                # "h16": fp16 (hi, lo) planes on the fp16 matrix pipe; "f32": v_mfma_f32_16x16x4_f32
+        self.exact_tail = "h16"                                # plain data (bench.py reads it): the fp16 (hi, lo) planes of the tail exist
         self._exact = e
         self.fused_embed_pool = True                          # the step graph may hand the engine's pending leaves straight to the kernel
 
     def forward_exact_emulated(self, x, r=None):
-        """What k_embed_pool_x + k_gemm_x compute, step by step from the same folded tables, in float64 torch on any device: the
+        """What k_embed_pool_x + the five k_gemm_h links compute, step by step from the same folded tables, in float64 torch on any device: the
         checker of the kernels (tests) and of the fold itself (against the plain forward, on the CPU)."""
         cfg = self.cfg
         r = r or self.exact_fold(x.device)
@@ -456,7 +451,7 @@ class PolicyValueNet:
         """The fp32-accurate folded cls path: boards (or the engine's pending leaves) -> z float32 [n, H, D] -> logits, tanh(value)."""
         import azk
         cfg, e = self.cfg, self._exact
-        if (e.get("foldu") is not None and self.use_fold_u and self.exact_tail == "h16"
+        if (e.get("foldu") is not None and self.use_fold_u
                 and (self.leaf_source is None or self.leaf_source.n_games <= azk.EMBED_FOLD_MAX_SLOTS)):
             # the token rows are never formed (k_embed_fold<EX>): float32 rows of token weights / L, 1 / L, pooled patch / L per head
             if self.leaf_source is not None:
@@ -475,7 +470,7 @@ class PolicyValueNet:
                                    timers=self.kernel_timers)
         return self.tail_fast(z)
 
-    def tail_exact_h(self, z):
+    def tail_exact(self, z):
         """The fp32-accurate cls-row tail on the fp16 matrix pipe (csrc/azk_nnx.hip k_gemm_h): every operand as two fp16 terms (22
         bits), activations handed from link to link as (hi, lo) planes, LayerNorm in the consuming epilogue; five launches, each
         honouring the device-side live count (nn.py:54-60, 78-83 for the row the heads read)."""
@@ -524,38 +519,6 @@ class PolicyValueNet:
         if f is not None and int(f.item()) != 0:
             raise FloatingPointError("fp32-accurate tail: an activation left the range of its fp16 (hi, lo) planes (|x| >= 4094): use the torch "
                                      "float32 forward (path='cls') for this network")
-
-    def tail_exact(self, z):
-        """The cls-row tail as five float32 launches (csrc/azk_nnx.hip k_gemm_x), each honouring the device-side live count
-        (nn.py:54-60, 78-83 for the row the heads read)."""
-        import azk
-        if self.exact_tail == "h16":
-            return self.tail_exact_h(z)
-        cfg, e = self.cfg, self._exact
-        n, A, D, H = z.shape[0], cfg.action_dim, cfg.embed_dim, cfg.num_heads
-        dev, cnt = z.device, self.live_count
-        key = ("x", id(self.leaf_source) if self.leaf_source is not None else None)
-        ws = self._tail_ws.get(key)
-        if ws is None or ws["rows"] < n:
-            rows = n if ws is None else max(n, 2 * ws["rows"])
-            if ws is not None:
-                self._tail_ws_retired.append(ws)                 # never freed: captured graphs may hold these addresses
-            f32 = dict(dtype=torch.float32, device=dev)
-            ws = dict(rows=rows, u=torch.empty((rows, D), **f32), x1=torch.empty((rows, D), **f32), hh=torch.empty((rows, 4 * D), **f32),
-                      x2=torch.empty((rows, D), **f32), st1=torch.empty((rows, D // 64, 2), **f32), st2=torch.empty((rows, D // 64, 2), **f32))
-            self._tail_ws[key] = ws
-        ws = {k_: (v[:n] if k_ != "rows" else v) for k_, v in ws.items()}
-        self._launch(azk.nnx_gemm, z.view(n, H * D), e["WvX"], D // H, D, azk.TAIL_BF16, nbatch=H, a_batch_stride=D, out=ws["u"], count=cnt)
-        self._launch(azk.nnx_gemm, ws["u"], e["WoX"], D, D, azk.TAIL_BF16, bias=e["bias1"], out=ws["x1"], stats_out=ws["st1"], count=cnt)
-        self._launch(azk.nnx_gemm, ws["x1"], e["W0GX"], 4 * D, D, azk.TAIL_GELU, bias=e["b0G"], out=ws["hh"], a_stats=ws["st1"], count=cnt)
-        self._launch(azk.nnx_gemm, ws["hh"], e["W3X"], D, 4 * D, azk.TAIL_RESID, bias=e["b3"], resid=ws["x1"], out=ws["x2"], stats_out=ws["st2"], count=cnt)
-        if self.out_buffers is not None:
-            lb, vb = self.out_buffers
-        else:
-            lb = torch.empty((n, A), dtype=torch.float32, device=dev)
-            vb = torch.empty(n, dtype=torch.float32, device=dev)
-        self._launch(azk.nnx_gemm, ws["x2"], e["WhGX"], 256, D, azk.TAIL_HEADS, bias=e["bhG"], a_stats=ws["st2"], logits=lb, values=vb, action_dim=A, count=cnt)
-        return lb, (vb if self.out_buffers is not None else vb[:, None])
 
     def _prepare_folded(self):
         """Operands of the folded cls-row attention of the LAST block (csrc/azk_embed_tok.hip k_cls_attn):
@@ -647,21 +610,13 @@ class PolicyValueNet:
             f["Wh"], f["bh"] = Wh.to(torch.bfloat16), bh.to(torch.bfloat16)
             f["W0T"] = m["blocks.0.mlp.0.weight"].to(dev, torch.bfloat16).contiguous().t()             # logical [D, 4D], stored [4D, D]
             f["W3T"] = m["blocks.0.mlp.3.weight"].to(dev, torch.bfloat16).contiguous().t()             # logical [4D, D], stored [D, 4D]
-            # the same tail for the hand-written small-M GEMM (azk_nn_gemm_rows): weights in MFMA fragment order, float32 biases
+            # the hand-written GEMMs take their weights in MFMA fragment order (azk.pack_linear_weight) and float32 biases
             import azk
-            f["WcombP"] = azk.pack_linear_weight(Wcomb.t().contiguous())                               # [D, H*D] as an nn.Linear weight
-            f["W0P"] = azk.pack_linear_weight(m[b + "mlp.0.weight"].to(dev))
-            f["W3P"] = azk.pack_linear_weight(m[b + "mlp.3.weight"].to(dev))
-            f["WhP"] = azk.pack_linear_weight(Wh)
             f["bias1_f"] = (x0 + bo + Wo @ bvn).float().contiguous()
-            f["b0_f"] = m[b + "mlp.0.bias"].to(dev, torch.float32).contiguous()
-            bhp = torch.zeros(f["WhP"].numel() // D, device=dev)
-            bhp[:Ap] = bh
-            f["bh_f"] = bhp
             # final LayerNorm's affine folded into the merged head: Wh (gamma * xn + beta) + bh = (Wh diag(gamma)) xn + (Wh beta + bh)
             gf, bf_ = m["norm.weight"].to(dev), m["norm.bias"].to(dev)
             f["WhGP"] = azk.pack_linear_weight(Wh * gf[None, :])
-            bhg = torch.zeros_like(bhp)
+            bhg = torch.zeros(f["WhGP"].numel() // D, device=dev)          # (the packed weight's padded row count)
             bhg[:Ap] = Wh @ bf_ + bh
             f["bhG_f"] = bhg
             self.hip_tail = D in (256, 512) and (H * D) % 256 == 0
@@ -678,6 +633,7 @@ class PolicyValueNet:
                 # LDS-staged wide links (azk_nn_tail_gemm_lds): LayerNorm2 is applied in the epilogue, which needs the column sums of the
                 # weight the matrix pipe really multiplies with (the bf16 values of W0GP)
                 f["W0GP_csum"] = azk.packed_weight_col_sums(f["W0GP"], 4 * D, D)
+                f["W3P"] = azk.pack_linear_weight(m[b + "mlp.3.weight"].to(dev))
                 f["b0G_f"] = (W0 @ b2 + b0_).float().contiguous()
                 f["b3_f"] = m[b + "mlp.3.bias"].to(dev, torch.float32).contiguous()
                 if self.fused_embed_pool:
@@ -817,37 +773,6 @@ class PolicyValueNet:
         self.last_forward_kernels = "hand-written"
         return out[:, :A].contiguous(), torch.tanh(out[:, A:A + 1])
 
-    def tail_hip(self, z):
-        """tail_fast on the hand-written kernels: every launch honours the device-side live count, split-K partial sums are
-        added by the row-wise kernel that follows (LayerNorm / finalize)."""
-        import azk
-        cfg, f = self.cfg, self._fold
-        n, A, D, H = z.shape[0], cfg.action_dim, cfg.embed_dim, cfg.num_heads
-        dev, cnt = z.device, self.live_count
-        bf = dict(dtype=torch.bfloat16, device=dev)
-        k1 = 8 if (H * D // 32) % 8 == 0 else 1
-        P1 = torch.empty((k1, n, D), dtype=torch.float32, device=dev)
-        azk.nn_gemm_rows(z.view(n, H * D), f["WcombP"], D, ksplit=k1, partials=P1, count=cnt)              # nn.py:54-56
-        h = torch.empty((n, D), **bf)
-        x1b = torch.empty((n, D), **bf)
-        azk.nn_layernorm_sum(P1, f["ln2_w"], f["ln2_b"], h, bias=f["bias1_f"], add_bias=f["b3"], x_out=x1b, count=cnt)
-        hh = torch.empty((n, 4 * D), **bf)
-        azk.nn_gemm_rows(h, f["W0P"], 4 * D, bias=f["b0_f"], gelu_out=hh, count=cnt)                       # nn.py:59 (Linear + GELU)
-        P3 = torch.empty((4, n, D), dtype=torch.float32, device=dev)
-        azk.nn_gemm_rows(hh, f["W3P"], D, ksplit=4, partials=P3, count=cnt)                                # nn.py:59-60
-        y = torch.empty((n, D), **bf)
-        azk.nn_layernorm_sum(P3, f["lnf_w"], f["lnf_b"], y, resid=x1b, count=cnt)                          # nn.py:78
-        Np = f["bh_f"].numel()
-        P4 = torch.empty((4, n, Np), dtype=torch.float32, device=dev)
-        azk.nn_gemm_rows(y, f["WhP"], Np, ksplit=4, partials=P4, count=cnt)                                # nn.py:82-83
-        if self.out_buffers is not None:
-            lb, vb = self.out_buffers
-        else:
-            lb = torch.empty((n, A), dtype=torch.float32, device=dev)
-            vb = torch.empty(n, dtype=torch.float32, device=dev)
-        azk.nn_heads_finalize_sum(P4, f["bh_f"], A, lb, vb, count=cnt)
-        return lb, (vb if self.out_buffers is not None else vb[:, None])
-
     def tail_chain(self, z):
         """The cls-row tail as five hand-written launches (csrc/azk_nn.hip k_tail_gemm), every one honouring the device-side live
         count:  u = blockdiag_h(Wv'_h) z_h  ->  x1 = u Wo^T + bias1 (+ row statistics)  ->  hh = GELU(LN2(x1) W0'^T + b0')  ->
@@ -916,20 +841,18 @@ class PolicyValueNet:
             kt.stop()
 
     def tail_choice(self, z):
-        """Which tail runs behind the pooled rows z: "exact" (float32 rows), "chain" (azk_nn_tail_gemm links), "hip" (azk_nn_gemm_rows)
-        or "library" (hipBLASLt GEMMs between the hand-written row kernels).  The first two time each of their launches themselves."""
+        """Which tail runs behind the pooled rows z: "exact" (float32 rows), "chain" (azk_nn_tail_gemm links) or "library" (hipBLASLt
+        GEMMs between the hand-written row kernels).  The first two time each of their launches themselves."""
         if z.dtype == torch.float32:
             return "exact"
         if self.chain_tail and self.use_chain_tail:
             return "chain"
-        if self.hip_tail and self.use_hip_tail:
-            return "hip"
         return "library"
 
     def _tail_fast(self, z):
         choice = self.tail_choice(z)
         if choice != "library":
-            return {"exact": self.tail_exact, "chain": self.tail_chain, "hip": self.tail_hip}[choice](z)
+            return {"exact": self.tail_exact, "chain": self.tail_chain}[choice](z)
         w, cfg, f = self.w, self.cfg, self._fold
         n, A = z.shape[0], cfg.action_dim
         import azk
@@ -948,7 +871,7 @@ class PolicyValueNet:
             else:
                 lb = torch.empty((n, A), dtype=torch.float32, device=z.device)
                 vb = torch.empty(n, dtype=torch.float32, device=z.device)
-            azk.nn_ln_heads(x2, None, None, f["WhGP"], f["bhG_f"], A, lb, vb, count=self.live_count)     # affine folded into WhGP / bhG_f
+            azk.nn_ln_heads(x2, f["WhGP"], f["bhG_f"], A, lb, vb, count=self.live_count)     # affine folded into WhGP / bhG_f
             return lb, (vb if self.out_buffers is not None else vb[:, None])
         out = F.linear(azk.nn_layernorm_rows(x2, f["lnf_w"], f["lnf_b"], 1e-5, count=self.live_count), f["Wh"], f["bh"])   # nn.py:78-83
         if self.out_buffers is not None:

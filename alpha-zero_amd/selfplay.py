@@ -214,6 +214,37 @@ def concurrent_streams(torch, device, n, spin_cycles=600_000):
     return chosen
 
 
+def _evaluate_step(ev, e, h, from_leaves, timer=None):
+    """The evaluator hand-off of one step of either runner: the evaluator runs over engine e's (fixed-size) leaf buffer - or reads
+    e's pending leaves itself (from_leaves) - honours the device-side leaf count and writes the step buffers of h.  Everything lent
+    to the evaluator is taken back afterwards: the step's row count belongs to THIS engine, and an evaluator shared with another
+    runner (or called directly afterwards) must not keep honouring it."""
+    if hasattr(ev, "leaf_source"):
+        ev.leaf_source = e.leaf_source() if from_leaves else None
+    had_fast = getattr(ev, "fast_outputs", False)
+    if hasattr(ev, "live_count"):
+        ev.live_count, ev.fast_outputs = e.n_leaf, True
+    if hasattr(ev, "kernel_timers"):
+        if timer is None:
+            ev.kernel_timers = None
+        elif getattr(ev, "fused_embed_pool", False):
+            ev.kernel_timers = (timer.child("k_embed_pool"), timer.child("k_tail"))
+        else:
+            ev.kernel_timers = (timer.child("k_embed"), timer.child("k_cls_pool"), timer.child("k_tail"))
+    if hasattr(ev, "out_buffers"):
+        ev.out_buffers = (h.logits_buf, h.values_buf)
+    logits, values = ev(e.leaf_boards)
+    if logits.data_ptr() != h.logits_buf.data_ptr():        # evaluators that do not write the step buffers themselves
+        h.logits_buf.copy_(logits)
+        h.values_buf.copy_(values.reshape(-1))
+    if hasattr(ev, "out_buffers"):
+        ev.out_buffers = None
+    if hasattr(ev, "leaf_source"):
+        ev.leaf_source = None
+    if hasattr(ev, "live_count"):
+        ev.live_count, ev.fast_outputs = None, had_fast
+
+
 class SelfPlayRunner:
     """Continuous self-play: G slots advance one move per `play_move()`; a slot whose game ends restarts
     from an empty board in the same call (azk_recycle_finished), so every move does G searches.
@@ -346,8 +377,6 @@ class SelfPlayRunner:
         older boards; kernels that honour `live_count` skip them and nothing ever reads their outputs."""
         e = h.eng
         from_leaves = getattr(self.evaluator, "fused_embed_pool", False) and self.leaf_source_ok
-        if hasattr(self.evaluator, "leaf_source"):
-            self.evaluator.leaf_source = e.leaf_source() if from_leaves else None
         if timer is not None:
             timer.start()
             e.step_tree(h.logits_buf, h.values_buf)
@@ -358,32 +387,7 @@ class SelfPlayRunner:
             e.step_tree(h.logits_buf, h.values_buf)          # the network kernel compacts the leaves itself
         else:
             e.step(h.logits_buf, h.values_buf)
-        had_fast = getattr(self.evaluator, "fast_outputs", False)
-        if hasattr(self.evaluator, "live_count"):
-            self.evaluator.live_count = e.n_leaf
-            self.evaluator.fast_outputs = True
-        if hasattr(self.evaluator, "kernel_timers"):
-            if timer is None:
-                self.evaluator.kernel_timers = None
-            elif getattr(self.evaluator, "fused_embed_pool", False):
-                self.evaluator.kernel_timers = (timer.child("k_embed_pool"), timer.child("k_tail"))
-            else:
-                self.evaluator.kernel_timers = (timer.child("k_embed"), timer.child("k_cls_pool"), timer.child("k_tail"))
-        if hasattr(self.evaluator, "out_buffers"):
-            self.evaluator.out_buffers = (h.logits_buf, h.values_buf)
-        logits, values = self.evaluator(e.leaf_boards)
-        if logits.data_ptr() != h.logits_buf.data_ptr():        # evaluators that do not write the step buffers themselves
-            h.logits_buf.copy_(logits)
-            h.values_buf.copy_(values.reshape(-1))
-        if hasattr(self.evaluator, "out_buffers"):
-            self.evaluator.out_buffers = None
-        if hasattr(self.evaluator, "leaf_source"):
-            self.evaluator.leaf_source = None
-        if hasattr(self.evaluator, "live_count"):
-            # the step's row count belongs to THIS engine: an evaluator shared with another runner (or called directly afterwards)
-            # must not keep honouring it
-            self.evaluator.live_count = None
-            self.evaluator.fast_outputs = had_fast
+        _evaluate_step(self.evaluator, e, h, from_leaves, timer)
 
     def _all_bodies(self):
         torch = self.torch
@@ -593,10 +597,8 @@ class AsyncSelfPlayRunner:
 
     # the lock-step runner's step body, with the asynchronous tree step in front
     def _step_body(self, timer=None):
-        h, e, ev = self.h, self.eng, self.evaluator
-        from_leaves = getattr(ev, "fused_embed_pool", False) and self.leaf_source_ok
-        if hasattr(ev, "leaf_source"):
-            ev.leaf_source = e.leaf_source() if from_leaves else None
+        h, e = self.h, self.eng
+        from_leaves = getattr(self.evaluator, "fused_embed_pool", False) and self.leaf_source_ok
         if timer is not None:
             timer.start()
             e.async_step(h.logits_buf, h.values_buf, 1)     # k_tree alone between the events
@@ -606,24 +608,7 @@ class AsyncSelfPlayRunner:
             e.async_step(h.logits_buf, h.values_buf, 3)
         if not from_leaves:
             e.step_gather()
-        had_fast = getattr(ev, "fast_outputs", False)
-        if hasattr(ev, "live_count"):
-            ev.live_count, ev.fast_outputs = e.n_leaf, True
-        if hasattr(ev, "kernel_timers"):
-            ev.kernel_timers = None if timer is None else ((timer.child("k_embed_pool"), timer.child("k_tail")) if getattr(ev, "fused_embed_pool", False)
-                                                            else (timer.child("k_embed"), timer.child("k_cls_pool"), timer.child("k_tail")))
-        if hasattr(ev, "out_buffers"):
-            ev.out_buffers = (h.logits_buf, h.values_buf)
-        logits, values = ev(e.leaf_boards)
-        if logits.data_ptr() != h.logits_buf.data_ptr():
-            h.logits_buf.copy_(logits)
-            h.values_buf.copy_(values.reshape(-1))
-        if hasattr(ev, "out_buffers"):
-            ev.out_buffers = None
-        if hasattr(ev, "leaf_source"):
-            ev.leaf_source = None
-        if hasattr(ev, "live_count"):
-            ev.live_count, ev.fast_outputs = None, had_fast
+        _evaluate_step(self.evaluator, e, h, from_leaves, timer)
 
     def _capture(self):
         torch = self.torch

@@ -28,8 +28,10 @@ extern "C" {
 #endif
 
 /* 2: azk_emit_finished's game_base_dev became int64*, azk_leaf_source gained cache_stamp, azk_config gained cache_shared /
- * leaves_per_step (round 2); callers compare azk_abi_version() with the header they were built against */
-#define AZK_ABI_VERSION 4
+ * leaves_per_step (round 2); 5: the split-K row GEMM with its two summing kernels and the float32-input MFMA tail
+ * link were retired, azk_nn_ln_heads lost its unfolded-affine operands; callers compare azk_abi_version() with the header they were
+ * built against */
+#define AZK_ABI_VERSION 5
 
 /* games (games/tictactoe.py, games/connect4.py, games/gomoku.py) */
 #define AZK_TICTACTOE 0
@@ -454,24 +456,16 @@ int32_t azk_nn_embed_pool_compact_leaves(const azk_leaf_source *src, const azk_e
                                          int32_t *sched_dev, void *stream);
 
 /* ---- cls-row tail (nn.py:54-60, 78-83 for the row the heads read): small-M GEMMs with a device-side row count.
- * azk_nn_gemm_rows: C = A W^T for A bf16 [m][lda] (first k columns), W = an nn.Linear weight [n_out][k] packed in MFMA
- *   B-fragment order: Wp[n_out/64][k/32][4][64][8] with element [g][s][c][lane][i] = W[64 g + 4 (lane&15) + c][32 s + 8 (lane>>4) + i]
- *   (n_out a multiple of 64, k of 32).  Either partials_out_dev != NULL: the K range is split over `ksplit` waves and
- *   float32 partial sums are written to [ksplit][m][n_out] planes (the row-wise kernel that follows adds them: no
- *   atomics); or gelu_out_bf16_dev != NULL (ksplit 1): bf16 [m][n_out] = GELU(A W^T + bias) (nn.GELU, exact erf).
- * azk_nn_layernorm_sum: x = sum of nsplit partial planes (plane stride m_stride rows) (+ bias) (+ resid bf16);
- *   y = LayerNorm(x) bf16; optional x_out = x + add_bias bf16 (the residual the next product is added to).
- * azk_nn_heads_finalize_sum: logits / tanh(value) from the partial planes of the merged head GEMM (+ bias).
- * n_valid_dev as above: rows at or beyond it are neither read nor written. */
-int32_t azk_nn_gemm_rows(const void *a_bf16_dev, int32_t lda, const void *w_packed_dev, int32_t m, int32_t n_out, int32_t k,
-                         int32_t ksplit, float *partials_out_dev, const float *bias_dev, void *gelu_out_bf16_dev,
-                         const int32_t *n_valid_dev, void *stream);
+ * Packed weights (azk.pack_linear_weight): an nn.Linear weight [n_out][k] as bf16 in MFMA B-fragment order
+ *   Wp[n_out/64][k/32][4][64][8] with element [g][s][c][lane][i] = W[64 g + 4 (lane&15) + c][32 s + 8 (lane>>4) + i]
+ *   (n_out a multiple of 64 - pad with zero rows -, k of 32): one 16-byte load per fragment, and a lane's four accumulators
+ *   of a row are four consecutive output columns. */
 /* azk_nn_tail_gemm - one link of the cls-row tail as a latency-shaped small GEMM (every load of a K chunk in flight before
  * the first MFMA, no LDS):  C[m][nbatch * n_out] = op(A) W^T (+ bias) through one of four epilogues.
  *   a_bf16 [m][lda] row-major; batch b reads A columns [b * a_batch_stride, b * a_batch_stride + k), multiplies them with
  *   weight block b and writes output columns [b * n_out, (b + 1) * n_out) - nbatch = 1 is a plain GEMM, nbatch = heads is the
  *   block-diagonal per-head value projection.  w_packed: nbatch consecutive nn.Linear weights [n_out][k] in
- *   azk_nn_gemm_rows' fragment packing.  k = 512 or 2048 (or 384 = AZK_EMBED_FOLD_ROW, plain bf16 epilogue only); n_out a multiple of 64.
+ *   azk.pack_linear_weight's fragment packing (above).  k = 512 or 2048 (or 384 = AZK_EMBED_FOLD_ROW, plain bf16 epilogue only); n_out a multiple of 64.
  *   layernorm_a (k = 512): A = LayerNorm(rows) without affine (fold it into weight / bias: W diag(gamma), W beta + b); the row
  *            statistics are read from a_stats [m][a_stats_groups][2] = per 64-column group (sum, sum of squares) of the row, as
  *            left by the GEMM that produced A (its stats_out); a_stats_groups must be 8 (= k / 64; 64-byte rows, 16-byte aligned).
@@ -512,20 +506,13 @@ int32_t azk_nn_tail_lds_footprint(int32_t small);
 int32_t azk_nn_embed_fold_grid(int32_t max_workgroups);
 
 /* azk_nn_ln_heads: final LayerNorm + merged policy/value head + finalize in one launch (nn.py:78-83 for the cls row):
- *   logits[n][A] = LN(x) Wh^T + bh (float32), values[n] = tanh(column A).  w_packed_dev: the merged head weight
- *   [n_out_padded][embed_dim] in azk_nn_gemm_rows' packing; each wave reads whole rows and takes their statistics itself.
- *   ln_w_dev = ln_b_dev = NULL: LayerNorm's affine is already folded into the operands (weight W diag(gamma), bias
- *   W beta + b); the kernel then fetches its 16-row slab once and normalises from registers (embed_dim 256 or 512). */
-int32_t azk_nn_ln_heads(const void *x_bf16_dev, const float *ln_w_dev, const float *ln_b_dev, float eps, const void *w_packed_dev,
-                        const float *bias_dev, int32_t n, int32_t embed_dim, int32_t n_out_padded, int32_t action_dim,
-                        float *logits_out_dev, float *values_out_dev, const int32_t *n_valid_dev, void *stream);
-int32_t azk_nn_layernorm_sum(const float *partials_dev, int32_t nsplit, int32_t m_stride, const float *bias_dev,
-                             const void *resid_bf16_dev, const float *w_dev, const float *b_dev, float eps, void *y_bf16_dev,
-                             const float *add_bias_dev, void *x_out_bf16_dev, int32_t n, int32_t embed_dim,
-                             const int32_t *n_valid_dev, void *stream);
-int32_t azk_nn_heads_finalize_sum(const float *partials_dev, int32_t nsplit, int32_t m_stride, int32_t ld, const float *bias_dev,
-                                  int32_t action_dim, int32_t n, float *logits_out_dev, float *values_out_dev,
-                                  const int32_t *n_valid_dev, void *stream);
+ *   logits[n][A] = LN(x) Wh^T + bh (float32), values[n] = tanh(column A).  LayerNorm's affine is folded into the operands by the
+ *   caller: w_packed_dev = the merged head weight times diag(gamma), [n_out_padded][embed_dim] in azk.pack_linear_weight's packing,
+ *   bias_dev = Wh beta + bh.  Each wave fetches its 16-row slab once, takes the row statistics from those registers and normalises
+ *   on the way into the MFMAs (embed_dim 256 or 512). */
+int32_t azk_nn_ln_heads(const void *x_bf16_dev, float eps, const void *w_packed_dev, const float *bias_dev, int32_t n,
+                        int32_t embed_dim, int32_t n_out_padded, int32_t action_dim, float *logits_out_dev, float *values_out_dev,
+                        const int32_t *n_valid_dev, void *stream);
 
 /* azk_nn_embed_fold(_leaves) - the embedding + cls pooling WITHOUT forming the token rows (round 3; ai/nn.py:7-27, 36-56 for the
  * cls row, as azk_nn_embed_pool_compact + the first azk_nn_tail_gemm link).  With x_t = Wc p_t + cpos_t (p_t: the 0/1 patch of token
@@ -603,35 +590,21 @@ int32_t azk_nnx_embed_pool(const void *boards_dev, int32_t boards_are_f32, const
                            const int32_t *n_valid_dev, int32_t *sched_dev, void *stream);
 int32_t azk_nnx_embed_pool_leaves(const azk_leaf_source *src, const azk_embed_pool_x_consts *consts, float *z_out_f32_dev,
                                   int32_t *sched_dev, void *stream);
-/* azk_nnx_gemm - azk_nn_tail_gemm in float32: a_f32 [m][lda], out_f32 / resid_f32 float32, w_packed = nbatch consecutive nn.Linear
- * weights [n_out][k] as float32 in fragment order Wp[n_out/64][k/16][4][64 lanes][4]: element [g][s][c][lane][i] =
- * W[64 g + 4 (lane&15) + c][16 s + 4 (lane>>4) + i].  k = 512 or 2048.  layernorm_a (k = 512): a_stats [m][8][2] as left by the producing
- * call's stats_out.  Epilogues 0-3 as azk_nn_tail_gemm (GELU = exact erf form via erff). */
-typedef struct azk_gemm_x {
-    const float *a_f32; int32_t lda, a_batch_stride;
-    const float *w_packed;
-    int32_t m, n_out, k, nbatch;
-    const int32_t *n_valid;
-    const float *bias;
-    int32_t layernorm_a, epilogue;
-    float ln_eps;
-    const float *a_stats;
-    float *stats_out;
-    float *out_f32; int32_t ldo;
-    const float *resid_f32; int32_t ldr;
-    float *logits_out, *values_out; int32_t action_dim;
-} azk_gemm_x;
-int32_t azk_nnx_gemm(const azk_gemm_x *desc, void *stream);
-
-/* azk_nnx_gemm_h - the same link with every operand as TWO fp16 terms (x scale = hi + lo, 22 significant bits; products hi*hi + hi*lo +
- * lo*hi exact in the float32 accumulator) on v_mfma_f32_16x16x32_f16: a fifth of the matrix-pipe time of the float32-input MFMA.
+/* azk_nnx_gemm_h - one link of the cls-row tail (azk_nn_tail_gemm's function: C[m][nbatch * n_out] = op(A) W^T (+ bias) through
+ * epilogues 0-3, batches and n_valid as there) in float32 accuracy: every operand as TWO fp16 terms (x scale = hi + lo, 22
+ * significant bits; products hi*hi + hi*lo + lo*hi exact in the float32 accumulator) on v_mfma_f32_16x16x32_f16, a fifth of the
+ * matrix-pipe time of the float32-input MFMA.  k = 512 or 2048 (or AZK_EMBED_FOLD_ROW with a_f32).
  *   A: either (a_hi, a_lo) fp16 planes [m][lda] holding a * a_scale (written by the producing call's out_hi / out_lo), or a_f32
- *      float32 [m][lda] split on the fly (first link only: k = 512, epilogue 0);
+ *      float32 [m][lda] split on the fly (first link only: epilogue 0);
  *   w_packed: nbatch weights [n_out][k] x w_scale as fp16 (hi, lo) in fragment order Wp[n_out/64][k/32][4][2][64 lanes][8]:
  *      element [g][s][c][p][lane][i] = term p of W[64 g + 4 (lane&15) + c][32 s + 8 (lane>>4) + i];
- *   layernorm_a: LayerNorm moves into the epilogue - out = rstd (acc - mean col_sums[n]) + bias, col_sums[n] = sum_k W[n][k] (of the
- *      reconstructed terms), mean / rstd from a_stats as in azk_nnx_gemm;
- *   outputs: out_f32 and / or (out_hi, out_lo) planes (x a_scale) [m][ldo]; stats_out / heads as azk_nnx_gemm. */
+ *   layernorm_a (k = 512): LayerNorm moves into the epilogue - out = rstd (acc - mean col_sums[n]) + bias, col_sums[n] = sum_k W[n][k]
+ *      (of the reconstructed terms), mean / rstd from a_stats [m][8][2] = per 64-column group (sum, sum of squares) of the row, as
+ *      left by the producing call's stats_out;
+ *   outputs: out_f32 and / or (out_hi, out_lo) planes (x a_scale) [m][ldo]; stats_out (optional, epilogues 0-2): float32
+ *      [m][nbatch * n_out / 64][2], the same partials of the rows written here;
+ *   epilogue 0: acc + bias;  1: GELU(acc + bias) (exact erf form via erff);  2: acc + bias + resid_f32;
+ *            3: merged heads - logits_out float32 [m][action_dim], values_out[m] = tanh(column action_dim). */
 typedef struct azk_gemm_h {
     const void *a_hi, *a_lo; const float *a_f32; int32_t lda, a_batch_stride;
     const void *w_packed;
@@ -668,7 +641,7 @@ int32_t azk_vanilla_search(azk_engine *e, int32_t n_sims, void *stream);
 
 /* ---- the full-token transformer block (ai/nn.py:38-61) for networks with depth > 1 (csrc/azk_block.hip) ----
  * azk_nn_gemm_tok: out[m][n_out] = A[m][k] W^T (+ bias) through an epilogue, LDS-staged (LDS-DMA in full lines, counted-wait ring):
- *   a_bf16 [m][lda] row-major; w_packed = an nn.Linear weight [n_out][k] in azk_nn_gemm_rows' fragment packing (n_out a multiple of
+ *   a_bf16 [m][lda] row-major; w_packed = an nn.Linear weight [n_out][k] in azk.pack_linear_weight's fragment packing (n_out a multiple of
  *   128 - pad with zero rows -, k a multiple of 64, k >= 128); epilogue 0: bf16 out; 1: bf16 GELU(.) (erf form); 2: bf16 out = . +
  *   resid_bf16[m][ldr]; 4: float32 out.  n_valid (optional, device): rows at or beyond it are neither read nor written. */
 typedef struct azk_gemm_tok {

@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 CFG = NetConfig(15, 15, 2, 225, 5, 512, 8, 1)
 CFG2 = NetConfig(15, 15, 2, 225, 5, 256, 8, 2)
-EXACT_TAILS = ("h16", "h16-conv", "f32")            # h16: k_embed_fold<EX>; h16-conv / f32: k_embed_pool_x (fp16-pipe / f32 MFMA tail)
+EXACT_TAILS = ("h16", "h16-conv")            # h16: k_embed_fold<EX>; h16-conv: k_embed_pool_x (both in front of the fp16-pipe tail)
 
 
 def canonical(cells, to_move):
@@ -113,10 +113,10 @@ def check_kat(tag, placed, ref_l, ref_v, tol_l, tol_v, names, value_rounding=Tru
 def test_every_evaluator_path_on_edge_boards_against_the_reference():
     """The reference's seed-0 logits / value on 139 boards (47 edge boards + the 92 search roots), each board placed twice inside a
     400-row batch with a device live count of 360.  Budgets: float32 paths logits 1e-5 / value 1e-6 (north_star's bar; the torch
-    'full' forward and the three fp32-accurate tails), bf16 paths logits 2e-2 / value 2e-3, plus the final rounding
+    'full' forward and the two fp32-accurate forms), bf16 paths logits 2e-2 / value 2e-3, plus the final rounding
     where the value is computed in bf16 to the end ('full', 'cls': tanh in bf16, whose half ulp at |v| in [0.5, 1) is 1.95e-3 - on the
     near-full board the torch bf16 forward lands 2.05e-3 from the reference, on the CPU as on the GPU).  A board's outputs are bit for
-    bit the same in both placements.  Measured (logits / value): fp32 'full' 2.4e-6 / 1.2e-7, the three fp32-accurate tails 1.2e-6 /
+    bit the same in both placements.  Measured (logits / value): fp32 'full' 2.4e-6 / 1.2e-7, the fp32-accurate forms 1.2e-6 /
     6e-8 - 1.2e-7; bf16 'full' 1.0e-2 / 2.1e-3, 'cls' 9.9e-3 / 2.3e-3, 'clsfold' (float32 value) 8.7e-3 / 4.6e-4."""
     x, rl, rv, _, _, _, names = kat_boards()
     failures = []
@@ -127,7 +127,7 @@ def test_every_evaluator_path_on_edge_boards_against_the_reference():
         net = PolicyValueNet(CFG, seed=0, device="cuda", dtype=dtype, path=path)
         if tail is not None:
             assert net._exact is not None
-            net.exact_tail, net.use_fold_u = tail.split("-")[0], tail == "h16"
+            net.use_fold_u = tail == "h16"
         failures += check_kat(f"{path} {str(dtype)[6:]}{' ' + tail if tail else ''}", run_placed(net, x, dtype), rl, rv, tol_l, tol_v, names)
     assert not failures, failures
 
@@ -191,11 +191,11 @@ EXPECTED_DIFFERING = []
 
 def test_exact_evaluator_searches_reproduce_the_reference():
     """800-simulation searches from the 92 positions of the reference's recorded 15x15 games with the fixture noise, under the
-    fp32-accurate evaluator (all three tails) and, as a control, the torch float32 'full' forward: every root child's cell order and
+    fp32-accurate evaluator (both embedding forms) and, as a control, the torch float32 'full' forward: every root child's cell order and
     visit count equal the reference's own search (north_star's 1e-5 on visit-count policies: not one visit moves), child Q within 1e-5
     (measured <= 1.8e-7), priors within 1e-6 relative for the hand-written kernels (measured 7.2e-7 - 7.9e-7) and 2e-6 for the torch
     control (measured 1.44e-6: its logits are up to 2.4e-6 from the reference's, against the kernels' 1.4e-6; a prior also carries
-    the engine's deterministic softmax, within 4 ulp of numpy's).  Measured: 92 / 92 positions identical under all four."""
+    the engine's deterministic softmax, within 4 ulp of numpy's).  Measured: 92 / 92 positions identical under every one."""
     positions, noise, ref, _, _ = reference_searches()
     assert len(positions) == 92
     found = {}
@@ -204,7 +204,7 @@ def test_exact_evaluator_searches_reproduce_the_reference():
         net = PolicyValueNet(CFG, seed=0, device="cuda", dtype=torch.float32, path=path)
         if tail is not None:
             assert net._exact is not None
-            net.exact_tail, net.use_fold_u = tail.split("-")[0], tail == "h16"
+            net.use_fold_u = tail == "h16"
         tag = f"fp32 {path}{' ' + tail if tail else ''}"
         got = search_children(net, "float32", positions, noise)
         found[tag] = compare_searches(got, ref, tag)

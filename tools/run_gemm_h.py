@@ -1,4 +1,4 @@
-"""Micro-driver: the five links of the fp32-accurate tail (azk_nnx_gemm_h / azk_nnx_gemm) in isolation, time per launch.
+"""Micro-driver: the five links of the fp32-accurate tail (azk_nnx_gemm_h) in isolation, time per launch.
 usage: run_gemm_h.py [rows live] [reps]"""
 import os
 import sys

@@ -59,4 +59,4 @@ netx.out_buffers = net.out_buffers
 for rnd in range(2):
     for lds in (True, False):
         netx.use_lds_tail = lds
-        print(f"round {rnd} fp32-accurate tail, wide links {'LDS-staged' if lds else 'in registers'}: rows {n} live {live}: {timeit(lambda: netx.tail_exact_h(zx)):.2f} us per tail")
+        print(f"round {rnd} fp32-accurate tail, wide links {'LDS-staged' if lds else 'in registers'}: rows {n} live {live}: {timeit(lambda: netx.tail_exact(zx)):.2f} us per tail")

@@ -305,7 +305,11 @@ int32_t azk_check_device_error(azk_engine *e, void *stream);
 
 /* Dirichlet(alpha) rows and uniforms from a counter-based generator keyed by
  * (seed, global game index, move index) - results do not depend on how games are sharded over GPUs.
- * noise_dev float64 [count][A]; uniforms_dev float64 [count] (either may be NULL). */
+ * noise_dev float64 [count][A]; uniforms_dev float64 [count] (either may be NULL).
+ * Philox4x32-10, key (seed lo, seed hi); the uniform's counter is {game lo, game hi, move, 0xFFFFFFFF}, entry a's tries it = 0..63 draw
+ * from {game lo, game hi ^ (a << 8), move, it} and it | 0x40000000.  A <= 400 keeps the action index in bits 8..16 of word 1, so the
+ * streams of distinct (game, action) pairs are distinct for global game indices below 2^40, and word 3 keeps the uniform and the
+ * playout-cap coin out of every row's draws (tests/rng_restated.py restates the whole chain in float64). */
 int32_t azk_gen_noise(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double alpha,
                       double *noise_dev, double *uniforms_dev, void *stream);
 

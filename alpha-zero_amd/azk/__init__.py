@@ -283,21 +283,31 @@ class Engine:
     def step_expand_backup(self, logits, values):
         self._chk(self.L.azk_step_expand_backup(self.h, _p(logits), _p(values), _stream()))
 
+    def evaluate_leaves(self, evaluator, n):
+        """Eager stepping's hand-off: the evaluator over the n pending leaf boards (n = the synced n_leaf, > 0), its outputs as
+        step / step_expand_backup take them - contiguous float32 logits [n, A] and values [n]."""
+        logits, values = evaluator(self.leaf_boards[:n])
+        logits = logits.to(self.torch.float32).contiguous()
+        values = values.to(self.torch.float32).reshape(-1).contiguous()
+        assert logits.shape == (n, self.action_dim) and values.shape[0] == n
+        return logits, values
+
+    def placeholder_rows(self):
+        """(logits [1, A], values [1]) to pass to a step whose pending leaves all came from the eval cache (nothing reads them), or
+        (None, None) on an engine that never has such a step."""
+        return self._no_logits, self._no_values
+
     def search(self, evaluator, n_sims, noise=None):
         """MCTS.mcts for all G games: n_sims simulations each, one in flight per game.
         evaluator(boards[n,F,R,C]) -> (logits[n,A] float32, values[n] or [n,1] float32), on the GPU."""
         assert n_sims <= self.max_sims
-        torch = self.torch
         self.begin_search(noise)
         logits = values = None
         for _ in range(n_sims):
             self.step(logits, values)
             n = int(self.n_leaf.item())
             if n > 0:
-                logits, values = evaluator(self.leaf_boards[:n])
-                logits = logits.to(torch.float32).contiguous()
-                values = values.to(torch.float32).reshape(-1).contiguous()
-                assert logits.shape == (n, self.action_dim) and values.shape[0] == n
+                logits, values = self.evaluate_leaves(evaluator, n)
             elif self.cache_entries:
                 logits, values = self._no_logits, self._no_values      # cache hits still need their expand + backup
             else:
@@ -309,7 +319,6 @@ class Engine:
         """The same search as `search` - bit-identical trees - with budget stepping: a game runs on inside a launch while its
         simulations need no evaluator, so n_sims simulations take about (share of simulations that miss the cache) * n_sims
         launches, each with a fuller evaluator batch.  Returns the number of launches."""
-        torch = self.torch
         self.begin_search_budget(noise, n_sims, per_launch, move_index)
         logits = values = None
         launches = 0
@@ -318,10 +327,7 @@ class Engine:
             launches += 1
             n = int(self.n_leaf.item())
             if n > 0:
-                logits, values = evaluator(self.leaf_boards[:n])
-                logits = logits.to(torch.float32).contiguous()
-                values = values.to(torch.float32).reshape(-1).contiguous()
-                assert logits.shape == (n, self.action_dim) and values.shape[0] == n
+                logits, values = self.evaluate_leaves(evaluator, n)
             else:
                 logits, values = (self._no_logits, self._no_values) if self._no_logits is not None else (None, None)
                 if self.unfinished() == 0:

@@ -46,9 +46,9 @@ int32_t azk_create(const azk_config *cfg, azk_engine **out) {
     d.G = cfg->n_games; d.cap = (int)cap; d.path_cap = g.state_dim + 2; d.rc_pad = up16(g.rc);
     d.leaf_dtype = cfg->leaf_dtype; d.table_size = table_size_for(g);
     { const char *ab = getenv("AZK_TREE_ABLATE"); d.ablate = ab ? atoi(ab) : 0; }
-    int off[15];
+    int off[LDS_REGIONS];
     d.lds_bytes = lds_layout(g, d.path_cap, d.table_size, off);
-    for (int i = 0; i < 12; i++) d.lds_off[i] = off[i];
+    for (int i = 0; i < LDS_REGIONS_DEV; i++) d.lds_off[i] = off[i];
     const size_t G = d.G, nodes = G * (size_t)d.cap;
     hipError_t s = hipSuccess;
 #define DA(ptr, count) if (s == hipSuccess) s = dalloc(e, &ptr, (count))

@@ -2,10 +2,11 @@
 // kernel-free azk_engine.hip): the device view of the engine and its LDS layout, the node-record helpers, the host
 // struct behind the opaque azk_engine, and the few host symbols that cross files.  Not part of the ABI (include/azk.h).  A __device__
 // function is here only if kernels of two files call it.
-// The device types stay in an UNNAMED namespace although struct azk_engine, a global type, has members of them (every file includes
-// this one definition, so the layouts cannot drift apart): Dev is a parameter of nearly every engine kernel, and as long as it is
-// `(anonymous namespace)::Dev` each kernel keeps the mangled name tools/compare_kernel_isa.py compares builds by.  A named namespace
-// would be the cleaner form and renames every engine kernel at once - a commit of its own.
+// The shared types and helpers live in namespace azk_eng, which every file that includes this header uses: struct azk_engine, a global
+// type whose members are of those types and whose pointers cross files (azk_launch_tree, azk_init_games), is then ONE type in every
+// translation unit.  The kernels themselves stay in each .hip file's unnamed namespace.  tools/compare_kernel_isa.py --strip-namespace
+// azk_eng compares such a build with one from before the namespace had a name (Dev is a parameter of nearly every engine kernel, so
+// naming it changed their mangled symbols and nothing else).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -19,16 +20,19 @@
 #include "azk.h"
 #include "azk_device.h"
 
-namespace {
+namespace azk_eng {
 
 enum { CNT_SIMS = 0, CNT_SCANNED, CNT_TRACE, CNT_CREATED, CNT_LEAVES, CNT_TERMINAL, CNT_MOVES, CNT_CACHE_HITS, CNT_REUSED, CNT_CARRIED, CNT_N };
 
 struct __attribute__((aligned(16))) NodeH { int N; float P; uint32_t meta; int fc; };
 
+enum { LDS_REGIONS = 14,      // regions of an engine block's LDS: what lds_layout() fills in
+       LDS_REGIONS_DEV = 12 };  // the first of them, whose offsets travel in Dev; carve_at() derives the last two
+
 struct Dev {               // device view of the engine, passed to kernels by value
     GameDesc g;
     int G, cap, path_cap, rc_pad, leaf_dtype, table_size, lds_bytes;
-    int lds_off[12];       // lds_layout()'s offsets, computed once on the host (k_tree reads them instead of redoing the arithmetic in every wave)
+    int lds_off[LDS_REGIONS_DEV];   // lds_layout()'s offsets, computed once on the host (k_tree reads them instead of redoing the arithmetic in every wave)
     int K;                 // leaves in flight per game (virtual-loss mode, opt-in; 1 = the reference's sequential search).  Every
                            // pending-leaf array below is [G * K], slot v = g * K + k
     // game state
@@ -118,7 +122,7 @@ struct LdsView {
 __host__ __device__ inline int up16(int x) { return (x + 15) & ~15; }
 
 __host__ __device__ inline int lds_layout(const GameDesc &g, int path_cap, int table_size, int *off) {
-    // offsets (bytes) of: board, path, moves, e, cnt, cdf, bits, pref, ord, tabA, tabB, claim, board1, hand-off words
+    // off[LDS_REGIONS]: offsets (bytes) of board, path, moves, e, cnt, cdf, bits, pref, ord, tabA, tabB, claim, board1, hand-off words
     int o = 0;
     off[0] = o; o += up16(g.rc);
     off[1] = o; o += up16(path_cap * 4);
@@ -163,26 +167,12 @@ __device__ __forceinline__ LdsView carve_at(const int *off, int table_size, int 
     return L;
 }
 
+// the same view for a kernel that has no Dev (or no reason to read its offsets): lds_layout() puts board1 and the hand-off words exactly
+// where carve_at() looks for them
 __device__ __forceinline__ LdsView carve(const GameDesc &g, int path_cap, int table_size) {
-    int off[14];
+    int off[LDS_REGIONS];
     lds_layout(g, path_cap, table_size, off);
-    LdsView L;
-    L.board = azk_smem + off[0];
-    L.path = (int *)(azk_smem + off[1]);
-    L.moves = (int16_t *)(azk_smem + off[2]);
-    L.e = (float *)(azk_smem + off[3]);
-    L.cnt = (int *)(azk_smem + off[4]);
-    L.cdf = (double *)(azk_smem + off[5]);
-    L.ms.bits = (uint32_t *)(azk_smem + off[6]);
-    L.ms.pref = (uint16_t *)(azk_smem + off[7]);
-    L.ms.ord = (int16_t *)(azk_smem + off[8]);
-    L.ms.tabA = (uint16_t *)(azk_smem + off[9]);
-    L.ms.tabB = (uint16_t *)(azk_smem + off[10]);
-    L.ms.claim = (uint32_t *)(azk_smem + off[11]);
-    L.ms.table_size = table_size;
-    L.board1 = azk_smem + off[12];
-    L.ho = (int *)(azk_smem + off[13]);
-    return L;
+    return carve_at(off, table_size, g.rc);
 }
 
 __device__ __forceinline__ uint32_t meta_pack(int cell, int nch) { return ((uint32_t)(cell & 0xffff) << 16) | (uint32_t)nch; }
@@ -246,7 +236,8 @@ inline bool make_game(int kind, int rows, int cols, GameDesc *g, std::string *er
 
 inline int table_size_for(const GameDesc &g) { return g.rc < 307 ? 512 : 2048; }   // CPython set growth: 8 -> 32 -> 128 -> 512 -> 2048
 
-}  // namespace
+}  // namespace azk_eng
+using namespace azk_eng;
 
 struct azk_engine {
     Dev d;

@@ -23,6 +23,9 @@ __device__ __forceinline__ void clear_leaf_slots(const Dev &d, int g) {
     for (int k = 0; k < d.K; k++) { d.leaf_node[g * d.K + k] = -1; d.leaf_flag[g * d.K + k] = 0; d.to_move_v[g * d.K + k] = d.to_move[g]; }
 }
 
+// Game() for game g less its board (gomoku.py: player 0 to move, no ply played, no winner); the caller clears the cells
+__device__ __forceinline__ void new_game_one(const Dev &d, int g) { d.to_move[g] = 0; d.move_count[g] = 0; d.done[g] = 0; d.winner[g] = -2; }
+
 // Node(None, None, current_player, move_count) for every game (gomoku.py:134)
 __device__ __forceinline__ void fresh_root_one(const Dev &d, int g) {
     drop_pending_cache_claim(d, g);
@@ -217,7 +220,7 @@ __global__ void k_reset_games(Dev d, int first, int count, int *chosen_node) {
     const int g = first + t / d.rc_pad, i = t % d.rc_pad;
     d.cells[(size_t)g * d.rc_pad + i] = 0;
     if (i == 0) drop_pending_cache_claim(d, g);
-    if (i == 0) { d.to_move[g] = 0; d.move_count[g] = 0; d.done[g] = 0; d.winner[g] = -2; clear_leaf_slots(d, g); if (chosen_node) chosen_node[g] = -1; }
+    if (i == 0) { new_game_one(d, g); clear_leaf_slots(d, g); if (chosen_node) chosen_node[g] = -1; }
 }
 
 // Continuous self-play: every finished game's slot restarts from Game() (empty board, player 0).
@@ -231,7 +234,7 @@ __global__ void k_recycle(Dev d, long long *stats, int *chosen_node) {
     atomicAdd((unsigned long long *)&stats[w == 0 ? 2 : (w == 1 ? 3 : 4)], 1ull);
     drop_pending_cache_claim(d, g);
     for (int i = 0; i < d.rc_pad; i++) d.cells[(size_t)g * d.rc_pad + i] = 0;
-    d.to_move[g] = 0; d.move_count[g] = 0; d.done[g] = 0; d.winner[g] = -2;
+    new_game_one(d, g);
     clear_leaf_slots(d, g);
     if (chosen_node) chosen_node[g] = -1;
 }
@@ -597,18 +600,11 @@ __global__ __launch_bounds__(AZK_WAVE) void k_gen_noise(int A, unsigned long lon
 // game, slot move counter) is known a whole search before its use, so the rows are generated one search ahead, off the step's chain
 // (k_noise_ahead in the drain) - in this function the Marsaglia-Tsang chain (float64 log / cos / pow, two Philox blocks per try) cost a
 // moving game's wave ~30 us inside a launch every other wave had left after 1 us.
-__device__ __forceinline__ void begin_search_one(const Dev &d, const AsyncDev &p, int g, double *red) {
-    const int lane = azk_lane();
-    if (lane == 0) {
-        drop_pending_cache_claim(d, g);
-        const size_t base = (size_t)g * d.cap;
-        d.H[base] = NodeH{0, 0.f, meta_pack(0xffff, 0), -1}; d.W[base] = 0.0;
-        d.arena_top[g] = 1; d.root_f64[g] = 0;
-        clear_leaf_slots(d, g);
-        d.sims_done[g] = 0;
+__device__ __forceinline__ void begin_search_one(const Dev &d, const AsyncDev &p, int g) {
+    if (azk_lane() == 0) {
+        fresh_root_one(d, g);
         atomicAdd((unsigned long long *)&p.stats[7], 1ull);
     }
-    (void)red;
 }
 
 // drain: the Dirichlet rows that fell due since the last drain - for every game that moved, the row of the search AFTER the one it has
@@ -711,7 +707,7 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
             p.reroot_list[atomicAdd(p.reroot_count, 1)] = g;
         }
     } else if (!dn) {
-        begin_search_one(d, p, g, L.cdf);
+        begin_search_one(d, p, g);
         if (CAP && lane == 0) cap_begin_fresh(d, cp, g, (int)mv + 1, true);
     }
 }
@@ -760,9 +756,9 @@ __device__ __forceinline__ void async_restart_body(Dev d, AsyncDev p, int recycl
         }
         if (!recycle) { if (lane == 0) d.done[g] = 3; continue; }
         for (int i = lane; i < d.rc_pad; i += AZK_WAVE) d.cells[(size_t)g * d.rc_pad + i] = 0;
-        if (lane == 0) { d.to_move[g] = 0; d.move_count[g] = 0; d.done[g] = 0; d.winner[g] = -2; }
+        if (lane == 0) new_game_one(d, g);
         __syncthreads();
-        begin_search_one(d, p, g, L.cdf);
+        begin_search_one(d, p, g);
         if (CAP && lane == 0) cap_begin_fresh(d, cp, g, (int)p.slot_moves[g], true);
         __syncthreads();
     }
@@ -847,6 +843,38 @@ int32_t azk_init_games(azk_engine *e) {
     return AZK_OK;
 }
 
+// the start of a search for every game, on the stream: a fresh root, or on a tree-reuse engine the subtree under the played child (n_sims:
+// the simulations the search may run).  move_index >= 0: a capped engine - the coin of (seed, global game, move_index) sets each game's target
+static void launch_begin_search(azk_engine *e, int n_sims, int move_index, hipStream_t st) {
+    const Dev &d = e->d;
+    const unsigned per_game = (unsigned)((d.G + 255) / 256);
+    if (move_index >= 0) {
+        if (e->ru.mode) k_reroot_cap<<<d.G, AZK_WAVE, 0, st>>>(d, e->ru, e->cp, move_index);
+        else k_begin_search_cap<<<per_game, 256, 0, st>>>(d, e->cp, move_index);
+    } else if (e->ru.mode) k_reroot<<<d.G, AZK_WAVE, 0, st>>>(d, e->ru, n_sims);
+    else k_begin_search<<<per_game, 256, 0, st>>>(d);
+}
+
+// (state, pi, z) emission on the stream: each finished game's tuple range, the tuples, done = 2.  list == nullptr: one block per (game, ply)
+// of all G games; else the blocks walk the *n_list listed games (asynchronous drain).  A capped engine emits the plies of full searches only
+static void launch_emit(azk_engine *e, float *states, double *pis, float *zs, long long capacity, unsigned long long *cursor, long long *game_base,
+                        const int *list, const int *n_list, hipStream_t st) {
+    const Dev &d = e->d;
+    const unsigned per_game = (unsigned)((d.G + 255) / 256), lds = (unsigned)up16(d.g.rc);
+    const int plies = d.G * d.g.state_dim;
+    const unsigned blocks = (unsigned)(list && plies > 16384 ? 16384 : plies);
+    if (e->cp.n_fast) {
+        k_emit_alloc_cap<<<per_game, 256, 0, st>>>(d, e->cp, cursor, game_base);
+        if (list) k_emit_tuples_cap<true><<<blocks, AZK_WAVE, lds, st>>>(d, e->cp, states, pis, zs, capacity, cursor, list, n_list);
+        else k_emit_tuples_cap<false><<<blocks, AZK_WAVE, lds, st>>>(d, e->cp, states, pis, zs, capacity, cursor, nullptr, nullptr);
+    } else {
+        k_emit_alloc<<<per_game, 256, 0, st>>>(d, cursor, game_base);
+        if (list) k_emit_tuples<true><<<blocks, AZK_WAVE, lds, st>>>(d, states, pis, zs, capacity, cursor, list, n_list);
+        else k_emit_tuples<false><<<blocks, AZK_WAVE, lds, st>>>(d, states, pis, zs, capacity, cursor, nullptr, nullptr);
+    }
+    k_emit_mark<<<per_game, 256, 0, st>>>(d);
+}
+
 extern "C" {
 
 int32_t azk_reset_games(azk_engine *e, int32_t first, int32_t count, void *stream) {
@@ -863,8 +891,7 @@ int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream) {
     e->d.noise = noise_dev; e->d.noise_sel = nullptr;
     if (e->ru.mode == 2) { e->err = "azk_begin_search: top-up tree reuse needs the budget (azk_begin_search_budget)"; return AZK_ERR_STATE; }
     e->multi = false;
-    if (e->ru.mode) k_reroot<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d, e->ru, e->cfg.max_sims);
-    else k_begin_search<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d);
+    launch_begin_search(e, e->cfg.max_sims, -1, (hipStream_t)stream);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -880,11 +907,7 @@ static int32_t begin_budget(azk_engine *e, const double *noise_dev, int32_t n_si
         HIPCHK(e, hipMemcpyAsync(e->d.budget, e->budget_host, sizeof e->budget_host, hipMemcpyHostToDevice, (hipStream_t)stream));
         HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     }
-    if (move_index >= 0) {                                        // playout cap: the coin of (seed, global game, move_index) sets each game's target
-        if (e->ru.mode) k_reroot_cap<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d, e->ru, e->cp, move_index);
-        else k_begin_search_cap<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d, e->cp, move_index);
-    } else if (e->ru.mode) k_reroot<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d, e->ru, n_sims);
-    else k_begin_search<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d);
+    launch_begin_search(e, n_sims, move_index, (hipStream_t)stream);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -1038,17 +1061,7 @@ int32_t azk_async_drain(azk_engine *e, float *states_dev, double *pis_dev, float
     k_async_list<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, e->ad);
     if (states_dev) {
         if (!pis_dev || !zs_dev || !cursor_dev || capacity < 1 || !d.traj_pi) { e->err = "azk_async_drain: bad replay arguments"; return AZK_ERR_ARG; }
-        const int blocks = d.G * d.g.state_dim < 16384 ? d.G * d.g.state_dim : 16384;
-        if (e->cp.n_fast) {
-            k_emit_alloc_cap<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, e->cp, (unsigned long long *)cursor_dev, nullptr);
-            k_emit_tuples_cap<true><<<(unsigned)blocks, AZK_WAVE, up16(d.g.rc), st>>>(d, e->cp, states_dev, pis_dev, zs_dev, (long long)capacity,
-                                                                                    (const unsigned long long *)cursor_dev, e->ad.fin_list, e->ad.fin_count);
-        } else {
-        k_emit_alloc<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, (unsigned long long *)cursor_dev, nullptr);
-        k_emit_tuples<true><<<(unsigned)blocks, AZK_WAVE, up16(d.g.rc), st>>>(d, states_dev, pis_dev, zs_dev, (long long)capacity,
-                                                                            (const unsigned long long *)cursor_dev, e->ad.fin_list, e->ad.fin_count);
-        }
-        k_emit_mark<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d);
+        launch_emit(e, states_dev, pis_dev, zs_dev, (long long)capacity, (unsigned long long *)cursor_dev, nullptr, e->ad.fin_list, e->ad.fin_count, st);
     }
     if (e->cp.n_fast) k_async_restart_cap<<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->async_recycle, e->cp);
     else k_async_restart<<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->async_recycle);
@@ -1070,17 +1083,7 @@ int32_t azk_emit_finished(azk_engine *e, float *states_dev, double *pis_dev, flo
     if (!e || !states_dev || !pis_dev || !zs_dev || !cursor_dev || capacity < 1) return AZK_ERR_ARG;
     const Dev &d = e->d;
     if (!d.traj_pi) { e->err = "azk_emit_finished: (state, pi, z) emission needs a square board with one action per cell"; return AZK_ERR_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    if (e->cp.n_fast) {                                           // playout cap: the plies of full searches only
-        k_emit_alloc_cap<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, e->cp, (unsigned long long *)cursor_dev, (long long *)game_base_dev);
-        k_emit_tuples_cap<false><<<(unsigned)(d.G * d.g.state_dim), AZK_WAVE, up16(d.g.rc), st>>>(d, e->cp, states_dev, pis_dev, zs_dev, (long long)capacity,
-                                                                                                 (const unsigned long long *)cursor_dev, nullptr, nullptr);
-    } else {
-    k_emit_alloc<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, (unsigned long long *)cursor_dev, (long long *)game_base_dev);
-    k_emit_tuples<false><<<(unsigned)(d.G * d.g.state_dim), AZK_WAVE, up16(d.g.rc), st>>>(d, states_dev, pis_dev, zs_dev, (long long)capacity,
-                                                                                         (const unsigned long long *)cursor_dev, nullptr, nullptr);
-    }
-    k_emit_mark<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d);
+    launch_emit(e, states_dev, pis_dev, zs_dev, (long long)capacity, (unsigned long long *)cursor_dev, (long long *)game_base_dev, nullptr, nullptr, (hipStream_t)stream);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }

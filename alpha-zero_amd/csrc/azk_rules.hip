@@ -96,7 +96,7 @@ static int32_t run_rules(int mode, int32_t game, int32_t rows, int32_t cols, con
     a.mode = mode; a.n = n; a.table_size = table_size_for(a.g);
     a.boards_in = in; a.boards = inout; a.players = players; a.cells = cells;
     a.moves = moves; a.counts = counts; a.mask = mask; a.out_i = out_i; a.out_f = out_f;
-    int off[15];
+    int off[LDS_REGIONS];
     const int lds = lds_layout(a.g, 4, a.table_size, off);
     k_rules<<<n, AZK_WAVE, lds, (hipStream_t)stream>>>(a);
     hipError_t s = hipGetLastError();

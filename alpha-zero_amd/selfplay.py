@@ -345,7 +345,7 @@ class SelfPlayRunner:
 
     def search(self, noise):
         """Eager stepping (host sync per simulation, n_leaf-sized evaluator batches); optional k_tree event timing."""
-        e, torch, kt = self.eng, self.torch, self.kernel_timer
+        e, kt = self.eng, self.kernel_timer
         if self.tree_reuse == 2 or self.playout_cap is not None:
             e.search_budget(self.evaluator, self.n_sims, noise if self.dirichlet else None, self.per_launch, move_index=self.move_idx)
             return
@@ -361,11 +361,9 @@ class SelfPlayRunner:
                 e.step(logits, values)
             n = int(e.n_leaf.item())
             if n > 0:
-                logits, values = self.evaluator(e.leaf_boards[:n])
-                logits = logits.to(torch.float32).contiguous()
-                values = values.to(torch.float32).reshape(-1).contiguous()
+                logits, values = e.evaluate_leaves(self.evaluator, n)
             elif e.cache_entries:
-                logits, values = e._no_logits, e._no_values
+                logits, values = e.placeholder_rows()
             else:
                 logits = values = None
         if logits is not None:

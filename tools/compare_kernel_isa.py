@@ -3,12 +3,16 @@
 
     python3 tools/compare_kernel_isa.py OLD/csrc/build alpha-zero_amd/csrc/build [--match k_tree]
     python3 tools/compare_kernel_isa.py OLD/libazk.so alpha-zero_amd/azk/libazk.so
+    python3 tools/compare_kernel_isa.py OLD/csrc/build alpha-zero_amd/csrc/build --strip-namespace azk_eng
 
 Each side is a build directory (every *.o in it) or a library.  Every code object bundled in them is extracted (one per translation
 unit: csrc/azk_search.hip, azk_moves.hip, azk_nn.hip, ...), every kernel is cut at its symbol's size (llvm-readelf -s: llvm-objdump -d goes on to
 disassemble a section's padding as if it were code) and the instruction text is compared symbol by symbol, whichever file the
 symbol lives in on either side (addresses and encodings left out; kernels in anonymous namespaces keep their mangled names when
-they move between files).  The 64-byte kernel descriptors (register counts, LDS size, ...) are compared too, less the code's own
+they move between files).  A mangled name also spells the namespaces of the kernel's parameter types, so a type that moves to
+another namespace renames every kernel that takes it: --strip-namespace NS (repeatable) compares by DEMANGLED name instead
+(c++filt), with the qualifiers `NS::` and `(anonymous namespace)::` taken out on both sides; two kernels of one build that
+fall onto the same name that way are an error, never a silent pairing.  The 64-byte kernel descriptors (register counts, LDS size, ...) are compared too, less the code's own
 offset.  --match keeps the kernels whose name contains the string.  Exit status 1 if a kernel differs, is missing or is new.  This is
 how "k_tree's instruction stream did not change"  and "moving code between files left the device code alone"
  are checked."""
@@ -88,15 +92,38 @@ def kernels(path, work, tag):
     return out
 
 
+def plain_names(ks, namespaces, path):
+    """ks keyed by demangled name without the given namespace qualifiers (and never with `(anonymous namespace)::`)."""
+    names = sorted(ks)
+    cxxfilt = os.path.join(LLVM, "llvm-cxxfilt")
+    plain = subprocess.check_output([cxxfilt if os.path.exists(cxxfilt) else "c++filt"], input="\n".join(names), text=True).splitlines()
+    if len(plain) != len(names):
+        sys.exit("c++filt returned %d names for %d symbols of %s" % (len(plain), len(names), path))
+    strip = re.compile(r"\(anonymous namespace\)::|" + "|".join(r"\b%s::" % re.escape(ns) for ns in namespaces))
+    out = {}
+    for sym, name in zip(names, plain):
+        name = strip.sub("", name)
+        if name in out:
+            sys.exit("two kernels of " + path + " are both `" + name + "` once the namespaces are stripped (the second: " + sym + ")")
+        out[name] = ks[sym]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("old", help="build directory (csrc/build) or libazk.so of the build to compare against")
     ap.add_argument("new", help="the same of the build under test")
-    ap.add_argument("--match", default="", help="compare only the kernels whose (mangled) name contains this")
+    ap.add_argument("--match", default="", help="compare only the kernels whose name (mangled; demangled under --strip-namespace) contains this")
     ap.add_argument("--quiet", action="store_true", help="print only the kernels that differ and the summary line")
+    ap.add_argument("--strip-namespace", action="append", default=[], metavar="NS",
+                    help="compare by demangled name less the qualifiers NS:: and (anonymous namespace):: (repeatable)")
     a = ap.parse_args()
+    if "" in a.strip_namespace:
+        ap.error("--strip-namespace needs a name")
     with tempfile.TemporaryDirectory() as work:
         old, new = kernels(a.old, work, "old"), kernels(a.new, work, "new")
+    if a.strip_namespace:
+        old, new = plain_names(old, a.strip_namespace, a.old), plain_names(new, a.strip_namespace, a.new)
     old = {k: v for k, v in old.items() if a.match in k}
     new = {k: v for k, v in new.items() if a.match in k}
     if not old:

@@ -48,6 +48,7 @@ struct EmbedFoldArgs {
     unsigned long long *wstats;
     long long *dbg;                // debug only (AZK_EP_STAMPS build + AZK_EMBED_POOL_STAMPS): [8] cycle sums per phase, wave 0 of every workgroup
     int n, R, Cc, T;
+    int rdivR, rdivC;              // 65536 / R + 1, 65536 / Cc + 1: x / d = (x m) >> 16 for x < 256, d <= 64
     float eps;
     azk_leaf_source src;
 };
@@ -88,70 +89,94 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
         // A non-zero leaf flag is 1 + the leaf's cost class (0..7, by stone count).  Board r of the launch is the r-th flagged game in
         // the order (class descending, game ascending): the stone-heavy boards are handed out first, the light ones fill the gaps at
         // the end.  Every workgroup derives the same ranks - per-class counts of its threads' games (thread t owns games [t per, (t+1)
-        // per)), an exclusive scan over the 256 threads with the eight 16-bit counters packed in two 64-bit words - and keeps the
-        // inverse (game of rank r) in LDS: a board's game is then one LDS read, whoever asks.
+        // per)), an exclusive scan over the 256 threads - and keeps the inverse (game of rank r) in LDS: a board's game is then one LDS
+        // read, whoever asks.  All of it in 32-bit arithmetic without a branch per flag: the eight counts of one 8-byte flag word are at
+        // most 8 and sit in the 4-bit fields of one dword; they are widened to 16-bit fields (two classes a dword) only where counts of
+        // many games meet - the thread's total, the wave scan, the class bases.  A thread's first flag word (all of its flags up to
+        // 2 048 games) is read once and kept for the second pass; the further words of larger engines are read again there.
         const int my_per = ((((a.src.n_games + 255) >> 8) + 7) >> 3) << 3, my_lo = tid * my_per;
-        unsigned long long c_lo = 0ull, c_hi = 0ull;              // classes 0-3 / 4-7, 16 bits each
-        for (int w = 0; w < my_per; w += 8)
-            if (my_lo + w < a.src.flag_bytes) {
-                const unsigned long long f = *(const unsigned long long *)(a.src.leaf_flag + my_lo + w);
+        auto flag_word = [&](const int w) {                       // flags [my_lo + w, my_lo + w + 8), zero past the end
+            const bool in = my_lo + w < a.src.flag_bytes;
+            const uint2 f = *(const uint2 *)(a.src.leaf_flag + (in ? my_lo + w : 0));
+            return make_uint2(in ? f.x : 0u, in ? f.y : 0u);
+        };
+        const uint2 fw0 = flag_word(0);
+        auto flag_of = [](const uint2 f, const int q) { return ((q < 4 ? f.x : f.y) >> (8 * (q & 3))) & 0xffu; };
+        auto widen = [](const unsigned c4, const int q) { return ((c4 >> (8 * q)) & 0xfu) | (((c4 >> (8 * q + 4)) & 0xfu) << 16); };   // classes 2q, 2q + 1
+        unsigned cw[4] = {0u, 0u, 0u, 0u};                        // this thread's games per class, 16 bits each
+#pragma unroll 1
+        for (int w = 0; w < my_per; w += 8) {
+            const uint2 f = w ? flag_word(w) : fw0;
+            unsigned c4 = 0u;
 #pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const unsigned c = (unsigned)((f >> (8 * q)) & 0xffull);
-                    if (c) { if (c <= 4) c_lo += 1ull << (16 * (c - 1)); else c_hi += 1ull << (16 * (c - 5)); }
-                }
+            for (int q = 0; q < 8; q++) {
+                const unsigned c = flag_of(f, q);
+                c4 += min(c, 1u) << ((4u * c - 4u) & 31u);
             }
-        // inclusive wave scan of the eight packed 16-bit counters on DPP (row_shr 1, 2, 4, 8, then row_bcast 15 / 31: six dependent
-        // v_add per dword instead of six ds_bpermute round trips per 64-bit word - ~2 k cycles at the head of every launch).  The fields
-        // never carry into each other (a count is at most the slot count, < 65536), so the four dwords scan independently.
-        unsigned long long i_lo, i_hi;
-        {
-            int w4[4] = {(int)(unsigned)c_lo, (int)(unsigned)(c_lo >> 32), (int)(unsigned)c_hi, (int)(unsigned)(c_hi >> 32)};
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                int v = w4[q];
-                v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);
-                v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);
-                v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);
-                v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);
-                v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);
-                v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);
-                w4[q] = v;
-            }
-            i_lo = ((unsigned long long)(unsigned)w4[1] << 32) | (unsigned)w4[0];
-            i_hi = ((unsigned long long)(unsigned)w4[3] << 32) | (unsigned)w4[2];
+            for (int q = 0; q < 4; q++) cw[q] += widen(c4, q);
         }
-        unsigned long long *wtot = (unsigned long long *)(scan + 16);           // [4 waves][2]
-        if (lane == 63) { wtot[2 * wave] = i_lo; wtot[2 * wave + 1] = i_hi; }
+        // inclusive wave scan of the packed 16-bit counters on DPP (row_shr 1, 2, 4, 8, then row_bcast 15 / 31: six dependent v_add per
+        // dword instead of six ds_bpermute round trips).  The fields never carry into each other (a count is at most the slot count,
+        // < 65536), so the four dwords scan - and add, and subtract - independently.
+        unsigned iw[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            int v = (int)cw[q];
+            v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);
+            v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);
+            v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);
+            v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);
+            v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);
+            v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);
+            iw[q] = (unsigned)v;
+        }
+        unsigned *wtot = (unsigned *)(scan + 16);                 // [4 waves][4]
+        if (lane == 63) *(uint4 *)(wtot + 4 * wave) = make_uint4(iw[0], iw[1], iw[2], iw[3]);
         __syncthreads();
-        unsigned long long b_lo = 0ull, b_hi = 0ull, t_lo = 0ull, t_hi = 0ull;
+        unsigned ew[4], tw[4];                                    // exclusive prefix over lower threads / total, per class
+#pragma unroll
+        for (int q = 0; q < 4; q++) { ew[q] = iw[q] - cw[q]; tw[q] = 0u; }
+#pragma unroll
         for (int w = 0; w < 4; w++) {
-            if (w < wave) { b_lo += wtot[2 * w]; b_hi += wtot[2 * w + 1]; }
-            t_lo += wtot[2 * w]; t_hi += wtot[2 * w + 1];
+            const uint4 t = *(const uint4 *)(wtot + 4 * w);
+            const unsigned tq[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+            for (int q = 0; q < 4; q++) { ew[q] += w < wave ? tq[q] : 0u; tw[q] += tq[q]; }
         }
-        const unsigned long long e_lo = b_lo + i_lo - c_lo, e_hi = b_hi + i_hi - c_hi;   // exclusive prefix over lower threads, per class
-        unsigned long long cb_lo = 0ull, cb_hi = 0ull;            // rank of this thread's next game of each class, 16 bits each (classes 0-3 / 4-7)
+        unsigned cb[4] = {0u, 0u, 0u, 0u};                        // rank of this thread's next game of each class, 16 bits each
         unsigned start = 0;
 #pragma unroll
         for (int c = 7; c >= 0; c--) {                            // class 7 (most stones) first
-            const unsigned long long cb = (unsigned long long)(start + (unsigned)(((c < 4 ? e_lo : e_hi) >> (16 * (c & 3))) & 0xffffull)) << (16 * (c & 3));
-            if (c < 4) cb_lo |= cb; else cb_hi |= cb;
-            start += (unsigned)(((c < 4 ? t_lo : t_hi) >> (16 * (c & 3))) & 0xffffull);
+            cb[c >> 1] |= (start + ((ew[c >> 1] >> (16 * (c & 1))) & 0xffffu)) << (16 * (c & 1));
+            start += (tw[c >> 1] >> (16 * (c & 1))) & 0xffffu;
         }
         nvalid = (int)start;
-        for (int w = 0; w < my_per; w += 8)
-            if (my_lo + w < a.src.flag_bytes) {
-                const unsigned long long f = *(const unsigned long long *)(a.src.leaf_flag + my_lo + w);
+        // second pass: a game's rank is its class's base + the games of that class the thread has met in this flag word (4-bit running
+        // counts); the bases move on by the word's counts.  The thread's nine bases - entry 0 for "no leaf": 16 spare entries past the
+        // table that nobody reads - lie in an LDS row of its own (pwred is idle until the first board's sums), so a flag costs one
+        // LDS read and one LDS write and neither a select between the packed words nor a branch.
+        typedef unsigned __attribute__((may_alias)) u32a;
+        unsigned short *brow = (unsigned short *)pwred + 10 * tid;
+        const unsigned spare = (unsigned)(((a.src.n_games + 7) >> 3) << 3);
+#pragma unroll 1
+        for (int w = 0; w < my_per; w += 8) {
+            const uint2 f = w ? flag_word(w) : fw0;
+            u32a *br = (u32a *)brow;
+            br[0] = spare | (cb[0] << 16); br[1] = (cb[0] >> 16) | (cb[1] << 16); br[2] = (cb[1] >> 16) | (cb[2] << 16);
+            br[3] = (cb[2] >> 16) | (cb[3] << 16); br[4] = cb[3] >> 16;
+            unsigned base[8], run4 = 0u;
 #pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const unsigned c = (unsigned)((f >> (8 * q)) & 0xffull);
-                    const bool lo = c <= 4;
-                    const int sh = 16 * ((c - 1) & 3);
-                    if (c) gor[(unsigned)(((lo ? cb_lo : cb_hi) >> sh) & 0xffffull)] = (unsigned short)(my_lo + w + q);
-                    const unsigned long long inc = c ? 1ull << sh : 0ull;
-                    cb_lo += lo ? inc : 0ull; cb_hi += lo ? 0ull : inc;
-                }
+            for (int q = 0; q < 8; q++) base[q] = brow[flag_of(f, q)];   // (all eight reads in flight before the first write)
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const unsigned c = flag_of(f, q), sh4 = (4u * c - 4u) & 31u;
+                gor[base[q] + ((run4 >> sh4) & 0xfu)] = (unsigned short)(my_lo + w + q);
+                run4 += min(c, 1u) << sh4;
             }
+#pragma unroll
+            for (int q = 0; q < 4; q++) cb[q] += widen(run4, q);
+        }
         if (blockIdx.x == 0 && tid == 0) { *a.src.n_leaf = nvalid; if (a.src.cache_stamp) *a.src.cache_stamp += 1u; }
     } else {
         nvalid = a.count ? min(a.n, *a.count) : a.n;
@@ -193,11 +218,13 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
 #pragma unroll
         for (int q = 0; q < NQ; q++) {
             const int e = min(q * 64 + lv, ncell - 1);
-            codeN[q] = cells[(unsigned)(e - ((e >= RC) + (e >= 2 * RC)) * RC)];
+            codeN[q] = cells[(unsigned)(e - ((e >= RC) + (NC > 2 && e >= 2 * RC)) * RC)];
         }
         tmN = a.src.to_move[g]; ldN = a.src.leaf_depth[g];
     };
-    if (SRC) { game = gor[board]; if (fast) load_cells(game); }
+    // (a board's ticket and its game are LDS words every thread reads alike: taken to scalar registers, the row and cell addresses
+    //  below are a scalar base + 32-bit lane offsets)
+    if (SRC) { game = __builtin_amdgcn_readfirstlane((int)gor[board]); if (fast) load_cells(game); }
 
     while (board < nvalid) {
         // Everything below that depends only on the thread index is recomputed per board from an opaque copy of the index: hoisted out of
@@ -205,7 +232,7 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
         int tv = tid;
         asm volatile("" : "+v"(tv));
         const int lane_b = tv & 63;
-        const int tj = tv - 1, tr = tj / a.Cc, tc = tj - tr * a.Cc;
+        const int tj = max(tv - 1, 0), tr = (tj * a.rdivC) >> 16, tc = tj - tr * a.Cc;   // (tj < 256, Cc <= 28: the product form of the division is exact)
         const bool tlive = tv >= 1 && tv < T;
         int player = 0;
         if (SRC && tid == 0) a.src.leaf_slot[game] = board;       // the slot the next expansion reads this game's outputs from
@@ -217,7 +244,7 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
                 player = (tmN + ldN) & 1;                         // node.currentPlayer at the leaf
 #pragma unroll
                 for (int q = 0; q < NQ; q++) {
-                    const int e = min(q * 64 + lane_b, ncell - 1), chq = (e >= RC) + (e >= 2 * RC);
+                    const int e = min(q * 64 + lane_b, ncell - 1), chq = (e >= RC) + (NC > 2 && e >= 2 * RC);
                     on[q] = q * 64 + lane_b < ncell && (chq == 2 ? player != 0 : ((codeN[q] >> (chq ^ player)) & 1) != 0);
                 }
             } else if (a.boards_f32) {
@@ -263,31 +290,41 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
         // Row words first: lane L < NC R holds plane L / R, row L % R of the board with two zero bits on either side (two cross-lane reads
         // of the bit string + a funnel shift, once); a token then takes its KSZ bits of each of its NC KSZ rows with ONE cross-lane read
         // and a shift - no column mask, the margins are zero.
-        unsigned long long plo = 0;
+        // Straight-line: every cross-lane read is issued before the first is used, the rows off the board and the threads without a token
+        // take a zero mask (no branch between the reads), and the 64 patch bits are built as two 32-bit halves.
+        unsigned plx = 0u, ply = 0u;
         {
-            const int chL = lane_b / a.R, rL = lane_b - chL * a.R;
+            const int chL = (lane_b * a.rdivR) >> 16, rL = lane_b - chL * a.R;
             const int offL = 32 + chL * RC + rL * a.Cc - 2;
-            const unsigned loL = __shfl(wbits, offL >> 5), hiL = __shfl(wbits, (offL >> 5) + 1);
+            const unsigned loL = (unsigned)__builtin_amdgcn_ds_bpermute((offL >> 5) << 2, (int)wbits);
+            const unsigned hiL = (unsigned)__builtin_amdgcn_ds_bpermute(((offL >> 5) + 1) << 2, (int)wbits);
             const unsigned roww = lane_b < NC * a.R ? (__funnelshift_r(loL, hiL, offL & 31) & (((1u << a.Cc) - 1u) << 2)) : 0u;
+            unsigned vm[KSZ];
+            int src4[KSZ];
+#pragma unroll
+            for (int ky = 0; ky < KSZ; ky++) {
+                const int rr = tr + ky - pad;
+                vm[ky] = (tlive & ((unsigned)rr < (unsigned)a.R)) ? (1u << KSZ) - 1u : 0u;
+                src4[ky] = min(max(rr, 0), a.R - 1) << 2;
+            }
             unsigned rw[NC * KSZ];
 #pragma unroll
             for (int ch = 0; ch < NC; ch++)
 #pragma unroll
-                for (int ky = 0; ky < KSZ; ky++) {
-                    const int rr = tr + ky - pad;
-                    rw[ch * KSZ + ky] = __shfl(roww, ch * a.R + (rr < 0 ? 0 : (rr >= a.R ? a.R - 1 : rr)));
-                }
+                for (int ky = 0; ky < KSZ; ky++) rw[ch * KSZ + ky] = (unsigned)__builtin_amdgcn_ds_bpermute(src4[ky] + 4 * ch * a.R, (int)roww);
+            const unsigned sh = (unsigned)(tc + 2 - pad);
 #pragma unroll
             for (int ch = 0; ch < NC; ch++)
 #pragma unroll
                 for (int ky = 0; ky < KSZ; ky++) {
-                    const int rr = tr + ky - pad;
-                    unsigned bits = (rw[ch * KSZ + ky] >> (tc + 2 - pad)) & ((1u << KSZ) - 1u);
-                    if (!tlive || rr < 0 || rr >= a.R) bits = 0;
-                    plo |= (unsigned long long)bits << (ch * kk + ky * ksz);
+                    const unsigned bits = (rw[ch * KSZ + ky] >> sh) & vm[ky];
+                    const int p = ch * kk + ky * ksz;
+                    if (p < 32) plx |= bits << p;
+                    if (p >= 32) ply |= bits << (p & 31);
+                    else if (p + KSZ > 32) ply |= bits >> (32 - p);
                 }
         }
-        const bool dirty = plo != 0ull;
+        const bool dirty = (plx | ply) != 0u;
         const unsigned long long dm = __ballot(dirty);
         if (lane == 0) scan[4 + wave] = __popcll(dm);
         __syncthreads();                                  // (also: every wave is done with the previous board's lists and sums)
@@ -297,7 +334,7 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
         const int ntile = (nd + 15) >> 4;
         if (dirty) {
             dlist[dpos] = tid;
-            pbits[dpos] = make_uint2((unsigned)plo, (unsigned)(plo >> 32));
+            pbits[dpos] = make_uint2(plx, ply);
         }
         if (tid < 16 && nd + tid < ntile * 16) { dlist[nd + tid] = T; pbits[nd + tid] = make_uint2(0u, 0u); }   // null tokens fill the last tile
         __syncthreads();
@@ -446,20 +483,21 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
         }
         __syncthreads();
         // the next board is known to every thread now: its loads go out under this board's output phase
-        const int nxt = scan[10], nboard = (int)gridDim.x + nxt;
+        const int nxt = __builtin_amdgcn_readfirstlane(scan[10]), nboard = (int)gridDim.x + nxt;
         int ngame = 0;
-        if (SRC && nboard < nvalid) { ngame = gor[nboard]; if (fast) load_cells(ngame); }
+        if (SRC && nboard < nvalid) { ngame = __builtin_amdgcn_readfirstlane((int)gor[nboard]); if (fast) load_cells(ngame); }
         if (tid == 0 && nxt == nvalid - 1) a.sched[0] = 0;        // exactly nvalid tickets are drawn per launch: the last one leaves the queue zero
         // ---- output rows, straight to memory: [head][0, T) token weights / L, [T, T+3) 1 / L (hi, lo, hi), [256, 320) pooled patch / L ----
         {
-            float inv[NH];
+            // 1 / L once per wave: lane l sums head l & 7 (the four waves' shares in the order every thread used to add them, + l_all),
+            // one reciprocal, and the eight values go to scalar registers
+            float inv[NH], ivl;
             {
-                const f32x4 *lr = (const f32x4 *)lred;
-                f32x4 s0 = (lr[0] + lr[2]) + (lr[4] + lr[6]), s1 = (lr[1] + lr[3]) + (lr[5] + lr[7]);
-                const f32x4 *la = (const f32x4 *)lall_s;
-                s0 += la[0]; s1 += la[1];
+                const int hl = lane & 7;
+                const float sl = ((lred[hl] + lred[8 + hl]) + (lred[16 + hl] + lred[24 + hl])) + lall_s[hl];
+                ivl = EX ? 1.0f / sl : __builtin_amdgcn_rcpf(sl);   // (bf16 rows: 1 ulp is below their rounding)
 #pragma unroll
-                for (int h = 0; h < NH; h++) inv[h] = EX ? 1.0f / (h < 4 ? s0[h & 3] : s1[h & 3]) : __builtin_amdgcn_rcpf(h < 4 ? s0[h & 3] : s1[h & 3]);   // (bf16 rows: 1 ulp is below their rounding)
+                for (int h = 0; h < NH; h++) inv[h] = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(ivl), h));
             }
             const bool isL = tid >= T && tid < T + 3;
             f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};
@@ -481,12 +519,15 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
                 float *of = (float *)a.out + (size_t)board * NH * FOLD_ROW;
 #pragma unroll
                 for (int h = 0; h < NH; h++) of[h * FOLD_ROW + tid] = (h < 4 ? b0[h & 3] : b1[h & 3]) * tinv[h];
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-                    const int e = tid + 256 * i, h = e >> 6, k = e & 63;
+                {
+                    const int h = tid >> 5, k = 2 * (tid & 31);           // two columns a thread: one 8-byte store each for the patch and its zero half
+                    const float ih = __shfl(ivl, h);
                     if (h < NH) {
-                        of[h * FOLD_ROW + 256 + k] = ((pwred[(0 * 8 + h) * 64 + k] + pwred[(1 * 8 + h) * 64 + k]) + (pwred[(2 * 8 + h) * 64 + k] + pwred[(3 * 8 + h) * 64 + k])) * inv[h];
-                        of[h * FOLD_ROW + 320 + k] = 0.f;
+                        const f32x2 *pr = (const f32x2 *)(pwred + h * 64 + k);
+                        const f32x2 p0 = pr[0], p1 = pr[256], p2 = pr[512], p3 = pr[768];
+                        const f32x2 v = {((p0[0] + p1[0]) + (p2[0] + p3[0])) * ih, ((p0[1] + p1[1]) + (p2[1] + p3[1])) * ih};
+                        *(f32x2 *)(of + h * FOLD_ROW + 256 + k) = v;
+                        *(f32x2 *)(of + h * FOLD_ROW + 320 + k) = f32x2{0.f, 0.f};
                     }
                 }
             } else {
@@ -499,13 +540,15 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
                     ob[4 * FOLD_ROW + tid] = (unsigned short)p1[0]; ob[5 * FOLD_ROW + tid] = (unsigned short)(p1[0] >> 16);
                     ob[6 * FOLD_ROW + tid] = (unsigned short)p1[1]; ob[7 * FOLD_ROW + tid] = (unsigned short)(p1[1] >> 16);
                 }
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-                    const int e = tid + 256 * i, h = e >> 6, k = e & 63;                      // (a wave writes 64 consecutive entries)
+                {
+                    const int h = tid >> 5, k = 2 * (tid & 31);           // two columns a thread: one packed word each for the patch and its zero half
+                    const float ih = __shfl(ivl, h);
                     if (h < NH) {
-                        const float v = ((pwred[(0 * 8 + h) * 64 + k] + pwred[(1 * 8 + h) * 64 + k]) + (pwred[(2 * 8 + h) * 64 + k] + pwred[(3 * 8 + h) * 64 + k])) * inv[h];
-                        ob[h * FOLD_ROW + 256 + k] = (unsigned short)bf16_rne(v);
-                        ob[h * FOLD_ROW + 320 + k] = 0;
+                        const f32x2 *pr = (const f32x2 *)(pwred + h * 64 + k);
+                        const f32x2 p0 = pr[0], p1 = pr[256], p2 = pr[512], p3 = pr[768];
+                        const float v0 = ((p0[0] + p1[0]) + (p2[0] + p3[0])) * ih, v1 = ((p0[1] + p1[1]) + (p2[1] + p3[1])) * ih;
+                        *(unsigned *)(ob + h * FOLD_ROW + 256 + k) = bf16_rne(v0) | (bf16_rne(v1) << 16);
+                        *(unsigned *)(ob + h * FOLD_ROW + 320 + k) = 0u;
                     }
                 }
             }
@@ -531,7 +574,7 @@ int g_fold_grid = 0;
 template <int NC, int KSZ, int NH, bool SRC, bool EX>
 int launch_embed_fold(const EmbedFoldArgs &a, hipStream_t st) {
     const int tp16 = ((a.T + 15) / 16) * 16;
-    const int lds = 256 * 16 + tp16 * 8 + tp16 * 4 + 128 + 128 + 32 + tp16 * 32 + 4 * 8 * 64 * 4 + (SRC ? ((a.src.n_games + 7) / 8) * 16 : 0);   // 29 KB at 2 048 games
+    const int lds = 256 * 16 + tp16 * 8 + tp16 * 4 + 128 + 128 + 32 + tp16 * 32 + 4 * 8 * 64 * 4 + (SRC ? ((a.src.n_games + 7) / 8) * 16 + 32 : 0);   // 29 KB at 2 048 games (the rank -> game table + 16 spare entries)
     if (azk_set_max_lds((const void *)k_embed_fold<NC, KSZ, NH, SRC, EX>, lds + 2 * FOLD_MAX_SLOTS) != hipSuccess) return AZK_ERR_HIP;
     // two resident workgroups per CU by default; each pulls boards until the queue is dry.  azk_nn_embed_fold_grid(n): a caller that steps
     // several game groups on separate streams caps the grid (one workgroup per CU leaves the register file room for another group's
@@ -567,6 +610,7 @@ static int32_t embed_fold_impl(const void *boards_dev, int32_t boards_are_f32, c
     a.u2T = k->u2_tok; a.scoreT = k->score_tok; a.wcT = k->wconst_tok; a.lall = k->l_all; a.sref = k->score_ref; a.inv_scales = k->inv_scales;
     a.out = rows_out; a.count = n_valid_dev; a.sched = sched_dev; a.wstats = (unsigned long long *)k->work_stats;
     a.n = n; a.R = rows; a.Cc = cols; a.T = rows * cols + 1; a.eps = k->ln_eps;
+    a.rdivR = 65536 / rows + 1; a.rdivC = 65536 / cols + 1;
     if (src) a.src = *src;
     {
         static long long *dbg_buf = nullptr;

@@ -456,6 +456,8 @@ class Engine:
 # ---- stateless board-rule kernels (Game statics) over float32 boards [n, F, R, C] on the GPU ------------
 def _geom(game, size):
     gid = GAME_ID[game]
+    if isinstance(size, (tuple, list)):          # (rows, cols) or one side, as Engine takes it
+        return gid, int(size[0]), int(size[1])
     s = int(size or 0)
     return gid, s, s
 

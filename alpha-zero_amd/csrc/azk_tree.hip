@@ -405,7 +405,8 @@ __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd
             // second (and last) round trip of the expansion, all straight-line: logits, value, the node's header, root noise
             // a lane takes FOUR consecutive logits per load (actions 4 lane .. 4 lane + 3 of each block of 256; the lane at the row's end
             // takes the row's last four, overlapping its neighbour - the same values twice): one 16-byte load instead of four 4-byte ones,
-            // here and for the eval-cache row's stores and loads below
+            // here and for the eval-cache row's stores and loads below (row_first / row_load4 / row_store4: a row of fewer than four floats
+            // goes component by component, as on the expanding wave)
             constexpr int NV4 = (KSL * AZK_WAVE + 255) / 256;
             int la[NV4];                                              // first action of the lane's group
             bool lact[NV4];
@@ -413,8 +414,8 @@ __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd
 #pragma unroll
             for (int q = 0; q < NV4; q++) {
                 lact[q] = 256 * q + 4 * lane < A;
-                la[q] = min(256 * q + 4 * lane, A - 4);
-                lgv[q] = *(const f32x4_a4 *)(lg + la[q]);
+                la[q] = row_first(256 * q + 4 * lane, A);
+                lgv[q] = row_load4(lg, la[q], A);
             }
             const float vraw = hit ? (shared ? d.hit_value[vi] : d.cache_value[crow]) : values[slot];
             const uint32_t node_meta = d.H[base + node].meta;
@@ -448,7 +449,7 @@ __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd
 #pragma unroll
                 for (int c = 0; c < 4; c++) {
                     const float ev = (ablate & 1) ? 1.0f : azk_exp_det(lgv[q][c]);
-                    if (lact[q]) L.e[la[q] + c] = ev;
+                    if (lact[q] && la[q] + c < A) L.e[la[q] + c] = ev;
                 }
             }
             azk_wave_sync();
@@ -456,7 +457,7 @@ __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd
                 // (behind the exponentials: by now every logit is in its register, and the stores go out back to back - placed
                 //  right behind the loads, each store waited for the one before it, one write round trip per 64 actions)
 #pragma unroll
-                for (int q = 0; q < NV4; q++) if (lact[q]) *(f32x4_a4 *)(d.cache_logits + crow * A + la[q]) = lgv[q];
+                for (int q = 0; q < NV4; q++) if (lact[q]) row_store4(d.cache_logits + crow * A, la[q], A, lgv[q]);
                 if (lane == 0) d.cache_value[crow] = vraw;
             }
             if (xst) x2 = clock64();
@@ -751,10 +752,7 @@ __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd
                 c1v = __hip_atomic_load(d.cache_claim + entry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 kw = d.cache_key[(size_t)entry * KW + min(lane, KW - 1)];
 #pragma unroll
-                for (int q = 0; q < NV4P; q++) {
-                    if constexpr (TWO) row[q] = row_load4(d.cache_logits + (size_t)entry * A, row_first(256 * q + 4 * lane, A), A);
-                    else row[q] = *(const f32x4_a4 *)(d.cache_logits + (size_t)entry * A + min(256 * q + 4 * lane, A - 4));
-                }
+                for (int q = 0; q < NV4P; q++) row[q] = row_load4(d.cache_logits + (size_t)entry * A, row_first(256 * q + 4 * lane, A), A);
                 vv = d.cache_value[entry];
             } else {
                 entry = (int)(h & (unsigned long long)(d.cache_entries - 1));
@@ -818,10 +816,8 @@ __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd
                 if (maybe_hit && c2 == (unsigned)uniform_i32((int)c1v)) {   // nobody started rewriting the entry meanwhile: the copy is whole
                     cached = true;
 #pragma unroll
-                    for (int q = 0; q < NV4P; q++) if (256 * q + 4 * lane < A) {
-                        if constexpr (TWO) row_store4(d.hit_logits + (size_t)vi * A, row_first(256 * q + 4 * lane, A), A, row[q]);
-                        else *(f32x4_a4 *)(d.hit_logits + (size_t)vi * A + min(256 * q + 4 * lane, A - 4)) = row[q];
-                    }
+                    for (int q = 0; q < NV4P; q++)
+                        if (256 * q + 4 * lane < A) row_store4(d.hit_logits + (size_t)vi * A, row_first(256 * q + 4 * lane, A), A, row[q]);
                     if (lane == 0) d.hit_value[vi] = vv;
                 }
                 if (!cached && lane < KW) d.leaf_key[(size_t)vi * KW + lane] = mykey;      // written into the table at expansion

@@ -103,7 +103,7 @@ class OracleGame:
     def __init__(self, name, size=None):
         self.name = name
         self.g = _GameT()
-        rows = cols = size or 0
+        rows, cols = (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (size or 0, size or 0)   # (rows, cols) or one side
         if lib().azo_game_init(C.byref(self.g), KIND[name], rows, cols) != 0:
             raise ValueError((name, size))
         for n, _ in _GameT._fields_:

@@ -8,6 +8,7 @@ Outputs: tests/golden/*.npz (data only: inputs + the reference's outputs).
 The reference has no tests / golden vectors of its own, so every
 fixture here comes from importing its modules and calling its functions:
   games/{tictactoe,connect4,gomoku}.py  statics (rules)            -> rules_*.npz
+  games/gomoku.py statics on non-square and tiny boards            -> rules_gomoku_rect.npz
   ai/mcts.py MCTS.mcts + ai/node.py + utils.py (search)            -> search.npz
   <Game>.self_play + train.save_data_to_buffer (whole games)       -> games.npz
   ai/nn.py Net (small config, committed weights)                   -> nn_small.npz
@@ -76,9 +77,9 @@ for _G in (TTT, C4):
     _G.get_canonical_board = staticmethod(_canon3)
 
 
-def set_gomoku(n):
-    GMK.rows = GMK.cols = n
-    GMK.action_dim = GMK.state_dim = n * n
+def set_gomoku(rows, cols=None):
+    GMK.rows, GMK.cols = rows, rows if cols is None else cols
+    GMK.action_dim = GMK.state_dim = GMK.rows * GMK.cols
 
 
 def cells_of(Game, board):
@@ -197,6 +198,28 @@ def gen_random_boards(Game, n_boards, n_queries, seed):
             q_all.append((b, p, r, c, Game.check_winner(board, p, (r, c))))
     return dict(cells=np.stack(cells_all), valid_flat=np.array(valid_flat, np.int16),
                 valid_off=np.array(valid_off, np.int32), queries=np.array(q_all, np.int16))
+
+
+# Gomoku boards with rows != cols, one row or column, fewer than four cells, and cell counts at the engine's kernel switches
+# (256 / 257 cells per-lane count, 306 / 308 cells set-table size).  Only the rules are taken from the reference here: its
+# get_action_idx is r * rows + c (gomoku.py:48), which is not a cell index when rows != cols, so its searches are not recorded.
+RECT_GEOMETRIES = [(1, 1), (1, 2), (1, 3), (2, 1), (3, 1), (2, 2), (1, 30), (30, 1), (4, 6), (6, 4), (5, 5), (16, 16), (8, 30), (9, 28),
+                   (17, 18), (11, 28), (10, 29), (13, 30), (30, 13)]
+
+
+def gen_rules_gomoku_rect():
+    """Per geometry, under the key prefix 'g{R}x{C}_': gen_playouts' arrays and, behind 'rb_', gen_random_boards' arrays.  The playout
+    count shrinks with the board (a ply's legal-move list grows with it) to keep the file small."""
+    out = {"geometries": np.array(RECT_GEOMETRIES, np.int16)}
+    for i, (R, C) in enumerate(RECT_GEOMETRIES):
+        set_gomoku(R, C)
+        k = f"g{R}x{C}_"
+        n_playouts = 3 if R * C <= 64 else (2 if R * C <= 256 else 1)
+        for name, v in gen_playouts(GMK, n_playouts, 700 + i).items():
+            out[k + name] = v
+        for name, v in gen_random_boards(GMK, 24, 10, 800 + i).items():
+            out[k + "rb_" + name] = v
+    return out
 
 
 # =================================================================================
@@ -764,7 +787,7 @@ def gen_train(dropout=0.0, torch_seed_for_masks=None):
 
 
 def main():
-    which = sys.argv[1:] or ["rules", "search", "games", "compete", "nn", "nn_depth2", "nn_search15", "nn_edges", "train", "train_dropout"]
+    which = sys.argv[1:] or ["rules", "rules_rect", "search", "games", "compete", "nn", "nn_depth2", "nn_search15", "nn_edges", "train", "train_dropout"]
     print("python", sys.version.split()[0], "numpy", np.__version__, "torch", torch.__version__,
           "cpus", os.cpu_count(), "torch threads", torch.get_num_threads())
     if "rules" in which:
@@ -778,6 +801,8 @@ def main():
         set_gomoku(15)
         np.savez_compressed(os.path.join(HERE, "rules_gomoku15.npz"), **gen_playouts(GMK, 12, 5),
                             **{"rb_" + k: v for k, v in gen_random_boards(GMK, 60, 60, 6).items()})
+    if "rules_rect" in which:
+        np.savez_compressed(os.path.join(HERE, "rules_gomoku_rect.npz"), **gen_rules_gomoku_rect())
     if "search" in which:
         np.savez_compressed(os.path.join(HERE, "search.npz"), **gen_search_cases())
     if "games" in which:

@@ -96,7 +96,10 @@ def test_vanilla_golden_games(azk, m):
 
 
 @pytest.mark.parametrize("name,size,n_sims,moves,seed", [("gomoku", 7, 120, 6, 3), ("gomoku", 15, 60, 9, 4), ("gomoku", 7, 300, 0, 5),
-                                                        ("connect4", None, 150, 11, 6), ("tictactoe", None, 200, 3, 7)])
+                                                        ("connect4", None, 150, 11, 6), ("tictactoe", None, 200, 3, 7),
+                                                        # rows != cols (size = (rows, cols)): rollouts to the draw on three cells, a board
+                                                        # winnable along some directions only, 21 columns (row ends off the 64-cell groups)
+                                                        ("gomoku", (1, 3), 30, 0, 8), ("gomoku", (5, 6), 80, 5, 9), ("gomoku", (3, 21), 60, 8, 10)])
 def test_vanilla_tree_equals_oracle(azk, ao, name, size, n_sims, moves, seed):
     """Whole tree after a vanilla search from a mid-game position == the oracle's (driven by numpy's randint)."""
     game = ao.OracleGame(name, size)

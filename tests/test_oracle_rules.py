@@ -86,6 +86,28 @@ def test_playouts_and_random_boards(name, size, file):
     _check_random_boards(g, z)
 
 
+_RECT = load_golden("rules_gomoku_rect.npz")
+RECT_GEOMETRIES = [(int(r), int(c)) for r, c in _RECT["geometries"]]
+
+
+def rect_fixture(rows, cols):
+    """One geometry's arrays of rules_gomoku_rect.npz under the key names _check_playouts / _check_random_boards read."""
+    p = f"g{rows}x{cols}_"
+    return {k[len(p):]: _RECT[k] for k in _RECT.files if k.startswith(p)}
+
+
+@pytest.mark.parametrize("rows,cols", RECT_GEOMETRIES, ids=[f"{r}x{c}" for r, c in RECT_GEOMETRIES])
+def test_gomoku_rectangular_and_tiny_boards(rows, cols):
+    """Gomoku with rows != cols, one row or column, and fewer than four cells: the reference's statics with rows / cols overridden
+    (cells are row-major r * cols + c in the fixture; the reference's own get_action_idx is not used by the rules)."""
+    z = rect_fixture(rows, cols)
+    g = ao.OracleGame("gomoku", (rows, cols))
+    assert (g.rows, g.cols, g.action_dim, g.state_dim) == (rows, cols, rows * cols, rows * cols)
+    assert z["rb_cells"].shape == (24, rows * cols)
+    _check_playouts(g, z)
+    _check_random_boards(g, z)
+
+
 def test_tictactoe_random_boards():
     _check_random_boards(ao.OracleGame("tictactoe"), load_golden("rules_ttt_rand.npz"), prefix="")
 

@@ -34,6 +34,7 @@ SYMBOLS = [
     "azk_nnx_embed_pool", "azk_nnx_embed_pool_leaves", "azk_nnx_gemm_h", "azk_nnx_gemm_h_lds",
     "azk_async_begin", "azk_async_step", "azk_async_drain", "azk_async_set_budget", "azk_async_begin_reuse",
     "azk_set_playout_cap", "azk_begin_search_capped", "azk_get_search_full", "azk_async_record_flags",
+    "azk_set_resign", "azk_advance_resign", "azk_get_resigned", "azk_get_resign_stats", "azk_async_resign_flags",
 ]
 
 
@@ -160,6 +161,7 @@ class Engine:
         self.done = torch.zeros(self.G, dtype=torch.int32, device=dev)
         self._noise = None
         self.playout_cap = None                     # (p_full, n_fast) once set_playout_cap has switched the option on
+        self.resign = None                          # (v_resign, p_never, min_ply) once set_resign has switched the option on
         self.cache_entries = int(cache_entries)
         # with the eval cache a step can have pending (cached) leaves to expand although no leaf went to the evaluator
         need = cache_entries or self.K > 1
@@ -224,6 +226,32 @@ class Engine:
             raise AzkError("search_full: no playout cap is set (set_playout_cap)")
         self._chk(self.L.azk_get_search_full(self.h, _p(self._search_full), _stream()))
         return self._search_full
+
+    def set_resign(self, v_resign, p_never=0.0, min_ply=0, seed=0, first_global_game=0):
+        """OPT-IN resignation (azk_set_resign): from now on, after a move that does not end the game, the side that has just moved concedes
+        when the root's q (root_stats' q as it is: the outcome for the OPPONENT of the side to move, near +1 when the mover is lost) is
+        >= v_resign and the game has at least min_ply plies.  A coin keyed (seed, first_global_game + g, move key of the game's first search)
+        makes a share p_never of the games never-resign games, which are only marked.  Moves are then made with advance(..., move_index=...)
+        (lock-step) or by the asynchronous movers (async_begin keys the coin by its own seed / first game).  v_resign = 0 switches it off."""
+        self._chk(self.L.azk_set_resign(self.h, float(v_resign), int(min_ply), float(p_never), int(seed), int(first_global_game), _stream()))
+        self.resign = (float(v_resign), float(p_never), int(min_ply)) if float(v_resign) != 0.0 else None
+        if self.resign and getattr(self, "_resigned", None) is None:
+            self._resigned = self.torch.zeros(self.G, dtype=self.torch.uint8, device=self.device)
+
+    def resigned(self):
+        """uint8 CUDA tensor [G]: 1 = the game's last move ended it by resignation (azk_get_resigned; valid until the next call)."""
+        if self.resign is None:
+            raise AzkError("resigned: no resignation is set (set_resign)")
+        self._chk(self.L.azk_get_resigned(self.h, _p(self._resigned), _stream()))
+        return self._resigned
+
+    def resign_stats(self):
+        """[games ended by resignation, never-resign games ended, of those marked, of those whose marked side did not lose] (host sync)."""
+        if self.resign is None:
+            raise AzkError("resign_stats: no resignation is set (set_resign)")
+        out = np.zeros(4, np.int64)
+        self._chk(self.L.azk_get_resign_stats(self.h, _np(out), _stream()))
+        return [int(x) for x in out]
 
     def begin_search_budget(self, noise, n_sims, per_launch=8, move_index=None):
         """begin_search + a simulation budget: afterwards every step lets a game run on inside the launch while its simulations
@@ -353,6 +381,9 @@ class Engine:
             if self.playout_cap is not None:                  # the ring's kind column: 1 = the record's search was a full one
                 rec["full"] = torch.ones(record_capacity, dtype=torch.uint8, device=self.device)
                 self._chk(self.L.azk_async_record_flags(self.h, _p(rec["full"])))
+            if self.resign is not None:                       # ... and its resignation column: 1 = the record's move conceded the game
+                rec["resigned"] = torch.zeros(record_capacity, dtype=torch.uint8, device=self.device)
+                self._chk(self.L.azk_async_resign_flags(self.h, _p(rec["resigned"])))
         self.async_records = rec
         c = AsyncConfig()
         c.n_sims, c.max_sims_per_launch, c.sample_until_move = int(n_sims), int(per_launch), int(min(sample_until, 1 << 30))
@@ -404,9 +435,14 @@ class Engine:
         self._chk(self.L.azk_root_stats(self.h, _p(self.pi), _p(self.q), _p(self.root_visit), _stream()))
         return self.pi, self.q, self.root_visit
 
-    def advance(self, uniforms=None, sample_until_move=0):
+    def advance(self, uniforms=None, sample_until_move=0, move_index=None):
+        """With resignation set, move_index (the slots' move counter: the noise row's move_index) is required."""
         if uniforms is not None:
             assert uniforms.dtype == self.torch.float64 and uniforms.is_cuda and uniforms.numel() == self.G
+        if self.resign is not None and move_index is not None:
+            self._chk(self.L.azk_advance_resign(self.h, _p(uniforms), int(sample_until_move), int(move_index), _p(self.chosen), _p(self.winner),
+                                                _p(self.done), _stream()))
+            return self.chosen, self.winner, self.done
         self._chk(self.L.azk_advance(self.h, _p(uniforms), int(sample_until_move), _p(self.chosen), _p(self.winner),
                                      _p(self.done), _stream()))
         return self.chosen, self.winner, self.done

@@ -160,6 +160,11 @@ def declare(L, symbols):
     L.azk_begin_search_capped.argtypes = [vp, vp, i32, i32, i32, vp]
     L.azk_get_search_full.argtypes = [vp, vp, vp]
     L.azk_async_record_flags.argtypes = [vp, vp]
+    L.azk_set_resign.argtypes = [vp, f64, i32, f64, u64, i64, vp]
+    L.azk_advance_resign.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
+    L.azk_get_resigned.argtypes = [vp, vp, vp]
+    L.azk_get_resign_stats.argtypes = [vp, vp, vp]
+    L.azk_async_resign_flags.argtypes = [vp, vp]
     L.azk_nn_ln_heads.argtypes = [vp, C.c_float, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.azk_nn_layernorm_rows.argtypes = [vp, vp, vp, C.c_float, vp, vp, i32, i32, vp, vp]
     L.azk_nn_heads_finalize.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]

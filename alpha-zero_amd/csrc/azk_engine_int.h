@@ -107,6 +107,24 @@ struct CapDev {
     long long *stats;          // asynchronous movers: the caller's stats_dev ([8] full, [9] fast searches begun), else null
 };
 
+// resignation (azk_set_resign, opt-in; v_resign == 0 otherwise): after a move that does not end the game, the side that
+// has just moved concedes when the root's q (root.value / root.visit: the outcome as the mover's OPPONENT sees it) reached v_resign.  A coin
+// per game makes it a never-resign control game, which is only marked with the side that would have conceded first and played on.  Its own
+// argument of the kernels that exist only for it (k_*_rs in azk_moves.hip): every other argument block - and every kernel an engine
+// without the option launches - stays as it was
+struct ResignDev {
+    double v_resign;           // threshold on q, in (0, 1]; 0 = off
+    double p_never;            // share of never-resign games
+    int min_ply;               // no concession before the game has this many plies
+    unsigned long long seed;   // the game coin's key: (seed, first_game + g, move key of the game's first search), azk_async_begin puts its own here
+    long long first_game;
+    uint8_t *resigned;         // [G] 1 = the game's last move ended it by resignation (written by every move of a live game)
+    uint32_t *mark_start;      // [G] never-resign mark: the game (by its first search's move key) that mark_side belongs to
+    int *mark_side;            // [G] the side that would have conceded first, -1 = none; valid only while mark_start is the current game's
+    long long *stats;          // [4] games resigned, never-resign games ended, of those marked, of those whose marked side did not lose
+    uint8_t *rec_resigned;     // asynchronous record ring: [record_capacity] 1 = the record's move was a resignation, or null
+};
+
 struct LdsView {
     uint8_t *board;
     int *path;
@@ -256,6 +274,7 @@ struct azk_engine {
     ReuseDev ru;                         // tree reuse (cfg.tree_reuse); ru.mode == 0: off, every pointer null
     AsyncDev ad;                         // asynchronous self-play (azk_async_begin); ad.slot_moves == nullptr: not set up
     CapDev cp = {};                      // playout-cap randomisation (azk_set_playout_cap); cp.n_fast == 0: off
+    ResignDev rs = {};                   // resignation (azk_set_resign); rs.v_resign == 0: off
     bool async_on = false;
     int async_recycle = 1;
 };

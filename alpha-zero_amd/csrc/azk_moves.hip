@@ -263,11 +263,17 @@ __global__ __launch_bounds__(AZK_WAVE) void k_root_stats(Dev d, double *pi, doub
     }
 }
 
+__device__ __forceinline__ bool resign_never(const ResignDev &rs, int g, uint32_t start);      // the game coin, beside cap_coin
+
 // gomoku.py:143-162 for one game (one wave): choose (sample ~ visits | first max-visit child), record pi / the action in the
 // trajectory, make_move, check_winner, draw.  Returns the chosen cell (-1: state error, already reported); *win_out / *done_out as
 // k_advance's outputs; pi of the move is left in L.cnt / sum_out (visit counts per action and their sum).
+// RESIGN (resigning engines, the k_*_rs kernels): after a move that does not end the game the mover concedes when the
+// root's q reached v_resign - or, in a never-resign game, is noted as the game's mark.  key = the slot's move counter at this move,
+// *rsg_out = 1 when the move ended the game by resignation.
+template <bool RESIGN>
 __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool have_u, double u, int sample_until, int *win_out, int *done_out,
-                                           int *sum_out) {
+                                           int *sum_out, const ResignDev &rs, int key, int *rsg_out) {
     const int lane = azk_lane();
     const GameDesc &gd = d.g;
     const size_t base = (size_t)g * d.cap;
@@ -339,6 +345,28 @@ __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool
     int win = -2, dn = 0;
     if (w != -1) { win = w; dn = 1; }
     else if (mc + 1 == gd.state_dim) { win = -1; dn = 1; }
+    if (RESIGN) {
+        // the game's first search had move key key - mc; q is the recorded q (k_root_stats, the movers' rec_q): the same float64 expression
+        const uint32_t start = (uint32_t)key - (uint32_t)mc;
+        const bool never = resign_never(rs, g, start);
+        const int side = uniform_i32(rs.mark_side[g]);
+        const bool marked = side >= 0 && (uint32_t)uniform_i32((int)rs.mark_start[g]) == start;
+        int rsg = 0;
+        if (dn == 0 && mc + 1 >= rs.min_ply && d.W[base] / (double)d.H[base].N >= rs.v_resign) {
+            if (!never) { win = 1 - mover; dn = 1; rsg = 1; }                                  // the mover concedes
+            else if (!marked && lane == 0) { rs.mark_start[g] = start; rs.mark_side[g] = mover; }   // ... would have: the game plays on
+        }
+        if (lane == 0) {
+            rs.resigned[g] = (uint8_t)rsg;
+            if (rsg) atomicAdd((unsigned long long *)&rs.stats[0], 1ull);
+            else if (dn && never) {
+                atomicAdd((unsigned long long *)&rs.stats[1], 1ull);
+                if (marked) atomicAdd((unsigned long long *)&rs.stats[2], 1ull);
+                if (marked && win != 1 - side) atomicAdd((unsigned long long *)&rs.stats[3], 1ull);     // a false positive: it won or drew
+            }
+        }
+        *rsg_out = rsg;
+    }
     if (lane == 0) {
         d.cells[(size_t)g * d.rc_pad + cellc] = L.board[cellc];
         d.to_move[g] = 1 - mover;
@@ -363,8 +391,10 @@ __device__ __forceinline__ int played_child(const Dev &d, int g, int cellc) {
     return (cellc >= 0 && found != 0x7fffffff) ? fc + found : -1;
 }
 
-template <bool CAP>      // CAP: playout-cap engines (k_advance_cap) - the ply's kind goes into traj_full beside its pi
-__device__ __forceinline__ void advance_body(Dev d, CapDev cp, const double *uniforms, int sample_until,
+// CAP: playout-cap engines (k_advance_cap) - the ply's kind goes into traj_full beside its pi; RESIGN: resigning engines (k_advance_rs),
+// move_index = the slot's move counter
+template <bool CAP, bool RESIGN>
+__device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int move_index, const double *uniforms, int sample_until,
                                              int *chosen, int *winner_out, int *done_out, int *chosen_node) {
     const int g = blockIdx.x, lane = azk_lane();
     LdsView L = carve(d.g, d.path_cap, d.table_size);
@@ -377,9 +407,10 @@ __device__ __forceinline__ void advance_body(Dev d, CapDev cp, const double *uni
         }
         return;
     }
-    int win = -2, dn = 0, sum = 0;
+    int win = -2, dn = 0, sum = 0, rsg = 0;
     const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
-    const int cellc = advance_one(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum);
+    const int cellc = advance_one<RESIGN>(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum,
+                                          rs, move_index, &rsg);
     if (CAP && cellc >= 0 && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = cp.search_full[g];
     if (chosen_node) {
         const int child = played_child(d, g, cellc);               // tree reuse: the next search's root
@@ -395,7 +426,7 @@ __device__ __forceinline__ void advance_body(Dev d, CapDev cp, const double *uni
 
 __global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *uniforms, int sample_until,
                                                        int *chosen, int *winner_out, int *done_out, int *chosen_node) {
-    advance_body<false>(d, CapDev{}, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
+    advance_body<false, false>(d, CapDev{}, ResignDev{}, 0, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -636,6 +667,16 @@ __device__ __forceinline__ bool cap_coin(const CapDev &c, int g, int move) {
     const double u = (double)((((unsigned long long)w[0] << 32) | w[1]) >> 11) * (1.0 / 9007199254740992.0);   // [0,1), as noise_uniform
     return u < c.p_full;
 }
+// the game coin of resignation: is the game of (seed, global game, move key of its first search) a NEVER-RESIGN control game?  Stateless: the
+// mover recomputes it at every move from start = (the slot's move counter) - (the game's plies), so no restart, recycle or reset kernel knows
+// of it.  Philox word 3 = 0xFFFFFFFD is no other draw's (cap_coin: 0xFFFFFFFE), so every existing stream is what it was.
+__device__ __forceinline__ bool resign_never(const ResignDev &rs, int g, uint32_t start) {
+    const unsigned long long gg = (unsigned long long)(rs.first_game + g);
+    uint32_t w[4] = {(uint32_t)gg, (uint32_t)(gg >> 32), start, 0xFFFFFFFDu};
+    philox4x32_10(w, (uint32_t)rs.seed, (uint32_t)(rs.seed >> 32));
+    const double u = (double)((((unsigned long long)w[0] << 32) | w[1]) >> 11) * (1.0 / 9007199254740992.0);   // [0,1), as cap_coin
+    return u < rs.p_never;
+}
 // simulations of a search of that kind under the budget as it stands (a fast search never exceeds the budget)
 __device__ __forceinline__ int cap_target(const CapDev &c, bool full, int budget) { return full ? budget : min(c.n_fast, budget); }
 
@@ -649,8 +690,8 @@ __device__ __forceinline__ void cap_begin_fresh(const Dev &d, const CapDev &c, i
     if (count && c.stats != nullptr) atomicAdd((unsigned long long *)&c.stats[full ? 8 : 9], 1ull);
 }
 
-template <bool REROOT, bool CAP>   // the body of k_move_async / k_move_async_cap
-__device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp) {
+template <bool REROOT, bool CAP, bool RESIGN>   // the body of k_move_async / k_move_async_cap and their _rs siblings
+__device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs) {
     const int g = blockIdx.x, lane = azk_lane();
     // one vector load for the three words that decide whether this game moves now (almost never: the wave then ends at once)
     const int *up = d.done + g;
@@ -671,11 +712,11 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
     const size_t base = (size_t)g * d.cap;
     const long long mv = p.slot_moves[g];
     const double q = d.W[base] / (double)d.H[base].N;                 // root.value / root.visit (gomoku.py:140), before the tree is reset
-    int win = -2, dn = 0, sum = 0;
+    int win = -2, dn = 0, sum = 0, rsg = 0;
     const double u = noise_uniform(p.seed, (unsigned long long)(p.first_game + g), (int)mv);
     const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
     const int kind = CAP ? uniform_i32((int)cp.search_full[g]) : 1;     // of the search that is complete
-    const int cellc = advance_one(d, L, g, true, u, p.sample_until, &win, &dn, &sum);
+    const int cellc = advance_one<RESIGN>(d, L, g, true, u, p.sample_until, &win, &dn, &sum, rs, (int)mv, &rsg);
     if (cellc < 0) return;
     if (CAP && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = (uint8_t)kind;
     if (p.rec_cap > 0) {                                           // the move's record: what the reference's self_play keeps per ply
@@ -688,6 +729,7 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
             int *m = p.rec_meta + (size_t)slot * 4;
             m[0] = g; m[1] = (int)mv; m[2] = cellc; m[3] = win;
             if (CAP && cp.rec_full != nullptr) cp.rec_full[slot] = (uint8_t)kind;
+            if (RESIGN && rs.rec_resigned != nullptr) rs.rec_resigned[slot] = (uint8_t)rsg;
         }
     }
     __syncthreads();
@@ -713,7 +755,7 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
 }
 
 template <bool REROOT>   // REROOT: a re-rooting engine - the moved game is parked for the drain's k_reroot_list instead of beginning its search here
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, ReuseDev r) { move_async_body<REROOT, false>(d, p, r, CapDev{}); }
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, ReuseDev r) { move_async_body<REROOT, false, false>(d, p, r, CapDev{}, ResignDev{}); }
 
 // drain, step 4 (re-rooting engines): the next search of every game parked since the last drain - its subtree under the played child
 // moved to the front of the arena, or a fresh root where reroot_one refuses; one wave per game.  The Dirichlet row is the one of the
@@ -794,7 +836,7 @@ __global__ __launch_bounds__(AZK_WAVE) void k_reroot_cap(Dev d, ReuseDev r, CapD
 
 __global__ __launch_bounds__(AZK_WAVE) void k_advance_cap(Dev d, CapDev cp, const double *uniforms, int sample_until,
                                                            int *chosen, int *winner_out, int *done_out, int *chosen_node) {
-    advance_body<true>(d, cp, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
+    advance_body<true, false>(d, cp, ResignDev{}, 0, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
 }
 
 __global__ void k_emit_alloc_cap(Dev d, CapDev cp, unsigned long long *cursor, long long *game_base_out) {
@@ -808,7 +850,7 @@ __global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples_cap(Dev d, CapDev cp, 
 }
 
 template <bool REROOT>
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async_cap(Dev d, AsyncDev p, ReuseDev r, CapDev cp) { move_async_body<REROOT, true>(d, p, r, cp); }
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async_cap(Dev d, AsyncDev p, ReuseDev r, CapDev cp) { move_async_body<REROOT, true, false>(d, p, r, cp, ResignDev{}); }
 
 // k_reroot_list with the coin of the game's new move key deciding the search's target
 __global__ __launch_bounds__(AZK_WAVE) void k_reroot_list_cap(Dev d, AsyncDev p, ReuseDev r, CapDev cp) {
@@ -832,6 +874,27 @@ __global__ __launch_bounds__(AZK_WAVE) void k_reroot_list_cap(Dev d, AsyncDev p,
 }
 
 __global__ __launch_bounds__(AZK_WAVE) void k_async_restart_cap(Dev d, AsyncDev p, int recycle, CapDev cp) { async_restart_body<true>(d, p, recycle, cp); }
+
+// ------------------------------------------------------------------------------------------------
+// Resignation (azk_set_resign, opt-in): the movers a resigning engine launches IN PLACE of their namesakes - each its
+// namesake's body with RESIGN set.  A resignation happens where a natural end happens (advance_one sets winner and done), so emission,
+// recycling, the drain and the re-root see an ordinary finished game and none of their kernels has a sibling here.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(AZK_WAVE) void k_advance_rs(Dev d, ResignDev rs, const double *uniforms, int sample_until, int move_index,
+                                                          int *chosen, int *winner_out, int *done_out, int *chosen_node) {
+    advance_body<false, true>(d, CapDev{}, rs, move_index, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
+}
+
+__global__ __launch_bounds__(AZK_WAVE) void k_advance_cap_rs(Dev d, CapDev cp, ResignDev rs, const double *uniforms, int sample_until, int move_index,
+                                                              int *chosen, int *winner_out, int *done_out, int *chosen_node) {
+    advance_body<true, true>(d, cp, rs, move_index, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
+}
+
+template <bool REROOT>
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async_rs(Dev d, AsyncDev p, ReuseDev r, ResignDev rs) { move_async_body<REROOT, false, true>(d, p, r, CapDev{}, rs); }
+
+template <bool REROOT>
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async_cap_rs(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs) { move_async_body<REROOT, true, true>(d, p, r, cp, rs); }
 
 }  // namespace
 
@@ -961,6 +1024,63 @@ int32_t azk_async_record_flags(azk_engine *e, uint8_t *rec_full_dev) {
     return AZK_OK;
 }
 
+// ---- resignation ------------------------------------------------------------------------------------------------------
+// no game resigned, no mark, zero statistics (azk_set_resign, and azk_async_begin where the slots' move counters start again at 0)
+static int32_t resign_clear(azk_engine *e, hipStream_t st) {
+    const ResignDev &r = e->rs;
+    HIPCHK(e, hipMemsetAsync(r.resigned, 0, (size_t)e->d.G, st));
+    HIPCHK(e, hipMemsetAsync(r.mark_start, 0, sizeof(uint32_t) * (size_t)e->d.G, st));
+    HIPCHK(e, hipMemsetAsync(r.mark_side, 0xff, sizeof(int) * (size_t)e->d.G, st));
+    HIPCHK(e, hipMemsetAsync(r.stats, 0, sizeof(long long) * 4, st));
+    return AZK_OK;
+}
+
+int32_t azk_set_resign(azk_engine *e, double v_resign, int32_t min_ply, double p_never, uint64_t seed, int64_t first_global_game, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_resign: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (!(v_resign >= 0.0 && v_resign <= 1.0)) { e->err = "azk_set_resign: v_resign must lie in [0, 1] (0 = off)"; return AZK_ERR_ARG; }
+    if (!(p_never >= 0.0 && p_never <= 1.0)) { e->err = "azk_set_resign: p_never must lie in [0, 1]"; return AZK_ERR_ARG; }
+    if (min_ply < 0) { e->err = "azk_set_resign: min_ply must not be negative"; return AZK_ERR_ARG; }
+    if (v_resign == 0.0) { e->rs.v_resign = 0.0; return AZK_OK; }  // off: the engine launches what it launched before
+    if (e->d.K > 1) { e->err = "azk_set_resign: resignation does not combine with leaves_per_step > 1 (a virtual-loss search is another search: its q is not the one a threshold was set on)"; return AZK_ERR_ARG; }
+    const Dev &d = e->d;
+    ResignDev &r = e->rs;
+    if (!r.resigned) {
+        HIPCHK(e, dalloc(e, &r.resigned, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &r.mark_start, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &r.mark_side, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &r.stats, 4));
+    }
+    const int32_t rc = resign_clear(e, (hipStream_t)stream);
+    if (rc != AZK_OK) return rc;
+    r.min_ply = min_ply; r.p_never = p_never; r.seed = seed; r.first_game = first_global_game; r.rec_resigned = nullptr;
+    r.v_resign = v_resign;
+    return AZK_OK;
+}
+
+int32_t azk_get_resigned(azk_engine *e, uint8_t *resigned_dev, void *stream) {
+    if (!e || !resigned_dev) return AZK_ERR_ARG;
+    if (e->rs.v_resign == 0.0) { e->err = "azk_get_resigned: no resignation is set (azk_set_resign)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(resigned_dev, e->rs.resigned, (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_get_resign_stats(azk_engine *e, int64_t *out4_host, void *stream) {
+    if (!e || !out4_host) return AZK_ERR_ARG;
+    if (e->rs.v_resign == 0.0) { e->err = "azk_get_resign_stats: no resignation is set (azk_set_resign)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(out4_host, e->rs.stats, sizeof(long long) * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_async_resign_flags(azk_engine *e, uint8_t *rec_resigned_dev) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->rs.v_resign == 0.0) { e->err = "azk_async_resign_flags: no resignation is set (azk_set_resign)"; return AZK_ERR_STATE; }
+    if (e->async_on) { e->err = "azk_async_resign_flags: call it before azk_async_begin"; return AZK_ERR_STATE; }
+    e->rs.rec_resigned = rec_resigned_dev;
+    return AZK_OK;
+}
+
 // ---- asynchronous self-play ---------------------------------------------------------------------------------------------
 static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *stream, bool reuse) {
     if (!e || !c || !c->stats_dev || c->n_sims < 1 || c->n_sims > e->cfg.max_sims || c->max_sims_per_launch < 1 || !(c->alpha > 0.0)) {
@@ -1009,6 +1129,11 @@ static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *strea
     d.noise_sel = a.dirichlet ? a.slot_moves : nullptr;
     e->multi = true;
     e->async_on = true;
+    if (e->rs.v_resign != 0.0) {                                  // the game coins share the noise rows' key too
+        e->rs.seed = a.seed; e->rs.first_game = a.first_game;
+        const int32_t rc = resign_clear(e, st);
+        if (rc != AZK_OK) return rc;
+    }
     // first search of every game: fresh roots + the Dirichlet rows of move keys 0 (this search) and 1 (the next one)
     if (e->cp.n_fast) {                                           // the coins share the noise rows' key: this run's seed and first game
         e->cp.seed = a.seed; e->cp.first_game = a.first_game; e->cp.stats = a.stats;
@@ -1034,7 +1159,13 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
     const Dev &d = e->d;
     hipStream_t st = (hipStream_t)stream;
     if (phases & 1) { const int32_t rc = azk_launch_tree(e, true, true, true, logits_dev, values_dev, st); if (rc != AZK_OK) return rc; }
-    if (phases & 2) {
+    if ((phases & 2) && e->rs.v_resign != 0.0) {
+        if (e->cp.n_fast) {
+            if (e->ru.mode) k_move_async_cap_rs<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp, e->rs);
+            else k_move_async_cap_rs<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp, e->rs);
+        } else if (e->ru.mode) k_move_async_rs<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->rs);
+        else k_move_async_rs<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->rs);
+    } else if (phases & 2) {
         if (e->cp.n_fast) {
             if (e->ru.mode) k_move_async_cap<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp);
             else k_move_async_cap<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp);
@@ -1105,10 +1236,23 @@ int32_t azk_root_stats(azk_engine *e, double *pi_dev, double *q_dev, int32_t *ro
 int32_t azk_advance(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t *chosen_cell_dev,
                     int32_t *winner_dev, int32_t *done_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
+    if (e->rs.v_resign != 0.0) { e->err = "azk_advance: resignation is set - its moves are made by azk_advance_resign (the game coin needs the move index)"; return AZK_ERR_STATE; }
     if (e->cp.n_fast) k_advance_cap<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, uniforms_dev, sample_until_move,
                                                                                                chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
     else k_advance<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, uniforms_dev, sample_until_move,
                                                                          chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_advance_resign(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t move_index, int32_t *chosen_cell_dev,
+                           int32_t *winner_dev, int32_t *done_dev, void *stream) {
+    if (!e || move_index < 0) { if (e) e->err = "azk_advance_resign: bad argument"; return AZK_ERR_ARG; }
+    if (e->rs.v_resign == 0.0) { e->err = "azk_advance_resign: no resignation is set (azk_set_resign)"; return AZK_ERR_STATE; }
+    if (e->cp.n_fast) k_advance_cap_rs<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, uniforms_dev, sample_until_move, move_index,
+                                                                                                  chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
+    else k_advance_rs<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->rs, uniforms_dev, sample_until_move, move_index,
+                                                                            chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }

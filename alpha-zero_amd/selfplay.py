@@ -48,13 +48,45 @@ def check_playout_cap(playout_cap, n_sims, leaves_per_step=1):
     return p_full, n_fast
 
 
+def check_resign(resign, leaves_per_step=1):
+    """resign = (v_resign, p_never[, min_ply]) -> (float, float, int), or None for off.  OPT-IN resignation (include/azk.h azk_set_resign;
+    DESIGN section 19): after a move that does not end the game the side that has just moved concedes when the recorded root q - the
+    outcome for the OPPONENT of the side to move, as it is, no sign change - is >= v_resign and the game has at least min_ply plies; a share
+    p_never of the games never resigns and is only marked.  Raises ValueError for what the engine refuses too: v_resign outside (0, 1]
+    (None is "off"), p_never outside [0, 1], a negative min_ply, virtual loss."""
+    if resign is None:
+        return None
+    try:
+        v, p_never, min_ply = resign if len(resign) == 3 else (resign[0], resign[1], 0) if len(resign) == 2 else (None, None, None)
+        if int(min_ply) != min_ply:
+            raise ValueError
+        v, p_never, min_ply = float(v), float(p_never), int(min_ply)
+    except (TypeError, ValueError):
+        raise ValueError(f"resign must be (v_resign, p_never) or (v_resign, p_never, min_ply), not {resign!r}")
+    if not 0.0 < v <= 1.0:                                        # (NaN fails both comparisons)
+        raise ValueError(f"resign: v_resign must lie in (0, 1] (None switches resignation off), not {v!r}")
+    if not 0.0 <= p_never <= 1.0:
+        raise ValueError(f"resign: p_never must lie in [0, 1], not {p_never!r}")
+    if min_ply < 0:
+        raise ValueError(f"resign: min_ply must not be negative, not {min_ply!r}")
+    if int(leaves_per_step) > 1:
+        raise ValueError("resign does not combine with leaves_per_step > 1 (a virtual-loss search is another search: its q is not the one a threshold was set on)")
+    return v, p_never, min_ply
+
+
+def _refuse_vanilla_resign(resign, evaluator):
+    if resign is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
+        raise ValueError("resign: vanilla MCTS (evaluator None) is refused - its q is a rollout mean and no threshold is defined for it")
+
+
 class SelfPlayResult:
-    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base", "full")
+    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base", "full", "resigned")
 
     def __init__(self):
         self.boards, self.actions, self.pis, self.qs, self.winner, self.cells = [], [(-1, -1)], [], [], None, []
         self.full = []               # per ply: was its search a full one (always True without playout_cap); only those plies are trained on
         self.replay_base = None      # first tuple index in the DeviceReplay stream (when a replay ring is attached)
+        self.resigned = False        # the game ended by resignation (resign=...): winner is then the side that did not concede
 
     def as_reference_tuple(self):
         """(boards, actions, policy_distributions, qs, winner) - gomoku.py:164"""
@@ -64,7 +96,7 @@ class SelfPlayResult:
 def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
                     alpha=0.03, noise_fn=None, uniform_fn=None, device=0, leaf_dtype="float32", engine=None,
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
-                    budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None):
+                    budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -79,9 +111,13 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     many as bring the root back to n_sims visits (driven by the simulation budget).  vanilla_rng: uint32 [G, 625] MT19937 states (default: one
     np.random.RandomState per global game index derived from `seed`).  playout_cap = (p_full, n_fast) (OPT-IN, check_playout_cap): per ply a
     coin keyed (seed, global game, move) makes the search full or fast; SelfPlayResult.full records it and a replay ring gets the full plies only.
+    resign = (v_resign, p_never[, min_ply]) (OPT-IN, check_resign): a game may end by resignation - SelfPlayResult.resigned, winner = the
+    other side, z and the replay tuples as for any finished game.
     """
     import torch
     cap = check_playout_cap(playout_cap, n_sims, leaves_per_step)
+    rsg = check_resign(resign, leaves_per_step)
+    _refuse_vanilla_resign(rsg, evaluator)
     if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
     max_sims = max(n_sims) if isinstance(n_sims, (tuple, list)) else n_sims
@@ -89,6 +125,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                            cache_shared=cache_shared, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse)
     if cap is not None:
         eng.set_playout_cap(cap[0], cap[1], seed, first_global_game)
+    if rsg is not None:
+        eng.set_resign(rsg[0], rsg[1], rsg[2], seed, first_global_game)
     # virtual-loss, top-up and capped engines are driven by the simulation budget
     budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
     assert eng.G == n_games
@@ -129,7 +167,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         full_h = eng.search_full().cpu().numpy() if eng.playout_cap is not None else None
         pi, q, _ = eng.root_stats()
         cells_before, to_move, _ = eng.get_positions()
-        chosen, winner, done = eng.advance(uni, su)
+        chosen, winner, done = eng.advance(uni, su, move_index=move)
+        resigned_h = eng.resigned().cpu().numpy() if eng.resign is not None else None
         bases = eng.emit_finished(replay).cpu().numpy() if replay is not None else None     # train.save_data_to_buffer on device
         pi_h, q_h = pi.cpu().numpy(), q.cpu().numpy()
         chosen_h, winner_h, done_h = chosen.cpu().numpy(), winner.cpu().numpy(), done.cpu().numpy()
@@ -144,6 +183,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
             r.actions.append((c // eng.cols, c % eng.cols))
             if done_h[g]:
                 r.winner = int(winner_h[g])
+                r.resigned = bool(resigned_h[g]) if resigned_h is not None else False
                 active[g] = False
                 if bases is not None:
                     r.replay_base = int(bases[g])
@@ -172,6 +212,7 @@ class _Half:
         self.h_done = torch.zeros(e.G, dtype=torch.int32, **pin)
         self.h_stats = torch.zeros(8, dtype=torch.int64, **pin)
         self.h_full = torch.ones(e.G, dtype=torch.uint8, **pin)      # playout cap: kind of each slot's search (1 = full); all ones without
+        self.h_resigned = torch.zeros(e.G, dtype=torch.uint8, **pin)  # resignation: 1 = the slot's move conceded the game; all zeros without
         # static buffers so a captured step graph always sees the same addresses
         self.noise_buf = torch.zeros((e.G, e.action_dim), dtype=torch.float64, device=e.device) if dirichlet else None
         self.logits_buf = torch.zeros((e.slots, e.action_dim), dtype=torch.float32, device=e.device)
@@ -260,16 +301,22 @@ class SelfPlayRunner:
     playout_cap = (p_full, n_fast) (OPT-IN, check_playout_cap): every search is full or fast by a coin of the same key; the searches run under
     the simulation budget (as tree_reuse=2), `record_full` (uint8 [group size], valid inside on_records) tells the kind of each record, and
     the replay ring gets the plies of full searches only.
+
+    resign = (v_resign, p_never[, min_ply]) (OPT-IN, check_resign; with any tree_reuse and with playout_cap): after a move the mover concedes
+    when the recorded q >= v_resign; the slot's record then carries the conceded winner and done, `record_resigned` (uint8 [group size], valid
+    inside on_records) is 1 for it, and the game is emitted and recycled like any finished game.  resign_stats() counts the outcomes.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
                  alpha=0.03, device=0, leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None,
                  use_graph=False, n_split=1, replay=None, cache_entries=0, cache_shared=False, budget_stepping=False, per_launch=8,
                  steps_per_graph=32,
-                 leaves_per_step=1, tree_reuse=0, playout_cap=None):
+                 leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None):
         import torch
         self.playout_cap = check_playout_cap(playout_cap, n_sims, leaves_per_step)
-        self.record_full = None
+        self.resign = check_resign(resign, leaves_per_step)
+        _refuse_vanilla_resign(self.resign, evaluator)
+        self.record_full = self.record_resigned = None
         self.replay = replay
         self.torch = torch
         # leaves_per_step > 1: OPT-IN virtual-loss expansion (K leaves in flight per game; changes search results); it is driven
@@ -306,6 +353,8 @@ class SelfPlayRunner:
             h.eng.reset_games()
             if self.playout_cap is not None:
                 h.eng.set_playout_cap(self.playout_cap[0], self.playout_cap[1], seed, first_global_game + i * per)
+            if self.resign is not None:
+                h.eng.set_resign(self.resign[0], self.resign[1], self.resign[2], seed, first_global_game + i * per)
 
     # ---- one move for every slot -------------------------------------------------------------------------
     def play_move(self):
@@ -326,7 +375,9 @@ class SelfPlayRunner:
             pi, q, _ = e.root_stats()
             h.h_pi.copy_(pi, non_blocking=True)
             h.h_q.copy_(q, non_blocking=True)
-            chosen, winner, done = e.advance(h.uni, self.sample_until)
+            chosen, winner, done = e.advance(h.uni, self.sample_until, move_index=self.move_idx)
+            if self.resign is not None:
+                h.h_resigned.copy_(e.resigned(), non_blocking=True)
             h.h_chosen.copy_(chosen, non_blocking=True)
             h.h_winner.copy_(winner, non_blocking=True)
             h.h_done.copy_(done, non_blocking=True)
@@ -339,7 +390,7 @@ class SelfPlayRunner:
         for i, h in enumerate(self.halves):
             self.plies_played += int((h.h_chosen >= 0).sum())
             if self.on_records is not None:
-                self.record_full = h.h_full
+                self.record_full, self.record_resigned = h.h_full, h.h_resigned
                 self.on_records(self.move_idx, i * per, h.h_pi, h.h_q, h.h_chosen, h.h_winner, h.h_done)
         self.move_idx += 1
 
@@ -497,6 +548,12 @@ class SelfPlayRunner:
         for st in self.streams:
             cur.wait_stream(st)
 
+    def resign_stats(self):
+        """[games ended by resignation, never-resign games ended, of those marked, of those whose marked side did not lose], all groups."""
+        if self.resign is None:
+            raise ValueError("resign_stats: the runner was built without resign=...")
+        return [sum(x) for x in zip(*(h.eng.resign_stats() for h in self.halves))]
+
     @property
     def games_finished(self):
         return sum(int(h.h_stats[0]) for h in self.halves)
@@ -541,15 +598,21 @@ class AsyncSelfPlayRunner:
     idles from its move to the next drain - about half of `steps_per_graph` steps.
 
     playout_cap = (p_full, n_fast) (OPT-IN, check_playout_cap; with any reroot): the games of SelfPlayRunner(playout_cap=...), slot for slot.
-    `record_full` (uint8 numpy, one per record, valid inside on_records) tells each record's kind; searches_full / searches_fast count them."""
+    `record_full` (uint8 numpy, one per record, valid inside on_records) tells each record's kind; searches_full / searches_fast count them.
+
+    resign = (v_resign, p_never[, min_ply]) (OPT-IN, check_resign; with any reroot and with playout_cap): the games of SelfPlayRunner(resign=...),
+    slot for slot - the move kernel applies the rule, the drain sees an ordinary finished game.  `record_resigned` (uint8 numpy, one per record,
+    valid inside on_records) is 1 where the record's move conceded; resign_stats() counts the outcomes."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
-                 playout_cap=None):
+                 playout_cap=None, resign=None):
         import torch
         self.playout_cap = check_playout_cap(playout_cap, n_sims)
-        self.record_full = None
+        self.resign = check_resign(resign)
+        _refuse_vanilla_resign(self.resign, evaluator)
+        self.record_full = self.record_resigned = None
         if tree_reuse:
             raise ValueError("AsyncSelfPlayRunner takes tree reuse as reroot=1 (carry) or reroot=2 (top-up): the re-root runs in the drain "
                              "(azk_async_begin_reuse), not where SelfPlayRunner(tree_reuse=...) has it")
@@ -569,6 +632,8 @@ class AsyncSelfPlayRunner:
         e.reset_games()
         if self.playout_cap is not None:
             e.set_playout_cap(self.playout_cap[0], self.playout_cap[1], seed, first_global_game)
+        if self.resign is not None:
+            e.set_resign(self.resign[0], self.resign[1], self.resign[2], seed, first_global_game)
         cap = (4 * n_games if record_capacity is None else record_capacity) if (on_records is not None or record_capacity) else 0
         self.stats, self.records = e.async_begin(n_sims, self.per_launch, SAMPLE_UNTIL[game], seed, first_global_game, alpha, dirichlet, recycle, cap,
                                                  young_launch_us=young_launch_us, reroot=bool(self.reroot))
@@ -671,6 +736,8 @@ class AsyncSelfPlayRunner:
             meta, q, pi = self.records["meta"][idx].cpu().numpy(), self.records["q"][idx].cpu().numpy(), self.records["pi"][idx].cpu().numpy()
             if "full" in self.records:
                 self.record_full = self.records["full"][idx].cpu().numpy()
+            if "resigned" in self.records:
+                self.record_resigned = self.records["resigned"][idx].cpu().numpy()
         self.rec_read = cursor
         self.on_records(meta, q, pi)
 
@@ -704,6 +771,12 @@ class AsyncSelfPlayRunner:
     @property
     def finished_plies(self):
         return int(self._seen[1])
+
+    def resign_stats(self):
+        """[games ended by resignation, never-resign games ended, of those marked, of those whose marked side did not lose] (host sync)."""
+        if self.resign is None:
+            raise ValueError("resign_stats: the runner was built without resign=...")
+        return self.eng.resign_stats()
 
     @property
     def searches_full(self):

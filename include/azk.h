@@ -221,6 +221,41 @@ int32_t azk_begin_search_capped(azk_engine *e, const double *noise_dev, int32_t 
 int32_t azk_get_search_full(azk_engine *e, uint8_t *full_dev, void *stream);
 int32_t azk_async_record_flags(azk_engine *e, uint8_t *rec_full_dev);
 
+/* ---- resignation (OPT-IN; off, the engine is what it was bit for bit).  AlphaGo Zero's rule: a game whose outcome is decided stops
+ * paying searches for it.  After a move that does not end the game, the side that has just moved concedes when the root value of the
+ * search behind that move reached a threshold; a share of the games never resigns, so that the threshold's false positives can be counted.
+ *   q          root.value / root.visit as azk_root_stats and the record ring give it, with NO sign change.  Node.backup stores in a node
+ *              the value as seen by the player who moved INTO it, so the root's q is the expected outcome for the OPPONENT of the side to
+ *              move: near +1 when the side to move - the mover of the ply - is lost.
+ *   the rule   for the ply with move_count = mc before the move: the move the search chose is always played and recorded.  If it neither
+ *              wins nor fills the board, and mc + 1 >= min_ply, and q >= v_resign (float64, the recorded q): in a game that may resign
+ *              done = 1, winner = 1 - mover, the game's resigned flag = 1; in a never-resign game the game is marked with the mover -
+ *              once, the first time - and plays on.  Everything downstream (emission and its z, recycling, the drain, restart, tree
+ *              reuse, the statistics of azk_recycle_finished / stats_dev) sees an ordinary finished game whose winner is set.
+ *   the coin   one per game, stateless: Philox4x32-10, counter {global game lo, global game hi, start, 0xFFFFFFFD}, key (seed lo, seed hi),
+ *              u = ((c0 << 32 | c1) >> 11) * 2^-53, never-resign iff u < p_never.  start = low 32 bits of (the slot's move counter at the
+ *              move - mc): the move key of the game's first search (a game that azk_set_positions started with move_count > 0 gets
+ *              whatever the subtraction gives - still a pure function of the key).  Word 3 = 0xFFFFFFFD belongs to no other draw, so
+ *              every noise row, move uniform and playout-cap coin is unchanged and the coins do not depend on the sharding.
+ *   statistics int64 [4], counted by the mover at the move that ends a game, whatever the drain / recycle timing: [0] games ended by
+ *              resignation, [1] never-resign games ended, [2] of those the marked ones, [3] of those the ones whose marked side did not
+ *              lose (a win or a draw): the false positives.
+ * azk_set_resign: v_resign in [0, 1] (0 switches the option off), p_never in [0, 1], min_ply >= 0, not with leaves_per_step > 1, else
+ * AZK_ERR_ARG; clears flags, marks and statistics.  Call it before azk_async_begin(_reuse), which then keys the coin by ITS seed and
+ * first_global_game, clears the same, and makes the movers apply the rule.  Lock-step drivers move with azk_advance_resign = azk_advance +
+ * move_index, the slot's move counter (the move_index of the search's noise row); azk_advance answers AZK_ERR_STATE while the option is
+ * set, azk_advance_resign while it is not.  Combines with tree_reuse and with a playout cap (a fast search resigns like a full one).
+ * azk_get_resigned: uint8 [G] into device memory, 1 = the game's last move was a resignation (asynchronous copy on the stream).
+ * azk_get_resign_stats: the four counts into host memory; synchronises.
+ * azk_async_resign_flags (optional, before azk_async_begin): a uint8 [record_capacity] column of the record ring, entry r % capacity = 1
+ * when record r's move was a resignation (its rec_meta winner is then the conceded one). */
+int32_t azk_set_resign(azk_engine *e, double v_resign, int32_t min_ply, double p_never, uint64_t seed, int64_t first_global_game, void *stream);
+int32_t azk_advance_resign(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t move_index,
+                           int32_t *chosen_cell_dev, int32_t *winner_dev, int32_t *done_dev, void *stream);
+int32_t azk_get_resigned(azk_engine *e, uint8_t *resigned_dev, void *stream);
+int32_t azk_get_resign_stats(azk_engine *e, int64_t *out4_host, void *stream);
+int32_t azk_async_resign_flags(azk_engine *e, uint8_t *rec_resigned_dev);
+
 /* One simulation per active game (ai/mcts.py:16-60), split around the evaluator:
  *   azk_step_select   - mcts.py:18-37: PUCT walk (node.py:42-47, utils.py:29-44), make_move along the
  *                       path, terminal test + immediate backup, get_valid_moves, canonical board.

@@ -35,6 +35,7 @@ SYMBOLS = [
     "azk_async_begin", "azk_async_step", "azk_async_drain", "azk_async_set_budget", "azk_async_begin_reuse",
     "azk_set_playout_cap", "azk_begin_search_capped", "azk_get_search_full", "azk_async_record_flags",
     "azk_set_resign", "azk_advance_resign", "azk_get_resigned", "azk_get_resign_stats", "azk_async_resign_flags",
+    "azk_set_forced_playouts", "azk_root_policy_target",
 ]
 
 
@@ -162,6 +163,7 @@ class Engine:
         self._noise = None
         self.playout_cap = None                     # (p_full, n_fast) once set_playout_cap has switched the option on
         self.resign = None                          # (v_resign, p_never, min_ply) once set_resign has switched the option on
+        self.forced_playouts = None                 # k once set_forced_playouts has switched the option on
         self.cache_entries = int(cache_entries)
         # with the eval cache a step can have pending (cached) leaves to expand although no leaf went to the evaluator
         need = cache_entries or self.K > 1
@@ -252,6 +254,22 @@ class Engine:
         out = np.zeros(4, np.int64)
         self._chk(self.L.azk_get_resign_stats(self.h, _np(out), _stream()))
         return [int(x) for x in out]
+
+    def set_forced_playouts(self, k):
+        """OPT-IN forced playouts and policy target pruning at the root (azk_set_forced_playouts; KataGo's k is 2): in every search with
+        root noise - on a capped engine every FULL one - a root child with N >= 1 visits and mixed prior P is selected first while
+        N * N < (k * P) * (root visits - 1), and the pi that advance / the asynchronous movers RECORD loses the visits only that floor
+        explains (root_policy_target shows it).  The move, root_stats, q, resignation and tree reuse keep raw visits.  k = 0 switches it off."""
+        self._chk(self.L.azk_set_forced_playouts(self.h, float(k), _stream()))
+        self.forced_playouts = float(k) if float(k) != 0.0 else None
+
+    def root_policy_target(self):
+        """float64 CUDA tensor [G, A]: the pi the next advance would record for each game (azk_root_policy_target; valid until the next
+        call).  With forced playouts off, or for a game whose search is a fast one, root_stats' pi bit for bit."""
+        if getattr(self, "_pi_target", None) is None:
+            self._pi_target = self.torch.empty((self.G, self.action_dim), dtype=self.torch.float64, device=self.device)
+        self._chk(self.L.azk_root_policy_target(self.h, _p(self._pi_target), _stream()))
+        return self._pi_target
 
     def begin_search_budget(self, noise, n_sims, per_launch=8, move_index=None):
         """begin_search + a simulation budget: afterwards every step lets a game run on inside the launch while its simulations

@@ -84,10 +84,11 @@ class AsyncConfig(C.Structure):
 
 class Counters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("sims", "edges_scanned", "trace_nodes", "edges_created",
-                                          "leaves_evaluated", "terminal_sims", "moves_played", "cache_hits", "roots_reused", "nodes_carried")] + [("reserved", C.c_int64 * 6)]
+                                          "leaves_evaluated", "terminal_sims", "moves_played", "cache_hits", "roots_reused", "nodes_carried",
+                                          "forced_selections", "visits_pruned", "visits_before_pruning")] + [("reserved", C.c_int64 * 3)]
 
     def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_[:10]}
+        return {n: int(getattr(self, n)) for n, _ in self._fields_[:13]}
 
 
 def declare(L, symbols):
@@ -164,6 +165,8 @@ def declare(L, symbols):
     L.azk_advance_resign.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
     L.azk_get_resigned.argtypes = [vp, vp, vp]
     L.azk_get_resign_stats.argtypes = [vp, vp, vp]
+    L.azk_set_forced_playouts.argtypes = [vp, f64, vp]
+    L.azk_root_policy_target.argtypes = [vp, vp, vp]
     L.azk_async_resign_flags.argtypes = [vp, vp]
     L.azk_nn_ln_heads.argtypes = [vp, C.c_float, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.azk_nn_layernorm_rows.argtypes = [vp, vp, vp, C.c_float, vp, vp, i32, i32, vp, vp]

@@ -22,7 +22,9 @@
 
 namespace azk_eng {
 
-enum { CNT_SIMS = 0, CNT_SCANNED, CNT_TRACE, CNT_CREATED, CNT_LEAVES, CNT_TERMINAL, CNT_MOVES, CNT_CACHE_HITS, CNT_REUSED, CNT_CARRIED, CNT_N };
+enum { CNT_SIMS = 0, CNT_SCANNED, CNT_TRACE, CNT_CREATED, CNT_LEAVES, CNT_TERMINAL, CNT_MOVES, CNT_CACHE_HITS, CNT_REUSED, CNT_CARRIED,
+       CNT_FORCED, CNT_PRUNED, CNT_PRUNE_OF,   // forced playouts: root selections that took a forced child; visits pruning removed from recorded pi, of how many
+       CNT_N };
 
 struct __attribute__((aligned(16))) NodeH { int N; float P; uint32_t meta; int fc; };
 
@@ -123,6 +125,16 @@ struct ResignDev {
     int *mark_side;            // [G] the side that would have conceded first, -1 = none; valid only while mark_start is the current game's
     long long *stats;          // [4] games resigned, never-resign games ended, of those marked, of those whose marked side did not lose
     uint8_t *rec_resigned;     // asynchronous record ring: [record_capacity] 1 = the record's move was a resignation, or null
+};
+
+// forced playouts and policy target pruning at the root (azk_set_forced_playouts, opt-in; k == 0 otherwise): in a FORCED
+// search - the option set and, on a capped engine, the search a full one - a root child with N >= 1 visits and mixed prior P is selected
+// before any PUCT comparison while  N * N < (k * P) * (Np - 1)  (float64), and the pi that is RECORDED for the move loses the visits that
+// only this floor explains.  Its own argument of the kernels that exist only for it (k_tree<.., FORCED> in azk_tree.hip, k_*_fp in
+// azk_moves.hip): every other argument block - and every kernel an engine without the option launches - stays as it was
+struct ForcedDev {
+    double k;                      // KataGo's 2; 0 = off
+    const uint8_t *search_full;    // [G] CapDev's kind of the game's current search (1 full: forced, 0 fast: not), or null without a cap
 };
 
 struct LdsView {
@@ -275,6 +287,8 @@ struct azk_engine {
     AsyncDev ad;                         // asynchronous self-play (azk_async_begin); ad.slot_moves == nullptr: not set up
     CapDev cp = {};                      // playout-cap randomisation (azk_set_playout_cap); cp.n_fast == 0: off
     ResignDev rs = {};                   // resignation (azk_set_resign); rs.v_resign == 0: off
+    double forced_k = 0.0;               // forced playouts + policy target pruning (azk_set_forced_playouts); 0: off
+    ForcedDev forced() const { return ForcedDev{forced_k, cp.n_fast ? cp.search_full : nullptr}; }   // the argument block as the options stand now
     bool async_on = false;
     int async_recycle = 1;
 };

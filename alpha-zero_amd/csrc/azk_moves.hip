@@ -265,15 +265,65 @@ __global__ __launch_bounds__(AZK_WAVE) void k_root_stats(Dev d, double *pi, doub
 
 __device__ __forceinline__ bool resign_never(const ResignDev &rs, int g, uint32_t start);      // the game coin, beside cap_coin
 
+// Policy target pruning (forced playouts; Wu 2019, section 3.2) for one game (one wave).  L.cnt holds the root children's
+// RAW visit counts by action; on return it holds the counts the recorded pi is made of, and the function returns their sum.  With
+// Np = root visits, s = sqrt(Np) and c* = the first child with the most visits (Node.max_visit_child):
+//     pstar = W* / N* + (P* * s) / (N* + 1)
+// and every other child with N >= 1 loses up to nf = floor(sqrt((k * P) * (Np - 1))) visits - the floor forced playouts gave it - one at a
+// time, while its PUCT score with that visit removed (q held at W / N) would still lose to c*:
+//     m = N;  while (m > N - nf && m > 0 && q + (P * s) / m < pstar) m -= 1;   if (m == 1 && nf >= 1) m = 0
+// All float64, P = the root's mixed priors (rootP); c* and unvisited children keep their counts.  At most nf <= sqrt(k * max_sims) rounds per
+// lane.  The tree is not touched: the move, q, resignation and tree reuse see raw visits.
+__device__ __forceinline__ int prune_counts(const Dev &d, const LdsView &L, int g, double k) {
+    const int lane = azk_lane();
+    const GameDesc &gd = d.g;
+    const size_t base = (size_t)g * d.cap;
+    const int fc = uniform_i32(d.H[base].fc), nch = uniform_i32(meta_nch(d.H[base].meta)), Np = uniform_i32(d.H[base].N);
+    const double *P = d.rootP + (size_t)g * gd.rc;
+    const double s = sqrt((double)Np);
+    int best = 0x7fffffff, bn = 0;                                  // Node.max_visit_child (node.py:76-81)
+    for (int i = lane; i < nch; i += AZK_WAVE) {
+        const int n = d.H[base + fc + i].N;
+        if (best == 0x7fffffff || n > bn) { bn = n; best = i; }
+    }
+    wave_argmax_first<int>(bn, best);
+    best = uniform_i32(best); bn = uniform_i32(bn);
+    const double pstar = d.W[base + fc + best] / (double)bn + (P[best] * s) / (double)(bn + 1);
+    int sum = 0;
+    for (int i = lane; i < nch; i += AZK_WAVE) {
+        const NodeH h = d.H[base + fc + i];
+        int m = h.N;
+        if (i != best && h.N >= 1) {
+            const double Pi = P[i];
+            const int nf = (int)floor(sqrt((k * Pi) * (double)(Np - 1)));
+            const double q = d.W[base + fc + i] / (double)h.N;
+            while (m > h.N - nf && m > 0 && q + (Pi * s) / (double)m < pstar) m -= 1;
+            if (m == 1 && nf >= 1) m = 0;
+            L.cnt[azk_action_idx(gd, meta_cell(h.meta))] = m;
+        }
+        sum += m;
+    }
+    sum = wave_sum_i32(sum);
+    __syncthreads();
+    return sum;
+}
+// is the search game g has just completed a forced one?  (the option set - the caller's template parameter - the search full, the root mixed)
+__device__ __forceinline__ bool forced_search(const Dev &d, const ForcedDev &fp, int g) {
+    const int full = fp.search_full != nullptr ? uniform_i32((int)fp.search_full[g]) : 1;
+    return full != 0 && uniform_i32(d.root_f64[g]) != 0;
+}
+
 // gomoku.py:143-162 for one game (one wave): choose (sample ~ visits | first max-visit child), record pi / the action in the
 // trajectory, make_move, check_winner, draw.  Returns the chosen cell (-1: state error, already reported); *win_out / *done_out as
 // k_advance's outputs; pi of the move is left in L.cnt / sum_out (visit counts per action and their sum).
 // RESIGN (resigning engines, the k_*_rs kernels): after a move that does not end the game the mover concedes when the
 // root's q reached v_resign - or, in a never-resign game, is noted as the game's mark.  key = the slot's move counter at this move,
 // *rsg_out = 1 when the move ended the game by resignation.
-template <bool RESIGN>
+// FORCED (engines with forced playouts, the k_*_fp kernels): once the cell is chosen - from raw visits - the counts of a
+// forced search are pruned in place (prune_counts), so that traj_pi and the caller's record hold the pruned pi.
+template <bool RESIGN, bool FORCED = false>
 __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool have_u, double u, int sample_until, int *win_out, int *done_out,
-                                           int *sum_out, const ResignDev &rs, int key, int *rsg_out) {
+                                           int *sum_out, const ResignDev &rs, int key, int *rsg_out, const ForcedDev &fp = ForcedDev{}) {
     const int lane = azk_lane();
     const GameDesc &gd = d.g;
     const size_t base = (size_t)g * d.cap;
@@ -330,6 +380,14 @@ __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool
     if (cellc < 0) {
         if (lane == 0) atomicExch(d.err, AZK_ERR_STATE);
         return -1;
+    }
+    if constexpr (FORCED) {
+        if (forced_search(d, fp, g)) {
+            const int raw = sum;
+            sum = prune_counts(d, L, g, fp.k);
+            *sum_out = sum;
+            if (lane == 0) { count_add(d, CNT_PRUNED, g, raw - sum); count_add(d, CNT_PRUNE_OF, g, raw); }
+        }
     }
     if (d.traj_pi != nullptr && mc < gd.state_dim) {               // gomoku.py:138-146: pi and the action of this ply
         double *tp = d.traj_pi + ((size_t)g * gd.state_dim + mc) * A;
@@ -392,10 +450,10 @@ __device__ __forceinline__ int played_child(const Dev &d, int g, int cellc) {
 }
 
 // CAP: playout-cap engines (k_advance_cap) - the ply's kind goes into traj_full beside its pi; RESIGN: resigning engines (k_advance_rs),
-// move_index = the slot's move counter
-template <bool CAP, bool RESIGN>
+// move_index = the slot's move counter; FORCED: engines with forced playouts (k_advance_fp)
+template <bool CAP, bool RESIGN, bool FORCED = false>
 __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int move_index, const double *uniforms, int sample_until,
-                                             int *chosen, int *winner_out, int *done_out, int *chosen_node) {
+                                             int *chosen, int *winner_out, int *done_out, int *chosen_node, const ForcedDev &fp = ForcedDev{}) {
     const int g = blockIdx.x, lane = azk_lane();
     LdsView L = carve(d.g, d.path_cap, d.table_size);
     if (uniform_i32(d.done[g]) != 0) {
@@ -409,8 +467,8 @@ __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int
     }
     int win = -2, dn = 0, sum = 0, rsg = 0;
     const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
-    const int cellc = advance_one<RESIGN>(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum,
-                                          rs, move_index, &rsg);
+    const int cellc = advance_one<RESIGN, FORCED>(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum,
+                                                  rs, move_index, &rsg, fp);
     if (CAP && cellc >= 0 && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = cp.search_full[g];
     if (chosen_node) {
         const int child = played_child(d, g, cellc);               // tree reuse: the next search's root
@@ -690,8 +748,8 @@ __device__ __forceinline__ void cap_begin_fresh(const Dev &d, const CapDev &c, i
     if (count && c.stats != nullptr) atomicAdd((unsigned long long *)&c.stats[full ? 8 : 9], 1ull);
 }
 
-template <bool REROOT, bool CAP, bool RESIGN>   // the body of k_move_async / k_move_async_cap and their _rs siblings
-__device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs) {
+template <bool REROOT, bool CAP, bool RESIGN, bool FORCED = false>   // the body of k_move_async / k_move_async_cap, their _rs siblings and k_move_async_fp
+__device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs, const ForcedDev &fp = ForcedDev{}) {
     const int g = blockIdx.x, lane = azk_lane();
     // one vector load for the three words that decide whether this game moves now (almost never: the wave then ends at once)
     const int *up = d.done + g;
@@ -716,7 +774,7 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
     const double u = noise_uniform(p.seed, (unsigned long long)(p.first_game + g), (int)mv);
     const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
     const int kind = CAP ? uniform_i32((int)cp.search_full[g]) : 1;     // of the search that is complete
-    const int cellc = advance_one<RESIGN>(d, L, g, true, u, p.sample_until, &win, &dn, &sum, rs, (int)mv, &rsg);
+    const int cellc = advance_one<RESIGN, FORCED>(d, L, g, true, u, p.sample_until, &win, &dn, &sum, rs, (int)mv, &rsg, fp);
     if (cellc < 0) return;
     if (CAP && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = (uint8_t)kind;
     if (p.rec_cap > 0) {                                           // the move's record: what the reference's self_play keeps per ply
@@ -896,6 +954,43 @@ __global__ __launch_bounds__(AZK_WAVE) void k_move_async_rs(Dev d, AsyncDev p, R
 template <bool REROOT>
 __global__ __launch_bounds__(AZK_WAVE) void k_move_async_cap_rs(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs) { move_async_body<REROOT, true, true>(d, p, r, cp, rs); }
 
+// ------------------------------------------------------------------------------------------------
+// Forced playouts and policy target pruning (azk_set_forced_playouts, opt-in): the movers an engine with the option
+// launches IN PLACE of their namesakes - each its namesake's body with FORCED set, one template over the cap and the resignation so that the
+// option does not double the list above.  The selection half of the option lives in k_tree<.., FORCED> (azk_tree.hip).
+// ------------------------------------------------------------------------------------------------
+template <bool CAP, bool RESIGN>
+__global__ __launch_bounds__(AZK_WAVE) void k_advance_fp(Dev d, CapDev cp, ResignDev rs, ForcedDev fp, const double *uniforms, int sample_until, int move_index,
+                                                          int *chosen, int *winner_out, int *done_out, int *chosen_node) {
+    advance_body<CAP, RESIGN, true>(d, cp, rs, move_index, uniforms, sample_until, chosen, winner_out, done_out, chosen_node, fp);
+}
+
+template <bool REROOT, bool CAP, bool RESIGN>
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async_fp(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs, ForcedDev fp) {
+    move_async_body<REROOT, CAP, RESIGN, true>(d, p, r, cp, rs, fp);
+}
+
+// azk_root_policy_target: the pi the next move would record - k_root_stats' counts, pruned where the game's search is a forced one
+__global__ __launch_bounds__(AZK_WAVE) void k_root_policy_target(Dev d, ForcedDev fp, double *pi) {
+    const int g = blockIdx.x, lane = azk_lane();
+    const size_t base = (size_t)g * d.cap;
+    const int A = d.g.action_dim;
+    LdsView L = carve(d.g, d.path_cap, d.table_size);
+    const int fc = uniform_i32(d.H[base].fc), nch = uniform_i32(meta_nch(d.H[base].meta));
+    for (int a = lane; a < A; a += AZK_WAVE) L.cnt[a] = 0;
+    __syncthreads();
+    int sum = 0;
+    for (int i = lane; i < nch; i += AZK_WAVE) {
+        const int n = d.H[base + fc + i].N;
+        L.cnt[azk_action_idx(d.g, meta_cell(d.H[base + fc + i].meta))] = n;
+        sum += n;
+    }
+    sum = wave_sum_i32(sum);
+    __syncthreads();
+    if (nch > 0 && sum > 0 && forced_search(d, fp, g)) sum = prune_counts(d, L, g, fp.k);
+    for (int a = lane; a < A; a += AZK_WAVE) pi[(size_t)g * A + a] = (double)L.cnt[a] / (double)sum;
+}
+
 }  // namespace
 
 int32_t azk_init_games(azk_engine *e) {
@@ -948,8 +1043,16 @@ int32_t azk_reset_games(azk_engine *e, int32_t first, int32_t count, void *strea
     return AZK_OK;
 }
 
+// forced playouts act on the root's float64 (noise-mixed) priors: a search without a noise row is refused while the option is set
+static bool forced_needs_noise(azk_engine *e, const double *noise_dev, const char *who) {
+    if (e->forced_k == 0.0 || noise_dev != nullptr) return false;
+    e->err = std::string(who) + ": forced playouts are set - a search needs its Dirichlet row (noise_dev = NULL is the noise-free search)";
+    return true;
+}
+
 int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
+    if (forced_needs_noise(e, noise_dev, "azk_begin_search")) return AZK_ERR_STATE;
     if (e->cp.n_fast) { e->err = "azk_begin_search: a playout cap is set - its searches begin with azk_begin_search_capped (budget + move index)"; return AZK_ERR_STATE; }
     e->d.noise = noise_dev; e->d.noise_sel = nullptr;
     if (e->ru.mode == 2) { e->err = "azk_begin_search: top-up tree reuse needs the budget (azk_begin_search_budget)"; return AZK_ERR_STATE; }
@@ -978,6 +1081,7 @@ static int32_t begin_budget(azk_engine *e, const double *noise_dev, int32_t n_si
 int32_t azk_begin_search_budget(azk_engine *e, const double *noise_dev, int32_t n_sims, int32_t max_sims_per_launch, void *stream) {
     if (!e || n_sims < 1 || n_sims > e->cfg.max_sims || max_sims_per_launch < 1) { if (e) e->err = "azk_begin_search_budget: bad argument"; return AZK_ERR_ARG; }
     if (e->cp.n_fast) { e->err = "azk_begin_search_budget: a playout cap is set - its searches begin with azk_begin_search_capped (the coin needs the move index)"; return AZK_ERR_STATE; }
+    if (forced_needs_noise(e, noise_dev, "azk_begin_search_budget")) return AZK_ERR_STATE;
     return begin_budget(e, noise_dev, n_sims, max_sims_per_launch, -1, stream);
 }
 
@@ -1006,6 +1110,7 @@ int32_t azk_begin_search_capped(azk_engine *e, const double *noise_dev, int32_t 
     if (!e || n_sims < 1 || n_sims > e->cfg.max_sims || max_sims_per_launch < 1 || move_index < 0) { if (e) e->err = "azk_begin_search_capped: bad argument"; return AZK_ERR_ARG; }
     if (!e->cp.n_fast) { e->err = "azk_begin_search_capped: no playout cap is set (azk_set_playout_cap)"; return AZK_ERR_STATE; }
     if (e->cp.n_fast > n_sims) { e->err = "azk_begin_search_capped: n_fast exceeds n_sims"; return AZK_ERR_ARG; }
+    if (forced_needs_noise(e, noise_dev, "azk_begin_search_capped")) return AZK_ERR_STATE;
     return begin_budget(e, noise_dev, n_sims, max_sims_per_launch, move_index, stream);
 }
 
@@ -1021,6 +1126,26 @@ int32_t azk_async_record_flags(azk_engine *e, uint8_t *rec_full_dev) {
     if (!e->cp.n_fast) { e->err = "azk_async_record_flags: no playout cap is set (azk_set_playout_cap)"; return AZK_ERR_STATE; }
     if (e->async_on) { e->err = "azk_async_record_flags: call it before azk_async_begin"; return AZK_ERR_STATE; }
     e->cp.rec_full = rec_full_dev;
+    return AZK_OK;
+}
+
+// ---- forced playouts and policy target pruning ------------------------------------------------------------------------------
+int32_t azk_set_forced_playouts(azk_engine *e, double k, void *stream) {
+    (void)stream;
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_forced_playouts: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (!(k >= 0.0) || k - k != 0.0) { e->err = "azk_set_forced_playouts: k must be finite and not negative (0 = off)"; return AZK_ERR_ARG; }
+    if (k == 0.0) { e->forced_k = 0.0; return AZK_OK; }              // off: the engine launches what it launched before
+    if (e->d.K > 1) { e->err = "azk_set_forced_playouts: forced playouts do not combine with leaves_per_step > 1 (a virtual-loss search counts a visit before its value exists: the floor would be met by visits that carry nothing)"; return AZK_ERR_ARG; }
+    e->forced_k = k;
+    return AZK_OK;
+}
+
+int32_t azk_root_policy_target(azk_engine *e, double *pi_dev, void *stream) {
+    if (!e || !pi_dev) return AZK_ERR_ARG;
+    if (e->forced_k == 0.0) k_root_stats<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, pi_dev, nullptr, nullptr);
+    else k_root_policy_target<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->forced(), pi_dev);
+    HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
 
@@ -1091,6 +1216,7 @@ static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *strea
     if (!e->ru.mode && reuse) { e->err = "azk_async_begin_reuse: the engine was created with tree_reuse = 0 (use azk_async_begin)"; return AZK_ERR_STATE; }
     if (c->record_capacity < 0 || (c->record_capacity > 0 && (!c->rec_meta_dev || !c->rec_q_dev || !c->rec_pi_dev))) { e->err = "azk_async_begin: record ring pointers missing"; return AZK_ERR_ARG; }
     if (e->cp.n_fast > c->n_sims) { e->err = "azk_async_begin: the playout cap's n_fast exceeds n_sims"; return AZK_ERR_ARG; }
+    if (e->forced_k != 0.0 && !c->dirichlet) { e->err = "azk_async_begin: forced playouts are set - the searches need root noise (dirichlet = 1)"; return AZK_ERR_STATE; }
     Dev &d = e->d;
     if (d.K > 1) { e->err = "azk_async_begin: asynchronous moves run the sequential search (leaves_per_step = 1)"; return AZK_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
@@ -1159,7 +1285,14 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
     const Dev &d = e->d;
     hipStream_t st = (hipStream_t)stream;
     if (phases & 1) { const int32_t rc = azk_launch_tree(e, true, true, true, logits_dev, values_dev, st); if (rc != AZK_OK) return rc; }
-    if ((phases & 2) && e->rs.v_resign != 0.0) {
+    if ((phases & 2) && e->forced_k != 0.0) {
+        const bool cap = e->cp.n_fast != 0, rsn = e->rs.v_resign != 0.0, rr = e->ru.mode != 0;
+        const ForcedDev fp = e->forced();
+#define AZK_MOVE_FP(RR, CAP, RS) k_move_async_fp<RR, CAP, RS><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp, e->rs, fp)
+        if (rr) { if (cap) { if (rsn) AZK_MOVE_FP(true, true, true); else AZK_MOVE_FP(true, true, false); } else { if (rsn) AZK_MOVE_FP(true, false, true); else AZK_MOVE_FP(true, false, false); } }
+        else { if (cap) { if (rsn) AZK_MOVE_FP(false, true, true); else AZK_MOVE_FP(false, true, false); } else { if (rsn) AZK_MOVE_FP(false, false, true); else AZK_MOVE_FP(false, false, false); } }
+#undef AZK_MOVE_FP
+    } else if ((phases & 2) && e->rs.v_resign != 0.0) {
         if (e->cp.n_fast) {
             if (e->ru.mode) k_move_async_cap_rs<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp, e->rs);
             else k_move_async_cap_rs<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp, e->rs);
@@ -1237,7 +1370,12 @@ int32_t azk_advance(azk_engine *e, const double *uniforms_dev, int32_t sample_un
                     int32_t *winner_dev, int32_t *done_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
     if (e->rs.v_resign != 0.0) { e->err = "azk_advance: resignation is set - its moves are made by azk_advance_resign (the game coin needs the move index)"; return AZK_ERR_STATE; }
-    if (e->cp.n_fast) k_advance_cap<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, uniforms_dev, sample_until_move,
+    if (e->forced_k != 0.0) {
+        if (e->cp.n_fast) k_advance_fp<true, false><<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, e->forced(), uniforms_dev, sample_until_move, 0,
+                                                                                                           chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
+        else k_advance_fp<false, false><<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, e->forced(), uniforms_dev, sample_until_move, 0,
+                                                                                                  chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
+    } else if (e->cp.n_fast) k_advance_cap<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, uniforms_dev, sample_until_move,
                                                                                                chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
     else k_advance<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, uniforms_dev, sample_until_move,
                                                                          chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
@@ -1249,7 +1387,12 @@ int32_t azk_advance_resign(azk_engine *e, const double *uniforms_dev, int32_t sa
                            int32_t *winner_dev, int32_t *done_dev, void *stream) {
     if (!e || move_index < 0) { if (e) e->err = "azk_advance_resign: bad argument"; return AZK_ERR_ARG; }
     if (e->rs.v_resign == 0.0) { e->err = "azk_advance_resign: no resignation is set (azk_set_resign)"; return AZK_ERR_STATE; }
-    if (e->cp.n_fast) k_advance_cap_rs<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, uniforms_dev, sample_until_move, move_index,
+    if (e->forced_k != 0.0) {
+        if (e->cp.n_fast) k_advance_fp<true, true><<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, e->forced(), uniforms_dev, sample_until_move, move_index,
+                                                                                                          chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
+        else k_advance_fp<false, true><<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, e->forced(), uniforms_dev, sample_until_move, move_index,
+                                                                                                 chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
+    } else if (e->cp.n_fast) k_advance_cap_rs<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, uniforms_dev, sample_until_move, move_index,
                                                                                                   chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
     else k_advance_rs<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->rs, uniforms_dev, sample_until_move, move_index,
                                                                             chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
@@ -1270,6 +1413,7 @@ int32_t azk_get_counters(azk_engine *e, azk_counters *out, void *stream) {
     out->edges_created = h[CNT_CREATED]; out->leaves_evaluated = h[CNT_LEAVES]; out->terminal_sims = h[CNT_TERMINAL];
     out->moves_played = h[CNT_MOVES]; out->cache_hits = h[CNT_CACHE_HITS];
     out->roots_reused = h[CNT_REUSED]; out->nodes_carried = h[CNT_CARRIED];
+    out->forced_selections = h[CNT_FORCED]; out->visits_pruned = h[CNT_PRUNED]; out->visits_before_pruning = h[CNT_PRUNE_OF];
     return AZK_OK;
 }
 

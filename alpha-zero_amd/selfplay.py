@@ -74,6 +74,31 @@ def check_resign(resign, leaves_per_step=1):
     return v, p_never, min_ply
 
 
+def check_forced_playouts(forced_playouts, evaluator=True, dirichlet=True, leaves_per_step=1):
+    """forced_playouts = k -> float, or None for off (None or 0).  OPT-IN forced playouts and policy target pruning at the root (include/azk.h
+    azk_set_forced_playouts): a root child with N >= 1 visits and mixed prior P is selected first while
+    N * N < (k * P) * (root visits - 1), and the recorded pi loses the visits only that floor explains.  Raises ValueError, before any engine
+    exists, for what the engine refuses too - a negative, NaN or infinite k, virtual loss - and for searches without the root's mixed priors:
+    vanilla MCTS (evaluator None) and dirichlet=False."""
+    if forced_playouts is None:
+        return None
+    try:
+        k = float(forced_playouts)
+    except (TypeError, ValueError):
+        raise ValueError(f"forced_playouts must be a number k >= 0 (KataGo: 2), not {forced_playouts!r}")
+    if not 0.0 <= k < float("inf"):                               # (NaN fails both comparisons)
+        raise ValueError(f"forced_playouts: k must be finite and not negative, not {forced_playouts!r}")
+    if k == 0.0:
+        return None
+    if evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator)):
+        raise ValueError("forced_playouts: vanilla MCTS (evaluator None) is refused - it has no priors for the floor to be proportional to")
+    if not dirichlet:
+        raise ValueError("forced_playouts needs root noise (dirichlet=True): the rule acts on the root's noise-mixed float64 priors")
+    if int(leaves_per_step) > 1:
+        raise ValueError("forced_playouts does not combine with leaves_per_step > 1 (a virtual-loss search counts a visit before its value exists)")
+    return k
+
+
 def _refuse_vanilla_resign(resign, evaluator):
     if resign is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("resign: vanilla MCTS (evaluator None) is refused - its q is a rollout mean and no threshold is defined for it")
@@ -96,7 +121,7 @@ class SelfPlayResult:
 def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
                     alpha=0.03, noise_fn=None, uniform_fn=None, device=0, leaf_dtype="float32", engine=None,
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
-                    budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None):
+                    budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -112,11 +137,13 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     np.random.RandomState per global game index derived from `seed`).  playout_cap = (p_full, n_fast) (OPT-IN, check_playout_cap): per ply a
     coin keyed (seed, global game, move) makes the search full or fast; SelfPlayResult.full records it and a replay ring gets the full plies only.
     resign = (v_resign, p_never[, min_ply]) (OPT-IN, check_resign): a game may end by resignation - SelfPlayResult.resigned, winner = the
-    other side, z and the replay tuples as for any finished game.
+    other side, z and the replay tuples as for any finished game.  forced_playouts = k (OPT-IN, check_forced_playouts): forced playouts at the
+    root; SelfPlayResult.pis and the replay tuples carry the PRUNED pi of every full search, the moves are those of the raw visits.
     """
     import torch
     cap = check_playout_cap(playout_cap, n_sims, leaves_per_step)
     rsg = check_resign(resign, leaves_per_step)
+    fpk = check_forced_playouts(forced_playouts, evaluator, dirichlet, leaves_per_step)
     _refuse_vanilla_resign(rsg, evaluator)
     if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
@@ -127,6 +154,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         eng.set_playout_cap(cap[0], cap[1], seed, first_global_game)
     if rsg is not None:
         eng.set_resign(rsg[0], rsg[1], rsg[2], seed, first_global_game)
+    if fpk is not None:
+        eng.set_forced_playouts(fpk)
     # virtual-loss, top-up and capped engines are driven by the simulation budget
     budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
     assert eng.G == n_games
@@ -166,6 +195,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
             eng.search(ev, ns, noise if dirichlet else None)
         full_h = eng.search_full().cpu().numpy() if eng.playout_cap is not None else None
         pi, q, _ = eng.root_stats()
+        if eng.forced_playouts is not None:
+            pi = eng.root_policy_target()                         # what advance records: pruned where the search was a forced one
         cells_before, to_move, _ = eng.get_positions()
         chosen, winner, done = eng.advance(uni, su, move_index=move)
         resigned_h = eng.resigned().cpu().numpy() if eng.resign is not None else None
@@ -305,17 +336,21 @@ class SelfPlayRunner:
     resign = (v_resign, p_never[, min_ply]) (OPT-IN, check_resign; with any tree_reuse and with playout_cap): after a move the mover concedes
     when the recorded q >= v_resign; the slot's record then carries the conceded winner and done, `record_resigned` (uint8 [group size], valid
     inside on_records) is 1 for it, and the game is emitted and recycled like any finished game.  resign_stats() counts the outcomes.
+
+    forced_playouts = k (OPT-IN, check_forced_playouts; with any tree_reuse, playout_cap and resign): forced playouts at the root of every
+    (full) search; the records' pi and the replay ring carry the pruned pi, the moves are those of the raw visits.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
                  alpha=0.03, device=0, leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None,
                  use_graph=False, n_split=1, replay=None, cache_entries=0, cache_shared=False, budget_stepping=False, per_launch=8,
                  steps_per_graph=32,
-                 leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None):
+                 leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None):
         import torch
         self.playout_cap = check_playout_cap(playout_cap, n_sims, leaves_per_step)
         self.resign = check_resign(resign, leaves_per_step)
         _refuse_vanilla_resign(self.resign, evaluator)
+        self.forced_playouts = check_forced_playouts(forced_playouts, evaluator, dirichlet, leaves_per_step)
         self.record_full = self.record_resigned = None
         self.replay = replay
         self.torch = torch
@@ -355,6 +390,8 @@ class SelfPlayRunner:
                 h.eng.set_playout_cap(self.playout_cap[0], self.playout_cap[1], seed, first_global_game + i * per)
             if self.resign is not None:
                 h.eng.set_resign(self.resign[0], self.resign[1], self.resign[2], seed, first_global_game + i * per)
+            if self.forced_playouts is not None:
+                h.eng.set_forced_playouts(self.forced_playouts)
 
     # ---- one move for every slot -------------------------------------------------------------------------
     def play_move(self):
@@ -373,6 +410,8 @@ class SelfPlayRunner:
             if self.playout_cap is not None:
                 h.h_full.copy_(e.search_full(), non_blocking=True)
             pi, q, _ = e.root_stats()
+            if self.forced_playouts is not None:
+                pi = e.root_policy_target()                   # what advance records: pruned where the search was a forced one
             h.h_pi.copy_(pi, non_blocking=True)
             h.h_q.copy_(q, non_blocking=True)
             chosen, winner, done = e.advance(h.uni, self.sample_until, move_index=self.move_idx)
@@ -602,16 +641,20 @@ class AsyncSelfPlayRunner:
 
     resign = (v_resign, p_never[, min_ply]) (OPT-IN, check_resign; with any reroot and with playout_cap): the games of SelfPlayRunner(resign=...),
     slot for slot - the move kernel applies the rule, the drain sees an ordinary finished game.  `record_resigned` (uint8 numpy, one per record,
-    valid inside on_records) is 1 where the record's move conceded; resign_stats() counts the outcomes."""
+    valid inside on_records) is 1 where the record's move conceded; resign_stats() counts the outcomes.
+
+    forced_playouts = k (OPT-IN, check_forced_playouts; with any reroot, playout_cap and resign): the games of SelfPlayRunner(forced_playouts=k),
+    slot for slot; the record ring's pi and the replay ring carry the pruned pi."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
-                 playout_cap=None, resign=None):
+                 playout_cap=None, resign=None, forced_playouts=None):
         import torch
         self.playout_cap = check_playout_cap(playout_cap, n_sims)
         self.resign = check_resign(resign)
         _refuse_vanilla_resign(self.resign, evaluator)
+        self.forced_playouts = check_forced_playouts(forced_playouts, evaluator, dirichlet)
         self.record_full = self.record_resigned = None
         if tree_reuse:
             raise ValueError("AsyncSelfPlayRunner takes tree reuse as reroot=1 (carry) or reroot=2 (top-up): the re-root runs in the drain "
@@ -634,6 +677,8 @@ class AsyncSelfPlayRunner:
             e.set_playout_cap(self.playout_cap[0], self.playout_cap[1], seed, first_global_game)
         if self.resign is not None:
             e.set_resign(self.resign[0], self.resign[1], self.resign[2], seed, first_global_game)
+        if self.forced_playouts is not None:
+            e.set_forced_playouts(self.forced_playouts)
         cap = (4 * n_games if record_capacity is None else record_capacity) if (on_records is not None or record_capacity) else 0
         self.stats, self.records = e.async_begin(n_sims, self.per_launch, SAMPLE_UNTIL[game], seed, first_global_game, alpha, dirichlet, recycle, cap,
                                                  young_launch_us=young_launch_us, reroot=bool(self.reroot))

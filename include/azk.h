@@ -108,7 +108,10 @@ typedef struct {
     int64_t cache_hits;       /* MCTS.matched (mcts.py:9,44): leaves served by the eval cache; leaves_evaluated counts the misses */
     int64_t roots_reused;     /* tree reuse: searches that began on a carried subtree (the others began on a fresh root) */
     int64_t nodes_carried;    /* tree reuse: nodes of those subtrees */
-    int64_t reserved[6];
+    int64_t forced_selections;      /* forced playouts: root selections that took a forced child (of `sims` root selections in all) */
+    int64_t visits_pruned;          /* policy target pruning: visits removed from the recorded pi ... */
+    int64_t visits_before_pruning;  /* ... of this many raw root-child visits (the moves of forced searches only) */
+    int64_t reserved[3];
 } azk_counters;
 
 int32_t azk_abi_version(void);
@@ -255,6 +258,39 @@ int32_t azk_advance_resign(azk_engine *e, const double *uniforms_dev, int32_t sa
 int32_t azk_get_resigned(azk_engine *e, uint8_t *resigned_dev, void *stream);
 int32_t azk_get_resign_stats(azk_engine *e, int64_t *out4_host, void *stream);
 int32_t azk_async_resign_flags(azk_engine *e, uint8_t *rec_resigned_dev);
+
+/* ---- forced playouts and policy target pruning at the root (OPT-IN; off, the engine is what it was bit for bit).  KataGo's third
+ * self-play economy (Wu 2019, section 3.2): every root child the search has tried gets a floor of visits proportional to the square root
+ * of its noised prior, so that a move the Dirichlet noise points at is followed up; and the pi that is RECORDED loses exactly the visits
+ * that only that floor explains, so that they do not pass for the search's liking.  All arithmetic float64; k > 0 (KataGo: 2).
+ *   forced     a search is FORCED when the option is set and - on an engine with a playout cap - the search is a full one (fast searches
+ *              run unforced; their pi is not recorded).  A forced search needs root noise: its priors are the root's float64 mixed
+ *              priors P (utils.py:24-25).  A search begun with noise_dev = NULL while the option is set: AZK_ERR_STATE (azk_async_begin
+ *              with dirichlet = 0 likewise).
+ *   selection  the root only, every simulation of a forced search.  Np = the root's visit count as the scan has it (Np - 1 = the sum of
+ *              its children's visits, for a fresh root and a re-rooted one alike).  A root child with N >= 1 visits is forced iff
+ *                  (double)N * (double)N  <  (k * P) * (double)(Np - 1)
+ *              and a forced child's score is +inf; everything else of the scan stays, "first maximum wins" (node.py:47) included: among
+ *              several forced children the first in list order is taken.  Children with N = 0 are never forced.  No square root is
+ *              taken.  Levels below the root are untouched.  The rule is stateless in (N, P, Np): it combines with tree_reuse 1 | 2.
+ *   pruning    once per move, after the move is chosen.  Np = root visits, s = sqrt((double)Np), c* = the first child with the most
+ *              visits (Node.max_visit_child):  pstar = W* / N* + (P* * s) / (double)(N* + 1).  For every other child with N >= 1:
+ *                  nf = (int)floor(sqrt((k * P) * (double)(Np - 1)));   q = W / (double)N;   m = N
+ *                  while (m > N - nf  &&  m > 0  &&  q + (P * s) / (double)m < pstar)  m -= 1
+ *                  if (m == 1 && nf >= 1)  m = 0
+ *              c* and children with N = 0 keep their counts; pi[action] = m / sum(m).
+ *   who sees   RAW visits: the move (sampled or arg-max), azk_root_stats, q, resignation, tree reuse - a search with the option on plays
+ *   what       exactly the move the same tree would play without it.  PRUNED counts: the recorded pi only - the trajectory behind
+ *              azk_emit_finished / azk_async_drain's (state, pi, z) tuples and the asynchronous record ring's rec_pi.  The record of a
+ *              fast search keeps raw counts.
+ * azk_set_forced_playouts: k = 0 switches the option off; k < 0, NaN or infinite: AZK_ERR_ARG; not with leaves_per_step > 1 (AZK_ERR_ARG).
+ * Call it before azk_async_begin(_reuse).  Combines with the playout cap, resignation, tree_reuse, plain and budget stepping and the
+ * asynchronous movers.  azk_counters.forced_selections / visits_pruned / visits_before_pruning count what it did.
+ * azk_root_policy_target: float64 [G][A] into device memory, what the next azk_advance would record for each game.  With the option off, or
+ * for a game whose search is a fast one, this is azk_root_stats' pi bit for bit - a root without a visited child (no search yet, a finished
+ * game) included: both divide by a zero sum and write NaN. */
+int32_t azk_set_forced_playouts(azk_engine *e, double k, void *stream);
+int32_t azk_root_policy_target(azk_engine *e, double *pi_dev, void *stream);
 
 /* One simulation per active game (ai/mcts.py:16-60), split around the evaluator:
  *   azk_step_select   - mcts.py:18-37: PUCT walk (node.py:42-47, utils.py:29-44), make_move along the

@@ -1,6 +1,7 @@
 """The hand-written path for networks deeper than one block (csrc/azk_block.hip; reference: ai/nn.py:38-61, main.py:186-188 builds
 Net(embed_dim=256, num_heads=8, depth=2)): the LDS-staged token GEMM, the all-token attention kernel, and the whole depth-2
-evaluator against the reference's outputs (tests/golden/nn_depth2.npz) with the library GEMM / attention entry points disabled."""
+evaluator against the reference's outputs (tests/golden/nn_depth2.npz) with the library GEMM / attention entry points disabled.
+The kernels one by one, bit-exact probes and float64 bounds at small shapes: tests/test_gpu_block_pinned.py."""
 import json
 
 import numpy as np

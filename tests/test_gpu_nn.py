@@ -86,7 +86,8 @@ def test_folded_cls_attention_matches_full_forward(R, D, heads, depth, k):
 
 
 def test_cls_attention_kernel_vs_torch():
-    """z = softmax(xhat m^T + c) weighted token sums, against the same op in plain PyTorch fp32."""
+    """z = softmax(xhat m^T + c) weighted token sums, against the same op in plain PyTorch fp32.
+    Bit-exact probes, T < 10 and a float64 bound: tests/test_gpu_block_pinned.py."""
     import azk
     torch.manual_seed(0)
     for (n, T, D, H, per_board) in [(33, 226, 512, 8, False), (17, 50, 256, 8, True), (9, 10, 128, 4, False), (5, 226, 512, 4, True)]:
@@ -105,7 +106,8 @@ def test_cls_attention_kernel_vs_torch():
 @pytest.mark.parametrize("D", [128, 256, 512])
 def test_layernorm_rows_and_heads_finalize_vs_torch_fp32(D):
     """azk_nn_layernorm_rows / azk_nn_heads_finalize against the plain fp32 ops on the same bf16 inputs.
-    Tolerance: outputs are rounded once to bf16 (2^-8 relative) -> 1e-2 absolute on O(1) values."""
+    Tolerance: outputs are rounded once to bf16 (2^-8 relative) -> 1e-2 absolute on O(1) values.
+    k_ln_rows to half a bf16 ulp of float64, constant / large-mean / one-hot rows, n < 4: tests/test_gpu_block_pinned.py."""
     import azk
     torch.manual_seed(D)
     n = 301

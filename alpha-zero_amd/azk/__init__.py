@@ -36,6 +36,7 @@ SYMBOLS = [
     "azk_set_playout_cap", "azk_begin_search_capped", "azk_get_search_full", "azk_async_record_flags",
     "azk_set_resign", "azk_advance_resign", "azk_get_resigned", "azk_get_resign_stats", "azk_async_resign_flags",
     "azk_set_forced_playouts", "azk_root_policy_target",
+    "azk_set_eval_symmetry", "azk_get_leaf_symmetry", "azk_eval_symmetry_restore",
 ]
 
 
@@ -118,7 +119,7 @@ class Engine:
     """G concurrent games + their search trees resident on one GPU (one engine per process / GPU)."""
 
     def __init__(self, game, n_games, max_sims, size=None, device=0, leaf_dtype="float32", arena_nodes=0, cache_entries=0,
-                 cache_shared=False, leaves_per_step=1, tree_reuse=0):
+                 cache_shared=False, leaves_per_step=1, tree_reuse=0, eval_symmetry=None):
         torch = _torch()
         self.torch = torch
         self.L = lib()
@@ -169,6 +170,9 @@ class Engine:
         need = cache_entries or self.K > 1
         self._no_logits = torch.zeros((1, self.action_dim), dtype=torch.float32, device=dev) if need else None
         self._no_values = torch.zeros(1, dtype=torch.float32, device=dev) if need else None
+        self.eval_symmetry = None                   # (mode, value) once set_eval_symmetry has switched the option on
+        if eval_symmetry is not None:
+            self.set_eval_symmetry(*eval_symmetry)
 
     def _chk(self, rc):
         if rc < 0:
@@ -262,6 +266,38 @@ class Engine:
         explains (root_policy_target shows it).  The move, root_stats, q, resignation and tree reuse keep raw visits.  k = 0 switches it off."""
         self._chk(self.L.azk_set_forced_playouts(self.h, float(k), _stream()))
         self.forced_playouts = float(k) if float(k) != 0.0 else None
+
+    def set_eval_symmetry(self, mode, value=0):
+        """OPT-IN evaluation under a board symmetry (azk_set_eval_symmetry): the evaluator sees every pending leaf turned by a D4 element
+        and its logits row is turned back before the tree expands from it.  mode 1 (or "position"): the element is a hash of (seed = value,
+        the leaf's position), so the evaluator stays a function of the position and cache modes, budget stepping, tree reuse and the
+        asynchronous movers keep their bit-for-bit equivalences; mode 2 (or "fixed"): element `value` for every leaf; mode 0: off.  Between
+        searches only (before async_begin)."""
+        mode = {"off": 0, "position": 1, "fixed": 2}.get(mode, mode)
+        self._chk(self.L.azk_set_eval_symmetry(self.h, int(mode), int(value), _stream()))
+        self.eval_symmetry = (int(mode), int(value)) if int(mode) else None
+        self._leaf_source = None                    # the cached struct holds the cells pointer of the mode it was made under
+        if self.eval_symmetry and getattr(self, "_leaf_sym", None) is None:
+            self._leaf_sym = self.torch.zeros(self.G, dtype=self.torch.uint8, device=self.device)
+
+    def leaf_symmetry(self):
+        """uint8 CUDA tensor [G]: the element each game's pending leaf is evaluated under (azk_get_leaf_symmetry; meaningful for the games
+        whose leaf went to the evaluator in the last step; valid until the next call)."""
+        if self.eval_symmetry is None:
+            raise AzkError("leaf_symmetry: no evaluation symmetry is set (set_eval_symmetry)")
+        self._chk(self.L.azk_get_leaf_symmetry(self.h, _p(self._leaf_sym), _stream()))
+        return self._leaf_sym
+
+    def restore_logits(self, logits, out=None):
+        """The restore step alone (azk_eval_symmetry_restore): rows of `logits` (float32 [n, A], in the order of the last step's leaves) turned
+        back into each position's frame, into `out` (default: a copy of logits) - rows that belong to no pending leaf are left alone."""
+        if self.eval_symmetry is None:
+            raise AzkError("restore_logits: no evaluation symmetry is set (set_eval_symmetry)")
+        assert logits.dtype == self.torch.float32 and logits.is_cuda and logits.is_contiguous() and logits.shape[-1] == self.action_dim
+        out = logits.clone() if out is None else out
+        assert out.dtype == self.torch.float32 and out.is_contiguous() and out.shape == logits.shape and out.data_ptr() != logits.data_ptr()
+        self._chk(self.L.azk_eval_symmetry_restore(self.h, _p(logits), _p(out), _stream()))
+        return out
 
     def root_policy_target(self):
         """float64 CUDA tensor [G, A]: the pi the next advance would record for each game (azk_root_policy_target; valid until the next

@@ -168,6 +168,9 @@ def declare(L, symbols):
     L.azk_set_forced_playouts.argtypes = [vp, f64, vp]
     L.azk_root_policy_target.argtypes = [vp, vp, vp]
     L.azk_async_resign_flags.argtypes = [vp, vp]
+    L.azk_set_eval_symmetry.argtypes = [vp, i32, u64, vp]
+    L.azk_get_leaf_symmetry.argtypes = [vp, vp, vp]
+    L.azk_eval_symmetry_restore.argtypes = [vp, vp, vp, vp]
     L.azk_nn_ln_heads.argtypes = [vp, C.c_float, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.azk_nn_layernorm_rows.argtypes = [vp, vp, vp, C.c_float, vp, vp, i32, i32, vp, vp]
     L.azk_nn_heads_finalize.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]

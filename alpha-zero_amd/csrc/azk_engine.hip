@@ -128,6 +128,7 @@ int32_t azk_set_positions(azk_engine *e, int32_t first, int32_t count, const int
     }
     const Dev &d = e->d;
     hipStream_t st = (hipStream_t)stream;
+    e->in_search = false;                  // a new position: whatever search was under way is over
     std::vector<uint8_t> padded((size_t)count * d.rc_pad, 0);
     std::vector<int> zeros(count, 0), win(count, -2);
     for (int i = 0; i < count; i++)

@@ -137,6 +137,21 @@ struct ForcedDev {
     const uint8_t *search_full;    // [G] CapDev's kind of the game's current search (1 full: forced, 0 fast: not), or null without a cap
 };
 
+// evaluation under a board symmetry (azk_set_eval_symmetry, opt-in; mode == 0 otherwise): the evaluator is shown each pending
+// leaf in orientation s = the fixed element, or a hash of (seed, the leaf's position), and its logits row is turned back before k_tree expands
+// from it.  Its own argument of the two kernels that exist only for it (azk_sym.hip): every other argument block - and every kernel an engine
+// without the option launches - stays as it was
+struct SymDev {
+    int mode;                  // 0 off, 1 position-keyed, 2 one fixed element
+    int fixed;                 // mode 2: the element
+    uint32_t seed_lo, seed_hi; // mode 1: the key's seed
+    uint32_t valid;            // the elements the geometry admits, four bits each, lowest first
+    int n_valid;
+    uint8_t *leaf_sym;         // [G] element of the slot's pending leaf (written for flagged slots by k_sym_leaves)
+    uint8_t *sym_cells;        // [G][rc_pad] the pending leaf's cells in that orientation: what k_gather and the fused evaluators read
+    float *sym_logits;         // [G][A] the evaluator's rows turned back into the position's frame: what k_tree expands from
+};
+
 struct LdsView {
     uint8_t *board;
     int *path;
@@ -291,6 +306,8 @@ struct azk_engine {
     ForcedDev forced() const { return ForcedDev{forced_k, cp.n_fast ? cp.search_full : nullptr}; }   // the argument block as the options stand now
     bool async_on = false;
     int async_recycle = 1;
+    SymDev sym = {};                     // evaluation under a board symmetry (azk_set_eval_symmetry); sym.mode == 0: off, nothing allocated
+    bool in_search = false;              // between a search's begin and the move (or new position) that ends it: azk_set_eval_symmetry refuses
 };
 
 #define HIPCHK(e, call)                                                                 \
@@ -319,3 +336,8 @@ extern AZK_INTERNAL thread_local std::string azk_create_error;   // azk_last_err
 AZK_INTERNAL int32_t azk_launch_tree(azk_engine *e, bool expand, bool select, bool multi, const float *logits, const float *values, hipStream_t st);
 // azk_create's last step: every game empty, every tree a fresh root (azk_moves.hip)
 AZK_INTERNAL int32_t azk_init_games(azk_engine *e);
+// evaluation under a board symmetry (azk_sym.hip); both return at once while the option is off.  azk_sym_leaves: behind a selecting tree
+// launch - element and turned cells of every flagged slot.  azk_sym_restore: in front of an expanding one - the rows it is to expand from
+// (the engine's turned-back copy of `logits`, or `logits` itself)
+AZK_INTERNAL int32_t azk_sym_leaves(azk_engine *e, hipStream_t st);
+AZK_INTERNAL const float *azk_sym_restore(azk_engine *e, const float *logits, hipStream_t st);

@@ -1038,6 +1038,7 @@ extern "C" {
 int32_t azk_reset_games(azk_engine *e, int32_t first, int32_t count, void *stream) {
     if (!e || first < 0 || count < 0 || first + count > e->d.G) { if (e) e->err = "azk_reset_games: bad range"; return AZK_ERR_ARG; }
     if (count == 0) return AZK_OK;
+    e->in_search = false;                  // new games: whatever search was under way is over
     k_reset_games<<<(unsigned)(((size_t)count * e->d.rc_pad + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d, first, count, e->ru.chosen_node);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
@@ -1057,6 +1058,7 @@ int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream) {
     e->d.noise = noise_dev; e->d.noise_sel = nullptr;
     if (e->ru.mode == 2) { e->err = "azk_begin_search: top-up tree reuse needs the budget (azk_begin_search_budget)"; return AZK_ERR_STATE; }
     e->multi = false;
+    e->in_search = true;
     launch_begin_search(e, e->cfg.max_sims, -1, (hipStream_t)stream);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
@@ -1066,6 +1068,7 @@ int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream) {
 static int32_t begin_budget(azk_engine *e, const double *noise_dev, int32_t n_sims, int32_t max_sims_per_launch, int32_t move_index, void *stream) {
     e->d.noise = noise_dev; e->d.noise_sel = nullptr;
     e->multi = true;
+    e->in_search = true;
     if (e->budget_host[0] != n_sims || e->budget_host[1] != (e->d.K > 1 ? e->d.K : max_sims_per_launch)) {
         // the budget lives in device memory so that a captured step graph keeps working when it changes
         e->budget_host[0] = n_sims; e->budget_host[1] = max_sims_per_launch; e->budget_host[2] = 0;
@@ -1306,7 +1309,7 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
         else k_move_async<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru);
     }
     HIPCHK(e, hipGetLastError());
-    return AZK_OK;
+    return azk_sym_leaves(e, st);                                 // (eval symmetry: the leaves the tree launch selected, behind the movers)
 }
 
 int32_t azk_async_set_budget(azk_engine *e, int32_t n_sims, int32_t max_sims_per_launch, void *stream) {
@@ -1370,6 +1373,7 @@ int32_t azk_advance(azk_engine *e, const double *uniforms_dev, int32_t sample_un
                     int32_t *winner_dev, int32_t *done_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
     if (e->rs.v_resign != 0.0) { e->err = "azk_advance: resignation is set - its moves are made by azk_advance_resign (the game coin needs the move index)"; return AZK_ERR_STATE; }
+    e->in_search = false;
     if (e->forced_k != 0.0) {
         if (e->cp.n_fast) k_advance_fp<true, false><<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, e->forced(), uniforms_dev, sample_until_move, 0,
                                                                                                            chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
@@ -1387,6 +1391,7 @@ int32_t azk_advance_resign(azk_engine *e, const double *uniforms_dev, int32_t sa
                            int32_t *winner_dev, int32_t *done_dev, void *stream) {
     if (!e || move_index < 0) { if (e) e->err = "azk_advance_resign: bad argument"; return AZK_ERR_ARG; }
     if (e->rs.v_resign == 0.0) { e->err = "azk_advance_resign: no resignation is set (azk_set_resign)"; return AZK_ERR_STATE; }
+    e->in_search = false;
     if (e->forced_k != 0.0) {
         if (e->cp.n_fast) k_advance_fp<true, true><<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, e->forced(), uniforms_dev, sample_until_move, move_index,
                                                                                                           chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);

@@ -315,8 +315,12 @@ static void launch_k_tree_forced(const Dev &d, const float *logits, const float 
 //   DBG     chosen from d.ablate.
 //   FORCED  an engine with forced playouts set (e->forced_k != 0) launches the FORCED sibling of whichever product kernel selects; its
 //           expand-only launches and an ablation build's DBG kernels are the plain ones (no selection / debug only).
+//   symmetry  an engine with azk_set_eval_symmetry on expands from ITS copy of the rows, turned back into each position's frame by
+//           k_sym_logits in front of the launch (the kernel is the same, it is handed another pointer); the callers run azk_sym_leaves
+//           behind a launch that selects.
 int32_t azk_launch_tree(azk_engine *e, bool expand, bool select, bool multi, const float *logits, const float *values, hipStream_t st) {
     const Dev &d = e->d;
+    if (expand || (multi && select)) logits = azk_sym_restore(e, logits, st);
     const bool forced = e->forced_k != 0.0 && select && (multi || !d.ablate);
     if (forced && multi) launch_k_tree_forced<true, true>(d, logits, values, e->forced(), st);
     else if (forced && expand) launch_k_tree_forced<true, false>(d, logits, values, e->forced(), st);
@@ -357,6 +361,13 @@ int32_t azk_search_unfinished(azk_engine *e, int32_t *count_host, void *stream) 
     return AZK_OK;
 }
 
+// what k_gather is handed: the engine's view - under azk_set_eval_symmetry a host-side copy of it whose leaf_cells are the turned ones
+static Dev gather_view(const azk_engine *e) {
+    Dev d = e->d;
+    if (e->sym.mode) d.leaf_cells = e->sym.sym_cells;
+    return d;
+}
+
 static int32_t launch_tree(azk_engine *e, bool expand, bool select, const float *logits, const float *values,
                            void *leaf_boards, int32_t *n_leaf, hipStream_t st) {
     const Dev &d = e->d;
@@ -365,7 +376,9 @@ static int32_t launch_tree(azk_engine *e, bool expand, bool select, const float 
     const int32_t rc = azk_launch_tree(e, expand, select, e->multi && !d.ablate, logits, values, st);
     if (rc != AZK_OK) return rc;
     if (select) {
-        k_gather<<<d.G * d.K, AZK_WAVE, 0, st>>>(d, leaf_boards, n_leaf);
+        const int32_t rs = azk_sym_leaves(e, st);
+        if (rs != AZK_OK) return rs;
+        k_gather<<<d.G * d.K, AZK_WAVE, 0, st>>>(gather_view(e), leaf_boards, n_leaf);
         HIPCHK(e, hipGetLastError());
     }
     return AZK_OK;
@@ -391,12 +404,13 @@ int32_t azk_step_tree(azk_engine *e, const float *logits_dev, const float *value
     if (!e) return AZK_ERR_ARG;
     if (logits_dev && !values_dev) { e->err = "values_dev missing"; return AZK_ERR_ARG; }
     // null logits: a select-only launch (no gather, no evaluator outputs)
-    return azk_launch_tree(e, logits_dev != nullptr, true, e->multi && !e->d.ablate, logits_dev, logits_dev ? values_dev : nullptr, (hipStream_t)stream);
+    const int32_t rc = azk_launch_tree(e, logits_dev != nullptr, true, e->multi && !e->d.ablate, logits_dev, logits_dev ? values_dev : nullptr, (hipStream_t)stream);
+    return rc != AZK_OK ? rc : azk_sym_leaves(e, (hipStream_t)stream);
 }
 
 int32_t azk_step_gather(azk_engine *e, void *leaf_boards_dev, int32_t *n_leaf_dev, void *stream) {
     if (!e || !leaf_boards_dev || !n_leaf_dev) return AZK_ERR_ARG;
-    k_gather<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d, leaf_boards_dev, n_leaf_dev);
+    k_gather<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(gather_view(e), leaf_boards_dev, n_leaf_dev);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -404,7 +418,7 @@ int32_t azk_step_gather(azk_engine *e, void *leaf_boards_dev, int32_t *n_leaf_de
 int32_t azk_leaf_source_of(azk_engine *e, int32_t *n_leaf_dev, azk_leaf_source *out) {
     if (!e || !n_leaf_dev || !out) return AZK_ERR_ARG;
     const Dev &d = e->d;
-    out->leaf_flag = d.leaf_flag; out->leaf_cells = d.leaf_cells; out->to_move = d.K > 1 ? d.to_move_v : d.to_move; out->leaf_depth = d.leaf_depth;
+    out->leaf_flag = d.leaf_flag; out->leaf_cells = e->sym.mode ? e->sym.sym_cells : d.leaf_cells; out->to_move = d.K > 1 ? d.to_move_v : d.to_move; out->leaf_depth = d.leaf_depth;
     out->leaf_slot = d.leaf_slot; out->n_leaf = n_leaf_dev;
     out->n_games = d.G * d.K; out->rows = d.g.rows; out->cols = d.g.cols; out->rc = d.g.rc; out->rc_pad = d.rc_pad; out->planes = d.g.planes;
     out->flag_bytes = ((d.G * d.K + 511) / 512) * 512 + 512;

@@ -99,6 +99,43 @@ def check_forced_playouts(forced_playouts, evaluator=True, dirichlet=True, leave
     return k
 
 
+def eval_symmetry_elements(game, size=None):
+    """The D4 elements (the emission's numbering: rot0, lr, tb, rot90, lr(rot90), tb(rot90), rot180, rot270) a game's geometry admits
+    (include/azk.h azk_set_eval_symmetry): all eight on a square board with one action per cell, {0, 1, 2, 6} on a Gomoku board with
+    rows != cols, {0, 1} for Connect4 (gravity)."""
+    if game == "connect4":
+        return (0, 1)
+    rows, cols = (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (int(size or 0), int(size or 0))
+    return tuple(range(8)) if game == "tictactoe" or rows == cols else (0, 1, 2, 6)
+
+
+def check_eval_symmetry(eval_symmetry, game, size=None, evaluator=True, leaves_per_step=1, seed=0):
+    """eval_symmetry = True | ("fixed", s) -> the (mode, value) of Engine.set_eval_symmetry, or None for off (None or False).  OPT-IN evaluation
+    under a board symmetry (include/azk.h azk_set_eval_symmetry): the evaluator sees every leaf turned by a D4 element and
+    its logits are turned back.  True: the element is a hash of (seed, the leaf's position) - mode 1 with `seed`; ("fixed", s): element s for
+    every leaf.  Raises ValueError, before any engine exists, for what the engine refuses too - an element the geometry does not admit, virtual
+    loss - and for vanilla MCTS (evaluator None), which evaluates nothing."""
+    if eval_symmetry is None or eval_symmetry is False:
+        return None
+    if eval_symmetry is True:
+        mode, value = 1, int(seed) & ((1 << 64) - 1)
+    else:
+        try:
+            kind, value = eval_symmetry
+            if kind != "fixed" or int(value) != value:
+                raise ValueError
+            mode, value = 2, int(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"eval_symmetry must be True (keyed by the position) or ('fixed', element), not {eval_symmetry!r}")
+        if value not in eval_symmetry_elements(game, size):
+            raise ValueError(f"eval_symmetry: element {value!r} is not one of {eval_symmetry_elements(game, size)}, the elements this board's geometry admits")
+    if evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator)):
+        raise ValueError("eval_symmetry: vanilla MCTS (evaluator None) is refused - it evaluates no leaf")
+    if int(leaves_per_step) > 1:
+        raise ValueError("eval_symmetry does not combine with leaves_per_step > 1 (the virtual-loss schedule is not pinned under it)")
+    return mode, value
+
+
 def _refuse_vanilla_resign(resign, evaluator):
     if resign is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("resign: vanilla MCTS (evaluator None) is refused - its q is a rollout mean and no threshold is defined for it")
@@ -121,7 +158,8 @@ class SelfPlayResult:
 def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
                     alpha=0.03, noise_fn=None, uniform_fn=None, device=0, leaf_dtype="float32", engine=None,
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
-                    budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None):
+                    budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
+                    eval_symmetry=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -139,11 +177,14 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     resign = (v_resign, p_never[, min_ply]) (OPT-IN, check_resign): a game may end by resignation - SelfPlayResult.resigned, winner = the
     other side, z and the replay tuples as for any finished game.  forced_playouts = k (OPT-IN, check_forced_playouts): forced playouts at the
     root; SelfPlayResult.pis and the replay tuples carry the PRUNED pi of every full search, the moves are those of the raw visits.
+    eval_symmetry = True | ("fixed", s) (OPT-IN, check_eval_symmetry): every leaf is evaluated in an orientation keyed by (seed, its position),
+    or in the one given.
     """
     import torch
     cap = check_playout_cap(playout_cap, n_sims, leaves_per_step)
     rsg = check_resign(resign, leaves_per_step)
     fpk = check_forced_playouts(forced_playouts, evaluator, dirichlet, leaves_per_step)
+    sym = check_eval_symmetry(eval_symmetry, game, size, evaluator, leaves_per_step, seed)
     _refuse_vanilla_resign(rsg, evaluator)
     if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
@@ -156,6 +197,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         eng.set_resign(rsg[0], rsg[1], rsg[2], seed, first_global_game)
     if fpk is not None:
         eng.set_forced_playouts(fpk)
+    if sym is not None:
+        eng.set_eval_symmetry(*sym)
     # virtual-loss, top-up and capped engines are driven by the simulation budget
     budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
     assert eng.G == n_games
@@ -339,14 +382,18 @@ class SelfPlayRunner:
 
     forced_playouts = k (OPT-IN, check_forced_playouts; with any tree_reuse, playout_cap and resign): forced playouts at the root of every
     (full) search; the records' pi and the replay ring carry the pruned pi, the moves are those of the raw visits.
+
+    eval_symmetry = True | ("fixed", s) (OPT-IN, check_eval_symmetry; with everything above): every leaf is evaluated in an orientation keyed by
+    (seed, its position) - or in the one given - and its logits are turned back; set at construction, before any graph is captured.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
                  alpha=0.03, device=0, leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None,
                  use_graph=False, n_split=1, replay=None, cache_entries=0, cache_shared=False, budget_stepping=False, per_launch=8,
                  steps_per_graph=32,
-                 leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None):
+                 leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None):
         import torch
+        self.eval_symmetry = check_eval_symmetry(eval_symmetry, game, size, evaluator, leaves_per_step, seed)
         self.playout_cap = check_playout_cap(playout_cap, n_sims, leaves_per_step)
         self.resign = check_resign(resign, leaves_per_step)
         _refuse_vanilla_resign(self.resign, evaluator)
@@ -392,6 +439,8 @@ class SelfPlayRunner:
                 h.eng.set_resign(self.resign[0], self.resign[1], self.resign[2], seed, first_global_game + i * per)
             if self.forced_playouts is not None:
                 h.eng.set_forced_playouts(self.forced_playouts)
+            if self.eval_symmetry is not None:
+                h.eng.set_eval_symmetry(*self.eval_symmetry)      # (the key is the position: the same for every group)
 
     # ---- one move for every slot -------------------------------------------------------------------------
     def play_move(self):
@@ -644,13 +693,17 @@ class AsyncSelfPlayRunner:
     valid inside on_records) is 1 where the record's move conceded; resign_stats() counts the outcomes.
 
     forced_playouts = k (OPT-IN, check_forced_playouts; with any reroot, playout_cap and resign): the games of SelfPlayRunner(forced_playouts=k),
-    slot for slot; the record ring's pi and the replay ring carry the pruned pi."""
+    slot for slot; the record ring's pi and the replay ring carry the pruned pi.
+
+    eval_symmetry = True | ("fixed", s) (OPT-IN, check_eval_symmetry; with everything above): the games of SelfPlayRunner(eval_symmetry=...), slot
+    for slot - the element is a function of the position, so it does not matter which step evaluates a leaf."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
-                 playout_cap=None, resign=None, forced_playouts=None):
+                 playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None):
         import torch
+        self.eval_symmetry = check_eval_symmetry(eval_symmetry, game, size, evaluator, 1, seed)
         self.playout_cap = check_playout_cap(playout_cap, n_sims)
         self.resign = check_resign(resign)
         _refuse_vanilla_resign(self.resign, evaluator)
@@ -679,6 +732,8 @@ class AsyncSelfPlayRunner:
             e.set_resign(self.resign[0], self.resign[1], self.resign[2], seed, first_global_game)
         if self.forced_playouts is not None:
             e.set_forced_playouts(self.forced_playouts)
+        if self.eval_symmetry is not None:
+            e.set_eval_symmetry(*self.eval_symmetry)
         cap = (4 * n_games if record_capacity is None else record_capacity) if (on_records is not None or record_capacity) else 0
         self.stats, self.records = e.async_begin(n_sims, self.per_launch, SAMPLE_UNTIL[game], seed, first_global_game, alpha, dirichlet, recycle, cap,
                                                  young_launch_us=young_launch_us, reroot=bool(self.reroot))

@@ -54,7 +54,7 @@ def save_data_to_buffer(Game, buffer, data, full=None):
 
 
 def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed=None, batched=True, playout_cap=None, resign=None,
-                 forced_playouts=None):
+                 forced_playouts=None, eval_symmetry=None):
     """train.py:54-83: `iterations` self-play games of Game with `model` into `buffer`; returns [first, second, draw] counts.
     batched=False plays the games one after the other through Game().self_play and save_data_to_buffer exactly as the
     reference does (global np.random stream: a seeded caller gets the reference's buffer); the default plays them as one
@@ -62,7 +62,8 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     fast searches choose their move and are not stored, in a DeviceReplay and in a host buffer alike.  resign = (v_resign, p_never[, min_ply])
     (OPT-IN, batched only; selfplay.check_resign): a game may end by resignation; its winner is the side that did not concede, and both
     buffer kinds get the positions played with z by that winner.  forced_playouts = k (OPT-IN, batched only; selfplay.check_forced_playouts):
-    forced playouts at the root; both buffer kinds get the pruned pi of every stored position."""
+    forced playouts at the root; both buffer kinds get the pruned pi of every stored position.  eval_symmetry = True | ("fixed", s) (OPT-IN,
+    batched only; selfplay.check_eval_symmetry): every leaf is evaluated in an orientation keyed by (seed, its position), or in the one given."""
     from azk import DeviceReplay
     from selfplay import self_play_batch
     if not batched:
@@ -72,6 +73,8 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
             raise ValueError("collect_data: resign needs the batched engine (batched=True)")
         if forced_playouts is not None:
             raise ValueError("collect_data: forced_playouts needs the batched engine (batched=True)")
+        if eval_symmetry is not None and eval_symmetry is not False:
+            raise ValueError("collect_data: eval_symmetry needs the batched engine (batched=True)")
         results = [0, 0, 0]
         for _ in range(iterations):
             game = Game()
@@ -84,7 +87,8 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     on_device = isinstance(buffer, DeviceReplay)
     leaf_dtype = "bfloat16" if getattr(model, "dtype", None) is not None and str(model.dtype).endswith("bfloat16") else "float32"
     res = self_play_batch(Game.engine_name, model, iterations, mcts_iter, size=Game._size(), seed=seed, leaf_dtype=leaf_dtype,
-                          replay=buffer if on_device else None, playout_cap=playout_cap, resign=resign, forced_playouts=forced_playouts)
+                          replay=buffer if on_device else None, playout_cap=playout_cap, resign=resign, forced_playouts=forced_playouts,
+                          eval_symmetry=eval_symmetry)
     results = [0, 0, 0]
     for r in res:
         results[2 if r.winner == -1 else r.winner] += 1

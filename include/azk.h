@@ -292,6 +292,49 @@ int32_t azk_async_resign_flags(azk_engine *e, uint8_t *rec_resigned_dev);
 int32_t azk_set_forced_playouts(azk_engine *e, double k, void *stream);
 int32_t azk_root_policy_target(azk_engine *e, double *pi_dev, void *stream);
 
+/* ---- evaluation under a board symmetry (OPT-IN; off, the engine is what it was bit for bit).  The self-play ingredient of AlphaGo Zero, Leela and
+ * KataGo: the network sees each leaf in one of the board's orientations and its policy row is turned back, so that whatever orientation
+ * bias the network has is mixed over instead of going straight into pi.  The element is a pure function of (seed, the leaf's POSITION) - not
+ * a draw per evaluation - so the evaluator the search sees stays a function of the position,
+ *     f'(pos) = restore_s(f(transform_s(pos))),   s = h(seed, pos),
+ * and everything the engine holds bit for bit survives: the eval cache stays transparent (off, per game, shared), budget stepping, tree
+ * reuse and the asynchronous movers play the trees and games of lock-step stepping with the same option.
+ *   elements   the emission's numbering (azk_emit_finished; np.rot90 is counter-clockwise):
+ *                  0 rot0   1 lr(rot0)   2 tb(rot0)   3 rot90   4 lr(rot90)   5 tb(rot90)   6 rot180   7 rot270
+ *              src_s(j) = the source cell of output cell j = (i, c), row-major on an R x C board (N = R = C where the element transposes):
+ *                  0 (i, c)   1 (i, C-1-c)   2 (R-1-i, c)   3 (c, N-1-i)   4 (N-1-c, N-1-i)   5 (c, i)   6 (R-1-i, C-1-c)   7 (N-1-c, i)
+ *              dst_s = src_s^-1 = src_t with t = s except 3 <-> 7.
+ *   valid      square boards with one action per cell (TicTacToe, square Gomoku): all eight;  Gomoku with rows != cols: {0, 1, 2, 6};
+ *              Connect4: {0, 1} (gravity keeps the rows), with the action map column a -> cols - 1 - a under element 1.
+ *   transform  the board the evaluator is shown: b'[j] = b[src_s(j)] over the cells (cell codes; padding bytes as the leaf's row has them);
+ *              azk_step_gather's planes and the rows azk_leaf_source_of hands the fused evaluators are built from b'.  The side to move
+ *              (plane 2, the plane order) is that of the leaf.
+ *   restore    the evaluator's row l' is in the transformed frame; the tree expands from out[src_s(j)] = l'[j], i.e. out[a] = l'[dst_s(a)]
+ *              (Connect4, element 1: out[a] = l'[cols - 1 - a]).  Values pass through.  The caller's logits buffer is read only: the engine
+ *              expands from a float32 copy of its own.
+ *   modes      0 off;  1 position-keyed, seed_or_element = the 64-bit seed;  2 one fixed element for every leaf, seed_or_element = the
+ *              element (for tests, and to look at a network's orientation bias).
+ *   the key    mode 1.  fmix = murmur3's 32-bit finaliser (h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16),
+ *              seed_lo / seed_hi the halves of the seed, side = (to_move + leaf depth) & 1 the side to move at the leaf, code_i = cell i's
+ *              code (1 = player 0's stone, 2 = player 1's), all arithmetic modulo 2^32:
+ *                  h = fmix(seed_hi ^ side ^ 0x9E3779B9) + sum over occupied cells i of fmix(((i << 2) | code_i) ^ seed_lo)
+ *                  r = fmix(h);   element = valid[((r >> 16) * n_valid) >> 16]          (valid in ascending order)
+ *              (tests/eval_symmetry_restated.py restates it; over the 6 046 count-balanced 3 x 3 boards every element's share is within
+ *              2.62 sigma of 1 / n_valid for seeds 0, 1, 12345, 2^40 + 7 and n_valid 8, 4, 2.)
+ * azk_set_eval_symmetry: AZK_ERR_ARG for a mode outside 0..2, an element the geometry does not admit, leaves_per_step > 1 (the virtual-loss
+ * schedule is not pinned under it), and for a call between the begin of a search and the azk_advance(_resign), azk_reset_games or
+ * azk_set_positions that ends it (after azk_async_begin: always) - the engine stays usable.  Allocates its buffers at first use; with the
+ * option off no kernel of it is launched and nothing is allocated.  Two small kernels beside the step (k_sym_leaves behind every tree
+ * launch that selects, k_sym_logits in front of every one that expands); k_tree, k_gather and the evaluator kernels are unchanged.
+ * Combines with tree_reuse, playout cap, resignation, forced playouts, plain and budget stepping, the eval cache and the asynchronous movers.
+ * azk_get_leaf_symmetry: uint8 [G] into device memory, the element of each game's pending leaf (valid where the game has one that needs
+ * the evaluator; asynchronous copy on the stream).  azk_eval_symmetry_restore: the restore alone, into a caller buffer - for every game with
+ * such a pending leaf, row r = its evaluator row: out_dev[r][a] = logits_dev[r][dst_s(a)]; other rows of out_dev are not written.  Both
+ * answer AZK_ERR_STATE while the option is off. */
+int32_t azk_set_eval_symmetry(azk_engine *e, int32_t mode, uint64_t seed_or_element, void *stream);
+int32_t azk_get_leaf_symmetry(azk_engine *e, uint8_t *out_dev, void *stream);
+int32_t azk_eval_symmetry_restore(azk_engine *e, const float *logits_dev, float *out_dev, void *stream);
+
 /* One simulation per active game (ai/mcts.py:16-60), split around the evaluator:
  *   azk_step_select   - mcts.py:18-37: PUCT walk (node.py:42-47, utils.py:29-44), make_move along the
  *                       path, terminal test + immediate backup, get_valid_moves, canonical board.

@@ -384,7 +384,8 @@ def test_tail_chain_vs_torch_fp32_and_library_tail():
     """The five-launch tail chain (azk_nn_tail_gemm: per-head value projection, output projection + LN statistics, LN2 + MLP up +
     GELU, MLP down + residual + LN statistics, final LN + merged heads) against the same cls-row computation in plain fp32 PyTorch
     from the same pooled tokens z, and against the library-GEMM tail.  bf16 activations between the links (as in the library
-    tail): logits within 3e-2 absolute, value within 1e-2; a device-side live count leaves the rows below it bit-identical."""
+    tail): logits within 3e-2 absolute, value within 1e-2; a device-side live count leaves the rows below it bit-identical.
+    (Each link on its own, bit for bit and against float64: tests/test_gpu_tail_pinned.py.)"""
     import azk
     cfg = NetConfig(15, 15, 2, 225, 5, 512, 8, 1)
     net = PolicyValueNet(cfg, seed=2, device="cuda", dtype=torch.bfloat16, path="clsfold")

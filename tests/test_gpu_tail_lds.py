@@ -1,5 +1,6 @@
 """The LDS-staged wide links of the cls-row tail (csrc/azk_tail.hip, azk_nn_tail_gemm_lds) against the whole-K-in-registers
-form (azk_nn_tail_gemm) and against float64 references.  Reference computation: ai/nn.py:58-60 for the cls row."""
+form (azk_nn_tail_gemm) and against float64 references.  Reference computation: ai/nn.py:58-60 for the cls row.
+(Either form of every link against exact probes and format-derived float64 bounds: tests/test_gpu_tail_pinned.py.)"""
 import numpy as np
 import pytest
 import torch

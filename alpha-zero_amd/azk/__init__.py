@@ -37,6 +37,7 @@ SYMBOLS = [
     "azk_set_resign", "azk_advance_resign", "azk_get_resigned", "azk_get_resign_stats", "azk_async_resign_flags",
     "azk_set_forced_playouts", "azk_root_policy_target",
     "azk_set_eval_symmetry", "azk_get_leaf_symmetry", "azk_eval_symmetry_restore",
+    "azk_emit_elements", "azk_replay_gather",
 ]
 
 
@@ -115,11 +116,43 @@ def _ok(rc, name):
         raise AzkError(f"{name} failed ({rc})")
 
 
+def board_elements(game, size=None):
+    """The D4 elements (the emission's numbering: rot0, lr, tb, rot90, lr(rot90), tb(rot90), rot180, rot270) a game's geometry admits
+    (include/azk.h azk_set_eval_symmetry): all eight on a square board with one action per cell, {0, 1, 2, 6} on a Gomoku board with
+    rows != cols, {0, 1} for Connect4 (gravity)."""
+    if game == "connect4":
+        return (0, 1)
+    rows, cols = (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (int(size or 0), int(size or 0))
+    return tuple(range(8)) if game == "tictactoe" or rows == cols else (0, 1, 2, 6)
+
+
+def emit_mask(emit_symmetry, game, size=None):
+    """emit_symmetry -> azk_config.emit_elements: None = 0 (off: the reference's emission), "board" = every element the geometry admits,
+    "none" = the identity alone (mask 1: one tuple per ply), an iterable of elements = their bits.  Only the form is checked here (ValueError);
+    which masks a geometry admits is azk_create's decision (selfplay.check_emit_symmetry says the same before an engine exists)."""
+    if emit_symmetry is None:
+        return 0
+    if isinstance(emit_symmetry, str):
+        if emit_symmetry == "board":
+            return sum(1 << s for s in board_elements(game, size))
+        if emit_symmetry == "none":
+            return 1
+        raise ValueError(f"emit_symmetry must be None, 'board', 'none' or an iterable of elements, not {emit_symmetry!r}")
+    try:
+        items = list(emit_symmetry)
+        els = [int(s) for s in items]
+        if not els or any(e != s for e, s in zip(els, items)) or any(not 0 <= e < 31 for e in els):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"emit_symmetry must be None, 'board', 'none' or an iterable of elements, not {emit_symmetry!r}")
+    return sum(1 << s for s in set(els))
+
+
 class Engine:
     """G concurrent games + their search trees resident on one GPU (one engine per process / GPU)."""
 
     def __init__(self, game, n_games, max_sims, size=None, device=0, leaf_dtype="float32", arena_nodes=0, cache_entries=0,
-                 cache_shared=False, leaves_per_step=1, tree_reuse=0, eval_symmetry=None):
+                 cache_shared=False, leaves_per_step=1, tree_reuse=0, eval_symmetry=None, emit_symmetry=None):
         torch = _torch()
         self.torch = torch
         self.L = lib()
@@ -138,6 +171,9 @@ class Engine:
         # (only as many as bring the root back to n_sims visits; budget stepping only).  0 = a fresh root every move, the reference's search
         self.tree_reuse = int(tree_reuse)
         cfg.tree_reuse = self.tree_reuse
+        # OPT-IN (state, pi, z) emission under a mask of D4 elements, on every geometry (azk.h azk_config.emit_elements):
+        # None = the reference's emission, "board" = every element the geometry admits, "none" = one tuple per ply, or an iterable of elements
+        cfg.emit_elements = emit_mask(emit_symmetry, game, size)
         cfg.leaf_dtype = LEAF_BF16 if leaf_dtype in ("bfloat16", "bf16", torch.bfloat16) else LEAF_F32
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
@@ -150,6 +186,11 @@ class Engine:
         self._chk(self.L.azk_geometry(self.h, *[C.byref(v) for v in vals]))
         self.planes, self.rows, self.cols, self.action_dim, self.state_dim = [v.value for v in vals]
         self.G, self.max_sims = int(n_games), int(max_sims)
+        vals = [C.c_int32(), C.c_int32()]
+        self._chk(self.L.azk_emit_elements(self.h, C.byref(vals[0]), C.byref(vals[1])))
+        # the engine's emission mask (0 = off) and its tuples per ply from the third on (8 with the option off on a square board, 0 where
+        # emission is refused): a finished game of p plies fills p <= 2 ? p : 2 + emit_group * (p - 2) ring slots
+        self.emit_elements, self.emit_group = vals[0].value, vals[1].value
         tdt = torch.bfloat16 if cfg.leaf_dtype == LEAF_BF16 else torch.float32
         dev = self.device
         self.slots = self.G * self.K                # pending-leaf slots = capacity of one evaluator batch

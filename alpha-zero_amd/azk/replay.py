@@ -35,12 +35,59 @@ class DeviceReplay:
     def size(self):
         return min(int(self.cursor.item()), self.capacity)
 
-    def sample(self, batch_size):
+    def sample(self, batch_size, augment=None):
+        """augment (OPT-IN; None: three gathers, no augmentation): "board" - every element the ring's geometry admits - or an iterable of D4
+        elements (the emission's numbering, element 0 among them): each drawn row is turned by an element drawn for it from torch's generator,
+        all in one azk_replay_gather launch (include/azk.h; planes and pi turned together, Connect4's pi mirrored).  For a ring that stores
+        one image per position (Engine(emit_symmetry="none"))."""
         n = self.size()
         if batch_size > n:          # np.random.choice(len, batch_size, replace=False) raises the same way (replay_buffer.py:16)
             raise ValueError(f"cannot sample {batch_size} tuples without replacement from a ring holding {n}")
         idx = self.torch.randperm(n, device=self.states.device)[:batch_size]
-        return self.states[idx], self.pis[idx].float(), self.zs[idx][:, None]
+        if augment is None:
+            return self.states[idx], self.pis[idx].float(), self.zs[idx][:, None]
+        draws = self.torch.randint(-(1 << 31), 1 << 31, (batch_size,), dtype=self.torch.int32, device=self.states.device)
+        s, p, z = self.gather(idx, draws, self.augment_mask(augment))
+        return s, p, z[:, None]
+
+    def augment_mask(self, augment):
+        """The element mask of sample's `augment`; the ring's action kind follows from action_dim: rows * cols = one action per cell, cols =
+        column actions (Connect4), anything else admits the identity alone."""
+        from . import board_elements
+        _, _, rows, cols = self.states.shape
+        A = self.pis.shape[1]
+        if isinstance(augment, str):
+            if augment != "board":
+                raise ValueError(f"augment must be None, 'board' or an iterable of elements, not {augment!r}")
+            # the elements of a Gomoku board of this shape, of Connect4's columns, or the identity alone
+            els = board_elements("gomoku", (rows, cols)) if A == rows * cols else board_elements("connect4") if A == cols else (0,)
+            return sum(1 << s for s in els)
+        els = [int(s) for s in augment]
+        if any(not 0 <= s < 32 for s in els):
+            raise ValueError(f"augment: elements are 0..7, not {augment!r}")
+        return sum(1 << s for s in set(els))
+
+    def gather(self, idx, draws=None, mask=1):
+        """azk_replay_gather: rows idx (int64 CUDA tensor) of the ring as (states float32, pis float32, zs float32 [n]); row b turned by
+        element valid[((uint32(draws[b]) >> 16) * n_valid) >> 16] of `mask` (draws: int32 CUDA tensor, None: the identity)."""
+        from . import AzkError, _p, _stream, lib
+        torch = self.torch
+        n = int(idx.numel())
+        _, planes, rows, cols = self.states.shape
+        A = self.pis.shape[1]
+        idx = idx.to(torch.int64).contiguous()
+        assert idx.device == self.states.device and (draws is None or (draws.dtype == torch.int32 and draws.is_contiguous() and draws.numel() == n))
+        dev = self.states.device
+        s = torch.empty((n, planes, rows, cols), dtype=torch.float32, device=dev)
+        p = torch.empty((n, A), dtype=torch.float32, device=dev)
+        z = torch.empty(n, dtype=torch.float32, device=dev)
+        L = lib()
+        with torch.cuda.device(dev):
+            rc = L.azk_replay_gather(rows, cols, planes, A, int(mask), _p(self.states), _p(self.pis), _p(self.zs), _p(idx), _p(draws), n,
+                                     _p(s), _p(p), _p(z), _stream())
+        if rc != 0:
+            raise AzkError(f"azk_replay_gather failed ({rc}): {L.azk_last_error(None).decode()}")
+        return s, p, z
 
     # ---- interchange with the reference's host-side ReplayBuffer (replay_buffer.py) ------------------------------
     def add(self, state, policy_distribution, reward):

@@ -12,7 +12,7 @@ class Config(C.Structure):
     _fields_ = [("game", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("n_games", C.c_int32),
                 ("max_sims", C.c_int32), ("leaf_dtype", C.c_int32), ("device", C.c_int32),
                 ("arena_nodes", C.c_int32), ("cache_entries", C.c_int32), ("cache_shared", C.c_int32), ("leaves_per_step", C.c_int32),
-                ("tree_reuse", C.c_int32), ("reserved", C.c_int32 * 4)]
+                ("tree_reuse", C.c_int32), ("emit_elements", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class LeafSource(C.Structure):
@@ -115,6 +115,8 @@ def declare(L, symbols):
     L.azk_reset_counters.argtypes = [vp, vp]
     L.azk_clear_cache.argtypes = [vp, vp]
     L.azk_emit_finished.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
+    L.azk_emit_elements.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.azk_replay_gather.argtypes = [i32, i32, i32, i32, C.c_uint32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.azk_debug_stamps.argtypes = [vp, vp]
     L.azk_check_device_error.argtypes = [vp, vp]
     L.azk_gen_noise.argtypes = [vp, u64, i64, i32, f64, vp, vp, vp]

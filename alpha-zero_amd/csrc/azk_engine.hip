@@ -3,6 +3,7 @@
 // launch them live with their families: azk_tree.hip (search step), azk_vanilla.hip, azk_moves.hip (searches begin and end, moves,
 // replay emission, noise, the asynchronous movers), azk_rules.hip (stateless rules); azk_engine_int.h is what they share.
 #include "azk_engine_int.h"
+#include "azk_sym_map.h"      // the elements a geometry admits (emit_elements)
 
 thread_local std::string azk_create_error;
 
@@ -30,6 +31,10 @@ int32_t azk_create(const azk_config *cfg, azk_engine **out) {
     const int tree_reuse = cfg->tree_reuse;
     if (tree_reuse < 0 || tree_reuse > 2) return fail(AZK_ERR_ARG, "tree_reuse must be 0 (off), 1 (carry) or 2 (top-up)");
     if (tree_reuse != 0 && cfg->leaves_per_step > 1) return fail(AZK_ERR_ARG, "tree_reuse does not combine with leaves_per_step > 1 (virtual loss)");
+    if (cfg->emit_elements != 0) {
+        if (const char *bad = sym_mask_error((uint32_t)cfg->emit_elements, d.g.rows, d.g.cols, d.g.action_dim)) return fail(AZK_ERR_ARG, std::string("emit_elements: ") + bad);
+        e->emit.els = sym_pack((uint32_t)cfg->emit_elements, &e->emit.n);
+    }
     if (cfg->cache_entries < 0 || (cfg->cache_entries & (cfg->cache_entries - 1)) != 0) return fail(AZK_ERR_ARG, "cache_entries must be 0 or a power of two");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
@@ -84,7 +89,7 @@ int32_t azk_create(const azk_config *cfg, azk_engine **out) {
             DA(d.hit_logits, GV * g.action_dim); DA(d.hit_value, GV);
         }
     }
-    if (g.rows == g.cols && g.action_dim == g.rc) { DA(d.traj_action, G * g.state_dim); DA(d.traj_pi, G * g.state_dim * g.action_dim); } DA(e->counter_sums, CNT_N); DA(e->n_leaf_scratch, 1);
+    if ((g.rows == g.cols && g.action_dim == g.rc) || e->emit.n) { DA(d.traj_action, G * g.state_dim); DA(d.traj_pi, G * g.state_dim * g.action_dim); } DA(e->counter_sums, CNT_N); DA(e->n_leaf_scratch, 1);
     if (s == hipSuccess) { uint8_t *ls = nullptr; s = dalloc(e, &ls, GV * g.planes * g.rc * 4); e->leaf_scratch = ls; }
 #undef DA
     if (s != hipSuccess) return fail(AZK_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(s));

@@ -73,7 +73,7 @@ struct Dev {               // device view of the engine, passed to kernels by va
     unsigned *cache_stamp;                 // shared: [1] stamp of the current launch (bumped by the leaf hand-off kernels)
     unsigned long long *leaf_key;          // shared: [G][key_words] key of the pending (missed) leaf
     float *hit_logits, *hit_value;         // shared: [G][A], [G] private copy of a hit
-    int16_t *traj_action;  // [G][state_dim] cell played at each ply of the current game (square boards only, else null)
+    int16_t *traj_action;  // [G][state_dim] cell played at each ply of the current game (square boards with one action per cell and emit_elements engines, else null)
     double *traj_pi;       // [G][state_dim][A] visit distribution recorded at each ply
     long long *emit_base;  // [G] first tuple index (64-bit: the stream never wraps) of a game being emitted, -1 = not emitting
     int *sims_done;        // [G] simulations of the current search already run (budget stepping, azk_begin_search_budget)
@@ -150,6 +150,15 @@ struct SymDev {
     uint8_t *leaf_sym;         // [G] element of the slot's pending leaf (written for flagged slots by k_sym_leaves)
     uint8_t *sym_cells;        // [G][rc_pad] the pending leaf's cells in that orientation: what k_gather and the fused evaluators read
     float *sym_logits;         // [G][A] the evaluator's rows turned back into the position's frame: what k_tree expands from
+};
+
+// (state, pi, z) emission under a mask of D4 elements (azk_config.emit_elements, opt-in; n == 0 otherwise): ply i >= 2 of
+// a finished game is emitted once per element of the mask instead of under the reference's eight.  Its own argument of the kernels that exist
+// only for it (k_emit_*_sym in azk_moves.hip): every other argument block - and every kernel an engine without the option launches - stays as
+// it was
+struct EmitSym {
+    uint32_t els;              // the mask's elements, four bits each, ascending, lowest first
+    int n;                     // how many; 0 = off
 };
 
 struct LdsView {
@@ -307,6 +316,7 @@ struct azk_engine {
     bool async_on = false;
     int async_recycle = 1;
     SymDev sym = {};                     // evaluation under a board symmetry (azk_set_eval_symmetry); sym.mode == 0: off, nothing allocated
+    EmitSym emit = {};                   // emission under a mask of elements (cfg.emit_elements); emit.n == 0: off, the reference's rule
     bool in_search = false;              // between a search's begin and the move (or new position) that ends it: azk_set_eval_symmetry refuses
 };
 

@@ -3,6 +3,7 @@
 // noise rows, counters, and the asynchronous movers that do all of it per game inside the step; the kernels and the C ABI calls
 // that launch them (include/azk.h).  Built with -ffp-contract=off like every engine file.
 #include "azk_engine_int.h"
+#include "azk_sym_map.h"      // sym_source: emission under a mask of elements
 
 namespace {
 
@@ -495,17 +496,21 @@ __global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *unifo
 // ------------------------------------------------------------------------------------------------
 // CAP (playout-cap engines, the k_*_cap kernels): only the plies of FULL searches are emitted - ply i's group (1 tuple for i < 2, else 8) sits at
 // the sum of the groups of the full plies before it; the board before ply i is rebuilt from every earlier ply, fast ones included.
-template <bool CAP>
-__device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full, unsigned long long *cursor, long long *game_base_out) {
+// SYM (engines created with emit_elements, the k_emit_*_sym kernels): the group of a ply from the third on is one tuple per
+// element of the mask (es.n of them, es.els in ascending order) instead of the reference's eight, on any R x C board and action kind.
+template <bool CAP, bool SYM = false>
+__device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full, unsigned long long *cursor, long long *game_base_out,
+                                                const EmitSym &es = EmitSym{}) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.G) return;
     long long base = -1;                                          // the stream index stays 64-bit end to end (2^31 tuples = hours of self-play)
     if (d.done[g] == 1) {
         const int n = d.move_count[g];
-        int tuples = n <= 2 ? n : 2 + 8 * (n - 2);
+        const int grp = SYM ? es.n : 8;
+        int tuples = n <= 2 ? n : 2 + grp * (n - 2);
         if (CAP) {
             tuples = 0;
-            for (int i = 0; i < n; i++) if (traj_full[(size_t)g * d.g.state_dim + i]) tuples += i < 2 ? 1 : 8;
+            for (int i = 0; i < n; i++) if (traj_full[(size_t)g * d.g.state_dim + i]) tuples += i < 2 ? 1 : grp;
         }
         base = (long long)atomicAdd(cursor, (unsigned long long)tuples);
     }
@@ -531,9 +536,9 @@ __device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
     return si * N + sj;
 }
 
-template <bool LIST, bool CAP>
+template <bool LIST, bool CAP, bool SYM = false>
 __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full, float *states, double *pis, float *zs, long long capacity,
-                                                 const unsigned long long *cursor, const int *list, const int *n_list) {
+                                                 const unsigned long long *cursor, const int *list, const int *n_list, const EmitSym &es = EmitSym{}) {
     const int S = d.g.state_dim, A = d.g.action_dim, rc = d.g.rc, F = d.g.planes, N = d.g.rows;
     const int lane = azk_lane();
     const int nb = LIST ? *n_list * S : (int)gridDim.x;
@@ -554,11 +559,12 @@ __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full
     const int side = i & 1, winner = d.winner[g];
     const float z = winner == -1 ? 0.0f : (side == winner ? 1.0f : -1.0f);
     const double *pi = d.traj_pi + ((size_t)g * S + i) * A;
-    const int ntr = i < 2 ? 1 : 8;
-    long long first = base + (i < 2 ? i : 2 + 8 * (i - 2));
+    const int grp = SYM ? es.n : 8;
+    const int ntr = i < 2 ? 1 : grp;
+    long long first = base + (i < 2 ? i : 2 + grp * (i - 2));
     if (CAP) {                                                    // tuples of the full plies before this one
         int before = 0;
-        for (int j = lane; j < i; j += AZK_WAVE) if (traj_full[(size_t)g * S + j]) before += j < 2 ? 1 : 8;
+        for (int j = lane; j < i; j += AZK_WAVE) if (traj_full[(size_t)g * S + j]) before += j < 2 ? 1 : grp;
         first = base + wave_sum_i32(before);
     }
     const long long stream_end = (long long)*cursor;              // after k_emit_alloc: one past the newest tuple of this call
@@ -567,14 +573,17 @@ __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full
         const long long slot = (first + t) % capacity;
         float *so = states + (size_t)slot * F * rc;
         double *po = pis + (size_t)slot * A;
+        const int el = SYM ? (int)((es.els >> (4 * t)) & 15u) : t;   // (plies 0 and 1: t = 0 and the mask's first element is the identity)
         for (int e = lane; e < rc; e += AZK_WAVE) {
-            const int src = d4_source(t, e / N, e % N, N);
+            const int src = SYM ? sym_source(el, e, d.g.rows, d.g.cols, d.g.inv_cols) : d4_source(t, e / N, e % N, N);
             const uint8_t code = cells[src];
             so[e] = (float)((code >> side) & 1);                    // canonical: own stones first (gomoku.py:34-40)
             so[rc + e] = (float)((code >> (side ^ 1)) & 1);
             if (F == 3) so[2 * rc + e] = (float)side;
-            po[e] = pi[src];                                        // square boards: action index == cell index
+            if (!SYM || A == rc) po[e] = pi[src];                   // one action per cell: action index == cell index
         }
+        if (SYM && A != rc)                                         // Connect4's columns, a -> cols - 1 - a under lr: the cells' map on a board of one row
+            for (int a = lane; a < A; a += AZK_WAVE) po[a] = pi[sym_source(el, a, 1, A, 0u)];
         if (lane == 0) zs[slot] = z;
     }
     }
@@ -584,6 +593,18 @@ template <bool LIST>     // LIST: the grid walks a list of finished games (async
 __global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(Dev d, float *states, double *pis, float *zs, long long capacity,
                                                             const unsigned long long *cursor, const int *list, const int *n_list) {
     emit_tuples_body<LIST, false>(d, nullptr, states, pis, zs, capacity, cursor, list, n_list);
+}
+
+// the emitters of an engine created with emit_elements, launched IN PLACE of k_emit_alloc(_cap) and k_emit_tuples(_cap) (one template over the cap)
+template <bool CAP>
+__global__ void k_emit_alloc_sym(Dev d, CapDev cp, EmitSym es, unsigned long long *cursor, long long *game_base_out) {
+    emit_alloc_body<CAP, true>(d, cp.traj_full, cursor, game_base_out, es);
+}
+
+template <bool LIST, bool CAP>
+__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples_sym(Dev d, CapDev cp, EmitSym es, float *states, double *pis, float *zs, long long capacity,
+                                                                const unsigned long long *cursor, const int *list, const int *n_list) {
+    emit_tuples_body<LIST, CAP, true>(d, cp.traj_full, states, pis, zs, capacity, cursor, list, n_list, es);
 }
 
 __global__ void k_emit_mark(Dev d) {
@@ -1021,7 +1042,18 @@ static void launch_emit(azk_engine *e, float *states, double *pis, float *zs, lo
     const unsigned per_game = (unsigned)((d.G + 255) / 256), lds = (unsigned)up16(d.g.rc);
     const int plies = d.G * d.g.state_dim;
     const unsigned blocks = (unsigned)(list && plies > 16384 ? 16384 : plies);
-    if (e->cp.n_fast) {
+    if (e->emit.n) {                                              // emit_elements: the mask's elements on any geometry
+        const EmitSym es = e->emit;
+        if (e->cp.n_fast) {
+            k_emit_alloc_sym<true><<<per_game, 256, 0, st>>>(d, e->cp, es, cursor, game_base);
+            if (list) k_emit_tuples_sym<true, true><<<blocks, AZK_WAVE, lds, st>>>(d, e->cp, es, states, pis, zs, capacity, cursor, list, n_list);
+            else k_emit_tuples_sym<false, true><<<blocks, AZK_WAVE, lds, st>>>(d, e->cp, es, states, pis, zs, capacity, cursor, nullptr, nullptr);
+        } else {
+            k_emit_alloc_sym<false><<<per_game, 256, 0, st>>>(d, CapDev{}, es, cursor, game_base);
+            if (list) k_emit_tuples_sym<true, false><<<blocks, AZK_WAVE, lds, st>>>(d, CapDev{}, es, states, pis, zs, capacity, cursor, list, n_list);
+            else k_emit_tuples_sym<false, false><<<blocks, AZK_WAVE, lds, st>>>(d, CapDev{}, es, states, pis, zs, capacity, cursor, nullptr, nullptr);
+        }
+    } else if (e->cp.n_fast) {
         k_emit_alloc_cap<<<per_game, 256, 0, st>>>(d, e->cp, cursor, game_base);
         if (list) k_emit_tuples_cap<true><<<blocks, AZK_WAVE, lds, st>>>(d, e->cp, states, pis, zs, capacity, cursor, list, n_list);
         else k_emit_tuples_cap<false><<<blocks, AZK_WAVE, lds, st>>>(d, e->cp, states, pis, zs, capacity, cursor, nullptr, nullptr);
@@ -1349,9 +1381,16 @@ int32_t azk_emit_finished(azk_engine *e, float *states_dev, double *pis_dev, flo
                           int64_t *cursor_dev, int64_t *game_base_dev, void *stream) {
     if (!e || !states_dev || !pis_dev || !zs_dev || !cursor_dev || capacity < 1) return AZK_ERR_ARG;
     const Dev &d = e->d;
-    if (!d.traj_pi) { e->err = "azk_emit_finished: (state, pi, z) emission needs a square board with one action per cell"; return AZK_ERR_ARG; }
+    if (!d.traj_pi) { e->err = "azk_emit_finished: (state, pi, z) emission needs a square board with one action per cell (or an engine created with emit_elements)"; return AZK_ERR_ARG; }
     launch_emit(e, states_dev, pis_dev, zs_dev, (long long)capacity, (unsigned long long *)cursor_dev, (long long *)game_base_dev, nullptr, nullptr, (hipStream_t)stream);
     HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_emit_elements(const azk_engine *e, int32_t *mask_out, int32_t *group_out) {
+    if (!e) return AZK_ERR_ARG;
+    if (mask_out) *mask_out = e->cfg.emit_elements;
+    if (group_out) *group_out = e->emit.n ? e->emit.n : (e->d.traj_pi ? 8 : 0);
     return AZK_OK;
 }
 

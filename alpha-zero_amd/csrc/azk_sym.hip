@@ -3,6 +3,7 @@
 // turns the evaluator's rows back.  Both are one wave per pending-leaf slot and sit beside the search step: k_tree, k_gather and every
 // evaluator kernel are the ones of an engine without the option - they are handed other pointers.
 #include "azk_engine_int.h"
+#include "azk_sym_map.h"      // sym_source, the elements a geometry admits
 
 namespace {
 
@@ -17,17 +18,6 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {   // wave_sum_i32
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
-}
-
-// source cell (row-major) of output cell j under element s of the emission's order (d4_source in azk_moves.hip), select-based: an element is
-// "transpose?" then "flip the source row?" and "flip the source column?".  Elements that transpose exist on square boards only.
-__device__ __forceinline__ int sym_source(int s, int j, int R, int C, unsigned inv_cols) {
-    const int i = (int)(((unsigned)j * inv_cols) >> 16), c = j - i * C;
-    const bool t = (0xB8u >> s) & 1u, fi = (0xD4u >> s) & 1u, fj = (0x5Au >> s) & 1u;
-    int si = t ? c : i, sj = t ? i : c;
-    si = fi ? R - 1 - si : si;
-    sj = fj ? C - 1 - sj : sj;
-    return si * C + sj;
 }
 
 __device__ __forceinline__ int sym_inverse(int s) { return (int)((0x36547210u >> (4 * s)) & 7u); }   // rot90 <-> rot270, the others their own
@@ -131,10 +121,8 @@ int32_t azk_set_eval_symmetry(azk_engine *e, int32_t mode, uint64_t seed_or_elem
     if (d.K > 1) { e->err = "azk_set_eval_symmetry: does not combine with leaves_per_step > 1 (the virtual-loss schedule is not pinned under it)"; return AZK_ERR_ARG; }
     SymDev &s = e->sym;
     const GameDesc &g = d.g;
-    uint32_t valid; int n_valid;
-    if (g.action_dim != g.rc) { valid = 0x10u; n_valid = 2; }                       // Connect4: gravity keeps the rows, {rot0, lr}
-    else if (g.rows != g.cols) { valid = 0x6210u; n_valid = 4; }                   // the elements that keep the shape
-    else { valid = 0x76543210u; n_valid = 8; }
+    int n_valid;
+    const uint32_t valid = sym_pack(sym_valid_mask(g.rows, g.cols, g.action_dim), &n_valid);    // Connect4 {rot0, lr}; rows != cols: the elements that keep the shape
     if (mode == 2) {
         bool ok = false;
         for (int i = 0; i < n_valid; i++) ok = ok || seed_or_element == (uint64_t)((valid >> (4 * i)) & 15u);

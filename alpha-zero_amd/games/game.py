@@ -30,7 +30,9 @@ class Game:
     # ---- helpers ---------------------------------------------------------------------------------
     @classmethod
     def _size(cls):
-        return cls.rows if cls.engine_name == "gomoku" else None
+        if cls.engine_name != "gomoku":
+            return None
+        return cls.rows if cls.rows == cls.cols else (cls.rows, cls.cols)    # a subclass with rows != cols: (rows, cols), as Engine takes it
 
     @classmethod
     def _dev(cls, board):

@@ -10,7 +10,7 @@ self_play_batch returns, per game, the tuple the reference's Gomoku.self_play re
 """
 import numpy as np
 
-from azk import Engine
+from azk import Engine, board_elements, emit_mask
 
 # gomoku.py:144 samples while move_count < 8; tictactoe.py:117 / connect4.py:135 sample every move
 SAMPLE_UNTIL = {"gomoku": 8, "tictactoe": 1 << 30, "connect4": 1 << 30}
@@ -103,10 +103,7 @@ def eval_symmetry_elements(game, size=None):
     """The D4 elements (the emission's numbering: rot0, lr, tb, rot90, lr(rot90), tb(rot90), rot180, rot270) a game's geometry admits
     (include/azk.h azk_set_eval_symmetry): all eight on a square board with one action per cell, {0, 1, 2, 6} on a Gomoku board with
     rows != cols, {0, 1} for Connect4 (gravity)."""
-    if game == "connect4":
-        return (0, 1)
-    rows, cols = (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (int(size or 0), int(size or 0))
-    return tuple(range(8)) if game == "tictactoe" or rows == cols else (0, 1, 2, 6)
+    return board_elements(game, size)
 
 
 def check_eval_symmetry(eval_symmetry, game, size=None, evaluator=True, leaves_per_step=1, seed=0):
@@ -136,6 +133,30 @@ def check_eval_symmetry(eval_symmetry, game, size=None, evaluator=True, leaves_p
     return mode, value
 
 
+def check_emit_symmetry(emit_symmetry, game, size=None):
+    """emit_symmetry = None | "board" | "none" | an iterable of elements -> the engine's azk_config.emit_elements mask (0 for None: off).  OPT-IN
+    (state, pi, z) emission under a mask of D4 elements, on every geometry (include/azk.h azk_config.emit_elements): plies 0
+    and 1 of a finished game are stored once, every later ply once per element of the mask - "board": every element the geometry admits, on a
+    square board the reference's eight; "none": the identity alone.  Raises ValueError, before any engine exists, for what azk_create refuses
+    too: an element above 7, a mask without element 0, an element the geometry does not admit (eval_symmetry_elements)."""
+    mask = emit_mask(emit_symmetry, game, size)
+    if mask == 0:
+        return 0
+    if mask & ~0xFF:
+        raise ValueError(f"emit_symmetry: elements are 0..7, not {emit_symmetry!r}")
+    if not mask & 1:
+        raise ValueError(f"emit_symmetry: the mask needs element 0 (the identity), not {emit_symmetry!r}")
+    admitted = eval_symmetry_elements(game, size)
+    if any((mask >> s) & 1 and s not in admitted for s in range(8)):
+        raise ValueError(f"emit_symmetry: {emit_symmetry!r} holds an element outside {admitted}, the elements this board's geometry admits")
+    return mask
+
+
+def mask_elements(mask):
+    """The elements of an emission mask, ascending."""
+    return tuple(s for s in range(8) if (mask >> s) & 1)
+
+
 def _refuse_vanilla_resign(resign, evaluator):
     if resign is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("resign: vanilla MCTS (evaluator None) is refused - its q is a rollout mean and no threshold is defined for it")
@@ -159,7 +180,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                     alpha=0.03, noise_fn=None, uniform_fn=None, device=0, leaf_dtype="float32", engine=None,
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
                     budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
-                    eval_symmetry=None):
+                    eval_symmetry=None, emit_symmetry=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -178,9 +199,14 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     other side, z and the replay tuples as for any finished game.  forced_playouts = k (OPT-IN, check_forced_playouts): forced playouts at the
     root; SelfPlayResult.pis and the replay tuples carry the PRUNED pi of every full search, the moves are those of the raw visits.
     eval_symmetry = True | ("fixed", s) (OPT-IN, check_eval_symmetry): every leaf is evaluated in an orientation keyed by (seed, its position),
-    or in the one given.
+    or in the one given.  emit_symmetry = "board" | "none" | elements (OPT-IN, check_emit_symmetry): the replay ring gets every ply from the
+    third on once per element of the mask, on every geometry (Connect4 and non-square Gomoku included); an engine handed in must have
+    been created with the same mask (ValueError).
     """
     import torch
+    emit = check_emit_symmetry(emit_symmetry, game, size)
+    if engine is not None and engine.emit_elements != emit:
+        raise ValueError(f"self_play_batch: emit_symmetry={emit_symmetry!r} is mask {emit:#x}, the engine handed in was created with {engine.emit_elements:#x}")
     cap = check_playout_cap(playout_cap, n_sims, leaves_per_step)
     rsg = check_resign(resign, leaves_per_step)
     fpk = check_forced_playouts(forced_playouts, evaluator, dirichlet, leaves_per_step)
@@ -190,7 +216,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
     max_sims = max(n_sims) if isinstance(n_sims, (tuple, list)) else n_sims
     eng = engine or Engine(game, n_games, max_sims, size=size, device=device, leaf_dtype=leaf_dtype, cache_entries=cache_entries,
-                           cache_shared=cache_shared, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse)
+                           cache_shared=cache_shared, leaves_per_step=leaves_per_step, tree_reuse=tree_reuse,
+                           emit_symmetry=mask_elements(emit) if emit else None)
     if cap is not None:
         eng.set_playout_cap(cap[0], cap[1], seed, first_global_game)
     if rsg is not None:
@@ -385,14 +412,18 @@ class SelfPlayRunner:
 
     eval_symmetry = True | ("fixed", s) (OPT-IN, check_eval_symmetry; with everything above): every leaf is evaluated in an orientation keyed by
     (seed, its position) - or in the one given - and its logits are turned back; set at construction, before any graph is captured.
+
+    emit_symmetry = "board" | "none" | elements (OPT-IN, check_emit_symmetry; with everything above): the replay ring gets every ply from the
+    third on once per element of the mask, on every geometry; the engines are created with it.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
                  alpha=0.03, device=0, leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None,
                  use_graph=False, n_split=1, replay=None, cache_entries=0, cache_shared=False, budget_stepping=False, per_launch=8,
                  steps_per_graph=32,
-                 leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None):
+                 leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None):
         import torch
+        self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
         self.eval_symmetry = check_eval_symmetry(eval_symmetry, game, size, evaluator, leaves_per_step, seed)
         self.playout_cap = check_playout_cap(playout_cap, n_sims, leaves_per_step)
         self.resign = check_resign(resign, leaves_per_step)
@@ -419,7 +450,8 @@ class SelfPlayRunner:
         per = n_games // self.n_split
         self.halves = [_Half(torch, Engine(game, per, n_sims, size=size, device=device, leaf_dtype=leaf_dtype,
                                            cache_entries=cache_entries, cache_shared=cache_shared, leaves_per_step=self.leaves_per_step,
-                                           tree_reuse=self.tree_reuse), dirichlet)
+                                           tree_reuse=self.tree_reuse, emit_symmetry=mask_elements(self.emit_elements) if self.emit_elements else None),
+                             dirichlet)
                        for _ in range(self.n_split)]
         self.eng = self.halves[0].eng
         self.G = n_games
@@ -696,13 +728,17 @@ class AsyncSelfPlayRunner:
     slot for slot; the record ring's pi and the replay ring carry the pruned pi.
 
     eval_symmetry = True | ("fixed", s) (OPT-IN, check_eval_symmetry; with everything above): the games of SelfPlayRunner(eval_symmetry=...), slot
-    for slot - the element is a function of the position, so it does not matter which step evaluates a leaf."""
+    for slot - the element is a function of the position, so it does not matter which step evaluates a leaf.
+
+    emit_symmetry = "board" | "none" | elements (OPT-IN, check_emit_symmetry; with everything above): the drain emits every ply from the third
+    on once per element of the mask, on every geometry - the tuples of SelfPlayRunner(emit_symmetry=...)."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
-                 playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None):
+                 playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None):
         import torch
+        self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
         self.eval_symmetry = check_eval_symmetry(eval_symmetry, game, size, evaluator, 1, seed)
         self.playout_cap = check_playout_cap(playout_cap, n_sims)
         self.resign = check_resign(resign)
@@ -717,7 +753,7 @@ class AsyncSelfPlayRunner:
         self.reroot = int(reroot)
         self.torch, self.replay, self.evaluator = torch, replay, evaluator
         self.eng = Engine(game, n_games, n_sims, size=size, device=device, leaf_dtype=leaf_dtype, cache_entries=cache_entries, cache_shared=cache_shared,
-                          tree_reuse=self.reroot, arena_nodes=arena_nodes)
+                          tree_reuse=self.reroot, arena_nodes=arena_nodes, emit_symmetry=mask_elements(self.emit_elements) if self.emit_elements else None)
         e = self.eng
         self.G, self._n_sims, self.n_split, self.leaves_per_step = n_games, n_sims, 1, 1
         self.per_launch, self.steps_per_graph, self.use_graph = int(per_launch), max(1, int(steps_per_graph)), use_graph

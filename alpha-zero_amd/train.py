@@ -1,9 +1,9 @@
 """train.py of the reference (train.py:8-123) with its names and signatures, on the batched engine.
 
     collect_data(Game, model, buffer, iterations, mcts_iter, display=False)   train.py:54-83
-    save_data_to_buffer(Game, buffer, data)                                   train.py:30-49
+    save_data_to_buffer(Game, buffer, data, full=None, elements=None)         train.py:30-49
     rotate_data / flip_data                                                   train.py:8-27
-    train(model, batch_size, buffer, train_iterations, lr, device)            train.py:85-123
+    train(model, batch_size, buffer, train_iterations, lr, device, augment=None)   train.py:85-123
 
 `buffer` is anything with the reference's ReplayBuffer interface (add / sample / size) - the reference's own class or
 azk.DeviceReplay.  With a DeviceReplay, collect_data plays all `iterations` games as ONE lock-step batch and the engine
@@ -29,10 +29,38 @@ def flip_data(board, policy, mode="lr"):
     return np.flip(board, axis=1), np.flipud(p).reshape(-1)
 
 
-def save_data_to_buffer(Game, buffer, data, full=None):
+def element_source_map(s, rows, cols):
+    """int array [rows * cols]: the image of a board under D4 element s of the emission's order (0 rot0, 1 lr, 2 tb, 3 rot90, 4 lr(rot90),
+    5 tb(rot90), 6 rot180, 7 rot270; np.rot90 is counter-clockwise) is flat[element_source_map] - numpy's own flips applied to the indices."""
+    idx = np.arange(rows * cols).reshape(rows, cols)
+    r90 = (lambda a: np.rot90(a, k=1))
+    img = [lambda a: a, np.fliplr, np.flipud, r90, lambda a: np.fliplr(r90(a)), lambda a: np.flipud(r90(a)),
+           lambda a: np.rot90(a, k=2), lambda a: np.rot90(a, k=3)][s](idx)
+    if img.shape != (rows, cols):
+        raise ValueError(f"element {s} transposes: a {rows} x {cols} board does not admit it")
+    return np.ascontiguousarray(img).reshape(-1)
+
+
+def element_image(board, policy, s):
+    """(board, policy) under element s: every plane turned; the policy turned with the cells where there is one action per cell, mirrored
+    under element 1 where there is one per column (Connect4: only elements 0 and 1 keep gravity)."""
+    planes, rows, cols = board.shape
+    src = element_source_map(s, rows, cols)
+    b = np.ascontiguousarray(board.reshape(planes, rows * cols)[:, src].reshape(planes, rows, cols))
+    policy = np.asarray(policy)
+    if len(policy) == rows * cols:
+        return b, policy[src].copy()
+    if s not in (0, 1):
+        raise ValueError(f"element {s}: a policy of {len(policy)} column actions admits elements 0 and 1 only")
+    return b, (policy[::-1].copy() if s == 1 else policy.copy())
+
+
+def save_data_to_buffer(Game, buffer, data, full=None, elements=None):
     """train.py:30-49: z = +reward for the winner's positions, -reward for the loser's; canonical boards; positions 0 and 1
     once, every later position with its 8 dihedral images in the reference's order.  full (playout cap, SelfPlayResult.full): one flag
-    per position; the positions of fast searches are left out, the others keep the group they would have had."""
+    per position; the positions of fast searches are left out, the others keep the group they would have had.  elements (OPT-IN; None:
+    the reference's code path): a tuple of D4 elements, ascending - every later position once per element instead (element_image), on any
+    board and for Connect4's column actions: what an engine created with that emit_symmetry puts into a DeviceReplay."""
     boards, actions, policies, qs, winner, reward = data
     current = 0
     for i in range(len(boards)):
@@ -44,6 +72,11 @@ def save_data_to_buffer(Game, buffer, data, full=None):
         if i < 2:
             buffer.add(canon, policies[i], target)
             continue
+        if elements is not None:
+            for s in elements:
+                b, p = element_image(np.asarray(canon), policies[i], s)
+                buffer.add(b, p, target)
+            continue
         for r in range(4):
             b, p = rotate_data(canon, policies[i], k=r)
             buffer.add(b, p, target)
@@ -54,7 +87,7 @@ def save_data_to_buffer(Game, buffer, data, full=None):
 
 
 def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed=None, batched=True, playout_cap=None, resign=None,
-                 forced_playouts=None, eval_symmetry=None):
+                 forced_playouts=None, eval_symmetry=None, emit_symmetry=None):
     """train.py:54-83: `iterations` self-play games of Game with `model` into `buffer`; returns [first, second, draw] counts.
     batched=False plays the games one after the other through Game().self_play and save_data_to_buffer exactly as the
     reference does (global np.random stream: a seeded caller gets the reference's buffer); the default plays them as one
@@ -63,10 +96,14 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     (OPT-IN, batched only; selfplay.check_resign): a game may end by resignation; its winner is the side that did not concede, and both
     buffer kinds get the positions played with z by that winner.  forced_playouts = k (OPT-IN, batched only; selfplay.check_forced_playouts):
     forced playouts at the root; both buffer kinds get the pruned pi of every stored position.  eval_symmetry = True | ("fixed", s) (OPT-IN,
-    batched only; selfplay.check_eval_symmetry): every leaf is evaluated in an orientation keyed by (seed, its position), or in the one given."""
+    batched only; selfplay.check_eval_symmetry): every leaf is evaluated in an orientation keyed by (seed, its position), or in the one given.
+    emit_symmetry = "board" | "none" | elements (OPT-IN, batched only; selfplay.check_emit_symmetry): every position from the third on is stored
+    once per element of the mask, on every board - Connect4 and non-square Gomoku included; both buffer kinds get the same tuples."""
     from azk import DeviceReplay
-    from selfplay import self_play_batch
+    from selfplay import check_emit_symmetry, mask_elements, self_play_batch
     if not batched:
+        if emit_symmetry is not None:
+            raise ValueError("collect_data: emit_symmetry needs the batched engine (batched=True)")
         if playout_cap is not None:
             raise ValueError("collect_data: playout_cap needs the batched engine (batched=True)")
         if resign is not None:
@@ -88,28 +125,32 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     leaf_dtype = "bfloat16" if getattr(model, "dtype", None) is not None and str(model.dtype).endswith("bfloat16") else "float32"
     res = self_play_batch(Game.engine_name, model, iterations, mcts_iter, size=Game._size(), seed=seed, leaf_dtype=leaf_dtype,
                           replay=buffer if on_device else None, playout_cap=playout_cap, resign=resign, forced_playouts=forced_playouts,
-                          eval_symmetry=eval_symmetry)
+                          eval_symmetry=eval_symmetry, emit_symmetry=emit_symmetry)
+    emit = check_emit_symmetry(emit_symmetry, Game.engine_name, Game._size())
     results = [0, 0, 0]
     for r in res:
         results[2 if r.winner == -1 else r.winner] += 1
         if not on_device:
             reward = 0 if r.winner == -1 else 1
-            save_data_to_buffer(Game, buffer, (r.boards, r.actions, r.pis, r.qs, r.winner, reward), full=r.full if playout_cap is not None else None)
+            save_data_to_buffer(Game, buffer, (r.boards, r.actions, r.pis, r.qs, r.winner, reward), full=r.full if playout_cap is not None else None,
+                                elements=mask_elements(emit) if emit else None)
         if display:
             Game.display_board(r.boards[-1])
     return results
 
 
-def train(model, batch_size, buffer, train_iterations, lr, device):
+def train(model, batch_size, buffer, train_iterations, lr, device, augment=None):
     """train.py:85-123 for a pvnet.PolicyValueNet: a fresh Adam, `train_iterations` sampled batches, the reference's loss;
-    the network's weights are updated in place; returns (loss, policy_loss, value_loss, l2) of the last iteration."""
+    the network's weights are updated in place; returns (loss, policy_loss, value_loss, l2) of the last iteration.  augment (OPT-IN; None:
+    buffer.sample(batch_size) as ever) goes to buffer.sample(batch_size, augment=augment) - azk.DeviceReplay turns every drawn row by a D4
+    element of its own."""
     import torch
     from trainer import Trainer
     tr = Trainer(model.cfg, model.state_dict(), device=device)
 
     def batches():
         for _ in range(train_iterations):
-            s, p, z = buffer.sample(batch_size)
+            s, p, z = buffer.sample(batch_size) if augment is None else buffer.sample(batch_size, augment=augment)
             yield s, p.to(torch.float32), z.reshape(-1, 1)
     dist = torch.distributed if torch.distributed.is_available() and torch.distributed.is_initialized() else None
     out = tr.train(batches(), lr, dist=dist)

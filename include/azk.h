@@ -93,7 +93,17 @@ typedef struct {
                             * x 800 simulations of 15x15 Gomoku) and drops a subtree of more than about max_sims expansions; top-up fits
                             * the default arena.  Not with leaves_per_step > 1 (AZK_ERR_ARG).  The asynchronous movers take such an engine through
                             * azk_async_begin_reuse; azk_async_begin answers AZK_ERR_STATE. */
-    int32_t reserved[4];
+    int32_t emit_elements; /* 0: (state, pi, z) emission as the reference does it (train.py:30-49; parity mode, the default) - eight images per
+                            * position from the third on, square boards with one action per cell only.
+                            * m != 0 (OPT-IN): emission under the D4 elements of the bit mask m, bit s = element s of the emission's numbering
+                            * (azk_set_eval_symmetry: 0 rot0, 1 lr, 2 tb, 3 rot90, 4 lr(rot90), 5 tb(rot90), 6 rot180, 7 rot270), on EVERY
+                            * geometry; azk_emit_finished below has the semantics.  azk_create answers AZK_ERR_ARG for bits above 7, a mask
+                            * without bit 0 and an element the geometry does not admit (azk_set_eval_symmetry's rule: all eight on square
+                            * boards with one action per cell, {0, 1, 2, 6} on Gomoku with rows != cols, {0, 1} on Connect4).  A create-time
+                            * field: the trajectory buffers such an engine always has exist before the first move, and no captured graph
+                            * ever sees another device view.  They cost n_games * state_dim * action_dim * 8 bytes (+ 2 per ply), the same
+                            * as a square board of equal cell count: 1.2 MB per game on a 13 x 30 Gomoku board, 2.4 kB on Connect4. */
+    int32_t reserved[3];
 } azk_config;
 
 /* device-side work counters; sums over all games since the last azk_reset_counters */
@@ -369,9 +379,44 @@ int32_t azk_recycle_finished(azk_engine *e, int64_t *stats_dev, void *stream);
  * lr, tb, rot180, rot270).  The engine appends at *cursor_dev (uint64, monotonically increasing) and writes tuple t to
  * slot t % capacity of the caller's ring buffers - the device-resident form of ReplayBuffer's deque(maxlen)
  * (replay_buffer.py:7-13).  game_base_dev (optional, int64 [G]) receives each emitted game's first tuple index, -1 for
- * the others.  Square boards with one action per cell only (Gomoku, TicTacToe); others return AZK_ERR_ARG. */
+ * the others.  Square boards with one action per cell only (Gomoku, TicTacToe); others return AZK_ERR_ARG - unless the engine was
+ * created with azk_config.emit_elements = m != 0 (OPT-IN; 0: everything above, bit for bit).  Then, on every geometry, with
+ * n = popcount(m):
+ *   - a finished game of p plies reserves  p <= 2 ? p : 2 + n * (p - 2)  tuples; plies 0 and 1 once, under element 0, as ever;
+ *   - ply i >= 2 gets one tuple per element of m, in ascending element order, at base + 2 + n * (i - 2);
+ *   - the tuple for element s: every plane of the canonical board turned, out[j] = in[src_s(j)] on the R x C board (src_s as
+ *     azk_set_eval_symmetry defines it); the side plane (F == 3) is the constant it was; with one action per cell
+ *     pi'[j] = pi[src_s(j)], with Connect4's column actions pi'[a] = pi[cols - 1 - a] under element 1; z is unchanged;
+ *   - on a playout-cap engine the group of a full ply is  i < 2 ? 1 : n; fast plies are left out, offsets are the sum over the full
+ *     plies before;
+ *   - the ring slot t % capacity, the 64-bit cursor, game_base_dev, the asynchronous drain, resignation's winner and the pruned pi of
+ *     forced playouts are what they are without the option.
+ * On a square board m = 0xFF fills the ring of an engine with the option off, byte for byte; m = 0x01 stores one image per position
+ * (for a caller that turns the batch when it is drawn: azk_replay_gather).
+ * azk_emit_elements: *mask_out = the engine's azk_config.emit_elements, *group_out = the tuples per ply from the third on - popcount of
+ * the mask; with the option off 8 on a board the reference's rule emits, 0 where emission answers AZK_ERR_ARG - to size a ring by. */
 int32_t azk_emit_finished(azk_engine *e, float *states_dev, double *pis_dev, float *zs_dev, int64_t capacity,
                           int64_t *cursor_dev, int64_t *game_base_dev, void *stream);
+int32_t azk_emit_elements(const azk_engine *e, int32_t *mask_out, int32_t *group_out);
+
+/* A training batch gathered from a replay ring, each row turned by a D4 element drawn for it (stateless; no engine).  The ring is the
+ * caller's: states_ring float32 [rows_ring][planes][rows][cols], pis_ring float64 [rows_ring][action_dim], zs_ring float32 [rows_ring]
+ * (azk_emit_finished's layout).  Row b of the output (b < n) comes from ring row r = idx_dev[b] (int64; the caller guarantees
+ * 0 <= r < rows_ring) under element
+ *     draws_dev == NULL ? 0 : valid[(((uint32_t)draws_dev[b] >> 16) * n_valid) >> 16]
+ * with valid = the elements of element_mask in ascending order (the pick of azk_set_eval_symmetry's mode 1):
+ *     states_out[b] = every plane turned, out[j] = in[src_s(j)];   zs_out[b] = zs_ring[r];
+ *     pis_out[b]    = the float64 row turned as azk_emit_finished turns it, rounded to float32 (round to nearest even).
+ * With draws_dev == NULL that is  states[idx], pis[idx].float(), zs[idx]  exactly.  The action kind follows from action_dim:
+ * rows * cols = one action per cell (all eight elements where rows == cols, else {0, 1, 2, 6}); cols = column actions, {0, 1} with pi
+ * mirrored; anything else: element 0 only.  AZK_ERR_ARG (message: azk_last_error(NULL)) for a mask without bit 0 or with bits above 7,
+ * an element the geometry and action kind do not admit (a transposing one with rows != cols), rows * cols > 400 or a dimension < 1
+ * (any rows x cols inside that: the engine's limit of 30 columns does not apply here, 1 x 400 is a board),
+ * n < 0, a null pointer; n == 0 does nothing.  One wave per output row; asynchronous on the stream. */
+int32_t azk_replay_gather(int32_t rows, int32_t cols, int32_t planes, int32_t action_dim, uint32_t element_mask,
+                          const float *states_ring, const double *pis_ring, const float *zs_ring,
+                          const int64_t *idx_dev, const int32_t *draws_dev, int32_t n,
+                          float *states_out, float *pis_out, float *zs_out, void *stream);
 
 /* MCTS.cache.clear() (main.py:55-57): must be called whenever the evaluator's weights change. */
 int32_t azk_clear_cache(azk_engine *e, void *stream);

@@ -78,15 +78,15 @@ __device__ __forceinline__ float gelu_erf(float x) {
     return 0.5f * x * (1.0f + copysignf(erf_abs, x));
 }
 
-// The same approximation with a true division in place of the reciprocal instruction: the fp32-accurate tail (k_gemm_h and its
-// LDS-staged form).  |error| <= 1.5e-7: 3e-7 on a hidden activation, below that path's 22-bit operands; erff costs fifty
-// instructions, and the wide link's epilogue runs it on 32 values per lane.
-__device__ __forceinline__ float gelu_as(float x) {
-    const float z = fabsf(x) * 0.70710678118654752f;
-    const float t = 1.0f / (1.0f + 0.3275911f * z);
-    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    const float erf_abs = 1.0f - poly * __expf(-z * z);
-    return 0.5f * x * (1.0f + copysignf(erf_abs, x));
+// nn.GELU (erf form) for the fp32-accurate tail (k_gemm_h and its LDS-staged form): libm's erff (a few float32 ulps: about 1e-7
+// on erf, so |x| / 2 times that on the result, plus the two roundings of 0.5 x (1 + erf)).  The Abramowitz & Stegun 7.1.26 form with
+// a true division stood here before: 1.5e-7 is the error of the FORMULA; evaluated in float32 (t = 1 / (1 + p z), whose rounding the
+// polynomial's slope of 3.4 at t = 1 multiplies, the Horner chain, and the cancellation in 1 - poly exp) its erf was off by up to
+// 6e-7 (largest near x = 0.035), 2.3 times the 1.5e-7 + __expf share the float64 tests allow ("What pins the fp16-plane
+// tail links").  erff costs about fifty instructions on 32 values per lane of the wide link's epilogue - the 512 -> 2048 link that bench.py's
+// fp32 line (`--nn-dtype fp32`, `fp32_line` of `--full`) runs on every simulation step; DESIGN.md, same place, has what that costs, measured.
+__device__ __forceinline__ float gelu_erff(float x) {
+    return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
 }
 
 // s_waitcnt vmcnt(N) for a compile-time N (the asm immediate wants an integer constant expression)

@@ -757,7 +757,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_h(GemmHArgs a) {
                 }
                 if (EPI == X_EPI_GELU) {
 #pragma unroll
-                    for (int c = 0; c < 4; c++) v[c] = gelu_as(v[c]);
+                    for (int c = 0; c < 4; c++) v[c] = gelu_erff(v[c]);
                 }
                 if (EPI == X_EPI_RESID) v += rr[i][j];
                 if (row < nvalid) {

@@ -415,7 +415,7 @@ __device__ __forceinline__ void gemm_h_lds_body(const HArgs &a, const int nvalid
             v += bv;
             if (EPI == TAIL_EPI_GELU) {
 #pragma unroll
-                for (int c = 0; c < 4; c++) v[c] = gelu_as(v[c]);
+                for (int c = 0; c < 4; c++) v[c] = gelu_erff(v[c]);
             }
             if (EPI == TAIL_EPI_RESID) v += rr[i][j];
             if (row < nvalid) {

@@ -96,8 +96,9 @@ struct ReuseDev {
 };
 
 // playout-cap randomisation (azk_set_playout_cap, opt-in; n_fast == 0 otherwise): a search is FULL (the budget's simulations) with probability
-// p_full and FAST (n_fast simulations) otherwise, by a coin keyed like the search's noise row.  Its own argument of the kernels that exist only
-// for it (k_*_cap in azk_moves.hip): Dev, AsyncDev and ReuseDev - and every kernel an engine without the option launches - stay as they were
+// p_full and FAST (n_fast simulations) otherwise, by a coin keyed like the search's noise row.  Its own argument block, passed only to the CAP
+// instantiations of the kernels it touches (azk_moves.hip, "the opt-ins"): Dev, AsyncDev and ReuseDev - and every kernel an engine without the
+// option launches - stay as they were
 struct CapDev {
     int n_fast;                // simulations of a fast search; 0 = off
     double p_full;
@@ -112,8 +113,8 @@ struct CapDev {
 // resignation (azk_set_resign, opt-in; v_resign == 0 otherwise): after a move that does not end the game, the side that
 // has just moved concedes when the root's q (root.value / root.visit: the outcome as the mover's OPPONENT sees it) reached v_resign.  A coin
 // per game makes it a never-resign control game, which is only marked with the side that would have conceded first and played on.  Its own
-// argument of the kernels that exist only for it (k_*_rs in azk_moves.hip): every other argument block - and every kernel an engine
-// without the option launches - stays as it was
+// argument block, passed only to the RESIGN instantiations of the two movers (azk_moves.hip, "the opt-ins"): every other argument block - and
+// every kernel an engine without the option launches - stays as it was
 struct ResignDev {
     double v_resign;           // threshold on q, in (0, 1]; 0 = off
     double p_never;            // share of never-resign games
@@ -130,8 +131,8 @@ struct ResignDev {
 // forced playouts and policy target pruning at the root (azk_set_forced_playouts, opt-in; k == 0 otherwise): in a FORCED
 // search - the option set and, on a capped engine, the search a full one - a root child with N >= 1 visits and mixed prior P is selected
 // before any PUCT comparison while  N * N < (k * P) * (Np - 1)  (float64), and the pi that is RECORDED for the move loses the visits that
-// only this floor explains.  Its own argument of the kernels that exist only for it (k_tree<.., FORCED> in azk_tree.hip, k_*_fp in
-// azk_moves.hip): every other argument block - and every kernel an engine without the option launches - stays as it was
+// only this floor explains.  Its own argument block, passed only to the FORCED instantiations (k_tree<.., FORCED> in azk_tree.hip, the two
+// movers in azk_moves.hip): every other argument block - and every kernel an engine without the option launches - stays as it was
 struct ForcedDev {
     double k;                      // KataGo's 2; 0 = off
     const uint8_t *search_full;    // [G] CapDev's kind of the game's current search (1 full: forced, 0 fast: not), or null without a cap
@@ -153,8 +154,8 @@ struct SymDev {
 };
 
 // (state, pi, z) emission under a mask of D4 elements (azk_config.emit_elements, opt-in; n == 0 otherwise): ply i >= 2 of
-// a finished game is emitted once per element of the mask instead of under the reference's eight.  Its own argument of the kernels that exist
-// only for it (k_emit_*_sym in azk_moves.hip): every other argument block - and every kernel an engine without the option launches - stays as
+// a finished game is emitted once per element of the mask instead of under the reference's eight.  Its own argument block, passed only to the SYM
+// instantiations of k_emit_alloc and k_emit_tuples (azk_moves.hip): every other argument block - and every kernel an engine without the option launches - stays as
 // it was
 struct EmitSym {
     uint32_t els;              // the mask's elements, four bits each, ascending, lowest first

@@ -4,8 +4,35 @@
 // that launch them (include/azk.h).  Built with -ffp-contract=off like every engine file.
 #include "azk_engine_int.h"
 #include "azk_sym_map.h"      // sym_source: emission under a mask of elements
+#include <type_traits>
 
 namespace {
+
+// ------------------------------------------------------------------------------------------------
+// The opt-ins (playout cap, resignation, forced playouts, emission under a mask of elements; DESIGN sections 18 to 20 and 22).  A kernel an
+// option touches is ONE __global__ template with a bool per option, and the options' argument blocks (CapDev, ResignDev, ForcedDev, EmitSym)
+// ride on the block in front of them as a Pack: that block plus exactly the blocks whose flag is set.  A block that is off is an empty
+// base, which takes no room, so with every flag off the Pack IS its first block: the kernel an engine without options launches has the
+// argument layout and the instruction stream it always had, and an option costs the others nothing.  The kernels are one line each: the
+// *_body functions behind them take the blocks by value, all zero where an option is off (opt), and fold on their flags.  The host turns the engine's state
+// into the template arguments in one place per kernel (with_flags, in front of the launchers).
+// A new option is a flag on each template it touches, an Opt<> in their Packs and a bool at their dispatch.
+// ------------------------------------------------------------------------------------------------
+template <class Block, bool ON> struct Opt {};
+template <class Block> struct Opt<Block, true> { Block v; };
+template <class First, class... Opts> struct Pack : First, Opts... {};
+// the option's block out of a pack, or the block of "off" (all zero) where the pack has none
+template <class Block, class P> __device__ __forceinline__ Block opt(const P &p) {
+    if constexpr (std::is_base_of_v<Opt<Block, true>, P>) return static_cast<const Opt<Block, true> &>(p).v;
+    else return Block{};
+}
+template <class Block> struct Keyed : Block { int key; };        // a block and the move key whose coin this launch flips
+template <class First, bool CAP> using CapPack = Pack<First, Opt<CapDev, CAP>>;
+template <class First, bool CAP> using CapKeyPack = Pack<First, Opt<Keyed<CapDev>, CAP>>;
+template <class First, bool CAP, bool RESIGN, bool FORCED> using MovePack = Pack<First, Opt<CapDev, CAP>, Opt<ResignDev, RESIGN>, Opt<ForcedDev, FORCED>>;
+template <bool CAP, bool SYM> using EmitPack = Pack<Dev, Opt<CapDev, CAP>, Opt<EmitSym, SYM>>;
+static_assert(sizeof(MovePack<Dev, false, false, false>) == sizeof(Dev) && sizeof(EmitPack<false, false>) == sizeof(Dev) &&
+              sizeof(CapPack<ReuseDev, false>) == sizeof(ReuseDev) && sizeof(CapKeyPack<ReuseDev, false>) == sizeof(ReuseDev), "a pack without options is its first block");
 
 // A leaf that missed the eval cache claims its entry's key at selection and fills logits/value at expansion; if the search
 // is abandoned in between (new search, reset, recycle) the half-written entry must not survive.
@@ -37,11 +64,60 @@ __device__ __forceinline__ void fresh_root_one(const Dev &d, int g) {
     d.sims_done[g] = 0;
 }
 
-__global__ void k_begin_search(Dev d) {
+// Philox4x32-10, the counter-based generator of every random number the product path draws (the noise rows and move uniforms further down)
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
+        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
+        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+// the options' coins: the uniform in [0, 1) of (seed, global game, word 2) under the Philox word 3 `tag`, made as noise_uniform makes its own.
+// A tag is no other draw's (noise_uniform: 0xFFFFFFFF; noise_row: it < 64 and it | 0x40000000), so every other stream is what it was.
+__device__ __forceinline__ double keyed_coin(unsigned long long seed, unsigned long long gg, uint32_t word2, uint32_t tag) {
+    uint32_t w[4] = {(uint32_t)gg, (uint32_t)(gg >> 32), word2, tag};
+    philox4x32_10(w, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return (double)((((unsigned long long)w[0] << 32) | w[1]) >> 11) * (1.0 / 9007199254740992.0);
+}
+// the coin of playout-cap randomisation (tag 0xFFFFFFFE): is the search of (seed, global game, move key) a FULL one?
+__device__ __forceinline__ bool cap_coin(const CapDev &c, int g, int move) {
+    return keyed_coin(c.seed, (unsigned long long)(c.first_game + g), (uint32_t)move, 0xFFFFFFFEu) < c.p_full;
+}
+// the game coin of resignation (tag 0xFFFFFFFD): is the game of (seed, global game, move key of its first search) a NEVER-RESIGN control
+// game?  Stateless: the mover recomputes it at every move from start = (the slot's move counter) - (the game's plies), so no restart,
+// recycle or reset kernel knows of it.
+__device__ __forceinline__ bool resign_never(const ResignDev &rs, int g, uint32_t start) {
+    return keyed_coin(rs.seed, (unsigned long long)(rs.first_game + g), start, 0xFFFFFFFDu) < rs.p_never;
+}
+// simulations of a search of that kind under the budget as it stands (a fast search never exceeds the budget)
+__device__ __forceinline__ int cap_target(const CapDev &c, bool full, int budget) { return full ? budget : min(c.n_fast, budget); }
+
+// a fresh-root search has just begun for game g (one lane): flip its coin and preset sims_done so that budget stepping stops a fast
+// search after n_fast simulations - what top-up does with the carried visits
+__device__ __forceinline__ void cap_begin_fresh(const Dev &d, const CapDev &c, int g, int move, bool count) {
+    const int n = d.budget[0];
+    const bool full = cap_coin(c, g, move);
+    c.search_full[g] = full ? 1 : 0;
+    d.sims_done[g] = n - cap_target(c, full, n);
+    if (count && c.stats != nullptr) atomicAdd((unsigned long long *)&c.stats[full ? 8 : 9], 1ull);
+}
+
+// CAP, here and in every kernel below (playout-cap randomisation, azk_set_playout_cap): a fast search is the same search
+// with fewer simulations - sims_done starts at budget - n_fast and budget stepping (k_tree<MULTI>, k_unfinished, the movers' "search complete"
+// test) ends it after n_fast.  The root's Dirichlet mix lives in k_tree and stays on for fast searches too.
+template <bool CAP>
+__global__ void k_begin_search(CapKeyPack<Dev, CAP> a) {
+    const Dev d = a;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.G) return;
     if (g == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
     fresh_root_one(d, g);
+    if constexpr (CAP) { const Keyed<CapDev> c = opt<Keyed<CapDev>>(a); cap_begin_fresh(d, c, g, c.key, false); }
 }
 
 // ================================================================================================
@@ -206,12 +282,21 @@ __device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_
     }
 }
 
-// azk_begin_search on a reuse engine: re-root on the child k_advance recorded, or a fresh root where there is none
-__global__ __launch_bounds__(AZK_WAVE) void k_reroot(Dev d, ReuseDev r, int n_sims) {
+// azk_begin_search on a reuse engine: re-root on the child k_advance recorded, or a fresh root where there is none.  CAP
+// (azk_begin_search_capped): n_sims is the budget, and the per-game target by the coin of the launch's move key replaces it in reroot_one
+template <bool CAP>
+__global__ __launch_bounds__(AZK_WAVE) void k_reroot(Dev d, CapKeyPack<ReuseDev, CAP> r, int n_sims) {
     const int g = blockIdx.x;
     if (g == 0 && azk_lane() == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
     const int c = uniform_i32(r.chosen_node[g]);
-    reroot_one(d, r, g, c, n_sims, d.noise != nullptr ? d.noise + (size_t)g * d.g.action_dim : nullptr);
+    const double *noise = d.noise != nullptr ? d.noise + (size_t)g * d.g.action_dim : nullptr;
+    if constexpr (CAP) {
+        const Keyed<CapDev> cp = opt<Keyed<CapDev>>(r);
+        const bool full = uniform_i32((int)cap_coin(cp, g, cp.key)) != 0;
+        const int target = cap_target(cp, full, n_sims);
+        reroot_one(d, r, g, c, target, noise, n_sims - target);
+        if (azk_lane() == 0) cp.search_full[g] = full ? 1 : 0;
+    } else reroot_one(d, r, g, c, n_sims, noise);
     if (azk_lane() == 0) r.chosen_node[g] = -1;                   // one search per recorded move
 }
 
@@ -264,8 +349,6 @@ __global__ __launch_bounds__(AZK_WAVE) void k_root_stats(Dev d, double *pi, doub
     }
 }
 
-__device__ __forceinline__ bool resign_never(const ResignDev &rs, int g, uint32_t start);      // the game coin, beside cap_coin
-
 // Policy target pruning (forced playouts; Wu 2019, section 3.2) for one game (one wave).  L.cnt holds the root children's
 // RAW visit counts by action; on return it holds the counts the recorded pi is made of, and the function returns their sum.  With
 // Np = root visits, s = sqrt(Np) and c* = the first child with the most visits (Node.max_visit_child):
@@ -317,14 +400,16 @@ __device__ __forceinline__ bool forced_search(const Dev &d, const ForcedDev &fp,
 // gomoku.py:143-162 for one game (one wave): choose (sample ~ visits | first max-visit child), record pi / the action in the
 // trajectory, make_move, check_winner, draw.  Returns the chosen cell (-1: state error, already reported); *win_out / *done_out as
 // k_advance's outputs; pi of the move is left in L.cnt / sum_out (visit counts per action and their sum).
-// RESIGN (resigning engines, the k_*_rs kernels): after a move that does not end the game the mover concedes when the
+// RESIGN (resigning engines, azk_set_resign): after a move that does not end the game the mover concedes when the
 // root's q reached v_resign - or, in a never-resign game, is noted as the game's mark.  key = the slot's move counter at this move,
-// *rsg_out = 1 when the move ended the game by resignation.
-// FORCED (engines with forced playouts, the k_*_fp kernels): once the cell is chosen - from raw visits - the counts of a
-// forced search are pruned in place (prune_counts), so that traj_pi and the caller's record hold the pruned pi.
-template <bool RESIGN, bool FORCED = false>
+// *rsg_out = 1 when the move ended the game by resignation.  A resignation happens where a natural end happens (winner and done are set
+// here), so emission, recycling, the drain and the re-root see an ordinary finished game.
+// FORCED (engines with forced playouts, azk_set_forced_playouts): once the cell is chosen - from raw visits - the counts
+// of a forced search are pruned in place (prune_counts), so that traj_pi and the caller's record hold the pruned pi.  The selection half of
+// the option lives in k_tree<.., FORCED> (azk_tree.hip).
+template <bool RESIGN, bool FORCED>
 __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool have_u, double u, int sample_until, int *win_out, int *done_out,
-                                           int *sum_out, const ResignDev &rs, int key, int *rsg_out, const ForcedDev &fp = ForcedDev{}) {
+                                           int *sum_out, const ResignDev &rs, int key, int *rsg_out, const ForcedDev &fp) {
     const int lane = azk_lane();
     const GameDesc &gd = d.g;
     const size_t base = (size_t)g * d.cap;
@@ -450,11 +535,11 @@ __device__ __forceinline__ int played_child(const Dev &d, int g, int cellc) {
     return (cellc >= 0 && found != 0x7fffffff) ? fc + found : -1;
 }
 
-// CAP: playout-cap engines (k_advance_cap) - the ply's kind goes into traj_full beside its pi; RESIGN: resigning engines (k_advance_rs),
-// move_index = the slot's move counter; FORCED: engines with forced playouts (k_advance_fp)
-template <bool CAP, bool RESIGN, bool FORCED = false>
+// The lock-step mover (azk_advance, azk_advance_resign): every game's move, one wave per game.  CAP: the ply's kind goes into traj_full beside its
+// pi; RESIGN (move_index = the slot's move counter), FORCED: as advance_one has them
+template <bool CAP, bool RESIGN, bool FORCED>
 __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int move_index, const double *uniforms, int sample_until,
-                                             int *chosen, int *winner_out, int *done_out, int *chosen_node, const ForcedDev &fp = ForcedDev{}) {
+                                             int *chosen, int *winner_out, int *done_out, int *chosen_node, const ForcedDev &fp) {
     const int g = blockIdx.x, lane = azk_lane();
     LdsView L = carve(d.g, d.path_cap, d.table_size);
     if (uniform_i32(d.done[g]) != 0) {
@@ -483,9 +568,17 @@ __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int
     }
 }
 
-__global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *uniforms, int sample_until,
+// the lock-step mover's scalars: move_index is an argument of resigning engines' kernels only
+template <bool RESIGN> struct Ply { int sample_until; };
+template <> struct Ply<true> { int sample_until, move_index; };
+
+template <bool CAP, bool RESIGN, bool FORCED>
+__global__ __launch_bounds__(AZK_WAVE) void k_advance(MovePack<Dev, CAP, RESIGN, FORCED> a, const double *uniforms, Ply<RESIGN> ply,
                                                        int *chosen, int *winner_out, int *done_out, int *chosen_node) {
-    advance_body<false, false>(d, CapDev{}, ResignDev{}, 0, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
+    int move_index = 0;
+    if constexpr (RESIGN) move_index = ply.move_index;
+    advance_body<CAP, RESIGN, FORCED>(a, opt<CapDev>(a), opt<ResignDev>(a), move_index, uniforms, ply.sample_until, chosen, winner_out, done_out, chosen_node,
+                                      opt<ForcedDev>(a));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -494,13 +587,12 @@ __global__ __launch_bounds__(AZK_WAVE) void k_advance(Dev d, const double *unifo
 // positions 0 and 1 once, the others 8 times in the order rot0, lr(rot0), tb(rot0), rot90, lr(rot90), tb(rot90),
 // rot180, rot270 (np.rot90 is counter-clockwise).  Tuple t of the stream lands in slot t % capacity (deque(maxlen)).
 // ------------------------------------------------------------------------------------------------
-// CAP (playout-cap engines, the k_*_cap kernels): only the plies of FULL searches are emitted - ply i's group (1 tuple for i < 2, else 8) sits at
+// CAP (playout-cap engines): only the plies of FULL searches are emitted - ply i's group (1 tuple for i < 2, else 8) sits at
 // the sum of the groups of the full plies before it; the board before ply i is rebuilt from every earlier ply, fast ones included.
-// SYM (engines created with emit_elements, the k_emit_*_sym kernels): the group of a ply from the third on is one tuple per
+// SYM (engines created with emit_elements): the group of a ply from the third on is one tuple per
 // element of the mask (es.n of them, es.els in ascending order) instead of the reference's eight, on any R x C board and action kind.
-template <bool CAP, bool SYM = false>
-__device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full, unsigned long long *cursor, long long *game_base_out,
-                                                const EmitSym &es = EmitSym{}) {
+template <bool CAP, bool SYM>
+__device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full, unsigned long long *cursor, long long *game_base_out, const EmitSym &es) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.G) return;
     long long base = -1;                                          // the stream index stays 64-bit end to end (2^31 tuples = hours of self-play)
@@ -518,7 +610,10 @@ __device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full,
     if (game_base_out) game_base_out[g] = base;
 }
 
-__global__ void k_emit_alloc(Dev d, unsigned long long *cursor, long long *game_base_out) { emit_alloc_body<false>(d, nullptr, cursor, game_base_out); }
+template <bool CAP, bool SYM>
+__global__ void k_emit_alloc(EmitPack<CAP, SYM> a, unsigned long long *cursor, long long *game_base_out) {
+    emit_alloc_body<CAP, SYM>(a, opt<CapDev>(a).traj_full, cursor, game_base_out, opt<EmitSym>(a));
+}
 
 __device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
     // source cell (row-major) of output cell (i, j) under transform t of the reference's emission order
@@ -536,9 +631,10 @@ __device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
     return si * N + sj;
 }
 
-template <bool LIST, bool CAP, bool SYM = false>
+// LIST: the grid walks a list of finished games (asynchronous drain) instead of covering all G
+template <bool LIST, bool CAP, bool SYM>
 __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full, float *states, double *pis, float *zs, long long capacity,
-                                                 const unsigned long long *cursor, const int *list, const int *n_list, const EmitSym &es = EmitSym{}) {
+                                                 const unsigned long long *cursor, const int *list, const int *n_list, const EmitSym &es) {
     const int S = d.g.state_dim, A = d.g.action_dim, rc = d.g.rc, F = d.g.planes, N = d.g.rows;
     const int lane = azk_lane();
     const int nb = LIST ? *n_list * S : (int)gridDim.x;
@@ -589,22 +685,10 @@ __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full
     }
 }
 
-template <bool LIST>     // LIST: the grid walks a list of finished games (asynchronous drain) instead of covering all G
-__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(Dev d, float *states, double *pis, float *zs, long long capacity,
+template <bool LIST, bool CAP, bool SYM>
+__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(EmitPack<CAP, SYM> a, float *states, double *pis, float *zs, long long capacity,
                                                             const unsigned long long *cursor, const int *list, const int *n_list) {
-    emit_tuples_body<LIST, false>(d, nullptr, states, pis, zs, capacity, cursor, list, n_list);
-}
-
-// the emitters of an engine created with emit_elements, launched IN PLACE of k_emit_alloc(_cap) and k_emit_tuples(_cap) (one template over the cap)
-template <bool CAP>
-__global__ void k_emit_alloc_sym(Dev d, CapDev cp, EmitSym es, unsigned long long *cursor, long long *game_base_out) {
-    emit_alloc_body<CAP, true>(d, cp.traj_full, cursor, game_base_out, es);
-}
-
-template <bool LIST, bool CAP>
-__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples_sym(Dev d, CapDev cp, EmitSym es, float *states, double *pis, float *zs, long long capacity,
-                                                                const unsigned long long *cursor, const int *list, const int *n_list) {
-    emit_tuples_body<LIST, CAP, true>(d, cp.traj_full, states, pis, zs, capacity, cursor, list, n_list, es);
+    emit_tuples_body<LIST, CAP, SYM>(a, opt<CapDev>(a).traj_full, states, pis, zs, capacity, cursor, list, n_list, opt<EmitSym>(a));
 }
 
 __global__ void k_emit_mark(Dev d) {
@@ -624,21 +708,9 @@ __global__ void k_sum_counters(const long long *counters, int G, long long *out)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Counter-based RNG for the product path: Philox4x32-10 keyed by (seed), counter = (game, move, lane idx, draw).
+// Counter-based RNG for the product path: Philox4x32-10 (philox4x32_10, above) keyed by (seed), counter = (game, move, lane idx, draw).
 // Dirichlet(alpha) via Gamma(alpha) = Gamma(alpha + 1) * U^(1/alpha) (Marsaglia-Tsang for the shape > 1 part).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
 __device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {     // uniform in (0, 1)
     const unsigned long long x = (((unsigned long long)hi << 32) | lo) >> 11;
     return ((double)x + 0.5) * (1.0 / 9007199254740992.0);
@@ -737,40 +809,11 @@ __global__ void k_fill_i32(int *p, int n, int v) {
     if (i < n) p[i] = v;
 }
 
-// the coin of playout-cap randomisation: is the search of (seed, global game, move key) a FULL one?  Philox word 3 = 0xFFFFFFFE is no other
-// draw's (noise_uniform: 0xFFFFFFFF; noise_row: it < 64 and it | 0x40000000), so every noise row and move uniform is what it was.
-__device__ __forceinline__ bool cap_coin(const CapDev &c, int g, int move) {
-    const unsigned long long gg = (unsigned long long)(c.first_game + g);
-    uint32_t w[4] = {(uint32_t)gg, (uint32_t)(gg >> 32), (uint32_t)move, 0xFFFFFFFEu};
-    philox4x32_10(w, (uint32_t)c.seed, (uint32_t)(c.seed >> 32));
-    const double u = (double)((((unsigned long long)w[0] << 32) | w[1]) >> 11) * (1.0 / 9007199254740992.0);   // [0,1), as noise_uniform
-    return u < c.p_full;
-}
-// the game coin of resignation: is the game of (seed, global game, move key of its first search) a NEVER-RESIGN control game?  Stateless: the
-// mover recomputes it at every move from start = (the slot's move counter) - (the game's plies), so no restart, recycle or reset kernel knows
-// of it.  Philox word 3 = 0xFFFFFFFD is no other draw's (cap_coin: 0xFFFFFFFE), so every existing stream is what it was.
-__device__ __forceinline__ bool resign_never(const ResignDev &rs, int g, uint32_t start) {
-    const unsigned long long gg = (unsigned long long)(rs.first_game + g);
-    uint32_t w[4] = {(uint32_t)gg, (uint32_t)(gg >> 32), start, 0xFFFFFFFDu};
-    philox4x32_10(w, (uint32_t)rs.seed, (uint32_t)(rs.seed >> 32));
-    const double u = (double)((((unsigned long long)w[0] << 32) | w[1]) >> 11) * (1.0 / 9007199254740992.0);   // [0,1), as cap_coin
-    return u < rs.p_never;
-}
-// simulations of a search of that kind under the budget as it stands (a fast search never exceeds the budget)
-__device__ __forceinline__ int cap_target(const CapDev &c, bool full, int budget) { return full ? budget : min(c.n_fast, budget); }
-
-// a fresh-root search has just begun for game g (one lane): flip its coin and preset sims_done so that budget stepping stops a fast
-// search after n_fast simulations - what top-up does with the carried visits
-__device__ __forceinline__ void cap_begin_fresh(const Dev &d, const CapDev &c, int g, int move, bool count) {
-    const int n = d.budget[0];
-    const bool full = cap_coin(c, g, move);
-    c.search_full[g] = full ? 1 : 0;
-    d.sims_done[g] = n - cap_target(c, full, n);
-    if (count && c.stats != nullptr) atomicAdd((unsigned long long *)&c.stats[full ? 8 : 9], 1ull);
-}
-
-template <bool REROOT, bool CAP, bool RESIGN, bool FORCED = false>   // the body of k_move_async / k_move_async_cap, their _rs siblings and k_move_async_fp
-__device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs, const ForcedDev &fp = ForcedDev{}) {
+// The asynchronous mover.  REROOT: a re-rooting engine - the moved game is parked for the drain's k_reroot_list instead of beginning its search
+// here; CAP: the kind of the completed search goes into the record and traj_full, and the next fresh-root search flips its coin; RESIGN, FORCED:
+// as advance_one has them
+template <bool REROOT, bool CAP, bool RESIGN, bool FORCED>
+__device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs, const ForcedDev &fp) {
     const int g = blockIdx.x, lane = azk_lane();
     // one vector load for the three words that decide whether this game moves now (almost never: the wave then ends at once)
     const int *up = d.done + g;
@@ -833,23 +876,37 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
     }
 }
 
-template <bool REROOT>   // REROOT: a re-rooting engine - the moved game is parked for the drain's k_reroot_list instead of beginning its search here
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, ReuseDev r) { move_async_body<REROOT, false, false>(d, p, r, CapDev{}, ResignDev{}); }
+template <bool REROOT, bool CAP, bool RESIGN, bool FORCED>
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, MovePack<ReuseDev, CAP, RESIGN, FORCED> r) {
+    move_async_body<REROOT, CAP, RESIGN, FORCED>(d, p, r, opt<CapDev>(r), opt<ResignDev>(r), opt<ForcedDev>(r));
+}
 
 // drain, step 4 (re-rooting engines): the next search of every game parked since the last drain - its subtree under the played child
 // moved to the front of the arena, or a fresh root where reroot_one refuses; one wave per game.  The Dirichlet row is the one of the
 // game's new key slot_moves[g] (the move kernel moved only once that row existed); k_noise_ahead, behind this kernel, writes the other.
-__global__ __launch_bounds__(AZK_WAVE) void k_reroot_list(Dev d, AsyncDev p, ReuseDev r) {
+// CAP: the coin of that key decides the search's target
+template <bool CAP>
+__global__ __launch_bounds__(AZK_WAVE) void k_reroot_list(Dev d, AsyncDev p, CapPack<ReuseDev, CAP> r) {
+    const CapDev cp = opt<CapDev>(r);
     const int n = uniform_i32(*p.reroot_count), n_sims = uniform_i32(d.budget[0]), A = d.g.action_dim;
     for (int f = blockIdx.x; f < n; f += gridDim.x) {
         const int g = uniform_i32(p.reroot_list[f]);
         const int c = uniform_i32(r.chosen_node[g]);
         const double *row = p.dirichlet ? p.noise + ((size_t)g * 2 + (size_t)(uniform_i32((int)p.slot_moves[g]) & 1)) * A : nullptr;
-        reroot_one(d, r, g, c, n_sims, row);
+        bool full = true;
+        if constexpr (CAP) {
+            full = uniform_i32((int)cap_coin(cp, g, uniform_i32((int)p.slot_moves[g]))) != 0;
+            const int target = cap_target(cp, full, n_sims);
+            reroot_one(d, r, g, c, target, row, n_sims - target);
+        } else reroot_one(d, r, g, c, n_sims, row);
         if (azk_lane() == 0) {
             r.chosen_node[g] = -1;                                 // one search per recorded move
             p.parked[g] = 0;
             atomicAdd((unsigned long long *)&p.stats[7], 1ull);
+            if (CAP) {
+                cp.search_full[g] = full ? 1 : 0;
+                if (cp.stats != nullptr) atomicAdd((unsigned long long *)&cp.stats[full ? 8 : 9], 1ull);
+            }
         }
     }
 }
@@ -885,111 +942,8 @@ __device__ __forceinline__ void async_restart_body(Dev d, AsyncDev p, int recycl
     }
 }
 
-__global__ __launch_bounds__(AZK_WAVE) void k_async_restart(Dev d, AsyncDev p, int recycle) { async_restart_body<false>(d, p, recycle, CapDev{}); }
-
-// ------------------------------------------------------------------------------------------------
-// Playout-cap randomisation (azk_set_playout_cap, opt-in): the kernels a capped engine launches IN PLACE of their
-// namesakes.  Each is its namesake's body with CAP set, so an engine without the option runs the instruction streams it always ran.
-// A fast search is the same search with fewer simulations: sims_done starts at budget - n_fast and budget stepping (k_tree<MULTI>,
-// k_unfinished, the movers' "search complete" test) ends it after n_fast.  The root's Dirichlet mix lives in k_tree and stays on for
-// fast searches too.
-// ------------------------------------------------------------------------------------------------
-__global__ void k_begin_search_cap(Dev d, CapDev c, int move) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= d.G) return;
-    if (g == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
-    fresh_root_one(d, g);
-    cap_begin_fresh(d, c, g, move, false);
-}
-
-// azk_begin_search_capped on a reuse engine: the per-game target replaces n_sims in reroot_one
-__global__ __launch_bounds__(AZK_WAVE) void k_reroot_cap(Dev d, ReuseDev r, CapDev cp, int move) {
-    const int g = blockIdx.x;
-    if (g == 0 && azk_lane() == 0 && d.cache_entries && d.cache_shared) d.cache_stamp[0] += 1u;
-    const int c = uniform_i32(r.chosen_node[g]), n_sims = uniform_i32(d.budget[0]);
-    const bool full = uniform_i32((int)cap_coin(cp, g, move)) != 0;
-    const int target = cap_target(cp, full, n_sims);
-    reroot_one(d, r, g, c, target, d.noise != nullptr ? d.noise + (size_t)g * d.g.action_dim : nullptr, n_sims - target);
-    if (azk_lane() == 0) { r.chosen_node[g] = -1; cp.search_full[g] = full ? 1 : 0; }
-}
-
-__global__ __launch_bounds__(AZK_WAVE) void k_advance_cap(Dev d, CapDev cp, const double *uniforms, int sample_until,
-                                                           int *chosen, int *winner_out, int *done_out, int *chosen_node) {
-    advance_body<true, false>(d, cp, ResignDev{}, 0, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
-}
-
-__global__ void k_emit_alloc_cap(Dev d, CapDev cp, unsigned long long *cursor, long long *game_base_out) {
-    emit_alloc_body<true>(d, cp.traj_full, cursor, game_base_out);
-}
-
-template <bool LIST>
-__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples_cap(Dev d, CapDev cp, float *states, double *pis, float *zs, long long capacity,
-                                                                const unsigned long long *cursor, const int *list, const int *n_list) {
-    emit_tuples_body<LIST, true>(d, cp.traj_full, states, pis, zs, capacity, cursor, list, n_list);
-}
-
-template <bool REROOT>
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async_cap(Dev d, AsyncDev p, ReuseDev r, CapDev cp) { move_async_body<REROOT, true, false>(d, p, r, cp, ResignDev{}); }
-
-// k_reroot_list with the coin of the game's new move key deciding the search's target
-__global__ __launch_bounds__(AZK_WAVE) void k_reroot_list_cap(Dev d, AsyncDev p, ReuseDev r, CapDev cp) {
-    const int n = uniform_i32(*p.reroot_count), n_sims = uniform_i32(d.budget[0]), A = d.g.action_dim;
-    for (int f = blockIdx.x; f < n; f += gridDim.x) {
-        const int g = uniform_i32(p.reroot_list[f]);
-        const int c = uniform_i32(r.chosen_node[g]);
-        const int key = uniform_i32((int)p.slot_moves[g]);
-        const double *row = p.dirichlet ? p.noise + ((size_t)g * 2 + (size_t)(key & 1)) * A : nullptr;
-        const bool full = uniform_i32((int)cap_coin(cp, g, key)) != 0;
-        const int target = cap_target(cp, full, n_sims);
-        reroot_one(d, r, g, c, target, row, n_sims - target);
-        if (azk_lane() == 0) {
-            r.chosen_node[g] = -1;                                 // one search per recorded move
-            p.parked[g] = 0;
-            atomicAdd((unsigned long long *)&p.stats[7], 1ull);
-            cp.search_full[g] = full ? 1 : 0;
-            if (cp.stats != nullptr) atomicAdd((unsigned long long *)&cp.stats[full ? 8 : 9], 1ull);
-        }
-    }
-}
-
-__global__ __launch_bounds__(AZK_WAVE) void k_async_restart_cap(Dev d, AsyncDev p, int recycle, CapDev cp) { async_restart_body<true>(d, p, recycle, cp); }
-
-// ------------------------------------------------------------------------------------------------
-// Resignation (azk_set_resign, opt-in): the movers a resigning engine launches IN PLACE of their namesakes - each its
-// namesake's body with RESIGN set.  A resignation happens where a natural end happens (advance_one sets winner and done), so emission,
-// recycling, the drain and the re-root see an ordinary finished game and none of their kernels has a sibling here.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(AZK_WAVE) void k_advance_rs(Dev d, ResignDev rs, const double *uniforms, int sample_until, int move_index,
-                                                          int *chosen, int *winner_out, int *done_out, int *chosen_node) {
-    advance_body<false, true>(d, CapDev{}, rs, move_index, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
-}
-
-__global__ __launch_bounds__(AZK_WAVE) void k_advance_cap_rs(Dev d, CapDev cp, ResignDev rs, const double *uniforms, int sample_until, int move_index,
-                                                              int *chosen, int *winner_out, int *done_out, int *chosen_node) {
-    advance_body<true, true>(d, cp, rs, move_index, uniforms, sample_until, chosen, winner_out, done_out, chosen_node);
-}
-
-template <bool REROOT>
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async_rs(Dev d, AsyncDev p, ReuseDev r, ResignDev rs) { move_async_body<REROOT, false, true>(d, p, r, CapDev{}, rs); }
-
-template <bool REROOT>
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async_cap_rs(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs) { move_async_body<REROOT, true, true>(d, p, r, cp, rs); }
-
-// ------------------------------------------------------------------------------------------------
-// Forced playouts and policy target pruning (azk_set_forced_playouts, opt-in): the movers an engine with the option
-// launches IN PLACE of their namesakes - each its namesake's body with FORCED set, one template over the cap and the resignation so that the
-// option does not double the list above.  The selection half of the option lives in k_tree<.., FORCED> (azk_tree.hip).
-// ------------------------------------------------------------------------------------------------
-template <bool CAP, bool RESIGN>
-__global__ __launch_bounds__(AZK_WAVE) void k_advance_fp(Dev d, CapDev cp, ResignDev rs, ForcedDev fp, const double *uniforms, int sample_until, int move_index,
-                                                          int *chosen, int *winner_out, int *done_out, int *chosen_node) {
-    advance_body<CAP, RESIGN, true>(d, cp, rs, move_index, uniforms, sample_until, chosen, winner_out, done_out, chosen_node, fp);
-}
-
-template <bool REROOT, bool CAP, bool RESIGN>
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async_fp(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs, ForcedDev fp) {
-    move_async_body<REROOT, CAP, RESIGN, true>(d, p, r, cp, rs, fp);
-}
+template <bool CAP>
+__global__ __launch_bounds__(AZK_WAVE) void k_async_restart(CapPack<Dev, CAP> d, AsyncDev p, int recycle) { async_restart_body<CAP>(d, p, recycle, opt<CapDev>(d)); }
 
 // azk_root_policy_target: the pi the next move would record - k_root_stats' counts, pruned where the game's search is a forced one
 __global__ __launch_bounds__(AZK_WAVE) void k_root_policy_target(Dev d, ForcedDev fp, double *pi) {
@@ -1012,26 +966,43 @@ __global__ __launch_bounds__(AZK_WAVE) void k_root_policy_target(Dev d, ForcedDe
     for (int a = lane; a < A; a += AZK_WAVE) pi[(size_t)g * A + a] = (double)L.cnt[a] / (double)sum;
 }
 
+// ---- the host side of the options: runtime flags -> template arguments, engine state -> argument packs ----------------------------------
+// f(std::bool_constant per flag), called once: the one place where a kernel's instantiation is chosen
+template <class F> void with_flags(F &&f) { f(); }
+template <class F, class... Rest> void with_flags(F &&f, bool flag, Rest... rest) {
+    if (flag) with_flags([&](auto... more) { f(std::true_type{}, more...); }, rest...);
+    else with_flags([&](auto... more) { f(std::false_type{}, more...); }, rest...);
+}
+// the option's block as a pack takes it: the block where the flag is set, nothing where it is not
+template <bool ON, class Block> Opt<Block, ON> on(const Block &b) {
+    if constexpr (ON) return {b};
+    else return {};
+}
+template <bool CAP, bool RESIGN, bool FORCED, class First> MovePack<First, CAP, RESIGN, FORCED> move_pack(const First &first, const azk_engine *e) {
+    return {first, on<CAP>(e->cp), on<RESIGN>(e->rs), on<FORCED>(e->forced())};
+}
+template <bool CAP, class First> CapKeyPack<First, CAP> cap_key_pack(const First &first, const azk_engine *e, int key) {
+    return {first, on<CAP>(Keyed<CapDev>{e->cp, key})};
+}
+
 }  // namespace
 
 int32_t azk_init_games(azk_engine *e) {
     const Dev &d = e->d;
     k_reset_games<<<(unsigned)(((size_t)d.G * d.rc_pad + 255) / 256), 256>>>(d, 0, d.G, e->ru.chosen_node);
-    k_begin_search<<<(unsigned)((d.G + 255) / 256), 256>>>(d);
+    k_begin_search<false><<<(unsigned)((d.G + 255) / 256), 256>>>(cap_key_pack<false>(d, e, 0));
     HIPCHK(e, hipDeviceSynchronize());
     return AZK_OK;
 }
 
 // the start of a search for every game, on the stream: a fresh root, or on a tree-reuse engine the subtree under the played child (n_sims:
-// the simulations the search may run).  move_index >= 0: a capped engine - the coin of (seed, global game, move_index) sets each game's target
+// the simulations the search may run).  On a capped engine the coin of (seed, global game, move_index) sets each game's target
 static void launch_begin_search(azk_engine *e, int n_sims, int move_index, hipStream_t st) {
     const Dev &d = e->d;
-    const unsigned per_game = (unsigned)((d.G + 255) / 256);
-    if (move_index >= 0) {
-        if (e->ru.mode) k_reroot_cap<<<d.G, AZK_WAVE, 0, st>>>(d, e->ru, e->cp, move_index);
-        else k_begin_search_cap<<<per_game, 256, 0, st>>>(d, e->cp, move_index);
-    } else if (e->ru.mode) k_reroot<<<d.G, AZK_WAVE, 0, st>>>(d, e->ru, n_sims);
-    else k_begin_search<<<per_game, 256, 0, st>>>(d);
+    with_flags([&](auto cap) {
+        if (e->ru.mode) k_reroot<cap.value><<<d.G, AZK_WAVE, 0, st>>>(d, cap_key_pack<cap.value>(e->ru, e, move_index), n_sims);
+        else k_begin_search<cap.value><<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(cap_key_pack<cap.value>(d, e, move_index));
+    }, e->cp.n_fast != 0);
 }
 
 // (state, pi, z) emission on the stream: each finished game's tuple range, the tuples, done = 2.  list == nullptr: one block per (game, ply)
@@ -1042,26 +1013,11 @@ static void launch_emit(azk_engine *e, float *states, double *pis, float *zs, lo
     const unsigned per_game = (unsigned)((d.G + 255) / 256), lds = (unsigned)up16(d.g.rc);
     const int plies = d.G * d.g.state_dim;
     const unsigned blocks = (unsigned)(list && plies > 16384 ? 16384 : plies);
-    if (e->emit.n) {                                              // emit_elements: the mask's elements on any geometry
-        const EmitSym es = e->emit;
-        if (e->cp.n_fast) {
-            k_emit_alloc_sym<true><<<per_game, 256, 0, st>>>(d, e->cp, es, cursor, game_base);
-            if (list) k_emit_tuples_sym<true, true><<<blocks, AZK_WAVE, lds, st>>>(d, e->cp, es, states, pis, zs, capacity, cursor, list, n_list);
-            else k_emit_tuples_sym<false, true><<<blocks, AZK_WAVE, lds, st>>>(d, e->cp, es, states, pis, zs, capacity, cursor, nullptr, nullptr);
-        } else {
-            k_emit_alloc_sym<false><<<per_game, 256, 0, st>>>(d, CapDev{}, es, cursor, game_base);
-            if (list) k_emit_tuples_sym<true, false><<<blocks, AZK_WAVE, lds, st>>>(d, CapDev{}, es, states, pis, zs, capacity, cursor, list, n_list);
-            else k_emit_tuples_sym<false, false><<<blocks, AZK_WAVE, lds, st>>>(d, CapDev{}, es, states, pis, zs, capacity, cursor, nullptr, nullptr);
-        }
-    } else if (e->cp.n_fast) {
-        k_emit_alloc_cap<<<per_game, 256, 0, st>>>(d, e->cp, cursor, game_base);
-        if (list) k_emit_tuples_cap<true><<<blocks, AZK_WAVE, lds, st>>>(d, e->cp, states, pis, zs, capacity, cursor, list, n_list);
-        else k_emit_tuples_cap<false><<<blocks, AZK_WAVE, lds, st>>>(d, e->cp, states, pis, zs, capacity, cursor, nullptr, nullptr);
-    } else {
-        k_emit_alloc<<<per_game, 256, 0, st>>>(d, cursor, game_base);
-        if (list) k_emit_tuples<true><<<blocks, AZK_WAVE, lds, st>>>(d, states, pis, zs, capacity, cursor, list, n_list);
-        else k_emit_tuples<false><<<blocks, AZK_WAVE, lds, st>>>(d, states, pis, zs, capacity, cursor, nullptr, nullptr);
-    }
+    with_flags([&](auto by_list, auto cap, auto sym) {             // sym: emit_elements, the mask's elements on any geometry
+        const EmitPack<cap.value, sym.value> a{d, on<cap.value>(e->cp), on<sym.value>(e->emit)};
+        k_emit_alloc<cap.value, sym.value><<<per_game, 256, 0, st>>>(a, cursor, game_base);
+        k_emit_tuples<by_list.value, cap.value, sym.value><<<blocks, AZK_WAVE, lds, st>>>(a, states, pis, zs, capacity, cursor, list, n_list);
+    }, list != nullptr, e->cp.n_fast != 0, e->emit.n != 0);
     k_emit_mark<<<per_game, 256, 0, st>>>(d);
 }
 
@@ -1296,10 +1252,8 @@ static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *strea
         if (rc != AZK_OK) return rc;
     }
     // first search of every game: fresh roots + the Dirichlet rows of move keys 0 (this search) and 1 (the next one)
-    if (e->cp.n_fast) {                                           // the coins share the noise rows' key: this run's seed and first game
-        e->cp.seed = a.seed; e->cp.first_game = a.first_game; e->cp.stats = a.stats;
-        k_begin_search_cap<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d, e->cp, 0);
-    } else k_begin_search<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(d);
+    if (e->cp.n_fast) { e->cp.seed = a.seed; e->cp.first_game = a.first_game; e->cp.stats = a.stats; }   // the coins share the noise rows' key: this run's seed and first game
+    with_flags([&](auto cap) { k_begin_search<cap.value><<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(cap_key_pack<cap.value>(d, e, 0)); }, e->cp.n_fast != 0);
     HIPCHK(e, hipMemsetAsync(a.todo_count, 0, sizeof(int), st));
     if (a.dirichlet) {
         const int A = d.g.action_dim;
@@ -1320,26 +1274,11 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
     const Dev &d = e->d;
     hipStream_t st = (hipStream_t)stream;
     if (phases & 1) { const int32_t rc = azk_launch_tree(e, true, true, true, logits_dev, values_dev, st); if (rc != AZK_OK) return rc; }
-    if ((phases & 2) && e->forced_k != 0.0) {
-        const bool cap = e->cp.n_fast != 0, rsn = e->rs.v_resign != 0.0, rr = e->ru.mode != 0;
-        const ForcedDev fp = e->forced();
-#define AZK_MOVE_FP(RR, CAP, RS) k_move_async_fp<RR, CAP, RS><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp, e->rs, fp)
-        if (rr) { if (cap) { if (rsn) AZK_MOVE_FP(true, true, true); else AZK_MOVE_FP(true, true, false); } else { if (rsn) AZK_MOVE_FP(true, false, true); else AZK_MOVE_FP(true, false, false); } }
-        else { if (cap) { if (rsn) AZK_MOVE_FP(false, true, true); else AZK_MOVE_FP(false, true, false); } else { if (rsn) AZK_MOVE_FP(false, false, true); else AZK_MOVE_FP(false, false, false); } }
-#undef AZK_MOVE_FP
-    } else if ((phases & 2) && e->rs.v_resign != 0.0) {
-        if (e->cp.n_fast) {
-            if (e->ru.mode) k_move_async_cap_rs<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp, e->rs);
-            else k_move_async_cap_rs<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp, e->rs);
-        } else if (e->ru.mode) k_move_async_rs<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->rs);
-        else k_move_async_rs<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->rs);
-    } else if (phases & 2) {
-        if (e->cp.n_fast) {
-            if (e->ru.mode) k_move_async_cap<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp);
-            else k_move_async_cap<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru, e->cp);
-        } else if (e->ru.mode) k_move_async<true><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru);
-        else k_move_async<false><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->ru);
-    }
+    if (phases & 2)
+        with_flags([&](auto reroot, auto cap, auto resign, auto forced) {
+            k_move_async<reroot.value, cap.value, resign.value, forced.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(
+                d, e->ad, move_pack<cap.value, resign.value, forced.value>(e->ru, e));
+        }, e->ru.mode != 0, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0);
     HIPCHK(e, hipGetLastError());
     return azk_sym_leaves(e, st);                                 // (eval symmetry: the leaves the tree launch selected, behind the movers)
 }
@@ -1362,13 +1301,12 @@ int32_t azk_async_drain(azk_engine *e, float *states_dev, double *pis_dev, float
         if (!pis_dev || !zs_dev || !cursor_dev || capacity < 1 || !d.traj_pi) { e->err = "azk_async_drain: bad replay arguments"; return AZK_ERR_ARG; }
         launch_emit(e, states_dev, pis_dev, zs_dev, (long long)capacity, (unsigned long long *)cursor_dev, nullptr, e->ad.fin_list, e->ad.fin_count, st);
     }
-    if (e->cp.n_fast) k_async_restart_cap<<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->async_recycle, e->cp);
-    else k_async_restart<<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, e->async_recycle);
-    if (e->ru.mode) {                                             // the next search of every game that moved since the last drain
-        if (e->cp.n_fast) k_reroot_list_cap<<<(unsigned)d.G, AZK_WAVE, 0, st>>>(d, e->ad, e->ru, e->cp);
-        else k_reroot_list<<<(unsigned)d.G, AZK_WAVE, 0, st>>>(d, e->ad, e->ru);
-        HIPCHK(e, hipMemsetAsync(e->ad.reroot_count, 0, sizeof(int), st));
-    }
+    with_flags([&](auto cap) {
+        k_async_restart<cap.value><<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(CapPack<Dev, cap.value>{d, on<cap.value>(e->cp)}, e->ad, e->async_recycle);
+        // re-rooting engines: the next search of every game that moved since the last drain
+        if (e->ru.mode) k_reroot_list<cap.value><<<(unsigned)d.G, AZK_WAVE, 0, st>>>(d, e->ad, CapPack<ReuseDev, cap.value>{e->ru, on<cap.value>(e->cp)});
+    }, e->cp.n_fast != 0);
+    if (e->ru.mode) HIPCHK(e, hipMemsetAsync(e->ad.reroot_count, 0, sizeof(int), st));
     if (e->ad.dirichlet) {                                        // the rows of the searches AFTER the ones begun since the last drain
         k_noise_ahead<<<(unsigned)(d.G < 512 ? d.G : 512), AZK_WAVE, 0, st>>>(d, e->ad);
         HIPCHK(e, hipMemsetAsync(e->ad.todo_count, 0, sizeof(int), st));
@@ -1408,40 +1346,33 @@ int32_t azk_root_stats(azk_engine *e, double *pi_dev, double *q_dev, int32_t *ro
     return AZK_OK;
 }
 
+// azk_advance and azk_advance_resign (move_index: the game coin's key, read on a resigning engine only)
+static int32_t advance(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t move_index, int32_t *chosen_cell_dev,
+                       int32_t *winner_dev, int32_t *done_dev, void *stream) {
+    const Dev &d = e->d;
+    e->in_search = false;
+    with_flags([&](auto cap, auto resign, auto forced) {
+        Ply<resign.value> ply{sample_until_move};
+        if constexpr (resign.value) ply.move_index = move_index;
+        k_advance<cap.value, resign.value, forced.value><<<d.G, AZK_WAVE, d.lds_bytes, (hipStream_t)stream>>>(
+            move_pack<cap.value, resign.value, forced.value>(d, e), uniforms_dev, ply, chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
+    }, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
 int32_t azk_advance(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t *chosen_cell_dev,
                     int32_t *winner_dev, int32_t *done_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
     if (e->rs.v_resign != 0.0) { e->err = "azk_advance: resignation is set - its moves are made by azk_advance_resign (the game coin needs the move index)"; return AZK_ERR_STATE; }
-    e->in_search = false;
-    if (e->forced_k != 0.0) {
-        if (e->cp.n_fast) k_advance_fp<true, false><<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, e->forced(), uniforms_dev, sample_until_move, 0,
-                                                                                                           chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
-        else k_advance_fp<false, false><<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, e->forced(), uniforms_dev, sample_until_move, 0,
-                                                                                                  chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
-    } else if (e->cp.n_fast) k_advance_cap<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, uniforms_dev, sample_until_move,
-                                                                                               chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
-    else k_advance<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, uniforms_dev, sample_until_move,
-                                                                         chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
-    HIPCHK(e, hipGetLastError());
-    return AZK_OK;
+    return advance(e, uniforms_dev, sample_until_move, 0, chosen_cell_dev, winner_dev, done_dev, stream);
 }
 
 int32_t azk_advance_resign(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t move_index, int32_t *chosen_cell_dev,
                            int32_t *winner_dev, int32_t *done_dev, void *stream) {
     if (!e || move_index < 0) { if (e) e->err = "azk_advance_resign: bad argument"; return AZK_ERR_ARG; }
     if (e->rs.v_resign == 0.0) { e->err = "azk_advance_resign: no resignation is set (azk_set_resign)"; return AZK_ERR_STATE; }
-    e->in_search = false;
-    if (e->forced_k != 0.0) {
-        if (e->cp.n_fast) k_advance_fp<true, true><<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, e->forced(), uniforms_dev, sample_until_move, move_index,
-                                                                                                          chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
-        else k_advance_fp<false, true><<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, e->forced(), uniforms_dev, sample_until_move, move_index,
-                                                                                                 chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
-    } else if (e->cp.n_fast) k_advance_cap_rs<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->cp, e->rs, uniforms_dev, sample_until_move, move_index,
-                                                                                                  chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
-    else k_advance_rs<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->rs, uniforms_dev, sample_until_move, move_index,
-                                                                            chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
-    HIPCHK(e, hipGetLastError());
-    return AZK_OK;
+    return advance(e, uniforms_dev, sample_until_move, move_index, chosen_cell_dev, winner_dev, done_dev, stream);
 }
 
 int32_t azk_get_counters(azk_engine *e, azk_counters *out, void *stream) {

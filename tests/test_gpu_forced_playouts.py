@@ -258,7 +258,7 @@ def test_with_the_cap_full_plies_are_forced_and_fast_plies_are_not():
     eng.check_error()
     assert 0 < sum(kinds) < len(kinds)
     assert pruned_full > 0                                         # the full plies were positions on which the option shows
-    # (the lock-step traj_pi of a fast ply is never emitted, so nothing reads it back; k_advance_fp and k_move_async_fp record through the
+    # (the lock-step traj_pi of a fast ply is never emitted, so nothing reads it back; k_advance and k_move_async record through the
     #  one advance_one, and the ring below is that function's output)
     # the record itself, as the capped mover writes it (the asynchronous ring's rec_pi; same keys, so the same games): a fast ply's
     # holds the RAW counts, a full ply's the pruned ones

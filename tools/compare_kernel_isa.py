@@ -4,6 +4,7 @@
     python3 tools/compare_kernel_isa.py OLD/csrc/build alpha-zero_amd/csrc/build [--match k_tree]
     python3 tools/compare_kernel_isa.py OLD/libazk.so alpha-zero_amd/azk/libazk.so
     python3 tools/compare_kernel_isa.py OLD/csrc/build alpha-zero_amd/csrc/build --strip-namespace azk_eng
+    python3 tools/compare_kernel_isa.py OLD/csrc/build alpha-zero_amd/csrc/build --strip-namespace azk_eng --rename profiles/mover_options_rename.tsv
 
 Each side is a build directory (every *.o in it) or a library.  Every code object bundled in them is extracted (one per translation
 unit: csrc/azk_search.hip, azk_moves.hip, azk_nn.hip, ...), every kernel is cut at its symbol's size (llvm-readelf -s: llvm-objdump -d goes on to
@@ -12,7 +13,10 @@ symbol lives in on either side (addresses and encodings left out; kernels in ano
 they move between files).  A mangled name also spells the namespaces of the kernel's parameter types, so a type that moves to
 another namespace renames every kernel that takes it: --strip-namespace NS (repeatable) compares by DEMANGLED name instead
 (c++filt), with the qualifiers `NS::` and `(anonymous namespace)::` taken out on both sides; two kernels of one build that
-fall onto the same name that way are an error, never a silent pairing.  The 64-byte kernel descriptors (register counts, LDS size, ...) are compared too, less the code's own
+fall onto the same name that way are an error, never a silent pairing.  --rename FILE (only with --strip-namespace) pairs kernels whose
+names changed on purpose: each line of FILE is `old demangled name<TAB>new demangled name`, both as the stripped comparison prints them,
+and the OLD side is renamed before pairing; a line that names no old kernel, or two old kernels that end on one name, are errors.  A kernel
+that differs is printed with the instruction counts of both sides.  The 64-byte kernel descriptors (register counts, LDS size, ...) are compared too, less the code's own
 offset.  --match keeps the kernels whose name contains the string.  Exit status 1 if a kernel differs, is missing or is new.  This is
 how "k_tree's instruction stream did not change"  and "moving code between files left the device code alone"
  are checked."""
@@ -109,6 +113,27 @@ def plain_names(ks, namespaces, path):
     return out
 
 
+def renamed(ks, path):
+    """ks (the old side, by plain name) under the map in the file at path: lines of `old name<TAB>new name`."""
+    table = {}
+    for n, line in enumerate(open(path).read().splitlines(), 1):
+        if not line.strip() or line.startswith("#"):
+            continue
+        pair = line.split("\t")
+        if len(pair) != 2 or not pair[0] or not pair[1] or pair[0] in table:
+            sys.exit("%s:%d: want `old name<TAB>new name`, each old name once" % (path, n))
+        if pair[0] not in ks:
+            sys.exit("%s:%d: no kernel of the old build is `%s`" % (path, n, pair[0]))
+        table[pair[0]] = pair[1]
+    out = {}
+    for name, v in ks.items():
+        to = table.get(name, name)
+        if to in out:
+            sys.exit("%s: two kernels of the old build end on the name `%s`" % (path, to))
+        out[to] = v
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("old", help="build directory (csrc/build) or libazk.so of the build to compare against")
@@ -117,13 +142,19 @@ def main():
     ap.add_argument("--quiet", action="store_true", help="print only the kernels that differ and the summary line")
     ap.add_argument("--strip-namespace", action="append", default=[], metavar="NS",
                     help="compare by demangled name less the qualifiers NS:: and (anonymous namespace):: (repeatable)")
+    ap.add_argument("--rename", metavar="FILE", help="lines of `old demangled name<TAB>new demangled name`, applied to the old side before "
+                    "pairing (needs --strip-namespace)")
     a = ap.parse_args()
     if "" in a.strip_namespace:
         ap.error("--strip-namespace needs a name")
+    if a.rename and not a.strip_namespace:
+        ap.error("--rename maps demangled names: it needs --strip-namespace")
     with tempfile.TemporaryDirectory() as work:
         old, new = kernels(a.old, work, "old"), kernels(a.new, work, "new")
     if a.strip_namespace:
         old, new = plain_names(old, a.strip_namespace, a.old), plain_names(new, a.strip_namespace, a.new)
+    if a.rename:
+        old = renamed(old, a.rename)
     old = {k: v for k, v in old.items() if a.match in k}
     new = {k: v for k, v in new.items() if a.match in k}
     if not old:
@@ -139,7 +170,8 @@ def main():
         if what:
             differ.append(k)
         if what or not a.quiet:
-            print("DIFFERENT (%s)" % ", ".join(what) if what else "same", len(old[k][0]), "instructions", k)
+            count = "%d -> %d" % (len(old[k][0]), len(new[k][0])) if what else "%d" % len(old[k][0])
+            print("DIFFERENT (%s)" % ", ".join(what) if what else "same", count, "instructions", k)
     added = sorted(k for k in new if k not in old)
     for k in added:
         print("NEW", k)

@@ -38,6 +38,7 @@ SYMBOLS = [
     "azk_set_forced_playouts", "azk_root_policy_target",
     "azk_set_eval_symmetry", "azk_get_leaf_symmetry", "azk_eval_symmetry_restore",
     "azk_emit_elements", "azk_replay_gather",
+    "azk_set_surprise_weighting", "azk_clear_surprise_weighting", "azk_advance_keyed", "azk_get_surprise", "azk_async_surprise_columns",
 ]
 
 
@@ -206,6 +207,7 @@ class Engine:
         self.playout_cap = None                     # (p_full, n_fast) once set_playout_cap has switched the option on
         self.resign = None                          # (v_resign, p_never, min_ply) once set_resign has switched the option on
         self.forced_playouts = None                 # k once set_forced_playouts has switched the option on
+        self.surprise_weight = None                 # lambda once set_surprise_weighting has switched the option on (0.0 is a live setting)
         self.cache_entries = int(cache_entries)
         # with the eval cache a step can have pending (cached) leaves to expand although no leaf went to the evaluator
         need = cache_entries or self.K > 1
@@ -307,6 +309,30 @@ class Engine:
         explains (root_policy_target shows it).  The move, root_stats, q, resignation and tree reuse keep raw visits.  k = 0 switches it off."""
         self._chk(self.L.azk_set_forced_playouts(self.h, float(k), _stream()))
         self.forced_playouts = float(k) if float(k) != 0.0 else None
+
+    def set_surprise_weighting(self, lam, seed=0, first_global_game=0):
+        """OPT-IN policy surprise weighting (azk_set_surprise_weighting): from now on every move records kl = KL(recorded pi ||
+        the network's raw prior over the root's children) and a coin keyed (seed, first_global_game + g, move key), and a finished game's
+        recorded ply i is emitted floor(w_i) + (coin_i < frac(w_i)) times, w_i = (1 - lam) + lam * n * kl_i / sum(kl) - n tuple groups per game
+        in expectation, as without the option.  lam in [0, 1]; lam = 0 still records kl and coin and emits the option-off ring.  Moves are
+        then made with advance(..., move_index=...) (lock-step) or by the asynchronous movers (async_begin keys the coin by its own seed /
+        first game).  lam = None switches it off (azk_clear_surprise_weighting)."""
+        if lam is None:
+            self._chk(self.L.azk_clear_surprise_weighting(self.h))
+            self.surprise_weight = None
+            return
+        self._chk(self.L.azk_set_surprise_weighting(self.h, float(lam), int(seed), int(first_global_game), _stream()))
+        self.surprise_weight = float(lam)
+        if getattr(self, "_surprise", None) is None:
+            self._surprise = (self.torch.zeros(self.G, dtype=self.torch.float64, device=self.device),
+                              self.torch.zeros(self.G, dtype=self.torch.float64, device=self.device))
+
+    def surprise(self):
+        """(kl, coin): float64 CUDA tensors [G], what each game's last move recorded (azk_get_surprise; valid until the next call)."""
+        if self.surprise_weight is None:
+            raise AzkError("surprise: no surprise weighting is set (set_surprise_weighting)")
+        self._chk(self.L.azk_get_surprise(self.h, _p(self._surprise[0]), _p(self._surprise[1]), _stream()))
+        return self._surprise
 
     def set_eval_symmetry(self, mode, value=0):
         """OPT-IN evaluation under a board symmetry (azk_set_eval_symmetry): the evaluator sees every pending leaf turned by a D4 element
@@ -479,6 +505,10 @@ class Engine:
             if self.resign is not None:                       # ... and its resignation column: 1 = the record's move conceded the game
                 rec["resigned"] = torch.zeros(record_capacity, dtype=torch.uint8, device=self.device)
                 self._chk(self.L.azk_async_resign_flags(self.h, _p(rec["resigned"])))
+            if self.surprise_weight is not None:              # ... and its surprise columns: the record's kl and coin
+                rec["kl"] = torch.zeros(record_capacity, dtype=torch.float64, device=self.device)
+                rec["coin"] = torch.zeros(record_capacity, dtype=torch.float64, device=self.device)
+                self._chk(self.L.azk_async_surprise_columns(self.h, _p(rec["kl"]), _p(rec["coin"])))
         self.async_records = rec
         c = AsyncConfig()
         c.n_sims, c.max_sims_per_launch, c.sample_until_move = int(n_sims), int(per_launch), int(min(sample_until, 1 << 30))
@@ -531,9 +561,13 @@ class Engine:
         return self.pi, self.q, self.root_visit
 
     def advance(self, uniforms=None, sample_until_move=0, move_index=None):
-        """With resignation set, move_index (the slots' move counter: the noise row's move_index) is required."""
+        """With resignation or surprise weighting set, move_index (the slots' move counter: the noise row's move_index) is required."""
         if uniforms is not None:
             assert uniforms.dtype == self.torch.float64 and uniforms.is_cuda and uniforms.numel() == self.G
+        if self.surprise_weight is not None and move_index is not None:
+            self._chk(self.L.azk_advance_keyed(self.h, _p(uniforms), int(sample_until_move), int(move_index), _p(self.chosen), _p(self.winner),
+                                               _p(self.done), _stream()))
+            return self.chosen, self.winner, self.done
         if self.resign is not None and move_index is not None:
             self._chk(self.L.azk_advance_resign(self.h, _p(uniforms), int(sample_until_move), int(move_index), _p(self.chosen), _p(self.winner),
                                                 _p(self.done), _stream()))

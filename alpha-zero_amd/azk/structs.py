@@ -170,6 +170,11 @@ def declare(L, symbols):
     L.azk_set_forced_playouts.argtypes = [vp, f64, vp]
     L.azk_root_policy_target.argtypes = [vp, vp, vp]
     L.azk_async_resign_flags.argtypes = [vp, vp]
+    L.azk_set_surprise_weighting.argtypes = [vp, f64, u64, i64, vp]
+    L.azk_clear_surprise_weighting.argtypes = [vp]
+    L.azk_advance_keyed.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
+    L.azk_get_surprise.argtypes = [vp, vp, vp, vp]
+    L.azk_async_surprise_columns.argtypes = [vp, vp, vp]
     L.azk_set_eval_symmetry.argtypes = [vp, i32, u64, vp]
     L.azk_get_leaf_symmetry.argtypes = [vp, vp, vp]
     L.azk_eval_symmetry_restore.argtypes = [vp, vp, vp, vp]

@@ -162,6 +162,22 @@ struct EmitSym {
     int n;                     // how many; 0 = off
 };
 
+// policy surprise weighting (azk_set_surprise_weighting, opt-in): every move records kl = KL(recorded pi || the root
+// children's raw float32 priors) and a coin keyed like the playout coin (Philox word 3 = 0xFFFFFFFC); at emission a recorded ply is written
+// c = floor(w) + (coin < frac(w)) times, w = (1 - lambda) + lambda * n_F * kl / (sum of kl over the game's recorded plies).  Its own
+// argument block, passed only to the SURPRISE instantiations of the two movers and the two emitters (azk_moves.hip): every other argument
+// block - and every kernel an engine without the option launches - stays as it was
+struct SurpriseDev {
+    double lambda;             // share of a game's weight that follows kl, in [0, 1] (0: one copy each, kl and coin still recorded)
+    unsigned long long seed;   // the ply coin's key: (seed, first_game + g, move key), azk_async_begin puts its own seed / first game here
+    long long first_game;
+    double *traj_kl;           // [G][state_dim] kl of each ply of the current game, beside traj_pi
+    double *traj_coin;         // [G][state_dim] the ply's coin
+    uint16_t *traj_copies;     // [G][state_dim] copies of each ply's tuple group: written by k_emit_alloc, read by k_emit_tuples
+    double *last_kl, *last_coin;   // [G] what the game's last move recorded (azk_get_surprise)
+    double *rec_kl, *rec_coin; // asynchronous record ring: [record_capacity] columns, or null
+};
+
 struct LdsView {
     uint8_t *board;
     int *path;
@@ -317,6 +333,8 @@ struct azk_engine {
     bool async_on = false;
     int async_recycle = 1;
     SymDev sym = {};                     // evaluation under a board symmetry (azk_set_eval_symmetry); sym.mode == 0: off, nothing allocated
+    SurpriseDev sp = {};                 // policy surprise weighting (azk_set_surprise_weighting); sp_on == false: off, nothing allocated
+    bool sp_on = false;                  // (lambda = 0 is a live setting, so the switch is its own word)
     EmitSym emit = {};                   // emission under a mask of elements (cfg.emit_elements); emit.n == 0: off, the reference's rule
     bool in_search = false;              // between a search's begin and the move (or new position) that ends it: azk_set_eval_symmetry refuses
 };

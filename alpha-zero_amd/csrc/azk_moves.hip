@@ -9,8 +9,8 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// The opt-ins (playout cap, resignation, forced playouts, emission under a mask of elements; DESIGN sections 18 to 20 and 22).  A kernel an
-// option touches is ONE __global__ template with a bool per option, and the options' argument blocks (CapDev, ResignDev, ForcedDev, EmitSym)
+// The opt-ins (playout cap, resignation, forced playouts, emission under a mask of elements, surprise weighting; DESIGN sections 18 to 20, 22 and
+// 23).  A kernel an option touches is ONE __global__ template with a bool per option, and the options' argument blocks (CapDev, ResignDev, ForcedDev, EmitSym, SurpriseDev)
 // ride on the block in front of them as a Pack: that block plus exactly the blocks whose flag is set.  A block that is off is an empty
 // base, which takes no room, so with every flag off the Pack IS its first block: the kernel an engine without options launches has the
 // argument layout and the instruction stream it always had, and an option costs the others nothing.  The kernels are one line each: the
@@ -29,9 +29,13 @@ template <class Block, class P> __device__ __forceinline__ Block opt(const P &p)
 template <class Block> struct Keyed : Block { int key; };        // a block and the move key whose coin this launch flips
 template <class First, bool CAP> using CapPack = Pack<First, Opt<CapDev, CAP>>;
 template <class First, bool CAP> using CapKeyPack = Pack<First, Opt<Keyed<CapDev>, CAP>>;
-template <class First, bool CAP, bool RESIGN, bool FORCED> using MovePack = Pack<First, Opt<CapDev, CAP>, Opt<ResignDev, RESIGN>, Opt<ForcedDev, FORCED>>;
-template <bool CAP, bool SYM> using EmitPack = Pack<Dev, Opt<CapDev, CAP>, Opt<EmitSym, SYM>>;
-static_assert(sizeof(MovePack<Dev, false, false, false>) == sizeof(Dev) && sizeof(EmitPack<false, false>) == sizeof(Dev) &&
+template <class First, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
+using MovePack = Pack<First, Opt<CapDev, CAP>, Opt<ResignDev, RESIGN>, Opt<ForcedDev, FORCED>, Opt<SurpriseDev, SURPRISE>>;
+template <bool CAP, bool SYM, bool SURPRISE> using EmitPack = Pack<Dev, Opt<CapDev, CAP>, Opt<EmitSym, SYM>, Opt<SurpriseDev, SURPRISE>>;
+static_assert(sizeof(MovePack<Dev, false, false, false, false>) == sizeof(Dev) && sizeof(EmitPack<false, false, false>) == sizeof(Dev) &&
+              sizeof(MovePack<ReuseDev, false, false, false, false>) == sizeof(ReuseDev) &&
+              sizeof(MovePack<Dev, true, true, true, false>) == sizeof(Pack<Dev, Opt<CapDev, true>, Opt<ResignDev, true>, Opt<ForcedDev, true>>) &&
+              sizeof(EmitPack<true, true, false>) == sizeof(Pack<Dev, Opt<CapDev, true>, Opt<EmitSym, true>>) &&
               sizeof(CapPack<ReuseDev, false>) == sizeof(ReuseDev) && sizeof(CapKeyPack<ReuseDev, false>) == sizeof(ReuseDev), "a pack without options is its first block");
 
 // A leaf that missed the eval cache claims its entry's key at selection and fills logits/value at expansion; if the search
@@ -93,6 +97,10 @@ __device__ __forceinline__ bool cap_coin(const CapDev &c, int g, int move) {
 // recycle or reset kernel knows of it.
 __device__ __forceinline__ bool resign_never(const ResignDev &rs, int g, uint32_t start) {
     return keyed_coin(rs.seed, (unsigned long long)(rs.first_game + g), start, 0xFFFFFFFDu) < rs.p_never;
+}
+// the ply coin of policy surprise weighting (tag 0xFFFFFFFC): the uniform that rounds the ply's weight to a whole number of copies
+__device__ __forceinline__ double surprise_coin(const SurpriseDev &sp, int g, int move) {
+    return keyed_coin(sp.seed, (unsigned long long)(sp.first_game + g), (uint32_t)move, 0xFFFFFFFCu);
 }
 // simulations of a search of that kind under the budget as it stands (a fast search never exceeds the budget)
 __device__ __forceinline__ int cap_target(const CapDev &c, bool full, int budget) { return full ? budget : min(c.n_fast, budget); }
@@ -397,6 +405,27 @@ __device__ __forceinline__ bool forced_search(const Dev &d, const ForcedDev &fp,
     return full != 0 && uniform_i32(d.root_f64[g]) != 0;
 }
 
+// Policy surprise (surprise weighting) of one game's move (one wave): KL(recorded pi || the network's prior) over the root's
+// children, all float64:  kl = max(0, sum over children with m > 0 of  p * log(p / P)),  p = m / sum  the recorded pi's entry (L.cnt: the
+// counts after pruning), P = the child's RAW float32 prior as k_tree stored it in the header (not rootP, the Dirichlet mix), floored at the
+// smallest normal float.  Lanes sum their children in list order, then the wave's butterfly: the same order in both movers.
+__device__ __forceinline__ double surprise_kl(const Dev &d, const LdsView &L, int g, int sum) {
+    const size_t base = (size_t)g * d.cap;
+    const int fc = uniform_i32(d.H[base].fc), nch = uniform_i32(meta_nch(d.H[base].meta));
+    double part = 0.0;
+    for (int i = azk_lane(); i < nch; i += AZK_WAVE) {
+        const NodeH h = d.H[base + fc + i];
+        const int m = L.cnt[azk_action_idx(d.g, meta_cell(h.meta))];
+        if (m > 0) {
+            const double p = (double)m / (double)sum, P = (double)fmaxf(h.P, 0x1p-126f);
+            part += p * log(p / P);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
+    return part > 0.0 ? part : 0.0;
+}
+
 // gomoku.py:143-162 for one game (one wave): choose (sample ~ visits | first max-visit child), record pi / the action in the
 // trajectory, make_move, check_winner, draw.  Returns the chosen cell (-1: state error, already reported); *win_out / *done_out as
 // k_advance's outputs; pi of the move is left in L.cnt / sum_out (visit counts per action and their sum).
@@ -407,9 +436,12 @@ __device__ __forceinline__ bool forced_search(const Dev &d, const ForcedDev &fp,
 // FORCED (engines with forced playouts, azk_set_forced_playouts): once the cell is chosen - from raw visits - the counts
 // of a forced search are pruned in place (prune_counts), so that traj_pi and the caller's record hold the pruned pi.  The selection half of
 // the option lives in k_tree<.., FORCED> (azk_tree.hip).
-template <bool RESIGN, bool FORCED>
+// SURPRISE (engines with surprise weighting, azk_set_surprise_weighting): the kl of the pi that is recorded - after the
+// pruning - and the ply's coin of the move key go into traj_kl / traj_coin beside traj_pi and into the game's last-move pair (lane 0 writes
+// them: the asynchronous mover's lane 0 copies the pair into its record).
+template <bool RESIGN, bool FORCED, bool SURPRISE>
 __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool have_u, double u, int sample_until, int *win_out, int *done_out,
-                                           int *sum_out, const ResignDev &rs, int key, int *rsg_out, const ForcedDev &fp) {
+                                           int *sum_out, const ResignDev &rs, int key, int *rsg_out, const ForcedDev &fp, const SurpriseDev &sp) {
     const int lane = azk_lane();
     const GameDesc &gd = d.g;
     const size_t base = (size_t)g * d.cap;
@@ -480,6 +512,13 @@ __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool
         for (int a = lane; a < A; a += AZK_WAVE) tp[a] = (double)L.cnt[a] / (double)sum;
         if (lane == 0) d.traj_action[(size_t)g * gd.state_dim + mc] = (int16_t)cellc;
     }
+    if constexpr (SURPRISE) {
+        const double kl = surprise_kl(d, L, g, sum), coin = surprise_coin(sp, g, key);
+        if (lane == 0) {
+            if (d.traj_pi != nullptr && mc < gd.state_dim) { sp.traj_kl[(size_t)g * gd.state_dim + mc] = kl; sp.traj_coin[(size_t)g * gd.state_dim + mc] = coin; }
+            sp.last_kl[g] = kl; sp.last_coin[g] = coin;
+        }
+    }
     if (lane == 0) {
         if (gd.kind == AZK_KIND_C4) L.board[cellc] |= (uint8_t)(1 << mover);
         else if (L.board[cellc] == 0) L.board[cellc] = (uint8_t)(1 << mover);
@@ -536,10 +575,10 @@ __device__ __forceinline__ int played_child(const Dev &d, int g, int cellc) {
 }
 
 // The lock-step mover (azk_advance, azk_advance_resign): every game's move, one wave per game.  CAP: the ply's kind goes into traj_full beside its
-// pi; RESIGN (move_index = the slot's move counter), FORCED: as advance_one has them
-template <bool CAP, bool RESIGN, bool FORCED>
+// pi; RESIGN, SURPRISE (move_index = the slot's move counter), FORCED: as advance_one has them
+template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
 __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int move_index, const double *uniforms, int sample_until,
-                                             int *chosen, int *winner_out, int *done_out, int *chosen_node, const ForcedDev &fp) {
+                                             int *chosen, int *winner_out, int *done_out, int *chosen_node, const ForcedDev &fp, const SurpriseDev &sp) {
     const int g = blockIdx.x, lane = azk_lane();
     LdsView L = carve(d.g, d.path_cap, d.table_size);
     if (uniform_i32(d.done[g]) != 0) {
@@ -553,8 +592,8 @@ __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int
     }
     int win = -2, dn = 0, sum = 0, rsg = 0;
     const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
-    const int cellc = advance_one<RESIGN, FORCED>(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum,
-                                                  rs, move_index, &rsg, fp);
+    const int cellc = advance_one<RESIGN, FORCED, SURPRISE>(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum,
+                                                            rs, move_index, &rsg, fp, sp);
     if (CAP && cellc >= 0 && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = cp.search_full[g];
     if (chosen_node) {
         const int child = played_child(d, g, cellc);               // tree reuse: the next search's root
@@ -568,17 +607,17 @@ __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int
     }
 }
 
-// the lock-step mover's scalars: move_index is an argument of resigning engines' kernels only
-template <bool RESIGN> struct Ply { int sample_until; };
+// the lock-step mover's scalars: move_index is an argument only of the kernels of engines with a keyed option (resignation, surprise weighting)
+template <bool KEYED> struct Ply { int sample_until; };
 template <> struct Ply<true> { int sample_until, move_index; };
 
-template <bool CAP, bool RESIGN, bool FORCED>
-__global__ __launch_bounds__(AZK_WAVE) void k_advance(MovePack<Dev, CAP, RESIGN, FORCED> a, const double *uniforms, Ply<RESIGN> ply,
+template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
+__global__ __launch_bounds__(AZK_WAVE) void k_advance(MovePack<Dev, CAP, RESIGN, FORCED, SURPRISE> a, const double *uniforms, Ply<RESIGN || SURPRISE> ply,
                                                        int *chosen, int *winner_out, int *done_out, int *chosen_node) {
     int move_index = 0;
-    if constexpr (RESIGN) move_index = ply.move_index;
-    advance_body<CAP, RESIGN, FORCED>(a, opt<CapDev>(a), opt<ResignDev>(a), move_index, uniforms, ply.sample_until, chosen, winner_out, done_out, chosen_node,
-                                      opt<ForcedDev>(a));
+    if constexpr (RESIGN || SURPRISE) move_index = ply.move_index;
+    advance_body<CAP, RESIGN, FORCED, SURPRISE>(a, opt<CapDev>(a), opt<ResignDev>(a), move_index, uniforms, ply.sample_until, chosen, winner_out, done_out,
+                                                chosen_node, opt<ForcedDev>(a), opt<SurpriseDev>(a));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -591,8 +630,13 @@ __global__ __launch_bounds__(AZK_WAVE) void k_advance(MovePack<Dev, CAP, RESIGN,
 // the sum of the groups of the full plies before it; the board before ply i is rebuilt from every earlier ply, fast ones included.
 // SYM (engines created with emit_elements): the group of a ply from the third on is one tuple per
 // element of the mask (es.n of them, es.els in ascending order) instead of the reference's eight, on any R x C board and action kind.
-template <bool CAP, bool SYM>
-__device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full, unsigned long long *cursor, long long *game_base_out, const EmitSym &es) {
+// SURPRISE (engines with surprise weighting): ply i of the recorded plies F (all, or with CAP the full ones; n_F of them, S = the
+// sequential sum of their kl in ply order) is written c_i = floor(w_i) + (coin_i < w_i - floor(w_i)) times,
+//     w_i = S > 0 ? (1 - lambda) + ((lambda * n_F) * kl_i) / S : 1      (float64)
+// copy-major at base + sum_{j<i} c_j * grp_j.  k_emit_alloc writes c into traj_copies (0 outside F) and reserves the sum; k_emit_tuples reads it.
+template <bool CAP, bool SYM, bool SURPRISE>
+__device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full, unsigned long long *cursor, long long *game_base_out, const EmitSym &es,
+                                                const SurpriseDev &sp) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.G) return;
     long long base = -1;                                          // the stream index stays 64-bit end to end (2^31 tuples = hours of self-play)
@@ -604,15 +648,32 @@ __device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full,
             tuples = 0;
             for (int i = 0; i < n; i++) if (traj_full[(size_t)g * d.g.state_dim + i]) tuples += i < 2 ? 1 : grp;
         }
+        if constexpr (SURPRISE) {
+            const size_t row = (size_t)g * d.g.state_dim;
+            int n_F = 0;
+            double S = 0.0;
+            for (int i = 0; i < n; i++) if (!CAP || traj_full[row + i]) { n_F += 1; S += sp.traj_kl[row + i]; }
+            tuples = 0;
+            for (int i = 0; i < n; i++) {
+                int c = 0;
+                if (!CAP || traj_full[row + i]) {
+                    const double w = S > 0.0 ? (1.0 - sp.lambda) + ((sp.lambda * (double)n_F) * sp.traj_kl[row + i]) / S : 1.0;
+                    const double f = floor(w);
+                    c = (int)f + (sp.traj_coin[row + i] < w - f ? 1 : 0);
+                }
+                sp.traj_copies[row + i] = (uint16_t)c;
+                tuples += c * (i < 2 ? 1 : grp);
+            }
+        }
         base = (long long)atomicAdd(cursor, (unsigned long long)tuples);
     }
     d.emit_base[g] = base;
     if (game_base_out) game_base_out[g] = base;
 }
 
-template <bool CAP, bool SYM>
-__global__ void k_emit_alloc(EmitPack<CAP, SYM> a, unsigned long long *cursor, long long *game_base_out) {
-    emit_alloc_body<CAP, SYM>(a, opt<CapDev>(a).traj_full, cursor, game_base_out, opt<EmitSym>(a));
+template <bool CAP, bool SYM, bool SURPRISE>
+__global__ void k_emit_alloc(EmitPack<CAP, SYM, SURPRISE> a, unsigned long long *cursor, long long *game_base_out) {
+    emit_alloc_body<CAP, SYM, SURPRISE>(a, opt<CapDev>(a).traj_full, cursor, game_base_out, opt<EmitSym>(a), opt<SurpriseDev>(a));
 }
 
 __device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
@@ -631,10 +692,12 @@ __device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
     return si * N + sj;
 }
 
-// LIST: the grid walks a list of finished games (asynchronous drain) instead of covering all G
-template <bool LIST, bool CAP, bool SYM>
+// LIST: the grid walks a list of finished games (asynchronous drain) instead of covering all G.  SURPRISE: the ply's group is written
+// traj_copies[i] times, copy-major, behind the copies of the plies before it (a capped engine's fast plies have 0 copies: traj_full is not read)
+template <bool LIST, bool CAP, bool SYM, bool SURPRISE>
 __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full, float *states, double *pis, float *zs, long long capacity,
-                                                 const unsigned long long *cursor, const int *list, const int *n_list, const EmitSym &es) {
+                                                 const unsigned long long *cursor, const int *list, const int *n_list, const EmitSym &es,
+                                                 const uint16_t *traj_copies) {
     const int S = d.g.state_dim, A = d.g.action_dim, rc = d.g.rc, F = d.g.planes, N = d.g.rows;
     const int lane = azk_lane();
     const int nb = LIST ? *n_list * S : (int)gridDim.x;
@@ -644,7 +707,9 @@ __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full
     const int g = LIST ? list[gi] : gi;
     const long long base = d.emit_base[g];
     if (base < 0 || i >= d.move_count[g]) continue;
-    if (CAP && traj_full[(size_t)g * S + i] == 0) continue;      // a fast ply: it chose the move, it is not trained on
+    if (CAP && !SURPRISE && traj_full[(size_t)g * S + i] == 0) continue;      // a fast ply: it chose the move, it is not trained on
+    const int copies = SURPRISE ? (int)traj_copies[(size_t)g * S + i] : 1;
+    if (SURPRISE && copies == 0) continue;                        // no copy of this ply: the coin rounded its weight down to none (or a fast ply)
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     uint8_t *cells = sm;                                          // board before ply i
     for (int c = lane; c < rc; c += AZK_WAVE) cells[c] = 0;
@@ -658,15 +723,21 @@ __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full
     const int grp = SYM ? es.n : 8;
     const int ntr = i < 2 ? 1 : grp;
     long long first = base + (i < 2 ? i : 2 + grp * (i - 2));
-    if (CAP) {                                                    // tuples of the full plies before this one
+    if (CAP && !SURPRISE) {                                       // tuples of the full plies before this one
         int before = 0;
         for (int j = lane; j < i; j += AZK_WAVE) if (traj_full[(size_t)g * S + j]) before += j < 2 ? 1 : grp;
         first = base + wave_sum_i32(before);
     }
+    if (SURPRISE) {                                               // tuples of every copy of the plies before this one
+        int before = 0;
+        for (int j = lane; j < i; j += AZK_WAVE) before += (int)traj_copies[(size_t)g * S + j] * (j < 2 ? 1 : grp);
+        first = base + wave_sum_i32(before);
+    }
     const long long stream_end = (long long)*cursor;              // after k_emit_alloc: one past the newest tuple of this call
-    for (int t = 0; t < ntr; t++) {
-        if (first + t < stream_end - capacity) continue;          // already pushed out of the ring by newer tuples (deque(maxlen))
-        const long long slot = (first + t) % capacity;
+    for (int tt = 0; tt < ntr * copies; tt++) {
+        const int t = SURPRISE ? tt % ntr : tt;                   // copy-major: copy tt / ntr of the group's tuple t
+        if (first + tt < stream_end - capacity) continue;         // already pushed out of the ring by newer tuples (deque(maxlen))
+        const long long slot = (first + tt) % capacity;
         float *so = states + (size_t)slot * F * rc;
         double *po = pis + (size_t)slot * A;
         const int el = SYM ? (int)((es.els >> (4 * t)) & 15u) : t;   // (plies 0 and 1: t = 0 and the mask's first element is the identity)
@@ -685,10 +756,11 @@ __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full
     }
 }
 
-template <bool LIST, bool CAP, bool SYM>
-__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(EmitPack<CAP, SYM> a, float *states, double *pis, float *zs, long long capacity,
+template <bool LIST, bool CAP, bool SYM, bool SURPRISE>
+__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(EmitPack<CAP, SYM, SURPRISE> a, float *states, double *pis, float *zs, long long capacity,
                                                             const unsigned long long *cursor, const int *list, const int *n_list) {
-    emit_tuples_body<LIST, CAP, SYM>(a, opt<CapDev>(a).traj_full, states, pis, zs, capacity, cursor, list, n_list, opt<EmitSym>(a));
+    emit_tuples_body<LIST, CAP, SYM, SURPRISE>(a, opt<CapDev>(a).traj_full, states, pis, zs, capacity, cursor, list, n_list, opt<EmitSym>(a),
+                                               opt<SurpriseDev>(a).traj_copies);
 }
 
 __global__ void k_emit_mark(Dev d) {
@@ -811,9 +883,9 @@ __global__ void k_fill_i32(int *p, int n, int v) {
 
 // The asynchronous mover.  REROOT: a re-rooting engine - the moved game is parked for the drain's k_reroot_list instead of beginning its search
 // here; CAP: the kind of the completed search goes into the record and traj_full, and the next fresh-root search flips its coin; RESIGN, FORCED:
-// as advance_one has them
-template <bool REROOT, bool CAP, bool RESIGN, bool FORCED>
-__device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs, const ForcedDev &fp) {
+// SURPRISE: as advance_one has them (the move key is the slot's move counter; kl and coin go into the record's columns too)
+template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
+__device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs, const ForcedDev &fp, const SurpriseDev &sp) {
     const int g = blockIdx.x, lane = azk_lane();
     // one vector load for the three words that decide whether this game moves now (almost never: the wave then ends at once)
     const int *up = d.done + g;
@@ -838,7 +910,7 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
     const double u = noise_uniform(p.seed, (unsigned long long)(p.first_game + g), (int)mv);
     const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
     const int kind = CAP ? uniform_i32((int)cp.search_full[g]) : 1;     // of the search that is complete
-    const int cellc = advance_one<RESIGN, FORCED>(d, L, g, true, u, p.sample_until, &win, &dn, &sum, rs, (int)mv, &rsg, fp);
+    const int cellc = advance_one<RESIGN, FORCED, SURPRISE>(d, L, g, true, u, p.sample_until, &win, &dn, &sum, rs, (int)mv, &rsg, fp, sp);
     if (cellc < 0) return;
     if (CAP && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = (uint8_t)kind;
     if (p.rec_cap > 0) {                                           // the move's record: what the reference's self_play keeps per ply
@@ -852,6 +924,8 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
             m[0] = g; m[1] = (int)mv; m[2] = cellc; m[3] = win;
             if (CAP && cp.rec_full != nullptr) cp.rec_full[slot] = (uint8_t)kind;
             if (RESIGN && rs.rec_resigned != nullptr) rs.rec_resigned[slot] = (uint8_t)rsg;
+            if (SURPRISE && sp.rec_kl != nullptr) sp.rec_kl[slot] = sp.last_kl[g];        // (this lane wrote the pair in advance_one)
+            if (SURPRISE && sp.rec_coin != nullptr) sp.rec_coin[slot] = sp.last_coin[g];
         }
     }
     __syncthreads();
@@ -876,9 +950,9 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
     }
 }
 
-template <bool REROOT, bool CAP, bool RESIGN, bool FORCED>
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, MovePack<ReuseDev, CAP, RESIGN, FORCED> r) {
-    move_async_body<REROOT, CAP, RESIGN, FORCED>(d, p, r, opt<CapDev>(r), opt<ResignDev>(r), opt<ForcedDev>(r));
+template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, MovePack<ReuseDev, CAP, RESIGN, FORCED, SURPRISE> r) {
+    move_async_body<REROOT, CAP, RESIGN, FORCED, SURPRISE>(d, p, r, opt<CapDev>(r), opt<ResignDev>(r), opt<ForcedDev>(r), opt<SurpriseDev>(r));
 }
 
 // drain, step 4 (re-rooting engines): the next search of every game parked since the last drain - its subtree under the played child
@@ -978,8 +1052,9 @@ template <bool ON, class Block> Opt<Block, ON> on(const Block &b) {
     if constexpr (ON) return {b};
     else return {};
 }
-template <bool CAP, bool RESIGN, bool FORCED, class First> MovePack<First, CAP, RESIGN, FORCED> move_pack(const First &first, const azk_engine *e) {
-    return {first, on<CAP>(e->cp), on<RESIGN>(e->rs), on<FORCED>(e->forced())};
+template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, class First>
+MovePack<First, CAP, RESIGN, FORCED, SURPRISE> move_pack(const First &first, const azk_engine *e) {
+    return {first, on<CAP>(e->cp), on<RESIGN>(e->rs), on<FORCED>(e->forced()), on<SURPRISE>(e->sp)};
 }
 template <bool CAP, class First> CapKeyPack<First, CAP> cap_key_pack(const First &first, const azk_engine *e, int key) {
     return {first, on<CAP>(Keyed<CapDev>{e->cp, key})};
@@ -1013,11 +1088,11 @@ static void launch_emit(azk_engine *e, float *states, double *pis, float *zs, lo
     const unsigned per_game = (unsigned)((d.G + 255) / 256), lds = (unsigned)up16(d.g.rc);
     const int plies = d.G * d.g.state_dim;
     const unsigned blocks = (unsigned)(list && plies > 16384 ? 16384 : plies);
-    with_flags([&](auto by_list, auto cap, auto sym) {             // sym: emit_elements, the mask's elements on any geometry
-        const EmitPack<cap.value, sym.value> a{d, on<cap.value>(e->cp), on<sym.value>(e->emit)};
-        k_emit_alloc<cap.value, sym.value><<<per_game, 256, 0, st>>>(a, cursor, game_base);
-        k_emit_tuples<by_list.value, cap.value, sym.value><<<blocks, AZK_WAVE, lds, st>>>(a, states, pis, zs, capacity, cursor, list, n_list);
-    }, list != nullptr, e->cp.n_fast != 0, e->emit.n != 0);
+    with_flags([&](auto by_list, auto cap, auto sym, auto surprise) {   // sym: emit_elements, the mask's elements on any geometry
+        const EmitPack<cap.value, sym.value, surprise.value> a{d, on<cap.value>(e->cp), on<sym.value>(e->emit), on<surprise.value>(e->sp)};
+        k_emit_alloc<cap.value, sym.value, surprise.value><<<per_game, 256, 0, st>>>(a, cursor, game_base);
+        k_emit_tuples<by_list.value, cap.value, sym.value, surprise.value><<<blocks, AZK_WAVE, lds, st>>>(a, states, pis, zs, capacity, cursor, list, n_list);
+    }, list != nullptr, e->cp.n_fast != 0, e->emit.n != 0, e->sp_on);
     k_emit_mark<<<per_game, 256, 0, st>>>(d);
 }
 
@@ -1197,6 +1272,56 @@ int32_t azk_async_resign_flags(azk_engine *e, uint8_t *rec_resigned_dev) {
     return AZK_OK;
 }
 
+// ---- policy surprise weighting ------------------------------------------------------------------------------------------
+int32_t azk_set_surprise_weighting(azk_engine *e, double lambda, uint64_t seed, int64_t first_global_game, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_surprise_weighting: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (!(lambda >= 0.0 && lambda <= 1.0)) { e->err = "azk_set_surprise_weighting: lambda must lie in [0, 1] (azk_clear_surprise_weighting switches the option off)"; return AZK_ERR_ARG; }
+    if (e->d.K > 1) { e->err = "azk_set_surprise_weighting: surprise weighting does not combine with leaves_per_step > 1 (a virtual-loss search's visit counts are not the ones the weight was defined on)"; return AZK_ERR_ARG; }
+    const Dev &d = e->d;
+    if (!d.traj_pi) { e->err = "azk_set_surprise_weighting: the engine records no trajectories (a square board with one action per cell, or an engine created with emit_elements)"; return AZK_ERR_ARG; }
+    SurpriseDev &s = e->sp;
+    const size_t plies = (size_t)d.G * d.g.state_dim;
+    if (!s.traj_kl) {
+        HIPCHK(e, dalloc(e, &s.traj_kl, plies));
+        HIPCHK(e, dalloc(e, &s.traj_coin, plies));
+        HIPCHK(e, dalloc(e, &s.traj_copies, plies));
+        HIPCHK(e, dalloc(e, &s.last_kl, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &s.last_coin, (size_t)d.G));
+    }
+    HIPCHK(e, hipMemsetAsync(s.traj_kl, 0, sizeof(double) * plies, (hipStream_t)stream));
+    HIPCHK(e, hipMemsetAsync(s.traj_coin, 0, sizeof(double) * plies, (hipStream_t)stream));
+    HIPCHK(e, hipMemsetAsync(s.traj_copies, 0, sizeof(uint16_t) * plies, (hipStream_t)stream));
+    HIPCHK(e, hipMemsetAsync(s.last_kl, 0, sizeof(double) * (size_t)d.G, (hipStream_t)stream));
+    HIPCHK(e, hipMemsetAsync(s.last_coin, 0, sizeof(double) * (size_t)d.G, (hipStream_t)stream));
+    s.lambda = lambda; s.seed = seed; s.first_game = first_global_game; s.rec_kl = nullptr; s.rec_coin = nullptr;
+    e->sp_on = true;
+    return AZK_OK;
+}
+
+int32_t azk_clear_surprise_weighting(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_surprise_weighting: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    e->sp_on = false;                                             // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+int32_t azk_get_surprise(azk_engine *e, double *kl_dev, double *coin_dev, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (!e->sp_on) { e->err = "azk_get_surprise: no surprise weighting is set (azk_set_surprise_weighting)"; return AZK_ERR_STATE; }
+    if (kl_dev) HIPCHK(e, hipMemcpyAsync(kl_dev, e->sp.last_kl, sizeof(double) * (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (coin_dev) HIPCHK(e, hipMemcpyAsync(coin_dev, e->sp.last_coin, sizeof(double) * (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_async_surprise_columns(azk_engine *e, double *rec_kl_dev, double *rec_coin_dev) {
+    if (!e) return AZK_ERR_ARG;
+    if (!e->sp_on) { e->err = "azk_async_surprise_columns: no surprise weighting is set (azk_set_surprise_weighting)"; return AZK_ERR_STATE; }
+    if (e->async_on) { e->err = "azk_async_surprise_columns: call it before azk_async_begin"; return AZK_ERR_STATE; }
+    e->sp.rec_kl = rec_kl_dev; e->sp.rec_coin = rec_coin_dev;
+    return AZK_OK;
+}
+
 // ---- asynchronous self-play ---------------------------------------------------------------------------------------------
 static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *stream, bool reuse) {
     if (!e || !c || !c->stats_dev || c->n_sims < 1 || c->n_sims > e->cfg.max_sims || c->max_sims_per_launch < 1 || !(c->alpha > 0.0)) {
@@ -1251,6 +1376,7 @@ static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *strea
         const int32_t rc = resign_clear(e, st);
         if (rc != AZK_OK) return rc;
     }
+    if (e->sp_on) { e->sp.seed = a.seed; e->sp.first_game = a.first_game; }      // ... and the ply coins of surprise weighting
     // first search of every game: fresh roots + the Dirichlet rows of move keys 0 (this search) and 1 (the next one)
     if (e->cp.n_fast) { e->cp.seed = a.seed; e->cp.first_game = a.first_game; e->cp.stats = a.stats; }   // the coins share the noise rows' key: this run's seed and first game
     with_flags([&](auto cap) { k_begin_search<cap.value><<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(cap_key_pack<cap.value>(d, e, 0)); }, e->cp.n_fast != 0);
@@ -1275,10 +1401,10 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
     hipStream_t st = (hipStream_t)stream;
     if (phases & 1) { const int32_t rc = azk_launch_tree(e, true, true, true, logits_dev, values_dev, st); if (rc != AZK_OK) return rc; }
     if (phases & 2)
-        with_flags([&](auto reroot, auto cap, auto resign, auto forced) {
-            k_move_async<reroot.value, cap.value, resign.value, forced.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(
-                d, e->ad, move_pack<cap.value, resign.value, forced.value>(e->ru, e));
-        }, e->ru.mode != 0, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0);
+        with_flags([&](auto reroot, auto cap, auto resign, auto forced, auto surprise) {
+            k_move_async<reroot.value, cap.value, resign.value, forced.value, surprise.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(
+                d, e->ad, move_pack<cap.value, resign.value, forced.value, surprise.value>(e->ru, e));
+        }, e->ru.mode != 0, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0, e->sp_on);
     HIPCHK(e, hipGetLastError());
     return azk_sym_leaves(e, st);                                 // (eval symmetry: the leaves the tree launch selected, behind the movers)
 }
@@ -1351,12 +1477,12 @@ static int32_t advance(azk_engine *e, const double *uniforms_dev, int32_t sample
                        int32_t *winner_dev, int32_t *done_dev, void *stream) {
     const Dev &d = e->d;
     e->in_search = false;
-    with_flags([&](auto cap, auto resign, auto forced) {
-        Ply<resign.value> ply{sample_until_move};
-        if constexpr (resign.value) ply.move_index = move_index;
-        k_advance<cap.value, resign.value, forced.value><<<d.G, AZK_WAVE, d.lds_bytes, (hipStream_t)stream>>>(
-            move_pack<cap.value, resign.value, forced.value>(d, e), uniforms_dev, ply, chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
-    }, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0);
+    with_flags([&](auto cap, auto resign, auto forced, auto surprise) {
+        Ply<resign.value || surprise.value> ply{sample_until_move};
+        if constexpr (resign.value || surprise.value) ply.move_index = move_index;
+        k_advance<cap.value, resign.value, forced.value, surprise.value><<<d.G, AZK_WAVE, d.lds_bytes, (hipStream_t)stream>>>(
+            move_pack<cap.value, resign.value, forced.value, surprise.value>(d, e), uniforms_dev, ply, chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
+    }, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0, e->sp_on);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -1364,6 +1490,7 @@ static int32_t advance(azk_engine *e, const double *uniforms_dev, int32_t sample
 int32_t azk_advance(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t *chosen_cell_dev,
                     int32_t *winner_dev, int32_t *done_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
+    if (e->sp_on) { e->err = "azk_advance: surprise weighting is set - its moves are made by azk_advance_keyed (the ply coin needs the move index)"; return AZK_ERR_STATE; }
     if (e->rs.v_resign != 0.0) { e->err = "azk_advance: resignation is set - its moves are made by azk_advance_resign (the game coin needs the move index)"; return AZK_ERR_STATE; }
     return advance(e, uniforms_dev, sample_until_move, 0, chosen_cell_dev, winner_dev, done_dev, stream);
 }
@@ -1371,7 +1498,15 @@ int32_t azk_advance(azk_engine *e, const double *uniforms_dev, int32_t sample_un
 int32_t azk_advance_resign(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t move_index, int32_t *chosen_cell_dev,
                            int32_t *winner_dev, int32_t *done_dev, void *stream) {
     if (!e || move_index < 0) { if (e) e->err = "azk_advance_resign: bad argument"; return AZK_ERR_ARG; }
+    if (e->sp_on) { e->err = "azk_advance_resign: surprise weighting is set - its moves are made by azk_advance_keyed"; return AZK_ERR_STATE; }
     if (e->rs.v_resign == 0.0) { e->err = "azk_advance_resign: no resignation is set (azk_set_resign)"; return AZK_ERR_STATE; }
+    return advance(e, uniforms_dev, sample_until_move, move_index, chosen_cell_dev, winner_dev, done_dev, stream);
+}
+
+int32_t azk_advance_keyed(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t move_index, int32_t *chosen_cell_dev,
+                          int32_t *winner_dev, int32_t *done_dev, void *stream) {
+    if (!e || move_index < 0) { if (e) e->err = "azk_advance_keyed: bad argument"; return AZK_ERR_ARG; }
+    if (!e->sp_on) { e->err = "azk_advance_keyed: no surprise weighting is set (azk_set_surprise_weighting)"; return AZK_ERR_STATE; }
     return advance(e, uniforms_dev, sample_until_move, move_index, chosen_cell_dev, winner_dev, done_dev, stream);
 }
 

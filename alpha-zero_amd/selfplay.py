@@ -152,6 +152,54 @@ def check_emit_symmetry(emit_symmetry, game, size=None):
     return mask
 
 
+def _is_vanilla(evaluator):
+    return evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))
+
+
+def check_surprise_weight(surprise_weight, evaluator=True, leaves_per_step=1):
+    """surprise_weight = lambda -> float in [0, 1], or None for off.  OPT-IN policy surprise weighting (include/azk.h azk_set_surprise_weighting;
+    DESIGN section 23): every move records kl = KL(recorded pi || the network's raw prior) and a keyed coin, and a finished game's recorded
+    ply i is stored floor(w_i) + (coin_i < frac(w_i)) times, w_i = (1 - lambda) + lambda * n * kl_i / sum(kl).  lambda = 0 is a live setting
+    (one copy each; kl and coin are still recorded).  Raises ValueError, before any engine exists, for what the engine refuses too - lambda
+    outside [0, 1] or NaN, virtual loss - and for vanilla MCTS (evaluator None), which has no priors to be surprised about."""
+    if surprise_weight is None:
+        return None
+    try:
+        if isinstance(surprise_weight, bool):
+            raise TypeError
+        lam = float(surprise_weight)
+    except (TypeError, ValueError):
+        raise ValueError(f"surprise_weight must be a number lambda in [0, 1], not {surprise_weight!r}")
+    if not 0.0 <= lam <= 1.0:                                     # (NaN fails both comparisons)
+        raise ValueError(f"surprise_weight: lambda must lie in [0, 1] (None switches the option off), not {surprise_weight!r}")
+    if _is_vanilla(evaluator):
+        raise ValueError("surprise_weight: vanilla MCTS (evaluator None) is refused - it has no priors for the search to disagree with")
+    if int(leaves_per_step) > 1:
+        raise ValueError("surprise_weight does not combine with leaves_per_step > 1 (a virtual-loss search's visit counts are not the ones the weight was defined on)")
+    return lam
+
+
+def surprise_copies(kl, coin, lam, full=None):
+    """The emission rule of surprise weighting for one finished game, for host buffers (train.save_data_to_buffer(copies=...)): kl, coin = the
+    game's per-ply records (SelfPlayResult.kl / .coin), full = the playout cap's per-ply flags (None: every ply is recorded).  -> int array,
+    copies per ply: with F the recorded plies, n = |F| and S = the sum of kl over F in ply order,
+        w_i = S > 0 ? (1 - lam) + ((lam * n) * kl_i) / S : 1,    c_i = floor(w_i) + (coin_i < w_i - floor(w_i)),    0 outside F
+    in float64, operation for operation what k_emit_alloc computes."""
+    kl, coin = np.asarray(kl, np.float64), np.asarray(coin, np.float64)
+    rec = np.ones(len(kl), bool) if full is None else np.asarray(full, bool)
+    lam = np.float64(lam)
+    n = np.float64(int(rec.sum()))
+    S = np.float64(0.0)
+    for i in np.nonzero(rec)[0]:
+        S = S + kl[i]
+    out = np.zeros(len(kl), np.int64)
+    for i in np.nonzero(rec)[0]:
+        w = (np.float64(1.0) - lam) + ((lam * n) * kl[i]) / S if S > 0.0 else np.float64(1.0)
+        f = np.floor(w)
+        out[i] = int(f) + (1 if coin[i] < w - f else 0)
+    return out
+
+
 def mask_elements(mask):
     """The elements of an emission mask, ascending."""
     return tuple(s for s in range(8) if (mask >> s) & 1)
@@ -163,13 +211,14 @@ def _refuse_vanilla_resign(resign, evaluator):
 
 
 class SelfPlayResult:
-    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base", "full", "resigned")
+    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base", "full", "resigned", "kl", "coin")
 
     def __init__(self):
         self.boards, self.actions, self.pis, self.qs, self.winner, self.cells = [], [(-1, -1)], [], [], None, []
         self.full = []               # per ply: was its search a full one (always True without playout_cap); only those plies are trained on
         self.replay_base = None      # first tuple index in the DeviceReplay stream (when a replay ring is attached)
         self.resigned = False        # the game ended by resignation (resign=...): winner is then the side that did not concede
+        self.kl, self.coin = [], []  # per ply with surprise_weight=...: KL(recorded pi || raw prior) and the ply's coin (empty without)
 
     def as_reference_tuple(self):
         """(boards, actions, policy_distributions, qs, winner) - gomoku.py:164"""
@@ -180,7 +229,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                     alpha=0.03, noise_fn=None, uniform_fn=None, device=0, leaf_dtype="float32", engine=None,
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
                     budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
-                    eval_symmetry=None, emit_symmetry=None):
+                    eval_symmetry=None, emit_symmetry=None, surprise_weight=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -201,7 +250,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     eval_symmetry = True | ("fixed", s) (OPT-IN, check_eval_symmetry): every leaf is evaluated in an orientation keyed by (seed, its position),
     or in the one given.  emit_symmetry = "board" | "none" | elements (OPT-IN, check_emit_symmetry): the replay ring gets every ply from the
     third on once per element of the mask, on every geometry (Connect4 and non-square Gomoku included); an engine handed in must have
-    been created with the same mask (ValueError).
+    been created with the same mask (ValueError).  surprise_weight = lambda (OPT-IN, check_surprise_weight): every ply records its policy surprise
+    and coin (SelfPlayResult.kl / .coin) and the replay ring gets each recorded ply as often as its weight says (surprise_copies).
     """
     import torch
     emit = check_emit_symmetry(emit_symmetry, game, size)
@@ -211,6 +261,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     rsg = check_resign(resign, leaves_per_step)
     fpk = check_forced_playouts(forced_playouts, evaluator, dirichlet, leaves_per_step)
     sym = check_eval_symmetry(eval_symmetry, game, size, evaluator, leaves_per_step, seed)
+    lam = check_surprise_weight(surprise_weight, evaluator, leaves_per_step)
     _refuse_vanilla_resign(rsg, evaluator)
     if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
@@ -226,6 +277,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         eng.set_forced_playouts(fpk)
     if sym is not None:
         eng.set_eval_symmetry(*sym)
+    if lam is not None:
+        eng.set_surprise_weighting(lam, seed, first_global_game)
     # virtual-loss, top-up and capped engines are driven by the simulation budget
     budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
     assert eng.G == n_games
@@ -270,6 +323,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         cells_before, to_move, _ = eng.get_positions()
         chosen, winner, done = eng.advance(uni, su, move_index=move)
         resigned_h = eng.resigned().cpu().numpy() if eng.resign is not None else None
+        kl_h, coin_h = [t.cpu().numpy() for t in eng.surprise()] if eng.surprise_weight is not None else (None, None)
         bases = eng.emit_finished(replay).cpu().numpy() if replay is not None else None     # train.save_data_to_buffer on device
         pi_h, q_h = pi.cpu().numpy(), q.cpu().numpy()
         chosen_h, winner_h, done_h = chosen.cpu().numpy(), winner.cpu().numpy(), done.cpu().numpy()
@@ -279,6 +333,9 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
             r.pis.append(pi_h[g].copy())
             r.qs.append(float(q_h[g]))
             r.full.append(True if full_h is None else bool(full_h[g]))
+            if kl_h is not None:
+                r.kl.append(float(kl_h[g]))
+                r.coin.append(float(coin_h[g]))
             c = int(chosen_h[g])
             r.cells.append(c)
             r.actions.append((c // eng.cols, c % eng.cols))
@@ -314,6 +371,8 @@ class _Half:
         self.h_stats = torch.zeros(8, dtype=torch.int64, **pin)
         self.h_full = torch.ones(e.G, dtype=torch.uint8, **pin)      # playout cap: kind of each slot's search (1 = full); all ones without
         self.h_resigned = torch.zeros(e.G, dtype=torch.uint8, **pin)  # resignation: 1 = the slot's move conceded the game; all zeros without
+        self.h_kl = torch.zeros(e.G, dtype=torch.float64, **pin)      # surprise weighting: kl and coin of each slot's move; zeros without
+        self.h_coin = torch.zeros(e.G, dtype=torch.float64, **pin)
         # static buffers so a captured step graph always sees the same addresses
         self.noise_buf = torch.zeros((e.G, e.action_dim), dtype=torch.float64, device=e.device) if dirichlet else None
         self.logits_buf = torch.zeros((e.slots, e.action_dim), dtype=torch.float32, device=e.device)
@@ -415,15 +474,22 @@ class SelfPlayRunner:
 
     emit_symmetry = "board" | "none" | elements (OPT-IN, check_emit_symmetry; with everything above): the replay ring gets every ply from the
     third on once per element of the mask, on every geometry; the engines are created with it.
+
+    surprise_weight = lambda (OPT-IN, check_surprise_weight; with everything above): every move records its policy surprise and coin -
+    `record_surprise` ((kl, coin), float64 [group size] each, valid inside on_records) - and the replay ring gets each recorded ply as often as
+    its weight says.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
                  alpha=0.03, device=0, leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None,
                  use_graph=False, n_split=1, replay=None, cache_entries=0, cache_shared=False, budget_stepping=False, per_launch=8,
                  steps_per_graph=32,
-                 leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None):
+                 leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None,
+                 surprise_weight=None):
         import torch
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
+        self.surprise_weight = check_surprise_weight(surprise_weight, evaluator, leaves_per_step)
+        self.record_surprise = None
         self.eval_symmetry = check_eval_symmetry(eval_symmetry, game, size, evaluator, leaves_per_step, seed)
         self.playout_cap = check_playout_cap(playout_cap, n_sims, leaves_per_step)
         self.resign = check_resign(resign, leaves_per_step)
@@ -473,6 +539,8 @@ class SelfPlayRunner:
                 h.eng.set_forced_playouts(self.forced_playouts)
             if self.eval_symmetry is not None:
                 h.eng.set_eval_symmetry(*self.eval_symmetry)      # (the key is the position: the same for every group)
+            if self.surprise_weight is not None:
+                h.eng.set_surprise_weighting(self.surprise_weight, seed, first_global_game + i * per)
 
     # ---- one move for every slot -------------------------------------------------------------------------
     def play_move(self):
@@ -498,6 +566,10 @@ class SelfPlayRunner:
             chosen, winner, done = e.advance(h.uni, self.sample_until, move_index=self.move_idx)
             if self.resign is not None:
                 h.h_resigned.copy_(e.resigned(), non_blocking=True)
+            if self.surprise_weight is not None:
+                kl, coin = e.surprise()
+                h.h_kl.copy_(kl, non_blocking=True)
+                h.h_coin.copy_(coin, non_blocking=True)
             h.h_chosen.copy_(chosen, non_blocking=True)
             h.h_winner.copy_(winner, non_blocking=True)
             h.h_done.copy_(done, non_blocking=True)
@@ -511,6 +583,7 @@ class SelfPlayRunner:
             self.plies_played += int((h.h_chosen >= 0).sum())
             if self.on_records is not None:
                 self.record_full, self.record_resigned = h.h_full, h.h_resigned
+                self.record_surprise = (h.h_kl, h.h_coin) if self.surprise_weight is not None else None
                 self.on_records(self.move_idx, i * per, h.h_pi, h.h_q, h.h_chosen, h.h_winner, h.h_done)
         self.move_idx += 1
 
@@ -731,14 +804,20 @@ class AsyncSelfPlayRunner:
     for slot - the element is a function of the position, so it does not matter which step evaluates a leaf.
 
     emit_symmetry = "board" | "none" | elements (OPT-IN, check_emit_symmetry; with everything above): the drain emits every ply from the third
-    on once per element of the mask, on every geometry - the tuples of SelfPlayRunner(emit_symmetry=...)."""
+    on once per element of the mask, on every geometry - the tuples of SelfPlayRunner(emit_symmetry=...).
+
+    surprise_weight = lambda (OPT-IN, check_surprise_weight; with everything above): the games and records of SelfPlayRunner(surprise_weight=...),
+    slot for slot - the move kernel records kl and coin, the drain writes each recorded ply as often as its weight says.  `record_surprise`
+    ((kl, coin), float64 numpy, one per record, valid inside on_records) carries them."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
-                 playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None):
+                 playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None):
         import torch
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
+        self.surprise_weight = check_surprise_weight(surprise_weight, evaluator)
+        self.record_surprise = None
         self.eval_symmetry = check_eval_symmetry(eval_symmetry, game, size, evaluator, 1, seed)
         self.playout_cap = check_playout_cap(playout_cap, n_sims)
         self.resign = check_resign(resign)
@@ -770,6 +849,8 @@ class AsyncSelfPlayRunner:
             e.set_forced_playouts(self.forced_playouts)
         if self.eval_symmetry is not None:
             e.set_eval_symmetry(*self.eval_symmetry)
+        if self.surprise_weight is not None:
+            e.set_surprise_weighting(self.surprise_weight, seed, first_global_game)
         cap = (4 * n_games if record_capacity is None else record_capacity) if (on_records is not None or record_capacity) else 0
         self.stats, self.records = e.async_begin(n_sims, self.per_launch, SAMPLE_UNTIL[game], seed, first_global_game, alpha, dirichlet, recycle, cap,
                                                  young_launch_us=young_launch_us, reroot=bool(self.reroot))
@@ -874,6 +955,8 @@ class AsyncSelfPlayRunner:
                 self.record_full = self.records["full"][idx].cpu().numpy()
             if "resigned" in self.records:
                 self.record_resigned = self.records["resigned"][idx].cpu().numpy()
+            if "kl" in self.records:
+                self.record_surprise = (self.records["kl"][idx].cpu().numpy(), self.records["coin"][idx].cpu().numpy())
         self.rec_read = cursor
         self.on_records(meta, q, pi)
 

@@ -1,7 +1,7 @@
 """train.py of the reference (train.py:8-123) with its names and signatures, on the batched engine.
 
     collect_data(Game, model, buffer, iterations, mcts_iter, display=False)   train.py:54-83
-    save_data_to_buffer(Game, buffer, data, full=None, elements=None)         train.py:30-49
+    save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=None)   train.py:30-49
     rotate_data / flip_data                                                   train.py:8-27
     train(model, batch_size, buffer, train_iterations, lr, device, augment=None)   train.py:85-123
 
@@ -55,12 +55,33 @@ def element_image(board, policy, s):
     return b, (policy[::-1].copy() if s == 1 else policy.copy())
 
 
-def save_data_to_buffer(Game, buffer, data, full=None, elements=None):
+def _add_group(Game, buffer, canon, policy, target, i, elements):
+    """One position's tuples: once for positions 0 and 1, else the reference's eight images, or one per element."""
+    if i < 2:
+        buffer.add(canon, policy, target)
+        return
+    if elements is not None:
+        for s in elements:
+            b, p = element_image(np.asarray(canon), policy, s)
+            buffer.add(b, p, target)
+        return
+    for r in range(4):
+        b, p = rotate_data(canon, policy, k=r)
+        buffer.add(b, p, target)
+        if r < 2:
+            for mode in ("lr", "tb"):
+                fb, fp = flip_data(b, p, mode)
+                buffer.add(fb, fp, target)
+
+
+def save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=None):
     """train.py:30-49: z = +reward for the winner's positions, -reward for the loser's; canonical boards; positions 0 and 1
     once, every later position with its 8 dihedral images in the reference's order.  full (playout cap, SelfPlayResult.full): one flag
     per position; the positions of fast searches are left out, the others keep the group they would have had.  elements (OPT-IN; None:
     the reference's code path): a tuple of D4 elements, ascending - every later position once per element instead (element_image), on any
-    board and for Connect4's column actions: what an engine created with that emit_symmetry puts into a DeviceReplay."""
+    board and for Connect4's column actions: what an engine created with that emit_symmetry puts into a DeviceReplay.  copies (OPT-IN surprise
+    weighting; None: once each): one count per position (selfplay.surprise_copies) - the position's whole group is added that many times, copy
+    after copy, what an engine with surprise weighting puts into a DeviceReplay; a position with 0 copies is left out."""
     boards, actions, policies, qs, winner, reward = data
     current = 0
     for i in range(len(boards)):
@@ -69,25 +90,12 @@ def save_data_to_buffer(Game, buffer, data, full=None, elements=None):
         current = 1 - current
         if full is not None and not full[i]:
             continue
-        if i < 2:
-            buffer.add(canon, policies[i], target)
-            continue
-        if elements is not None:
-            for s in elements:
-                b, p = element_image(np.asarray(canon), policies[i], s)
-                buffer.add(b, p, target)
-            continue
-        for r in range(4):
-            b, p = rotate_data(canon, policies[i], k=r)
-            buffer.add(b, p, target)
-            if r < 2:
-                for mode in ("lr", "tb"):
-                    fb, fp = flip_data(b, p, mode)
-                    buffer.add(fb, fp, target)
+        for _ in range(1 if copies is None else int(copies[i])):
+            _add_group(Game, buffer, canon, policies[i], target, i, elements)
 
 
 def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed=None, batched=True, playout_cap=None, resign=None,
-                 forced_playouts=None, eval_symmetry=None, emit_symmetry=None):
+                 forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None):
     """train.py:54-83: `iterations` self-play games of Game with `model` into `buffer`; returns [first, second, draw] counts.
     batched=False plays the games one after the other through Game().self_play and save_data_to_buffer exactly as the
     reference does (global np.random stream: a seeded caller gets the reference's buffer); the default plays them as one
@@ -98,10 +106,15 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     forced playouts at the root; both buffer kinds get the pruned pi of every stored position.  eval_symmetry = True | ("fixed", s) (OPT-IN,
     batched only; selfplay.check_eval_symmetry): every leaf is evaluated in an orientation keyed by (seed, its position), or in the one given.
     emit_symmetry = "board" | "none" | elements (OPT-IN, batched only; selfplay.check_emit_symmetry): every position from the third on is stored
-    once per element of the mask, on every board - Connect4 and non-square Gomoku included; both buffer kinds get the same tuples."""
+    once per element of the mask, on every board - Connect4 and non-square Gomoku included; both buffer kinds get the same tuples.
+    surprise_weight = lambda (OPT-IN, batched only; selfplay.check_surprise_weight): every stored position is stored as often as its policy
+    surprise weight says (selfplay.surprise_copies); both buffer kinds get the same tuples."""
     from azk import DeviceReplay
-    from selfplay import check_emit_symmetry, mask_elements, self_play_batch
+    from selfplay import check_emit_symmetry, check_surprise_weight, mask_elements, self_play_batch, surprise_copies
+    lam = check_surprise_weight(surprise_weight, model)
     if not batched:
+        if lam is not None:
+            raise ValueError("collect_data: surprise_weight needs the batched engine (batched=True)")
         if emit_symmetry is not None:
             raise ValueError("collect_data: emit_symmetry needs the batched engine (batched=True)")
         if playout_cap is not None:
@@ -125,15 +138,17 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     leaf_dtype = "bfloat16" if getattr(model, "dtype", None) is not None and str(model.dtype).endswith("bfloat16") else "float32"
     res = self_play_batch(Game.engine_name, model, iterations, mcts_iter, size=Game._size(), seed=seed, leaf_dtype=leaf_dtype,
                           replay=buffer if on_device else None, playout_cap=playout_cap, resign=resign, forced_playouts=forced_playouts,
-                          eval_symmetry=eval_symmetry, emit_symmetry=emit_symmetry)
+                          eval_symmetry=eval_symmetry, emit_symmetry=emit_symmetry, surprise_weight=surprise_weight)
     emit = check_emit_symmetry(emit_symmetry, Game.engine_name, Game._size())
     results = [0, 0, 0]
     for r in res:
         results[2 if r.winner == -1 else r.winner] += 1
         if not on_device:
             reward = 0 if r.winner == -1 else 1
-            save_data_to_buffer(Game, buffer, (r.boards, r.actions, r.pis, r.qs, r.winner, reward), full=r.full if playout_cap is not None else None,
-                                elements=mask_elements(emit) if emit else None)
+            full = r.full if playout_cap is not None else None
+            save_data_to_buffer(Game, buffer, (r.boards, r.actions, r.pis, r.qs, r.winner, reward), full=full,
+                                elements=mask_elements(emit) if emit else None,
+                                copies=surprise_copies(r.kl, r.coin, lam, full) if lam is not None else None)
         if display:
             Game.display_board(r.boards[-1])
     return results

@@ -345,6 +345,48 @@ int32_t azk_set_eval_symmetry(azk_engine *e, int32_t mode, uint64_t seed_or_elem
 int32_t azk_get_leaf_symmetry(azk_engine *e, uint8_t *out_dev, void *stream);
 int32_t azk_eval_symmetry_restore(azk_engine *e, const float *logits_dev, float *out_dev, void *stream);
 
+/* ---- policy surprise weighting (OPT-IN; off, the engine is what it was bit for bit).  KataGo's data-weighting rule ("KataGoMethods"): a
+ * recorded ply is written into the replay ring with a frequency proportional to how much the search disagreed with the network's own
+ * prior, so that the positions the network is most wrong about are seen most often - while a game still writes, in expectation, as many
+ * tuples as it has recorded plies.  Games, searches, moves and q are untouched.  All arithmetic float64.
+ *   kl         at each move, after the forced-playout pruning, on the counts m_a and their sum the recorded pi is made of: over the root's
+ *              children with m > 0,  p = (double)m / (double)sum,  P = (double)max(prior, 0x1p-126f),  t = p * log(p / P);
+ *              kl = max(0.0, sum of t).  prior is the child's RAW float32 softmax entry as the tree stores it (the softmax over all A
+ *              actions, turned back where evaluation symmetry is on) - not the root's Dirichlet mix.  Each lane of the mover's wave sums
+ *              its children (i, i + 64, ...) in list order and the wave adds the 64 partial sums pairwise (xor butterfly 32, 16, .. 1); log
+ *              is the device library's float64 log.
+ *   the coin   one per ply: Philox4x32-10, counter {global game lo, global game hi, move key, 0xFFFFFFFC}, key (seed lo, seed hi),
+ *              u = ((c0 << 32 | c1) >> 11) * 2^-53.  The move key is the slot's move counter (the move_index of the search's noise row).
+ *              Word 3 = 0xFFFFFFFC belongs to no other draw, so every noise row, move uniform, playout-cap coin and resignation coin is
+ *              unchanged and the coins do not depend on the sharding.
+ *   record     kl and coin go into two float64 trajectory columns [G][state_dim] beside the ply's pi, and into a per-game pair that holds
+ *              what the game's last move recorded (azk_get_surprise).  On a capped engine fast plies record both too; they carry no weight.
+ *   emission   for a finished game with recorded plies F (all plies; on a capped engine the full ones), n_F = |F|, S = the sequential
+ *              sum of kl_i over F in ply order:
+ *                  w_i = S > 0 ? (1.0 - lambda) + ((lambda * (double)n_F) * kl_i) / S : 1.0
+ *                  c_i = (int)floor(w_i) + (coin_i < w_i - floor(w_i) ? 1 : 0)                 (0 for plies outside F)
+ *              The game reserves sum c_i * grp_i tuples (grp_i = 1 for plies 0 and 1, else the ply's group: 8, or the mask's elements with
+ *              emit_elements); ply i's tuples start at base + sum_{j<i} c_j * grp_j and lie copy-major - copy 0's whole group, then copy
+ *              1's - each group byte for byte the one the ply gets without the option.  Ring slot t % capacity, the 64-bit cursor,
+ *              game_base_dev, the pushed-out skip, z and the asynchronous drain are as ever.  sum w_i = n_F, so the ring fills at the rate
+ *              it fills without the option; lambda = 0 gives c_i = 1: the option-off ring, byte for byte, with kl and coin still recorded.
+ * azk_set_surprise_weighting: lambda in [0, 1] (lambda = 0 is a live setting), else - NaN included - AZK_ERR_ARG; not with leaves_per_step
+ * > 1 and not on an engine without trajectory buffers (where azk_emit_finished answers AZK_ERR_ARG): AZK_ERR_ARG.  Allocates the three
+ * columns at first use.  Call it before azk_async_begin(_reuse), which then keys the coin by ITS seed and first_global_game.
+ * azk_clear_surprise_weighting switches the option off: the engine launches what it launched before.  Lock-step drivers move with
+ * azk_advance_keyed = azk_advance + move_index (it applies resignation too where that is set); azk_advance and azk_advance_resign answer
+ * AZK_ERR_STATE while the option is set, azk_advance_keyed while it is not.  Combines with tree_reuse, the playout cap, resignation, forced
+ * playouts (kl of the pruned pi), evaluation symmetry, emit_elements and the asynchronous movers.
+ * azk_get_surprise: float64 [G] each into device memory, the kl and the coin each game's last move recorded (either pointer may be NULL;
+ * asynchronous copies on the stream).  azk_async_surprise_columns (optional, before azk_async_begin): float64 [record_capacity] columns of
+ * the record ring, entry r % capacity = record r's kl and coin (either may be NULL). */
+int32_t azk_set_surprise_weighting(azk_engine *e, double lambda, uint64_t seed, int64_t first_global_game, void *stream);
+int32_t azk_clear_surprise_weighting(azk_engine *e);
+int32_t azk_advance_keyed(azk_engine *e, const double *uniforms_dev, int32_t sample_until_move, int32_t move_index,
+                          int32_t *chosen_cell_dev, int32_t *winner_dev, int32_t *done_dev, void *stream);
+int32_t azk_get_surprise(azk_engine *e, double *kl_dev, double *coin_dev, void *stream);
+int32_t azk_async_surprise_columns(azk_engine *e, double *rec_kl_dev, double *rec_coin_dev);
+
 /* One simulation per active game (ai/mcts.py:16-60), split around the evaluator:
  *   azk_step_select   - mcts.py:18-37: PUCT walk (node.py:42-47, utils.py:29-44), make_move along the
  *                       path, terminal test + immediate backup, get_valid_moves, canonical board.

@@ -21,10 +21,10 @@
 //   are linear in them, and the value-projected pooled row u_h = (1/L_h) sum_t a_t[h] (M_h p_t + D_t[h]) is linear in x_t: what a
 //   board contributes is, per head, one weight per token, 1/L, and the pooled patch sum_t a_t p_t / L - 384 bf16 per head, which the
 //   tail's first GEMM multiplies with [D_t; U_all; M_h].  No conv, no D-wide normalisation, no gather of D-wide rows.
-//   Board queue, leaf ranks, board bits, patch bits and the compaction of the stone-touched ("dirty") tokens do what the front end of
+//   Board hand-out, leaf ranks, board bits, patch bits and the compaction of the stone-touched ("dirty") tokens do what the front end of
 //   k_embed_pool_c (azk_embed_conv.hip) and k_embed_pool_x (azk_nnx.hip) does, in a copy that is tuned apart on purpose: the rank scan
 //   runs on DPP (no shuffles), the ranks are inverted once into an LDS table (gor: game of rank r) instead of searched per board, and
-//   the next board's cell codes are prefetched under the output phase (load_cells).
+//   the next board - known from a fixed schedule, no queue - has its cell codes prefetched behind the last tile (load_cells).
 //   Tile loop: a WAVE owns 16-token tiles (tile = wave, wave + 4, ...), nothing between the waves until the board's sums meet:
 //     Y = P G (16 x 64, fp16 hi + lo terms: exact products with the 0/1 patch), E = P S (scores), both v_mfma_f32_16x16x32_f16;
 //     var_t = (sum_k p_tk (Y_tk + u2_tk) + n_t) / D from the accumulator layout (DPP row sum); w = exp(rstd (E + sc) - ref);
@@ -44,7 +44,7 @@ struct EmbedFoldArgs {
     const float *u2T, *scoreT, *wcT, *lall, *sref, *inv_scales;
     void *out;                     // [n][NH][FOLD_ROW] bf16 (EX: float32)
     const int *count;
-    int *sched;
+    int *sched;                    // two zero words of the caller's: the boards are handed out by a fixed schedule, the kernel touches neither
     unsigned long long *wstats;
     long long *dbg;                // debug only (AZK_EP_STAMPS build + AZK_EMBED_POOL_STAMPS): [8] cycle sums per phase, wave 0 of every workgroup
     int n, R, Cc, T;
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
     const int Tp16 = ((a.T + 15) >> 4) << 4;
     uint2 *pbits = (uint2 *)(alut + 256);                         // [Tp16] patch bits of the compacted dirty tokens
     int *dlist = (int *)(pbits + Tp16);                           // [Tp16] their token indices (null token = T past the end)
-    int *scan = dlist + Tp16;                                     // [4 dirty counts per wave at 4..7], [10] next ticket, [16..31] class totals of the rank scan
+    int *scan = dlist + Tp16;                                     // [4 dirty counts per wave at 4..7], [16..31] class totals of the rank scan
     float *lred = (float *)(scan + 32);                           // [4 waves][8 heads]
     float *lall_s = lred + 32;                                    // [8] l_all
     float *bw = lall_s + 8;                                       // [Tp16][8]  a - aconst per dirty token and head
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
     AZK_FSTAMP(0);                                                // launch prologue: ranks, fragments staged
 
     // Boards of up to 512 plane cells: every load of a board is issued at once (one round trip), and the NEXT board's loads are issued
-    // as soon as its ticket is known - behind the tiles' barrier, under the output phase - so a board starts with its cells on hand.
+    // behind the wave's last tile - in front of the sums' barrier and the output phase - so a board starts with its cells on hand.
     constexpr int NQ = 8;
     const bool fast = ncell <= 64 * NQ;
     int codeN[NQ], tmN = 0, ldN = 0, game = 0;
@@ -222,8 +222,8 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
         }
         tmN = a.src.to_move[g]; ldN = a.src.leaf_depth[g];
     };
-    // (a board's ticket and its game are LDS words every thread reads alike: taken to scalar registers, the row and cell addresses
-    //  below are a scalar base + 32-bit lane offsets)
+    // (a board's rank is uniform and its game an LDS word every thread reads alike: taken to scalar registers, the row and cell
+    //  addresses below are a scalar base + 32-bit lane offsets)
     if (SRC) { game = __builtin_amdgcn_readfirstlane((int)gor[board]); if (fast) load_cells(game); }
 
     while (board < nvalid) {
@@ -465,9 +465,14 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
                 }
             }
         }
-        // next board: one ticket per board, drawn by the wave with the fewest tiles behind its last one (a returning atomic is waited
-        // for where it is issued: in wave 0 it sat on the board's critical path)
-        if (tid == 192) scan[10] = atomicAdd(a.sched, 1);
+        // next board, by a fixed schedule: workgroup b of Gd sweeps the ranks forth and back - b, 2 Gd - 1 - b, 2 Gd + b, 4 Gd - 1 - b, ... -
+        // so the heavy head of the rank order is paired with the light end of the next sweep, every rank below nvalid is taken exactly
+        // once, and nobody waits for anybody: the board's game and cell codes are asked for behind the wave's last tile, in front of the
+        // sums' barrier.  (Before: one ticket per board from a shared word - the ~400 workgroups that end their first, equally heavy
+        // board together queued up on it, and the ticket's return was waited for at the barrier.)
+        const int nboard = (ws_boards & 1) ? (ws_boards + 1) * (int)gridDim.x - 1 - (int)blockIdx.x : ws_boards * (int)gridDim.x + (int)blockIdx.x;
+        int ngame = 0;
+        if (SRC && nboard < nvalid) { ngame = __builtin_amdgcn_readfirstlane((int)gor[nboard]); if (fast) load_cells(ngame); }
         AZK_FSTAMP(3);                                            // wave 0's tiles
         // ---- the waves' sums meet ----
         {
@@ -482,11 +487,6 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
             }
         }
         __syncthreads();
-        // the next board is known to every thread now: its loads go out under this board's output phase
-        const int nxt = __builtin_amdgcn_readfirstlane(scan[10]), nboard = (int)gridDim.x + nxt;
-        int ngame = 0;
-        if (SRC && nboard < nvalid) { ngame = __builtin_amdgcn_readfirstlane((int)gor[nboard]); if (fast) load_cells(ngame); }
-        if (tid == 0 && nxt == nvalid - 1) a.sched[0] = 0;        // exactly nvalid tickets are drawn per launch: the last one leaves the queue zero
         // ---- output rows, straight to memory: [head][0, T) token weights / L, [T, T+3) 1 / L (hi, lo, hi), [256, 320) pooled patch / L ----
         {
             // 1 / L once per wave: lane l sums head l & 7 (the four waves' shares in the order every thread used to add them, + l_all),
@@ -576,7 +576,7 @@ int launch_embed_fold(const EmbedFoldArgs &a, hipStream_t st) {
     const int tp16 = ((a.T + 15) / 16) * 16;
     const int lds = 256 * 16 + tp16 * 8 + tp16 * 4 + 128 + 128 + 32 + tp16 * 32 + 4 * 8 * 64 * 4 + (SRC ? ((a.src.n_games + 7) / 8) * 16 + 32 : 0);   // 29 KB at 2 048 games (the rank -> game table + 16 spare entries)
     if (azk_set_max_lds((const void *)k_embed_fold<NC, KSZ, NH, SRC, EX>, lds + 2 * FOLD_MAX_SLOTS) != hipSuccess) return AZK_ERR_HIP;
-    // two resident workgroups per CU by default; each pulls boards until the queue is dry.  azk_nn_embed_fold_grid(n): a caller that steps
+    // two resident workgroups per CU by default; each sweeps the ranks forth and back (k_embed_fold, "next board").  azk_nn_embed_fold_grid(n): a caller that steps
     // several game groups on separate streams caps the grid (one workgroup per CU leaves the register file room for another group's
     // tree waves)
     const int cap = g_fold_grid > 0 ? g_fold_grid : 512;

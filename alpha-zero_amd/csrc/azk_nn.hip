@@ -51,6 +51,7 @@ struct EmbedFoldArgs {
     int rdivR, rdivC;              // 65536 / R + 1, 65536 / Cc + 1: x / d = (x m) >> 16 for x < 256, d <= 64
     float eps;
     azk_leaf_source src;
+    int cwmax;                     // leaf boards by dword (embed_fold_impl decides): index of a row's last cell dword, -1 = the source does not qualify
 };
 
 constexpr int FOLD_ROW = AZK_EMBED_FOLD_ROW;
@@ -208,17 +209,27 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
     // Boards of up to 512 plane cells: every load of a board is issued at once (one round trip), and the NEXT board's loads are issued
     // behind the wave's last tile - in front of the sums' barrier and the output phase - so a board starts with its cells on hand.
     constexpr int NQ = 8;
-    const bool fast = ncell <= 64 * NQ;
+    // Leaf boards of two planes (CW) take their fast path by dword: rows of leaf_cells are whole dwords, four cells each (the engine writes
+    // them so, azk_tree_step.h), and a board of the fold is at most 252 cells, so the board is ONE load per lane - lane l takes cells
+    // 4 l .. 4 l + 3, the lanes past the row its last dword - held in codeN[0] across the previous board's output phase, and the bit string
+    // is built from it without a ballot (below).  Whether a source qualifies is decided on the host (a.cwmax); one that does not - rows
+    // that are no multiple of four bytes, a misaligned base - takes the general loop of the boards past the fast path.
+    constexpr bool CW = SRC && NC == 2;
+    const bool fast = CW ? a.cwmax >= 0 : ncell <= 64 * NQ;
     int codeN[NQ], tmN = 0, ldN = 0, game = 0;
     auto load_cells = [&](int g) {                                // SRC: cell codes (one byte per cell) + the two words that give the side to move
         const auto *cells = a.src.leaf_cells + (size_t)g * a.src.rc_pad;           // uniform base + 32-bit lane offsets
         int lv = tid;                                             // (opaque: the eight offsets are recomputed per call, not kept across the board loop)
         asm volatile("" : "+v"(lv));
         lv &= 63;
+        if (CW) {
+            codeN[0] = (int)((const unsigned *)cells)[(unsigned)min(lv, a.cwmax)];
+        } else {
 #pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            const int e = min(q * 64 + lv, ncell - 1);
-            codeN[q] = cells[(unsigned)(e - ((e >= RC) + (NC > 2 && e >= 2 * RC)) * RC)];
+            for (int q = 0; q < NQ; q++) {
+                const int e = min(q * 64 + lv, ncell - 1);
+                codeN[q] = cells[(unsigned)(e - ((e >= RC) + (NC > 2 && e >= 2 * RC)) * RC)];
+            }
         }
         tmN = a.src.to_move[g]; ldN = a.src.leaf_depth[g];
     };
@@ -237,7 +248,22 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
         int player = 0;
         if (SRC && tid == 0) a.src.leaf_slot[game] = board;       // the slot the next expansion reads this game's outputs from
         unsigned wbits = 0;                             // lane i holds bits [32 (i-1), 32 i) of the board bit string (lane 0: zeros)
-        if (fast) {
+                                                        // (CW: lane 8 i + 4 ch + (0..3) holds bits [32 i, 32 i + 32) of plane ch's own bit string)
+        if (CW && fast) {
+            // canonical plane ch = bit ch ^ player of every code byte.  A lane's four bits of a plane meet in a nibble by one multiply
+            // (bits 0, 8, 16, 24 times 2^24 + 2^17 + 2^10 + 2^3 land on bits 24..27, every cross term below bit 20 or past bit 31);
+            // the eight nibbles of a lane group meet by three DPP steps.  Lanes 0..3 of a group keep plane 0 and hand plane 1 to lanes
+            // 4..7 in the half-mirror step, and the other way round, so ONE register ends up holding both planes' strings.
+            player = (tmN + ldN) & 1;
+            const unsigned cw = (unsigned)codeN[0];
+            const unsigned sk = ((unsigned)(lane_b >> 2) ^ (unsigned)player) & 1u, j4 = 4u * (unsigned)(lane_b & 7);
+            const unsigned keep = ((((cw >> sk) & 0x01010101u) * 0x01020408u) >> 24) << j4;
+            const unsigned send = ((((cw >> (sk ^ 1u)) & 0x01010101u) * 0x01020408u) >> 24) << j4;
+            int v = (int)keep | __builtin_amdgcn_update_dpp(0, (int)send, 0x141, 0xF, 0xF, false);     // row_half_mirror: lane j of eight <-> 7 - j
+            v |= __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);                              // quad_perm [1, 0, 3, 2]
+            v |= __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);                              // quad_perm [2, 3, 0, 1]
+            wbits = (unsigned)v;
+        } else if (fast) {
             bool on[NQ];
             if (SRC) {
                 // canonical planes from the cell codes (gomoku.py:34-40; 3-plane: mcts.py:126-137)
@@ -295,9 +321,17 @@ __global__ __launch_bounds__(256, 2) void k_embed_fold(EmbedFoldArgs a) {
         unsigned plx = 0u, ply = 0u;
         {
             const int chL = (lane_b * a.rdivR) >> 16, rL = lane_b - chL * a.R;
-            const int offL = 32 + chL * RC + rL * a.Cc - 2;
-            const unsigned loL = (unsigned)__builtin_amdgcn_ds_bpermute((offL >> 5) << 2, (int)wbits);
-            const unsigned hiL = (unsigned)__builtin_amdgcn_ds_bpermute(((offL >> 5) + 1) << 2, (int)wbits);
+            int offL = 32 + chL * RC + rL * a.Cc - 2, loA = (offL >> 5) << 2, hiA = loA + 4;
+            if (CW && fast) {
+                // the row's words straight from its plane's own string (word i of plane ch: lane 8 i + 4 ch).  Row 0 starts two bits in
+                // front of the string and the last row may end in its last word: the words that do not exist come from whichever lane
+                // the address wraps to, and the row mask below drops their bits - as it drops every cell at or past rc, so the
+                // padding of a leaf_cells row never reaches a patch.
+                offL = rL * a.Cc - 2;
+                loA = ((offL >> 5) << 5) + (chL << 4); hiA = loA + 32;
+            }
+            const unsigned loL = (unsigned)__builtin_amdgcn_ds_bpermute(loA, (int)wbits);
+            const unsigned hiL = (unsigned)__builtin_amdgcn_ds_bpermute(hiA, (int)wbits);
             const unsigned roww = lane_b < NC * a.R ? (__funnelshift_r(loL, hiL, offL & 31) & (((1u << a.Cc) - 1u) << 2)) : 0u;
             unsigned vm[KSZ];
             int src4[KSZ];
@@ -612,6 +646,9 @@ static int32_t embed_fold_impl(const void *boards_dev, int32_t boards_are_f32, c
     a.n = n; a.R = rows; a.Cc = cols; a.T = rows * cols + 1; a.eps = k->ln_eps;
     a.rdivR = 65536 / rows + 1; a.rdivC = 65536 / cols + 1;
     if (src) a.src = *src;
+    // leaf boards by dword: two planes, at most 64 dwords of cells, rows that start and end on a dword (k_embed_fold, load_cells)
+    a.cwmax = src && channels == 2 && src->rc <= 256 && src->rc_pad >= src->rc && src->rc_pad % 4 == 0 && ((uintptr_t)src->leaf_cells & 3) == 0
+                  ? src->rc_pad / 4 - 1 : -1;
     {
         static long long *dbg_buf = nullptr;
         const char *ds = getenv("AZK_EMBED_POOL_STAMPS");

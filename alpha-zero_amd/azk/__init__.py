@@ -39,6 +39,7 @@ SYMBOLS = [
     "azk_set_eval_symmetry", "azk_get_leaf_symmetry", "azk_eval_symmetry_restore",
     "azk_emit_elements", "azk_replay_gather",
     "azk_set_surprise_weighting", "azk_clear_surprise_weighting", "azk_advance_keyed", "azk_get_surprise", "azk_async_surprise_columns",
+    "azk_set_gumbel_root", "azk_clear_gumbel_root", "azk_gen_gumbel", "azk_gen_gumbel_uniforms",
 ]
 
 
@@ -207,6 +208,7 @@ class Engine:
         self.playout_cap = None                     # (p_full, n_fast) once set_playout_cap has switched the option on
         self.resign = None                          # (v_resign, p_never, min_ply) once set_resign has switched the option on
         self.forced_playouts = None                 # k once set_forced_playouts has switched the option on
+        self.gumbel_root = None                     # (m, n_sims, c_visit, c_scale) once set_gumbel_root has switched the option on
         self.surprise_weight = None                 # lambda once set_surprise_weighting has switched the option on (0.0 is a live setting)
         self.cache_entries = int(cache_entries)
         # with the eval cache a step can have pending (cached) leaves to expand although no leaf went to the evaluator
@@ -309,6 +311,27 @@ class Engine:
         explains (root_policy_target shows it).  The move, root_stats, q, resignation and tree reuse keep raw visits.  k = 0 switches it off."""
         self._chk(self.L.azk_set_forced_playouts(self.h, float(k), _stream()))
         self.forced_playouts = float(k) if float(k) != 0.0 else None
+
+    def set_gumbel_root(self, m, n_sims, c_visit=50.0, c_scale=1.0):
+        """OPT-IN Gumbel root search (azk_set_gumbel_root; Danihelka et al. 2022): every search of n_sims simulations
+        samples m root actions by Gumbel-top-k, spreads its simulations over them by sequential halving, and advance / the asynchronous
+        movers play the survivor and RECORD softmax(logits + sigma(completed Q)) (root_policy_target shows it).  The noise argument of
+        begin_search / search / search_budget then carries Gumbel rows (gen_gumbel; zeros = the noise-free search), and advance ignores
+        its uniforms.  root_stats, q, resignation and the counters keep raw visits."""
+        self._chk(self.L.azk_set_gumbel_root(self.h, int(m), int(n_sims), float(c_visit), float(c_scale), _stream()))
+        self.gumbel_root = (int(m), int(n_sims), float(c_visit), float(c_scale))
+
+    def clear_gumbel_root(self):
+        self._chk(self.L.azk_clear_gumbel_root(self.h))
+        self.gumbel_root = None
+
+    def gen_gumbel(self, seed, first_global_game, move_index, uniforms=False):
+        """float64 CUDA tensor [G, A]: the games' Gumbel(0, 1) rows of (seed, first_global_game + g, move_index) (azk_gen_gumbel), or with
+        uniforms=True the uniforms underneath them (azk_gen_gumbel_uniforms)."""
+        rows = self.torch.empty((self.G, self.action_dim), dtype=self.torch.float64, device=self.device)
+        fn = self.L.azk_gen_gumbel_uniforms if uniforms else self.L.azk_gen_gumbel
+        self._chk(fn(self.h, int(seed), int(first_global_game), int(move_index), _p(rows), _stream()))
+        return rows
 
     def set_surprise_weighting(self, lam, seed=0, first_global_game=0):
         """OPT-IN policy surprise weighting (azk_set_surprise_weighting): from now on every move records kl = KL(recorded pi ||

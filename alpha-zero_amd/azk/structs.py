@@ -175,6 +175,10 @@ def declare(L, symbols):
     L.azk_advance_keyed.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
     L.azk_get_surprise.argtypes = [vp, vp, vp, vp]
     L.azk_async_surprise_columns.argtypes = [vp, vp, vp]
+    L.azk_set_gumbel_root.argtypes = [vp, i32, i32, f64, f64, vp]
+    L.azk_clear_gumbel_root.argtypes = [vp]
+    L.azk_gen_gumbel.argtypes = [vp, u64, i64, i32, vp, vp]
+    L.azk_gen_gumbel_uniforms.argtypes = [vp, u64, i64, i32, vp, vp]
     L.azk_set_eval_symmetry.argtypes = [vp, i32, u64, vp]
     L.azk_get_leaf_symmetry.argtypes = [vp, vp, vp]
     L.azk_eval_symmetry_restore.argtypes = [vp, vp, vp, vp]

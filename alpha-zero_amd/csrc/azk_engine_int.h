@@ -138,6 +138,20 @@ struct ForcedDev {
     const uint8_t *search_full;    // [G] CapDev's kind of the game's current search (1 full: forced, 0 fast: not), or null without a cap
 };
 
+// Gumbel root search (azk_set_gumbel_root, opt-in; m == 0 otherwise): the root's children are scored gl = logit + Gumbel
+// draw (rootP holds gl), a child is eligible for a simulation iff its visit count equals the word of the sequential-halving table at the
+// simulation's index, and the move and the recorded pi come from completed Q values.  Its own argument block, passed only to the GUMBEL
+// instantiations (k_tree<.., GUMBEL> in azk_tree.hip, the movers and the target kernel in azk_moves.hip): every other argument block - and
+// every kernel an engine without the option launches - stays as it was
+struct GumbelDev {
+    int m;                     // actions sampled at the root, 1..64; 0 = off
+    int n;                     // words per table row: n_sims - 1 (simulation 0 expands the root and selects nothing)
+    double c_visit, c_scale;   // sigma(q) = (c_visit + max visits) * c_scale * q
+    const int *table;          // [m + 1][n] row m' = schedule(m', n): the visit count a child must have to be eligible at root selection t
+    float *logit;              // [G][rc] the root children's raw float32 logits, by child position
+    float *v0;                 // [G] the root's value as its evaluation (or the eval cache) gave it, for the side to move
+};
+
 // evaluation under a board symmetry (azk_set_eval_symmetry, opt-in; mode == 0 otherwise): the evaluator is shown each pending
 // leaf in orientation s = the fixed element, or a hash of (seed, the leaf's position), and its logits row is turned back before k_tree expands
 // from it.  Its own argument of the two kernels that exist only for it (azk_sym.hip): every other argument block - and every kernel an engine
@@ -330,6 +344,8 @@ struct azk_engine {
     ResignDev rs = {};                   // resignation (azk_set_resign); rs.v_resign == 0: off
     double forced_k = 0.0;               // forced playouts + policy target pruning (azk_set_forced_playouts); 0: off
     ForcedDev forced() const { return ForcedDev{forced_k, cp.n_fast ? cp.search_full : nullptr}; }   // the argument block as the options stand now
+    GumbelDev gb = {};                   // Gumbel root search (azk_set_gumbel_root); gb.m == 0: off
+    int gumbel_sims = 0;                 // ... the n_sims its table was built for
     bool async_on = false;
     int async_recycle = 1;
     SymDev sym = {};                     // evaluation under a board symmetry (azk_set_eval_symmetry); sym.mode == 0: off, nothing allocated

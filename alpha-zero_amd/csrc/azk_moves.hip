@@ -5,6 +5,7 @@
 #include "azk_engine_int.h"
 #include "azk_sym_map.h"      // sym_source: emission under a mask of elements
 #include <type_traits>
+#include <algorithm>
 
 namespace {
 
@@ -16,7 +17,8 @@ namespace {
 // argument layout and the instruction stream it always had, and an option costs the others nothing.  The kernels are one line each: the
 // *_body functions behind them take the blocks by value, all zero where an option is off (opt), and fold on their flags.  The host turns the engine's state
 // into the template arguments in one place per kernel (with_flags, in front of the launchers).
-// A new option is a flag on each template it touches, an Opt<> in their Packs and a bool at their dispatch.
+// A new option is a flag on each template it touches, an Opt<> in their Packs and a bool at their dispatch.  (An option that combines with few
+// of the others can keep the existing kernels' names instead: the Gumbel root's movers are overloads on a pack of their own, GumbelPack.)
 // ------------------------------------------------------------------------------------------------
 template <class Block, bool ON> struct Opt {};
 template <class Block> struct Opt<Block, true> { Block v; };
@@ -32,6 +34,9 @@ template <class First, bool CAP> using CapKeyPack = Pack<First, Opt<Keyed<CapDev
 template <class First, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
 using MovePack = Pack<First, Opt<CapDev, CAP>, Opt<ResignDev, RESIGN>, Opt<ForcedDev, FORCED>, Opt<SurpriseDev, SURPRISE>>;
 template <bool CAP, bool SYM, bool SURPRISE> using EmitPack = Pack<Dev, Opt<CapDev, CAP>, Opt<EmitSym, SYM>, Opt<SurpriseDev, SURPRISE>>;
+// Gumbel root search combines with resignation only, and the kernels of the other options keep their names: the movers'
+// GUMBEL forms are overloads that take this pack
+template <class First, bool RESIGN> using GumbelPack = Pack<First, Opt<ResignDev, RESIGN>, Opt<GumbelDev, true>>;
 static_assert(sizeof(MovePack<Dev, false, false, false, false>) == sizeof(Dev) && sizeof(EmitPack<false, false, false>) == sizeof(Dev) &&
               sizeof(MovePack<ReuseDev, false, false, false, false>) == sizeof(ReuseDev) &&
               sizeof(MovePack<Dev, true, true, true, false>) == sizeof(Pack<Dev, Opt<CapDev, true>, Opt<ResignDev, true>, Opt<ForcedDev, true>>) &&
@@ -426,6 +431,84 @@ __device__ __forceinline__ double surprise_kl(const Dev &d, const LdsView &L, in
     return part > 0.0 ? part : 0.0;
 }
 
+// Gumbel root search (azk_set_gumbel_root): the move and the recorded pi of one game's search (one wave), all float64,
+// children in list order.  With N_i, W_i, P_i (the header's float32 prior), gl_i = rootP, logit_i and v0 as the root's expansion kept them:
+//     S = sum N;  q_i = W_i / N_i (N_i > 0);  pv = sum over visited of P_i;  pq = sum over visited of P_i * q_i   (both sequential, list order)
+//     vmix = S > 0 ? (v0 + S * (pq / pv)) / (1 + S) : v0;  qh_i = N_i > 0 ? q_i : vmix;  sigf = (c_visit + max N) * c_scale
+//     move    among the children with N_i == max N, the first maximum of gl_i + sigf * qh_i
+//     pi      y_i = logit_i + sigf * qh_i;  pi[a_i] = exp(y_i - max y) / sum_j exp(y_j - max y), 0 on every other action
+// Returns the played child's list index (wave-uniform) and leaves pi, by action, in L.cdf.  The tree is not touched.
+__device__ __forceinline__ int gumbel_target(const Dev &d, const LdsView &L, int g, const GumbelDev &gb) {
+    constexpr int KMAX = 7;                                           // children per lane: make_game allows 400 cells
+    const int lane = azk_lane();
+    const GameDesc &gd = d.g;
+    const size_t base = (size_t)g * d.cap;
+    const int A = gd.action_dim, rc = gd.rc;
+    const int fc = uniform_i32(d.H[base].fc), nch = min(uniform_i32(meta_nch(d.H[base].meta)), KMAX * AZK_WAVE);
+    int *Nl = (int *)L.ms.claim;                                      // visits by child position (table_size words: more than any board has cells)
+    int nv[KMAX], cellv[KMAX];
+    double qv[KMAX], yv[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; k++) {
+        const int i = lane + AZK_WAVE * k;
+        nv[k] = 0; cellv[k] = 0; qv[k] = 0.0; yv[k] = 0.0;
+        if (i < nch) {
+            const NodeH h = d.H[base + fc + i];
+            nv[k] = h.N; cellv[k] = meta_cell(h.meta);
+            qv[k] = h.N > 0 ? d.W[base + fc + i] / (double)h.N : 0.0;
+            Nl[i] = h.N; L.e[i] = h.P; L.cdf[i] = qv[k];
+        }
+    }
+    __syncthreads();
+    double vmix = 0.0;
+    int maxn = 0;
+    if (lane == 0) {
+        int S = 0;
+        double pv = 0.0, pq = 0.0;
+        for (int i = 0; i < nch; i++) {
+            const int n = Nl[i];
+            S += n; maxn = max(maxn, n);
+            if (n > 0) { const double P = (double)L.e[i]; pv += P; pq += P * L.cdf[i]; }
+        }
+        const double v0 = (double)gb.v0[g];
+        vmix = S > 0 ? (v0 + (double)S * (pq / pv)) / (1.0 + (double)S) : v0;
+    }
+    vmix = __shfl(vmix, 0); maxn = __shfl(maxn, 0);
+    const double sigf = (gb.c_visit + (double)maxn) * gb.c_scale;
+    int best = 0x7fffffff;
+    double bs = -__builtin_huge_val(), ym = -__builtin_huge_val();
+#pragma unroll
+    for (int k = 0; k < KMAX; k++) {
+        const int i = lane + AZK_WAVE * k;
+        if (i < nch) {
+            const double qh = nv[k] > 0 ? qv[k] : vmix;
+            const double sc = d.rootP[(size_t)g * rc + i] + sigf * qh;
+            yv[k] = (double)gb.logit[(size_t)g * rc + i] + sigf * qh;
+            if (nv[k] == maxn && (best == 0x7fffffff || sc > bs)) { bs = sc; best = i; }
+            ym = fmax(ym, yv[k]);
+        }
+    }
+    wave_argmax_first<double>(bs, best);
+    best = uniform_i32(best);
+    ym = wave_max_f64(ym);
+    double part = 0.0;
+#pragma unroll
+    for (int k = 0; k < KMAX; k++) {
+        if (lane + AZK_WAVE * k < nch) { yv[k] = exp(yv[k] - ym); part += yv[k]; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
+    __syncthreads();
+    for (int a = lane; a < A; a += AZK_WAVE) L.cdf[a] = 0.0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < KMAX; k++) {
+        if (lane + AZK_WAVE * k < nch) L.cdf[azk_action_idx(gd, cellv[k])] = yv[k] / part;
+    }
+    __syncthreads();
+    return best;
+}
+
 // gomoku.py:143-162 for one game (one wave): choose (sample ~ visits | first max-visit child), record pi / the action in the
 // trajectory, make_move, check_winner, draw.  Returns the chosen cell (-1: state error, already reported); *win_out / *done_out as
 // k_advance's outputs; pi of the move is left in L.cnt / sum_out (visit counts per action and their sum).
@@ -439,9 +522,13 @@ __device__ __forceinline__ double surprise_kl(const Dev &d, const LdsView &L, in
 // SURPRISE (engines with surprise weighting, azk_set_surprise_weighting): the kl of the pi that is recorded - after the
 // pruning - and the ply's coin of the move key go into traj_kl / traj_coin beside traj_pi and into the game's last-move pair (lane 0 writes
 // them: the asynchronous mover's lane 0 copies the pair into its record).
-template <bool RESIGN, bool FORCED, bool SURPRISE>
+// GUMBEL (engines with a Gumbel root, azk_set_gumbel_root): the move is gumbel_target's - the uniform and sample_until are
+// not looked at, the Gumbel arg-max is the sample - and the recorded pi is its float64 row in L.cdf (the caller's record reads it there too);
+// L.cnt / sum_out still hold the raw visits.
+template <bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false>
 __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool have_u, double u, int sample_until, int *win_out, int *done_out,
-                                           int *sum_out, const ResignDev &rs, int key, int *rsg_out, const ForcedDev &fp, const SurpriseDev &sp) {
+                                           int *sum_out, const ResignDev &rs, int key, int *rsg_out, const ForcedDev &fp, const SurpriseDev &sp,
+                                           const GumbelDev &gb = GumbelDev{}) {
     const int lane = azk_lane();
     const GameDesc &gd = d.g;
     const size_t base = (size_t)g * d.cap;
@@ -465,6 +552,9 @@ __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool
         if (lane == 0) atomicExch(d.err, AZK_ERR_STATE);
         return -1;
     }
+    if constexpr (GUMBEL) {
+        cellc = meta_cell(d.H[base + fc + gumbel_target(d, L, g, gb)].meta);
+    } else
     if (have_u && mc < sample_until) {
         // Node.sample_child (node.py:83-93) -> legacy np.random.choice(p=pi): cdf = cumsum(pi); cdf /= cdf[-1];
         // index = searchsorted(cdf, u, side='right').  cumsum is sequential in float64.
@@ -509,6 +599,8 @@ __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool
     }
     if (d.traj_pi != nullptr && mc < gd.state_dim) {               // gomoku.py:138-146: pi and the action of this ply
         double *tp = d.traj_pi + ((size_t)g * gd.state_dim + mc) * A;
+        if constexpr (GUMBEL) { for (int a = lane; a < A; a += AZK_WAVE) tp[a] = L.cdf[a]; }
+        else
         for (int a = lane; a < A; a += AZK_WAVE) tp[a] = (double)L.cnt[a] / (double)sum;
         if (lane == 0) d.traj_action[(size_t)g * gd.state_dim + mc] = (int16_t)cellc;
     }
@@ -576,9 +668,10 @@ __device__ __forceinline__ int played_child(const Dev &d, int g, int cellc) {
 
 // The lock-step mover (azk_advance, azk_advance_resign): every game's move, one wave per game.  CAP: the ply's kind goes into traj_full beside its
 // pi; RESIGN, SURPRISE (move_index = the slot's move counter), FORCED: as advance_one has them
-template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
+template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false>
 __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int move_index, const double *uniforms, int sample_until,
-                                             int *chosen, int *winner_out, int *done_out, int *chosen_node, const ForcedDev &fp, const SurpriseDev &sp) {
+                                             int *chosen, int *winner_out, int *done_out, int *chosen_node, const ForcedDev &fp, const SurpriseDev &sp,
+                                             const GumbelDev &gb = GumbelDev{}) {
     const int g = blockIdx.x, lane = azk_lane();
     LdsView L = carve(d.g, d.path_cap, d.table_size);
     if (uniform_i32(d.done[g]) != 0) {
@@ -592,7 +685,9 @@ __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int
     }
     int win = -2, dn = 0, sum = 0, rsg = 0;
     const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
-    const int cellc = advance_one<RESIGN, FORCED, SURPRISE>(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum,
+    int cellc;
+    if constexpr (GUMBEL) cellc = advance_one<RESIGN, false, false, true>(d, L, g, false, 0.0, 0, &win, &dn, &sum, rs, move_index, &rsg, fp, sp, gb);
+    else cellc = advance_one<RESIGN, FORCED, SURPRISE>(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum,
                                                             rs, move_index, &rsg, fp, sp);
     if (CAP && cellc >= 0 && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = cp.search_full[g];
     if (chosen_node) {
@@ -618,6 +713,15 @@ __global__ __launch_bounds__(AZK_WAVE) void k_advance(MovePack<Dev, CAP, RESIGN,
     if constexpr (RESIGN || SURPRISE) move_index = ply.move_index;
     advance_body<CAP, RESIGN, FORCED, SURPRISE>(a, opt<CapDev>(a), opt<ResignDev>(a), move_index, uniforms, ply.sample_until, chosen, winner_out, done_out,
                                                 chosen_node, opt<ForcedDev>(a), opt<SurpriseDev>(a));
+}
+
+// the lock-step mover of an engine with a Gumbel root (with or without resignation)
+template <bool RESIGN>
+__global__ __launch_bounds__(AZK_WAVE) void k_advance(GumbelPack<Dev, RESIGN> a, Ply<RESIGN> ply, int *chosen, int *winner_out, int *done_out) {
+    int move_index = 0;
+    if constexpr (RESIGN) move_index = ply.move_index;
+    advance_body<false, RESIGN, false, false, true>(a, CapDev{}, opt<ResignDev>(a), move_index, nullptr, 0, chosen, winner_out, done_out, nullptr, ForcedDev{},
+                                                    SurpriseDev{}, opt<GumbelDev>(a));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -836,6 +940,26 @@ __global__ __launch_bounds__(AZK_WAVE) void k_gen_noise(int A, unsigned long lon
     noise_row(A, seed, gg, move, alpha, noise + (size_t)g * (size_t)row_stride, red);
 }
 
+// The Gumbel(0, 1) row of (seed, global game, move), by one wave (Gumbel root search): entry a draws ONE Philox block at
+// counter {gg lo, gg hi ^ (a << 8), move, 0xFFFFFFFB} - a word 3 that is no other stream's -, u = (((c0 << 32 | c1) >> 12) + 0.5) * 2^-52
+// (exact, strictly inside (0, 1)) and g = -log(-log(u)).
+__device__ __forceinline__ void gumbel_row(int A, unsigned long long seed, unsigned long long gg, int move, double *row, double *urow = nullptr) {
+    for (int a = azk_lane(); a < A; a += AZK_WAVE) {
+        uint32_t c[4] = {(uint32_t)gg, (uint32_t)(gg >> 32) ^ ((uint32_t)a << 8), (uint32_t)move, 0xFFFFFFFBu};
+        philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+        const double u = ((double)((((unsigned long long)c[0] << 32) | c[1]) >> 12) + 0.5) * (1.0 / 4503599627370496.0);
+        if (row != nullptr) row[a] = -log(-log(u));
+        if (urow != nullptr) urow[a] = u;
+    }
+}
+
+__global__ __launch_bounds__(AZK_WAVE) void k_gen_gumbel(int A, unsigned long long seed, long long first_game, int move, double *rows, double *uniforms,
+                                                          long long row_stride) {
+    const int g = blockIdx.x;
+    const size_t o = (size_t)g * (size_t)row_stride;
+    gumbel_row(A, seed, (unsigned long long)(first_game + g), move, rows != nullptr ? rows + o : nullptr, uniforms != nullptr ? uniforms + o : nullptr);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Asynchronous self-play (games/gomoku.py:132-162: a game moves as soon as ITS search is done).  After every tree launch
 // k_move_async looks at every game: one whose search is complete (its simulation budget used up, nothing pending) gets its move
@@ -876,6 +1000,19 @@ __global__ __launch_bounds__(AZK_WAVE) void k_noise_ahead(Dev d, AsyncDev p) {
     }
 }
 
+// ... and its Gumbel form (an engine with a Gumbel root keeps Gumbel rows where the others keep Dirichlet rows)
+__global__ __launch_bounds__(AZK_WAVE) void k_gumbel_ahead(Dev d, AsyncDev p) {
+    const int n = *p.todo_count, A = d.g.action_dim;
+    for (int f = blockIdx.x; f < n; f += gridDim.x) {
+        const int g = p.todo_list[f];
+        const int key = (int)p.slot_moves[g] + 1;
+        if (uniform_i32(p.noise_key[g]) >= key) continue;
+        gumbel_row(A, p.seed, (unsigned long long)(p.first_game + g), key, p.noise + ((size_t)g * 2 + (size_t)(key & 1)) * A);
+        __syncthreads();
+        if (azk_lane() == 0) p.noise_key[g] = key;
+    }
+}
+
 __global__ void k_fill_i32(int *p, int n, int v) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -884,8 +1021,9 @@ __global__ void k_fill_i32(int *p, int n, int v) {
 // The asynchronous mover.  REROOT: a re-rooting engine - the moved game is parked for the drain's k_reroot_list instead of beginning its search
 // here; CAP: the kind of the completed search goes into the record and traj_full, and the next fresh-root search flips its coin; RESIGN, FORCED:
 // SURPRISE: as advance_one has them (the move key is the slot's move counter; kl and coin go into the record's columns too)
-template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
-__device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs, const ForcedDev &fp, const SurpriseDev &sp) {
+template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false>
+__device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs, const ForcedDev &fp, const SurpriseDev &sp,
+                                                const GumbelDev &gb = GumbelDev{}) {
     const int g = blockIdx.x, lane = azk_lane();
     // one vector load for the three words that decide whether this game moves now (almost never: the wave then ends at once)
     const int *up = d.done + g;
@@ -910,13 +1048,17 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
     const double u = noise_uniform(p.seed, (unsigned long long)(p.first_game + g), (int)mv);
     const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
     const int kind = CAP ? uniform_i32((int)cp.search_full[g]) : 1;     // of the search that is complete
-    const int cellc = advance_one<RESIGN, FORCED, SURPRISE>(d, L, g, true, u, p.sample_until, &win, &dn, &sum, rs, (int)mv, &rsg, fp, sp);
+    int cellc;
+    if constexpr (GUMBEL) cellc = advance_one<RESIGN, false, false, true>(d, L, g, false, 0.0, 0, &win, &dn, &sum, rs, (int)mv, &rsg, fp, sp, gb);
+    else cellc = advance_one<RESIGN, FORCED, SURPRISE>(d, L, g, true, u, p.sample_until, &win, &dn, &sum, rs, (int)mv, &rsg, fp, sp);
     if (cellc < 0) return;
     if (CAP && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = (uint8_t)kind;
     if (p.rec_cap > 0) {                                           // the move's record: what the reference's self_play keeps per ply
         long long slot = 0;
         if (lane == 0) slot = (long long)(atomicAdd((unsigned long long *)&p.stats[6], 1ull) % (unsigned long long)p.rec_cap);
         slot = ((long long)__builtin_amdgcn_readfirstlane((int)(slot >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)slot);
+        if constexpr (GUMBEL) { for (int a = lane; a < A; a += AZK_WAVE) p.rec_pi[(size_t)slot * A + a] = L.cdf[a]; }
+        else
         for (int a = lane; a < A; a += AZK_WAVE) p.rec_pi[(size_t)slot * A + a] = (double)L.cnt[a] / (double)sum;
         if (lane == 0) {
             p.rec_q[slot] = q;
@@ -953,6 +1095,12 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
 template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
 __global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, MovePack<ReuseDev, CAP, RESIGN, FORCED, SURPRISE> r) {
     move_async_body<REROOT, CAP, RESIGN, FORCED, SURPRISE>(d, p, r, opt<CapDev>(r), opt<ResignDev>(r), opt<ForcedDev>(r), opt<SurpriseDev>(r));
+}
+
+// the asynchronous mover of an engine with a Gumbel root (no re-rooting, no cap; with or without resignation)
+template <bool RESIGN>
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, GumbelPack<ReuseDev, RESIGN> r) {
+    move_async_body<false, false, RESIGN, false, false, true>(d, p, r, CapDev{}, opt<ResignDev>(r), ForcedDev{}, SurpriseDev{}, opt<GumbelDev>(r));
 }
 
 // drain, step 4 (re-rooting engines): the next search of every game parked since the last drain - its subtree under the played child
@@ -1040,6 +1188,16 @@ __global__ __launch_bounds__(AZK_WAVE) void k_root_policy_target(Dev d, ForcedDe
     for (int a = lane; a < A; a += AZK_WAVE) pi[(size_t)g * A + a] = (double)L.cnt[a] / (double)sum;
 }
 
+// ... and of an engine with a Gumbel root: gumbel_target's row
+__global__ __launch_bounds__(AZK_WAVE) void k_root_policy_target_gumbel(Dev d, GumbelDev gb, double *pi) {
+    const int g = blockIdx.x, lane = azk_lane();
+    const int A = d.g.action_dim;
+    LdsView L = carve(d.g, d.path_cap, d.table_size);
+    const bool searched = uniform_i32(meta_nch(d.H[(size_t)g * d.cap].meta)) > 0 && uniform_i32(d.root_f64[g]) != 0;
+    if (searched) gumbel_target(d, L, g, gb);
+    for (int a = lane; a < A; a += AZK_WAVE) pi[(size_t)g * A + a] = searched ? L.cdf[a] : 0.0;
+}
+
 // ---- the host side of the options: runtime flags -> template arguments, engine state -> argument packs ----------------------------------
 // f(std::bool_constant per flag), called once: the one place where a kernel's instantiation is chosen
 template <class F> void with_flags(F &&f) { f(); }
@@ -1114,8 +1272,17 @@ static bool forced_needs_noise(azk_engine *e, const double *noise_dev, const cha
     return true;
 }
 
+// a Gumbel root's searches read their Gumbel rows through noise_dev and run the option's own budget
+static bool gumbel_refuses(azk_engine *e, const double *noise_dev, int n_sims, const char *who) {
+    if (e->gb.m == 0) return false;
+    if (noise_dev == nullptr) { e->err = std::string(who) + ": a Gumbel root is set - noise_dev carries the games' Gumbel rows (a row of zeros is the noise-free search, NULL is not)"; return true; }
+    if (n_sims > 0 && n_sims != e->gumbel_sims) { e->err = std::string(who) + ": a Gumbel root is set - n_sims differs from the n_sims its halving table was built for (azk_set_gumbel_root)"; return true; }
+    return false;
+}
+
 int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
+    if (gumbel_refuses(e, noise_dev, 0, "azk_begin_search")) return AZK_ERR_STATE;
     if (forced_needs_noise(e, noise_dev, "azk_begin_search")) return AZK_ERR_STATE;
     if (e->cp.n_fast) { e->err = "azk_begin_search: a playout cap is set - its searches begin with azk_begin_search_capped (budget + move index)"; return AZK_ERR_STATE; }
     e->d.noise = noise_dev; e->d.noise_sel = nullptr;
@@ -1148,6 +1315,7 @@ int32_t azk_begin_search_budget(azk_engine *e, const double *noise_dev, int32_t 
     if (!e || n_sims < 1 || n_sims > e->cfg.max_sims || max_sims_per_launch < 1) { if (e) e->err = "azk_begin_search_budget: bad argument"; return AZK_ERR_ARG; }
     if (e->cp.n_fast) { e->err = "azk_begin_search_budget: a playout cap is set - its searches begin with azk_begin_search_capped (the coin needs the move index)"; return AZK_ERR_STATE; }
     if (forced_needs_noise(e, noise_dev, "azk_begin_search_budget")) return AZK_ERR_STATE;
+    if (gumbel_refuses(e, noise_dev, n_sims, "azk_begin_search_budget")) return AZK_ERR_STATE;
     return begin_budget(e, noise_dev, n_sims, max_sims_per_launch, -1, stream);
 }
 
@@ -1156,6 +1324,7 @@ int32_t azk_set_playout_cap(azk_engine *e, double p_full, int32_t n_fast, uint64
     if (!e) return AZK_ERR_ARG;
     if (e->async_on) { e->err = "azk_set_playout_cap: set the cap before azk_async_begin"; return AZK_ERR_STATE; }
     if (n_fast == 0) { e->cp.n_fast = 0; return AZK_OK; }         // off: the engine launches what it launched before
+    if (e->gb.m) { e->err = "azk_set_playout_cap: a Gumbel root is set - its halving table is built for one budget"; return AZK_ERR_STATE; }
     if (!(p_full >= 0.0 && p_full <= 1.0)) { e->err = "azk_set_playout_cap: p_full must lie in [0, 1]"; return AZK_ERR_ARG; }
     if (n_fast < 1 || n_fast > e->cfg.max_sims) { e->err = "azk_set_playout_cap: n_fast must lie in [1, max_sims]"; return AZK_ERR_ARG; }
     if (e->d.K > 1) { e->err = "azk_set_playout_cap: a playout cap does not combine with leaves_per_step > 1 (virtual loss counts completed simulations differently)"; return AZK_ERR_ARG; }
@@ -1202,14 +1371,90 @@ int32_t azk_set_forced_playouts(azk_engine *e, double k, void *stream) {
     if (e->async_on) { e->err = "azk_set_forced_playouts: set it before azk_async_begin"; return AZK_ERR_STATE; }
     if (!(k >= 0.0) || k - k != 0.0) { e->err = "azk_set_forced_playouts: k must be finite and not negative (0 = off)"; return AZK_ERR_ARG; }
     if (k == 0.0) { e->forced_k = 0.0; return AZK_OK; }              // off: the engine launches what it launched before
+    if (e->gb.m) { e->err = "azk_set_forced_playouts: a Gumbel root is set - its eligibility rule needs raw root selection"; return AZK_ERR_STATE; }
     if (e->d.K > 1) { e->err = "azk_set_forced_playouts: forced playouts do not combine with leaves_per_step > 1 (a virtual-loss search counts a visit before its value exists: the floor would be met by visits that carry nothing)"; return AZK_ERR_ARG; }
     e->forced_k = k;
     return AZK_OK;
 }
 
+// ---- Gumbel root search -----------------------------------------------------------------------------------------------------
+// schedule(m, n): the visit count a root child must have at each of the n root selections of a search that halves m sampled children
+static void gumbel_schedule(int m, int n, int *out) {
+    if (m <= 1) { for (int t = 0; t < n; t++) out[t] = t; return; }
+    int L = 0;
+    while ((1 << L) < m) L++;
+    std::vector<int> v((size_t)m, 0);
+    int c = m, len = 0;
+    while (len < n) {
+        const int extra = std::max(1, n / (L * c));
+        for (int x = 0; x < extra && len < n; x++)
+            for (int i = 0; i < c; i++) { if (len < n) out[len++] = v[i]; v[i] += 1; }
+        c = std::max(2, c / 2);
+    }
+}
+
+int32_t azk_set_gumbel_root(azk_engine *e, int32_t m, int32_t n_sims, double c_visit, double c_scale, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_gumbel_root: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (m < 1 || m > 64) { e->err = "azk_set_gumbel_root: m must lie in [1, 64]"; return AZK_ERR_ARG; }
+    if (n_sims < 2 || n_sims > e->cfg.max_sims) { e->err = "azk_set_gumbel_root: n_sims must lie in [2, max_sims]"; return AZK_ERR_ARG; }
+    if (!(c_visit >= 0.0) || c_visit - c_visit != 0.0) { e->err = "azk_set_gumbel_root: c_visit must be finite and not negative"; return AZK_ERR_ARG; }
+    if (!(c_scale > 0.0) || c_scale - c_scale != 0.0) { e->err = "azk_set_gumbel_root: c_scale must be finite and positive"; return AZK_ERR_ARG; }
+    if (e->d.K > 1) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with leaves_per_step > 1 (a virtual-loss search counts a visit before its value exists: eligibility by visit count would pass over it)"; return AZK_ERR_ARG; }
+    if (e->ru.mode) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with tree reuse (the eligibility rule needs a fresh root: every child at 0 visits)"; return AZK_ERR_STATE; }
+    if (e->cp.n_fast) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with a playout cap (the halving table is built for one budget)"; return AZK_ERR_STATE; }
+    if (e->forced_k != 0.0) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with forced playouts (the eligibility rule needs raw root selection)"; return AZK_ERR_STATE; }
+    if (e->sp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with surprise weighting (its recorded pi is not a visit distribution)"; return AZK_ERR_STATE; }
+    const Dev &d = e->d;
+    GumbelDev &gb = e->gb;
+    hipStream_t st = (hipStream_t)stream;
+    const int n = n_sims - 1;
+    std::vector<int> table((size_t)(m + 1) * n);
+    for (int mm = 0; mm <= m; mm++) gumbel_schedule(mm, n, table.data() + (size_t)mm * n);
+    int *tab = nullptr;                                              // (a table of its own per call: a captured step graph may still hold the last one)
+    HIPCHK(e, dalloc(e, &tab, table.size()));
+    if (!gb.logit) {
+        HIPCHK(e, dalloc(e, &gb.logit, (size_t)d.G * d.g.rc));
+        HIPCHK(e, dalloc(e, &gb.v0, (size_t)d.G));
+        HIPCHK(e, hipMemsetAsync(gb.logit, 0, sizeof(float) * (size_t)d.G * d.g.rc, st));
+        HIPCHK(e, hipMemsetAsync(gb.v0, 0, sizeof(float) * (size_t)d.G, st));
+    }
+    HIPCHK(e, hipMemcpyAsync(tab, table.data(), sizeof(int) * table.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    gb.table = tab; gb.n = n; gb.c_visit = c_visit; gb.c_scale = c_scale;
+    gb.m = m;
+    e->gumbel_sims = n_sims;
+    return AZK_OK;
+}
+
+int32_t azk_clear_gumbel_root(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_gumbel_root: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    e->gb.m = 0;                                                   // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+static int32_t gen_gumbel(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double *gumbel_dev, double *uniforms_dev, void *stream) {
+    k_gen_gumbel<<<e->d.G, AZK_WAVE, 0, (hipStream_t)stream>>>(e->d.g.action_dim, seed, first_global_game, move_index, gumbel_dev, uniforms_dev,
+                                                             (long long)e->d.g.action_dim);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_gen_gumbel(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double *gumbel_dev, void *stream) {
+    if (!e || !gumbel_dev) return AZK_ERR_ARG;
+    return gen_gumbel(e, seed, first_global_game, move_index, gumbel_dev, nullptr, stream);
+}
+
+int32_t azk_gen_gumbel_uniforms(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double *uniforms_dev, void *stream) {
+    if (!e || !uniforms_dev) return AZK_ERR_ARG;
+    return gen_gumbel(e, seed, first_global_game, move_index, nullptr, uniforms_dev, stream);
+}
+
 int32_t azk_root_policy_target(azk_engine *e, double *pi_dev, void *stream) {
     if (!e || !pi_dev) return AZK_ERR_ARG;
-    if (e->forced_k == 0.0) k_root_stats<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, pi_dev, nullptr, nullptr);
+    if (e->gb.m) k_root_policy_target_gumbel<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->gb, pi_dev);
+    else if (e->forced_k == 0.0) k_root_stats<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, pi_dev, nullptr, nullptr);
     else k_root_policy_target<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->forced(), pi_dev);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
@@ -1276,6 +1521,7 @@ int32_t azk_async_resign_flags(azk_engine *e, uint8_t *rec_resigned_dev) {
 int32_t azk_set_surprise_weighting(azk_engine *e, double lambda, uint64_t seed, int64_t first_global_game, void *stream) {
     if (!e) return AZK_ERR_ARG;
     if (e->async_on) { e->err = "azk_set_surprise_weighting: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (e->gb.m) { e->err = "azk_set_surprise_weighting: a Gumbel root is set - its recorded pi is not a visit distribution, which the weight is defined on"; return AZK_ERR_STATE; }
     if (!(lambda >= 0.0 && lambda <= 1.0)) { e->err = "azk_set_surprise_weighting: lambda must lie in [0, 1] (azk_clear_surprise_weighting switches the option off)"; return AZK_ERR_ARG; }
     if (e->d.K > 1) { e->err = "azk_set_surprise_weighting: surprise weighting does not combine with leaves_per_step > 1 (a virtual-loss search's visit counts are not the ones the weight was defined on)"; return AZK_ERR_ARG; }
     const Dev &d = e->d;
@@ -1333,6 +1579,9 @@ static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *strea
     if (c->record_capacity < 0 || (c->record_capacity > 0 && (!c->rec_meta_dev || !c->rec_q_dev || !c->rec_pi_dev))) { e->err = "azk_async_begin: record ring pointers missing"; return AZK_ERR_ARG; }
     if (e->cp.n_fast > c->n_sims) { e->err = "azk_async_begin: the playout cap's n_fast exceeds n_sims"; return AZK_ERR_ARG; }
     if (e->forced_k != 0.0 && !c->dirichlet) { e->err = "azk_async_begin: forced playouts are set - the searches need root noise (dirichlet = 1)"; return AZK_ERR_STATE; }
+    if (e->gb.m && !c->dirichlet) { e->err = "azk_async_begin: a Gumbel root is set - the searches need their Gumbel rows (dirichlet = 1 makes the movers generate them)"; return AZK_ERR_STATE; }
+    if (e->gb.m && reuse) { e->err = "azk_async_begin_reuse: a Gumbel root is set - it does not combine with re-rooting (the eligibility rule needs a fresh root)"; return AZK_ERR_STATE; }
+    if (e->gb.m && c->n_sims != e->gumbel_sims) { e->err = "azk_async_begin: a Gumbel root is set - n_sims differs from the n_sims its halving table was built for (azk_set_gumbel_root)"; return AZK_ERR_STATE; }
     Dev &d = e->d;
     if (d.K > 1) { e->err = "azk_async_begin: asynchronous moves run the sequential search (leaves_per_step = 1)"; return AZK_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
@@ -1383,8 +1632,13 @@ static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *strea
     HIPCHK(e, hipMemsetAsync(a.todo_count, 0, sizeof(int), st));
     if (a.dirichlet) {
         const int A = d.g.action_dim;
+        if (e->gb.m) {                                            // a Gumbel root: Gumbel rows where the others keep Dirichlet rows
+            k_gen_gumbel<<<d.G, AZK_WAVE, 0, st>>>(A, a.seed, a.first_game, 0, a.noise, nullptr, 2LL * A);
+            k_gen_gumbel<<<d.G, AZK_WAVE, 0, st>>>(A, a.seed, a.first_game, 1, a.noise + A, nullptr, 2LL * A);
+        } else {
         k_gen_noise<<<d.G, AZK_WAVE, 0, st>>>(A, a.seed, a.first_game, 0, a.alpha, a.noise, nullptr, 2LL * A);
         k_gen_noise<<<d.G, AZK_WAVE, 0, st>>>(A, a.seed, a.first_game, 1, a.alpha, a.noise + A, nullptr, 2LL * A);
+        }
         k_fill_i32<<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(a.noise_key, d.G, 1);
     }
     HIPCHK(e, hipGetLastError());
@@ -1400,7 +1654,11 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
     const Dev &d = e->d;
     hipStream_t st = (hipStream_t)stream;
     if (phases & 1) { const int32_t rc = azk_launch_tree(e, true, true, true, logits_dev, values_dev, st); if (rc != AZK_OK) return rc; }
-    if (phases & 2)
+    if ((phases & 2) && e->gb.m)
+        with_flags([&](auto resign) {
+            k_move_async<resign.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, GumbelPack<ReuseDev, resign.value>{e->ru, on<resign.value>(e->rs), on<true>(e->gb)});
+        }, e->rs.v_resign != 0.0);
+    else if (phases & 2)
         with_flags([&](auto reroot, auto cap, auto resign, auto forced, auto surprise) {
             k_move_async<reroot.value, cap.value, resign.value, forced.value, surprise.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(
                 d, e->ad, move_pack<cap.value, resign.value, forced.value, surprise.value>(e->ru, e));
@@ -1411,6 +1669,7 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
 
 int32_t azk_async_set_budget(azk_engine *e, int32_t n_sims, int32_t max_sims_per_launch, void *stream) {
     if (!e || !e->async_on || n_sims < 1 || n_sims > e->cfg.max_sims || max_sims_per_launch < 1) { if (e) e->err = "azk_async_set_budget: bad argument"; return AZK_ERR_ARG; }
+    if (e->gb.m && n_sims != e->gumbel_sims) { e->err = "azk_async_set_budget: a Gumbel root is set - n_sims differs from the n_sims its halving table was built for"; return AZK_ERR_STATE; }
     e->budget_host[0] = n_sims; e->budget_host[1] = max_sims_per_launch;
     HIPCHK(e, hipMemcpyAsync(e->d.budget, e->budget_host, sizeof e->budget_host, hipMemcpyHostToDevice, (hipStream_t)stream));
     HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
@@ -1434,7 +1693,8 @@ int32_t azk_async_drain(azk_engine *e, float *states_dev, double *pis_dev, float
     }, e->cp.n_fast != 0);
     if (e->ru.mode) HIPCHK(e, hipMemsetAsync(e->ad.reroot_count, 0, sizeof(int), st));
     if (e->ad.dirichlet) {                                        // the rows of the searches AFTER the ones begun since the last drain
-        k_noise_ahead<<<(unsigned)(d.G < 512 ? d.G : 512), AZK_WAVE, 0, st>>>(d, e->ad);
+        if (e->gb.m) k_gumbel_ahead<<<(unsigned)(d.G < 512 ? d.G : 512), AZK_WAVE, 0, st>>>(d, e->ad);
+        else k_noise_ahead<<<(unsigned)(d.G < 512 ? d.G : 512), AZK_WAVE, 0, st>>>(d, e->ad);
         HIPCHK(e, hipMemsetAsync(e->ad.todo_count, 0, sizeof(int), st));
     }
     HIPCHK(e, hipGetLastError());
@@ -1477,6 +1737,16 @@ static int32_t advance(azk_engine *e, const double *uniforms_dev, int32_t sample
                        int32_t *winner_dev, int32_t *done_dev, void *stream) {
     const Dev &d = e->d;
     e->in_search = false;
+    if (e->gb.m) {                                                // a Gumbel root: the Gumbel arg-max is the sample - no uniforms, no sample_until
+        with_flags([&](auto resign) {
+            Ply<resign.value> ply{0};
+            if constexpr (resign.value) ply.move_index = move_index;
+            k_advance<resign.value><<<d.G, AZK_WAVE, d.lds_bytes, (hipStream_t)stream>>>(
+                GumbelPack<Dev, resign.value>{d, on<resign.value>(e->rs), on<true>(e->gb)}, ply, chosen_cell_dev, winner_dev, done_dev);
+        }, e->rs.v_resign != 0.0);
+        HIPCHK(e, hipGetLastError());
+        return AZK_OK;
+    }
     with_flags([&](auto cap, auto resign, auto forced, auto surprise) {
         Ply<resign.value || surprise.value> ply{sample_until_move};
         if constexpr (resign.value || surprise.value) ply.move_index = move_index;

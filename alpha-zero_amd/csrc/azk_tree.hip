@@ -1,4 +1,4 @@
-// azk_tree.hip - the AlphaZero search step of the batched self-play engine for MI355X (gfx950): k_tree (all twenty instantiations
+// azk_tree.hip - the AlphaZero search step of the batched self-play engine for MI355X (gfx950): k_tree (all twenty-eight instantiations
 // live in this one translation unit), its expanding wave, the leaf gather, and the C ABI calls that launch them (include/azk.h).
 // One 64-lane wavefront owns one game (the plain k_tree gives it a helper wave); the tree is
 // a structure-of-arrays arena in HBM whose child blocks are contiguous, so a PUCT scan is a coalesced read
@@ -6,6 +6,7 @@
 // Built with -ffp-contract=off: every float result is the same sequence of IEEE operations the oracle runs.
 // Reference lines cited as file:line relative to the reference root.
 #include "azk_engine_int.h"
+#include <type_traits>
 
 namespace {
 
@@ -36,8 +37,13 @@ enum { HO_OK = 0, HO_FC, HO_NV, HO_ROOTF64, HO_END_LO, HO_END_HI };   // hand-of
 // Hook: the move generator's (empty) mid-way hook type.  The FORCED kernels pass one of their own, so that their wave 1 calls an instantiation of
 // azk_valid_moves_gomoku of its own and the other kernels' copy keeps the callers - and with them the inlining order and the device code - it had.
 struct TreeForcedHook { __device__ __forceinline__ void operator()() const {} };
+// The GUMBEL kernels' hook type says more: their wave 1 writes a root's children as a Gumbel search wants them (gb, read under that type only) -
+// rootP = the child's raw logit + the game's Gumbel draw for its action, the logit and the root's value kept in the GumbelDev block.
+struct TreeGumbelHook { __device__ __forceinline__ void operator()() const {} };
 template <bool DBG, int KSL, typename Hook = AzkNoHook>
-__device__ __forceinline__ void tree_expand_wave(const Dev &d, const LdsView &L, const float *__restrict__ logits, const float *__restrict__ values, int ablate) {
+__device__ __forceinline__ void tree_expand_wave(const Dev &d, const LdsView &L, const float *__restrict__ logits, const float *__restrict__ values, int ablate,
+                                                 const GumbelDev &gb = GumbelDev{}) {
+    constexpr bool GUMBEL = std::is_same_v<Hook, TreeGumbelHook>;
     const int g = blockIdx.x, vi = g * d.K, lane = azk_lane();        // (slot 0 of the game, as in wave 0)
     const GameDesc &gd = d.g;
     const int A = gd.action_dim, rc = gd.rc;
@@ -158,8 +164,12 @@ __device__ __forceinline__ void tree_expand_wave(const Dev &d, const LdsView &L,
                 const float p = L.e[a] / s;
                 const size_t idx = base + fc + i;
                 d.H[idx] = NodeH{0, p, meta_pack(cell, 0), -1}; d.W[idx] = 0.0;
+                if constexpr (GUMBEL) {                               // the child's base score: its raw logit + the game's Gumbel draw for its action
+                    if (mix) { const float lga = lg[a]; d.rootP[(size_t)g * rc + i] = (double)lga + nzv[k4]; gb.logit[(size_t)g * rc + i] = lga; }
+                } else
                 if (mix) d.rootP[(size_t)g * rc + i] = (double)(0.75f * p) + 0.25 * nzv[k4];   // utils.py:24-25
             }
+            if constexpr (GUMBEL) { if (mix && lane == 0) gb.v0[g] = vraw; }
             if (lane == 0) {
                 d.H[base + node].fc = fc;
                 d.H[base + node].meta = (node_meta & 0xffff0000u) | (uint32_t)nv;
@@ -226,21 +236,49 @@ __device__ __forceinline__ double tree_forced_score(double u, int N, double P, d
     else return u;
 }
 
+// GUMBEL (Gumbel root search, azk_set_gumbel_root): the float64 root scan - and only it, in all three of its forms - scores
+// a child  gl + sig * (W / N)  (gl alone while N = 0) if its visit count N equals cv, the sequential-halving table's word for this root
+// selection, and -inf otherwise; gl = rootP (raw logit + Gumbel draw, written at the root's expansion), sig = (c_visit + cv) * c_scale.  "First
+// maximum wins" stays.  The table guarantees an eligible child at every selection; were there none, the first child would be taken.
+template <bool GUMBEL>
+__device__ __forceinline__ double tree_gumbel_score(double u, int N, double q, double gl, int cv, double sig) {
+    if constexpr (GUMBEL) return N == cv ? (N != 0 ? gl + sig * q : gl) : -__builtin_huge_val();
+    else return u;
+}
+
 // The kernels.  The fourteen instantiations without FORCED keep the name, the arguments and the device code they had before the option
-// existed (tools/compare_kernel_isa.py); the six with it - fused, select-only and MULTI, each at KSL 4 and 7 - take the extra argument block.
+// existed (tools/compare_kernel_isa.py); the six with it - fused, select-only and MULTI, each at KSL 4 and 7 - take the extra argument block,
+// and so do the eight with GUMBEL (theirs is the GumbelDev block).
 template <bool EXPAND, bool SELECT, bool DBG, bool MULTI = false, int KSL = 7>
 __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd, const float *__restrict__ logits, const float *__restrict__ values) {
     constexpr bool FORCED = false;
+    constexpr bool GUMBEL = false;
 #define AZK_TREE_FORCED_ARG ForcedDev{}
+#define AZK_TREE_GUMBEL_ARG GumbelDev{}
 #include "azk_tree_step.h"
+#undef AZK_TREE_GUMBEL_ARG
 #undef AZK_TREE_FORCED_ARG
 }
 
 template <bool EXPAND, bool SELECT, bool DBG, bool MULTI, int KSL, bool FORCED>
 __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd, const float *__restrict__ logits, const float *__restrict__ values, ForcedDev fd_arg) {
     static_assert(FORCED && SELECT && !DBG, "FORCED exists for the product kernels that select");
+    constexpr bool GUMBEL = false;
 #define AZK_TREE_FORCED_ARG fd_arg
+#define AZK_TREE_GUMBEL_ARG GumbelDev{}
 #include "azk_tree_step.h"
+#undef AZK_TREE_GUMBEL_ARG
+#undef AZK_TREE_FORCED_ARG
+}
+
+// the eight GUMBEL kernels: fused, select-only, expand-only (the root's expansion writes rootP its own way) and MULTI, each at KSL 4 and 7
+template <bool EXPAND, bool SELECT, bool DBG, bool MULTI, int KSL, bool FORCED, bool GUMBEL>
+__global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd, const float *__restrict__ logits, const float *__restrict__ values, GumbelDev gb_arg) {
+    static_assert(GUMBEL && !FORCED && !DBG, "GUMBEL exists for the product kernels, without forced playouts");
+#define AZK_TREE_FORCED_ARG ForcedDev{}
+#define AZK_TREE_GUMBEL_ARG gb_arg
+#include "azk_tree_step.h"
+#undef AZK_TREE_GUMBEL_ARG
 #undef AZK_TREE_FORCED_ARG
 }
 
@@ -306,7 +344,14 @@ static void launch_k_tree_forced(const Dev &d, const float *logits, const float 
     else k_tree<E, true, false, M, 7, true><<<d.G, nthr, d.lds_bytes, st>>>(d, logits, values, fd);
 }
 
-// The one place that picks a k_tree instantiation: seven (EXPAND, SELECT, DBG, MULTI) forms and three FORCED ones, each at KSL 4 and 7.
+template <bool E, bool S, bool M>                                     // Gumbel root search: the product kernels
+static void launch_k_tree_gumbel(const Dev &d, const float *logits, const float *values, const GumbelDev &gb, hipStream_t st) {
+    const int nthr = M ? AZK_WAVE : 2 * AZK_WAVE;
+    if (d.g.rc <= 4 * AZK_WAVE && d.g.action_dim <= 4 * AZK_WAVE) k_tree<E, S, false, M, 4, false, true><<<d.G, nthr, d.lds_bytes, st>>>(d, logits, values, gb);
+    else k_tree<E, S, false, M, 7, false, true><<<d.G, nthr, d.lds_bytes, st>>>(d, logits, values, gb);
+}
+
+// The one place that picks a k_tree instantiation: seven (EXPAND, SELECT, DBG, MULTI) forms, three FORCED ones and four GUMBEL ones, each at KSL 4 and 7.
 //   multi   the caller wants budget stepping.  The lock-step entry points pass `e->multi && !d.ablate` - an ablation build
 //           (AZK_TREE_ABLATE) never runs MULTI from them; azk_async_step passes true and has never looked at the ablation word.
 //           MULTI exists only with SELECT: budget stepping with `select` always launches <true, true, false, true>, whatever
@@ -315,6 +360,8 @@ static void launch_k_tree_forced(const Dev &d, const float *logits, const float 
 //   DBG     chosen from d.ablate.
 //   FORCED  an engine with forced playouts set (e->forced_k != 0) launches the FORCED sibling of whichever product kernel selects; its
 //           expand-only launches and an ablation build's DBG kernels are the plain ones (no selection / debug only).
+//   GUMBEL  an engine with a Gumbel root set (e->gb.m != 0; never together with FORCED) launches the GUMBEL sibling of every product kernel,
+//           the expand-only one included; an ablation build's DBG kernels are the plain ones.
 //   symmetry  an engine with azk_set_eval_symmetry on expands from ITS copy of the rows, turned back into each position's frame by
 //           k_sym_logits in front of the launch (the kernel is the same, it is handed another pointer); the callers run azk_sym_leaves
 //           behind a launch that selects.
@@ -322,7 +369,12 @@ int32_t azk_launch_tree(azk_engine *e, bool expand, bool select, bool multi, con
     const Dev &d = e->d;
     if (expand || (multi && select)) logits = azk_sym_restore(e, logits, st);
     const bool forced = e->forced_k != 0.0 && select && (multi || !d.ablate);
-    if (forced && multi) launch_k_tree_forced<true, true>(d, logits, values, e->forced(), st);
+    const bool gumbel = e->gb.m != 0 && (multi || !d.ablate);
+    if (gumbel && multi && select) launch_k_tree_gumbel<true, true, true>(d, logits, values, e->gb, st);
+    else if (gumbel && expand && select) launch_k_tree_gumbel<true, true, false>(d, logits, values, e->gb, st);
+    else if (gumbel && expand) launch_k_tree_gumbel<true, false, false>(d, logits, values, e->gb, st);
+    else if (gumbel) launch_k_tree_gumbel<false, true, false>(d, logits, values, e->gb, st);
+    else if (forced && multi) launch_k_tree_forced<true, true>(d, logits, values, e->forced(), st);
     else if (forced && expand) launch_k_tree_forced<true, false>(d, logits, values, e->forced(), st);
     else if (forced) launch_k_tree_forced<false, false>(d, logits, values, e->forced(), st);
     else if (multi && select) launch_k_tree<true, true, false, true>(d, logits, values, st);

@@ -2,7 +2,8 @@
 // with it are two overloads (the second takes one more argument block), and the first must keep the device code it had before the option
 // existed - a body shared through a __forceinline__ function does not (the inliner hands the scheduler another instruction order;
 // tools/compare_kernel_isa.py), the same text compiled in place does.  In scope here: the template parameters EXPAND, SELECT, DBG, MULTI,
-// KSL, a constant FORCED, the kernel arguments dd, logits, values, and AZK_TREE_FORCED_ARG = the ForcedDev block (read under FORCED only).
+// KSL, a constant FORCED, the kernel arguments dd, logits, values, and AZK_TREE_FORCED_ARG = the ForcedDev block (read under FORCED only);
+// a constant GUMBEL and AZK_TREE_GUMBEL_ARG = the GumbelDev block (read under GUMBEL only), the third overload's.
     const Dev &d = dd;
     const int ablate = DBG ? dd.ablate : 0;
     const int g = blockIdx.x;
@@ -18,7 +19,8 @@
     if constexpr (TWO) {
         if (uniform_i32((int)(threadIdx.x >> 6)) != 0) {             // wave-uniform: the role split is a scalar branch
             if constexpr (EXPAND) {
-                if constexpr (FORCED) tree_expand_wave<DBG, KSL, TreeForcedHook>(d, L, logits, values, ablate);
+                if constexpr (GUMBEL) tree_expand_wave<DBG, KSL, TreeGumbelHook>(d, L, logits, values, ablate, AZK_TREE_GUMBEL_ARG);
+                else if constexpr (FORCED) tree_expand_wave<DBG, KSL, TreeForcedHook>(d, L, logits, values, ablate);
                 else tree_expand_wave<DBG, KSL>(d, L, logits, values, ablate);
             }
             // every store above has been acknowledged and the hand-off words are in LDS before the barrier (the workgroup-scope
@@ -275,8 +277,12 @@
                     const float p = L.e[a] / s;
                     const size_t idx = base + fc + i;
                     d.H[idx] = NodeH{0, p, meta_pack(cell, 0), -1}; d.W[idx] = 0.0;
+                    if constexpr (GUMBEL) {                           // the child's base score: its raw logit + the game's Gumbel draw for its action
+                        if (mix) { const float lga = lg[a]; d.rootP[(size_t)g * rc + i] = (double)lga + nzv[k4]; AZK_TREE_GUMBEL_ARG.logit[(size_t)g * rc + i] = lga; }
+                    } else
                     if (mix) d.rootP[(size_t)g * rc + i] = (double)(0.75f * p) + 0.25 * nzv[k4];   // utils.py:24-25
                 }
+                if constexpr (GUMBEL) { if (mix && lane == 0) AZK_TREE_GUMBEL_ARG.v0[g] = vraw; }
                 if (lane == 0) {
                     d.H[base + node].fc = fc;
                     d.H[base + node].meta = (node_meta & 0xffff0000u) | (uint32_t)nv;
@@ -354,6 +360,15 @@
             if (nch <= 0 || (ablate & 2)) break;
             if (ablate & 64) seg_t = clock64();
             const bool f64 = node == 0 && root_f64;
+            int gcv = 0;                                              // GUMBEL: the visit count a root child must have to be eligible now
+            double gsig = 0.0;                                        // ... and sigma's factor at that count
+            if constexpr (GUMBEL) {
+                if (f64) {                                            // (a uniform word of (nch, Np): its load goes out with the children's)
+                    const GumbelDev &gb = AZK_TREE_GUMBEL_ARG;
+                    gcv = gb.table[(size_t)min(gb.m, nch) * gb.n + max(0, min(Np - 1, gb.n - 1))];
+                    gsig = (gb.c_visit + (double)gcv) * gb.c_scale;
+                }
+            }
             double bu64 = 0.0;
             float bu32 = 0.f;
             int best = 0x7fffffff, bN = 0, bfc = -1;
@@ -375,7 +390,7 @@
                     const double s = sqrt((double)Np);
                     const double u0 = P64 * s / (double)(Nc + 1);
                     const double q = Wc / (double)Nc;                 // N = 0: inf/nan, discarded by the select
-                    const double u = valid ? tree_forced_score<FORCED>(Nc != 0 ? q + u0 : u0, Nc, P64, fk, Np) : -__builtin_huge_val();
+                    const double u = valid ? tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc != 0 ? q + u0 : u0, Nc, P64, fk, Np), Nc, q, P64, gcv, gsig) : -__builtin_huge_val();
                     const double um = wave_max_f64(u);               // (all lanes take part: never under the short-circuit below)
                     winners = __ballot(valid & (u == um));
                     if constexpr (FORCED) forced_sel = um == __builtin_huge_val();
@@ -406,8 +421,8 @@
                     const double s = sqrt((double)Np);
                     const double u0a = Qa * s / (double)(Na + 1), u0b = Qb * s / (double)(Nb + 1);
                     const double qa = Wa / (double)Na, qb = Wb / (double)Nb;
-                    const double ua = tree_forced_score<FORCED>(Na != 0 ? qa + u0a : u0a, Na, Qa, fk, Np);
-                    const double ub = vb ? tree_forced_score<FORCED>(Nb != 0 ? qb + u0b : u0b, Nb, Qb, fk, Np) : -__builtin_huge_val();
+                    const double ua = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Na != 0 ? qa + u0a : u0a, Na, Qa, fk, Np), Na, qa, Qa, gcv, gsig);
+                    const double ub = vb ? tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nb != 0 ? qb + u0b : u0b, Nb, Qb, fk, Np), Nb, qb, Qb, gcv, gsig) : -__builtin_huge_val();
                     const double um = wave_max_f64(fmax(ua, ub));
                     wa = __ballot(va & (ua == um)); wb = __ballot(vb & (ub == um));
                     if constexpr (FORCED) forced_sel = um == __builtin_huge_val();
@@ -462,7 +477,7 @@
                         const int i = c0 + lane + AZK_WAVE * k;
                         const double u0 = P64[k] * s / (double)(Nc[k] + 1);
                         const double q = Wc[k] / (double)Nc[k];          // N = 0: inf/nan, discarded by the select below
-                        const double u = tree_forced_score<FORCED>(Nc[k] != 0 ? q + u0 : u0, Nc[k], P64[k], fk, Np);
+                        const double u = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc[k] != 0 ? q + u0 : u0, Nc[k], P64[k], fk, Np), Nc[k], q, P64[k], gcv, gsig);
                         const bool take = (i < nch) & ((best == 0x7fffffff) | (u > bu64));
                         bu64 = take ? u : bu64; best = take ? i : best; bN = take ? Nc[k] : bN;
                         bmeta = take ? mc[k] : bmeta; bfc = take ? fcc[k] : bfc;

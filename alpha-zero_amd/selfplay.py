@@ -99,6 +99,46 @@ def check_forced_playouts(forced_playouts, evaluator=True, dirichlet=True, leave
     return k
 
 
+def check_gumbel_root(gumbel_root, n_sims=None, evaluator=True, dirichlet=True, leaves_per_step=1, tree_reuse=0, playout_cap=None,
+                      forced_playouts=None, surprise_weight=None):
+    """gumbel_root = (m, c_visit, c_scale) -> (int, float, float), or None for off.  OPT-IN Gumbel root search (include/azk.h azk_set_gumbel_root;
+    DESIGN section 24): m root actions sampled by Gumbel-top-k, the search's simulations spread over them by sequential halving, the survivor
+    played and softmax(logits + sigma(completed Q)) recorded.  Raises ValueError, before any engine exists, for what the engine refuses too - m
+    outside 1..64, a negative or non-finite c_visit, a c_scale that is not positive and finite, fewer than 2 simulations, virtual loss, tree
+    reuse, a playout cap, forced playouts, surprise weighting - and for searches without a network or without the Gumbel rows: vanilla MCTS
+    (evaluator None) and dirichlet=False."""
+    if gumbel_root is None:
+        return None
+    try:
+        m, c_visit, c_scale = gumbel_root
+        m, c_visit, c_scale = int(m), float(c_visit), float(c_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"gumbel_root must be (m, c_visit, c_scale), not {gumbel_root!r}")
+    if not 1 <= m <= 64:
+        raise ValueError(f"gumbel_root: m must lie in [1, 64], not {m!r}")
+    if not 0.0 <= c_visit < float("inf"):
+        raise ValueError(f"gumbel_root: c_visit must be finite and not negative, not {c_visit!r}")
+    if not 0.0 < c_scale < float("inf"):
+        raise ValueError(f"gumbel_root: c_scale must be finite and positive, not {c_scale!r}")
+    if n_sims is not None and (isinstance(n_sims, (tuple, list)) or int(n_sims) < 2):
+        raise ValueError(f"gumbel_root: n_sims must be one number >= 2 (the halving table is built for one budget), not {n_sims!r}")
+    if evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator)):
+        raise ValueError("gumbel_root: vanilla MCTS (evaluator None) is refused - it has no logits for the Gumbel draws to be added to")
+    if not dirichlet:
+        raise ValueError("gumbel_root takes the place of root noise (dirichlet=True): the runners pass Gumbel rows where they pass Dirichlet rows")
+    if int(leaves_per_step) > 1:
+        raise ValueError("gumbel_root does not combine with leaves_per_step > 1 (a virtual-loss search counts a visit before its value exists)")
+    if tree_reuse:
+        raise ValueError("gumbel_root does not combine with tree reuse (the eligibility rule needs a fresh root)")
+    if playout_cap is not None:
+        raise ValueError("gumbel_root does not combine with playout_cap (the halving table is built for one budget)")
+    if forced_playouts:
+        raise ValueError("gumbel_root does not combine with forced_playouts (the eligibility rule needs raw root selection)")
+    if surprise_weight is not None:
+        raise ValueError("gumbel_root does not combine with surprise_weight (its recorded pi is not a visit distribution)")
+    return m, c_visit, c_scale
+
+
 def eval_symmetry_elements(game, size=None):
     """The D4 elements (the emission's numbering: rot0, lr, tb, rot90, lr(rot90), tb(rot90), rot180, rot270) a game's geometry admits
     (include/azk.h azk_set_eval_symmetry): all eight on a square board with one action per cell, {0, 1, 2, 6} on a Gomoku board with
@@ -229,7 +269,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                     alpha=0.03, noise_fn=None, uniform_fn=None, device=0, leaf_dtype="float32", engine=None,
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
                     budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
-                    eval_symmetry=None, emit_symmetry=None, surprise_weight=None):
+                    eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -252,6 +292,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     third on once per element of the mask, on every geometry (Connect4 and non-square Gomoku included); an engine handed in must have
     been created with the same mask (ValueError).  surprise_weight = lambda (OPT-IN, check_surprise_weight): every ply records its policy surprise
     and coin (SelfPlayResult.kl / .coin) and the replay ring gets each recorded ply as often as its weight says (surprise_copies).
+    gumbel_root = (m, c_visit, c_scale) (OPT-IN, check_gumbel_root): a Gumbel root search of n_sims simulations per move - the engine's Gumbel
+    rows (or noise_fn's) where the Dirichlet rows go, SelfPlayResult.pis and the replay tuples carry softmax(logits + sigma(completed Q)).
     """
     import torch
     emit = check_emit_symmetry(emit_symmetry, game, size)
@@ -262,6 +304,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     fpk = check_forced_playouts(forced_playouts, evaluator, dirichlet, leaves_per_step)
     sym = check_eval_symmetry(eval_symmetry, game, size, evaluator, leaves_per_step, seed)
     lam = check_surprise_weight(surprise_weight, evaluator, leaves_per_step)
+    gum = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, cap, fpk, lam)
     _refuse_vanilla_resign(rsg, evaluator)
     if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
@@ -279,6 +322,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         eng.set_eval_symmetry(*sym)
     if lam is not None:
         eng.set_surprise_weighting(lam, seed, first_global_game)
+    if gum is not None:
+        eng.set_gumbel_root(gum[0], n_sims, gum[1], gum[2])
     # virtual-loss, top-up and capped engines are driven by the simulation budget
     budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
     assert eng.G == n_games
@@ -303,6 +348,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
             nz = noise_fn(move)
             noise = torch.from_numpy(np.ascontiguousarray(nz, np.float64)).to(eng.device) if nz is not None else None
             uni = None
+        elif gum is not None:
+            noise, uni = eng.gen_gumbel(seed, first_global_game, move), None
         else:
             noise, uni = eng.gen_noise(seed, first_global_game, move, alpha, want_noise=dirichlet)
         if uniform_fn is not None:
@@ -318,8 +365,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
             eng.search(ev, ns, noise if dirichlet else None)
         full_h = eng.search_full().cpu().numpy() if eng.playout_cap is not None else None
         pi, q, _ = eng.root_stats()
-        if eng.forced_playouts is not None:
-            pi = eng.root_policy_target()                         # what advance records: pruned where the search was a forced one
+        if eng.forced_playouts is not None or eng.gumbel_root is not None:
+            pi = eng.root_policy_target()                         # what advance records: pruned where the search was a forced one; a Gumbel root's target
         cells_before, to_move, _ = eng.get_positions()
         chosen, winner, done = eng.advance(uni, su, move_index=move)
         resigned_h = eng.resigned().cpu().numpy() if eng.resign is not None else None
@@ -478,6 +525,10 @@ class SelfPlayRunner:
     surprise_weight = lambda (OPT-IN, check_surprise_weight; with everything above): every move records its policy surprise and coin -
     `record_surprise` ((kl, coin), float64 [group size] each, valid inside on_records) - and the replay ring gets each recorded ply as often as
     its weight says.
+
+    gumbel_root = (m, c_visit, c_scale) (OPT-IN, check_gumbel_root; with resign, eval_symmetry, emit_symmetry, the eval cache, plain and budget
+    stepping): every search is a Gumbel root search of n_sims simulations; the groups get Gumbel rows of the same key where they get Dirichlet
+    rows, the records' pi and the replay ring carry softmax(logits + sigma(completed Q)).
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
@@ -485,8 +536,10 @@ class SelfPlayRunner:
                  use_graph=False, n_split=1, replay=None, cache_entries=0, cache_shared=False, budget_stepping=False, per_launch=8,
                  steps_per_graph=32,
                  leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None,
-                 surprise_weight=None):
+                 surprise_weight=None, gumbel_root=None):
         import torch
+        self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, playout_cap, forced_playouts,
+                                             surprise_weight)
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
         self.surprise_weight = check_surprise_weight(surprise_weight, evaluator, leaves_per_step)
         self.record_surprise = None
@@ -541,13 +594,18 @@ class SelfPlayRunner:
                 h.eng.set_eval_symmetry(*self.eval_symmetry)      # (the key is the position: the same for every group)
             if self.surprise_weight is not None:
                 h.eng.set_surprise_weighting(self.surprise_weight, seed, first_global_game + i * per)
+            if self.gumbel_root is not None:
+                h.eng.set_gumbel_root(self.gumbel_root[0], n_sims, self.gumbel_root[1], self.gumbel_root[2])
 
     # ---- one move for every slot -------------------------------------------------------------------------
     def play_move(self):
         torch = self.torch
         per = self.halves[0].eng.G
         for i, h in enumerate(self.halves):
-            noise, h.uni = h.eng.gen_noise(self.seed, self.first + i * per, self.move_idx, self.alpha, want_noise=self.dirichlet)
+            if self.gumbel_root is not None:                  # Gumbel rows where the Dirichlet rows go; the move needs no uniform
+                noise, h.uni = h.eng.gen_gumbel(self.seed, self.first + i * per, self.move_idx), None
+            else:
+                noise, h.uni = h.eng.gen_noise(self.seed, self.first + i * per, self.move_idx, self.alpha, want_noise=self.dirichlet)
             if self.dirichlet:
                 h.noise_buf.copy_(noise)
         if self.use_graph:
@@ -559,8 +617,8 @@ class SelfPlayRunner:
             if self.playout_cap is not None:
                 h.h_full.copy_(e.search_full(), non_blocking=True)
             pi, q, _ = e.root_stats()
-            if self.forced_playouts is not None:
-                pi = e.root_policy_target()                   # what advance records: pruned where the search was a forced one
+            if self.forced_playouts is not None or self.gumbel_root is not None:
+                pi = e.root_policy_target()                   # what advance records: pruned where the search was a forced one; a Gumbel root's target
             h.h_pi.copy_(pi, non_blocking=True)
             h.h_q.copy_(q, non_blocking=True)
             chosen, winner, done = e.advance(h.uni, self.sample_until, move_index=self.move_idx)
@@ -808,13 +866,18 @@ class AsyncSelfPlayRunner:
 
     surprise_weight = lambda (OPT-IN, check_surprise_weight; with everything above): the games and records of SelfPlayRunner(surprise_weight=...),
     slot for slot - the move kernel records kl and coin, the drain writes each recorded ply as often as its weight says.  `record_surprise`
-    ((kl, coin), float64 numpy, one per record, valid inside on_records) carries them."""
+    ((kl, coin), float64 numpy, one per record, valid inside on_records) carries them.
+
+    gumbel_root = (m, c_visit, c_scale) (OPT-IN, check_gumbel_root; with resign, eval_symmetry, emit_symmetry and the eval cache; not with
+    reroot): the games and records of SelfPlayRunner(gumbel_root=...), slot for slot - the movers make the Gumbel rows a search ahead where they
+    make Dirichlet rows, play the survivor and record the Gumbel target.  n_sims is fixed for the run."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
-                 playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None):
+                 playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None):
         import torch
+        self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, 1, tree_reuse or reroot, playout_cap, forced_playouts, surprise_weight)
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
         self.surprise_weight = check_surprise_weight(surprise_weight, evaluator)
         self.record_surprise = None
@@ -851,6 +914,8 @@ class AsyncSelfPlayRunner:
             e.set_eval_symmetry(*self.eval_symmetry)
         if self.surprise_weight is not None:
             e.set_surprise_weighting(self.surprise_weight, seed, first_global_game)
+        if self.gumbel_root is not None:
+            e.set_gumbel_root(self.gumbel_root[0], n_sims, self.gumbel_root[1], self.gumbel_root[2])
         cap = (4 * n_games if record_capacity is None else record_capacity) if (on_records is not None or record_capacity) else 0
         self.stats, self.records = e.async_begin(n_sims, self.per_launch, SAMPLE_UNTIL[game], seed, first_global_game, alpha, dirichlet, recycle, cap,
                                                  young_launch_us=young_launch_us, reroot=bool(self.reroot))

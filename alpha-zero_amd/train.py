@@ -95,7 +95,7 @@ def save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=Non
 
 
 def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed=None, batched=True, playout_cap=None, resign=None,
-                 forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None):
+                 forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None):
     """train.py:54-83: `iterations` self-play games of Game with `model` into `buffer`; returns [first, second, draw] counts.
     batched=False plays the games one after the other through Game().self_play and save_data_to_buffer exactly as the
     reference does (global np.random stream: a seeded caller gets the reference's buffer); the default plays them as one
@@ -108,7 +108,9 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     emit_symmetry = "board" | "none" | elements (OPT-IN, batched only; selfplay.check_emit_symmetry): every position from the third on is stored
     once per element of the mask, on every board - Connect4 and non-square Gomoku included; both buffer kinds get the same tuples.
     surprise_weight = lambda (OPT-IN, batched only; selfplay.check_surprise_weight): every stored position is stored as often as its policy
-    surprise weight says (selfplay.surprise_copies); both buffer kinds get the same tuples."""
+    surprise weight says (selfplay.surprise_copies); both buffer kinds get the same tuples.  gumbel_root = (m, c_visit, c_scale) (OPT-IN,
+    batched only; selfplay.check_gumbel_root): every search is a Gumbel root search of mcts_iter simulations; both buffer kinds get
+    softmax(logits + sigma(completed Q)) as the pi of every stored position."""
     from azk import DeviceReplay
     from selfplay import check_emit_symmetry, check_surprise_weight, mask_elements, self_play_batch, surprise_copies
     lam = check_surprise_weight(surprise_weight, model)
@@ -123,6 +125,8 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
             raise ValueError("collect_data: resign needs the batched engine (batched=True)")
         if forced_playouts is not None:
             raise ValueError("collect_data: forced_playouts needs the batched engine (batched=True)")
+        if gumbel_root is not None:
+            raise ValueError("collect_data: gumbel_root needs the batched engine (batched=True)")
         if eval_symmetry is not None and eval_symmetry is not False:
             raise ValueError("collect_data: eval_symmetry needs the batched engine (batched=True)")
         results = [0, 0, 0]
@@ -138,7 +142,7 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     leaf_dtype = "bfloat16" if getattr(model, "dtype", None) is not None and str(model.dtype).endswith("bfloat16") else "float32"
     res = self_play_batch(Game.engine_name, model, iterations, mcts_iter, size=Game._size(), seed=seed, leaf_dtype=leaf_dtype,
                           replay=buffer if on_device else None, playout_cap=playout_cap, resign=resign, forced_playouts=forced_playouts,
-                          eval_symmetry=eval_symmetry, emit_symmetry=emit_symmetry, surprise_weight=surprise_weight)
+                          eval_symmetry=eval_symmetry, emit_symmetry=emit_symmetry, surprise_weight=surprise_weight, gumbel_root=gumbel_root)
     emit = check_emit_symmetry(emit_symmetry, Game.engine_name, Game._size())
     results = [0, 0, 0]
     for r in res:

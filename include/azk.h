@@ -387,6 +387,49 @@ int32_t azk_advance_keyed(azk_engine *e, const double *uniforms_dev, int32_t sam
 int32_t azk_get_surprise(azk_engine *e, double *kl_dev, double *coin_dev, void *stream);
 int32_t azk_async_surprise_columns(azk_engine *e, double *rec_kl_dev, double *rec_coin_dev);
 
+/* ---- Gumbel root search (OPT-IN; off, the engine is what it was bit for bit).  "Policy improvement by planning with Gumbel" (Danihelka et
+ * al., ICLR 2022): m root actions are sampled without replacement by the Gumbel-top-k trick, the search's simulations are spread over them by
+ * sequential halving, the survivor is played, and the recorded pi is softmax(logits + sigma(completed Q)) - a policy improvement at any
+ * budget, 16 or 32 simulations included.  Levels below the root keep the reference's PUCT.  All arithmetic float64.
+ *   rows       while the option is set, noise_dev of azk_begin_search / azk_begin_search_budget carries the games' GUMBEL rows g[G][A] instead
+ *              of Dirichlet rows: no Dirichlet mixing takes place, a row of zeros is the noise-free (arena) search, NULL: AZK_ERR_STATE.
+ *   schedule   schedule(m, n) is a list of n visit counts.  m <= 1: 0, 1, .., n - 1.  Else L = ceil(log2 m), v[0..m-1] = 0, c = m, and while
+ *              the list is shorter than n:  extra = max(1, n / (L * c)) (integer division);  extra times: append v[0..c-1], then add 1 to each
+ *              of v[0..c-1];  then c = max(2, c / 2).  Cut to n.  The engine keeps the rows m' = 0..m for n = n_sims - 1 (simulation 0 expands
+ *              the root and selects nothing).  schedule(4, 15) = 0,0,0,0,1,1,2,2,3,3,4,4,5,5,6.
+ *   expansion  of the root: children, float32 priors and the eval-cache write as ever; child i with action a also gets its base score
+ *              gl_i = (double)logit_a + g[a]  (the raw float32 logit), which azk_root_children / azk_export_tree report as its prior; its
+ *              logit and the root's float32 value v0 (the evaluator's or the cache's, for the side to move) are kept.
+ *   selection  the root only, in every simulation.  Np = the root's visit count, t = Np - 1, m' = min(m, children),
+ *              cv = schedule(m', n)[min(t, n - 1)],  sig = (c_visit + (double)cv) * c_scale.  A child with N visits and value sum W scores
+ *                  N == cv ? (N != 0 ? gl + sig * (W / (double)N) : gl) : -inf
+ *              and the first maximum wins.  Every simulation finds an eligible child and exactly min(m, children) children are ever visited.
+ *   move and   once per move, children in list order.  S = sum N;  q_i = W_i / N_i for N_i > 0;  P_i = the child's float32 prior;
+ *   target     pv = sum over visited of P_i,  pq = sum over visited of P_i * q_i  (both sequential in list order);
+ *                  vmix = S > 0 ? (v0 + S * (pq / pv)) / (1 + S) : v0;   qh_i = N_i > 0 ? q_i : vmix;   sigf = (c_visit + max N) * c_scale
+ *              The move: among the children with N_i == max N, the first maximum of gl_i + sigf * qh_i.  The recorded pi:
+ *                  y_i = logit_i + sigf * qh_i;   pi[a_i] = exp(y_i - max y) / sum_j exp(y_j - max y);   0 on every other action
+ *              (each lane of the mover's wave sums its children's exponentials in list order, the wave adds the 64 partial sums pairwise).
+ *              azk_advance(_resign) ignores uniforms_dev and sample_until_move (the Gumbel arg-max is the sample), and so do the asynchronous
+ *              movers with azk_async_config.sample_until_move.
+ *   who sees   the recorded pi goes where pi goes: the trajectory behind azk_emit_finished / azk_async_drain's tuples, the asynchronous
+ *   what       record ring's rec_pi, and azk_root_policy_target.  azk_root_stats, q, resignation and the counters keep raw visits.
+ *   gen        azk_gen_gumbel: float64 [G][A] into device memory.  Entry a of game g draws one Philox4x32-10 block at counter
+ *              {gg lo, gg hi ^ (a << 8), move_index, 0xFFFFFFFB}, gg = first_global_game + g, key (seed lo, seed hi);
+ *              u = (((c0 << 32 | c1) >> 12) + 0.5) * 2^-52 (exact, strictly inside (0, 1));  g = -log(-log(u)).  Word 3 = 0xFFFFFFFB is no
+ *              other stream's.  The asynchronous movers (dirichlet = 1) make these rows a search ahead where they make Dirichlet rows now.
+ *              azk_gen_gumbel_uniforms: the same call's uniforms u, float64 [G][A] (what a restatement compares bit for bit).
+ * azk_set_gumbel_root: 1 <= m <= 64, 2 <= n_sims <= max_sims, c_visit >= 0 and c_scale > 0, both finite, else AZK_ERR_ARG; not with
+ * leaves_per_step > 1 (AZK_ERR_ARG).  AZK_ERR_STATE in combination with tree reuse, a playout cap, forced playouts or surprise weighting (the
+ * eligibility rule needs a fresh root, one budget and raw root selection; those options' setters refuse likewise while a Gumbel root is
+ * set), for a budget search or azk_async_begin whose n_sims differs from the option's, for azk_async_begin with dirichlet = 0 and for
+ * azk_async_begin_reuse, and after azk_async_begin.  azk_clear_gumbel_root switches the option off.  Combines with resignation,
+ * evaluation symmetry, emit_elements, the eval cache, plain and budget stepping and the asynchronous movers. */
+int32_t azk_set_gumbel_root(azk_engine *e, int32_t m, int32_t n_sims, double c_visit, double c_scale, void *stream);
+int32_t azk_clear_gumbel_root(azk_engine *e);
+int32_t azk_gen_gumbel(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double *gumbel_dev, void *stream);
+int32_t azk_gen_gumbel_uniforms(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double *uniforms_dev, void *stream);
+
 /* One simulation per active game (ai/mcts.py:16-60), split around the evaluator:
  *   azk_step_select   - mcts.py:18-37: PUCT walk (node.py:42-47, utils.py:29-44), make_move along the
  *                       path, terminal test + immediate backup, get_valid_moves, canonical board.

@@ -115,20 +115,11 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     from selfplay import check_emit_symmetry, check_surprise_weight, mask_elements, self_play_batch, surprise_copies
     lam = check_surprise_weight(surprise_weight, model)
     if not batched:
-        if lam is not None:
-            raise ValueError("collect_data: surprise_weight needs the batched engine (batched=True)")
-        if emit_symmetry is not None:
-            raise ValueError("collect_data: emit_symmetry needs the batched engine (batched=True)")
-        if playout_cap is not None:
-            raise ValueError("collect_data: playout_cap needs the batched engine (batched=True)")
-        if resign is not None:
-            raise ValueError("collect_data: resign needs the batched engine (batched=True)")
-        if forced_playouts is not None:
-            raise ValueError("collect_data: forced_playouts needs the batched engine (batched=True)")
-        if gumbel_root is not None:
-            raise ValueError("collect_data: gumbel_root needs the batched engine (batched=True)")
-        if eval_symmetry is not None and eval_symmetry is not False:
-            raise ValueError("collect_data: eval_symmetry needs the batched engine (batched=True)")
+        for name, value in (("surprise_weight", lam), ("emit_symmetry", emit_symmetry), ("playout_cap", playout_cap), ("resign", resign),
+                            ("forced_playouts", forced_playouts), ("gumbel_root", gumbel_root),
+                            ("eval_symmetry", None if eval_symmetry is False else eval_symmetry)):
+            if value is not None:
+                raise ValueError(f"collect_data: {name} needs the batched engine (batched=True)")
         results = [0, 0, 0]
         for _ in range(iterations):
             game = Game()

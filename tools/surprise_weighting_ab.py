@@ -16,18 +16,14 @@ the two lines are one workload and ms per G moves compares directly.  Then each 
 """
 import argparse
 import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "alpha-zero_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import ab_common as ab
 
 # (name, surprise weighting on)
 LINES = [("async off", False), ("async surprise weighting", True)]
+FORWARDED = ("games", "sims", "size", "lam", "steps", "warmup", "preroll_cheap", "preroll_full", "stat_moves", "cache_entries", "replay_capacity",
+             "per_launch", "steps_per_graph", "timer_stride")
 
 
 def game_statistics(games, lam):
@@ -51,73 +47,18 @@ def game_statistics(games, lam):
 
 
 def worker(args):
-    import torch
-    import azk
-    from pvnet import NetConfig, PolicyValueNet
-    from selfplay import AsyncSelfPlayRunner, KernelTimer
+    from selfplay import KernelTimer
     name, on = LINES[args.line - 1]
-    torch.cuda.set_device(0)
-    A = args.size * args.size
-    net = PolicyValueNet(NetConfig(args.size, args.size, 2, A, 5, 512, 8, 1), seed=0, device="cuda:0", dtype=torch.bfloat16, path="clsfold")
-    kt = KernelTimer(stride=args.timer_stride)
-    replay = azk.DeviceReplay(args.replay_capacity, 2, args.size, args.size, A)
+    kt, replay = KernelTimer(stride=args.timer_stride), ab.device_replay(args)
     # the record ring exists in both lines (the movers write a record per move either way); nobody reads it inside the timed window
-    runner = AsyncSelfPlayRunner("gomoku", net, args.games, args.sims, per_launch=args.per_launch, size=args.size, seed=0, device=0,
-                                 leaf_dtype="bfloat16", recycle=True, kernel_timer=kt, cache_entries=args.cache_entries, cache_shared=True,
-                                 steps_per_graph=args.steps_per_graph, replay=replay, record_capacity=8 * args.games,
-                                 surprise_weight=args.lam if on else None)
+    runner = ab.async_runner(args, kt, replay, record_capacity=8 * args.games, surprise_weight=args.lam if on else None)
     drain_events = []
-    eng, plain_drain = runner.eng, runner.eng.async_drain
-
-    def timed_drain(*a, **k):
-        if not kt.enabled:
-            return plain_drain(*a, **k)
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        r = plain_drain(*a, **k)
-        e.record()
-        drain_events.append((s, e))
-        return r
-    eng.async_drain = timed_drain
-
-    def totals():
-        st = runner.finish()
-        return dict(moves=int(st[5]), games=int(st[0]), plies=int(st[1]), searches=int(st[7]), tuples=int(replay.cursor.item()))
-
-    full = runner.n_sims
-    runner.n_sims = 16
-    for _ in range(args.preroll_cheap):
-        runner.play_move()
-    runner.n_sims = full
-    for _ in range(args.preroll_full + args.warmup):
-        runner.play_move()
-    t_a = totals()
-    runner.reset_counters()
-    launches0, chunks0 = runner.launches, runner.chunks
-    kt.enabled = True
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        runner.play_move()
-    t_b = totals()                                            # (waits for everything enqueued)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    kt.enabled = False
-    runner.check_error()
-    c = runner.counters()
-    d = {k: t_b[k] - t_a[k] for k in t_a}
-    moves = max(1, d["moves"])
-    tree = kt.robust_mean_ms()
-    out = dict(line=args.line, name=name, surprise_weight=args.lam if on else None, steps_per_graph=args.steps_per_graph,
-               per_launch=args.per_launch, games=args.games, sims=args.sims, size=args.size, steps=args.steps,
-               ms_per_G_moves=1e3 * dt * args.games / moves, moves_per_s=d["moves"] / dt,
-               games_per_s=d["games"] / dt, mean_plies_of_finished_games=d["plies"] / max(1, d["games"]),
-               tuples_per_finished_ply=d["tuples"] / max(1, d["plies"]), finished_plies=d["plies"], tuples=d["tuples"],
-               sims_per_move=c["sims"] / moves, tree_launches_per_G_moves=(runner.launches - launches0) * args.games / moves,
-               k_tree_us_per_launch=None if tree[0] is None else 1e3 * tree[0], k_tree_samples=tree[2],
-               drains=runner.chunks - chunks0,
-               drain_us_per_call=1e3 * sum(a.elapsed_time(b) for a, b in drain_events) / max(1, len(drain_events)),
-               drain_share_of_time=1e-3 * sum(a.elapsed_time(b) for a, b in drain_events) / dt)
+    ab.bracket_calls(runner.eng, "async_drain", drain_events, lambda *a, **k: kt.enabled)
+    ab.preroll(runner, args)
+    dt, d, c, fields = ab.timed_window(runner, replay, args, args.steps)
+    out = dict(fields, line=args.line, name=name, surprise_weight=args.lam if on else None,
+               tuples_per_finished_ply=d["tuples"] / max(1, d["plies"]), finished_plies=d["plies"], tuples=d["tuples"], drains=d["drains"],
+               **ab.drain_fields(drain_events, dt))
     if on and args.stat_moves > 0:
         # untimed: the records of the next moves, by slot; a game counts once it was seen from the record after a game's end to its own end
         open_games, whole = {}, []
@@ -146,92 +87,42 @@ def worker(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--line", type=int, default=None, help="internal: run one line in this process and print its JSON line")
+    ab.add_common_args(ap, "line")
     ap.add_argument("--rounds", type=int, default=2, help="off / on pairs, alternated")
-    ap.add_argument("--games", type=int, default=2048)
-    ap.add_argument("--sims", type=int, default=800)
-    ap.add_argument("--size", type=int, default=15)
+    ab.add_common_args(ap, "games", "sims", "size")
     ap.add_argument("--lam", type=float, default=0.5, help="lambda of line 2")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--preroll-cheap", type=int, default=128)
-    ap.add_argument("--preroll-full", type=int, default=26)
+    ab.add_common_args(ap, "steps", "warmup", "preroll_cheap", "preroll_full")
     ap.add_argument("--stat-moves", type=int, default=60, help="line 2: untimed moves per slot whose records give the copy statistics")
-    ap.add_argument("--cache-entries", type=int, default=32768)
-    ap.add_argument("--replay-capacity", type=int, default=200000)
-    ap.add_argument("--per-launch", type=int, default=1, help="most simulations a game runs inside one tree launch")
-    ap.add_argument("--steps-per-graph", type=int, default=32, help="steps between two drains")
-    ap.add_argument("--timer-stride", type=int, default=176)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per line")
+    ab.add_common_args(ap, "cache_entries", "replay_capacity", "per_launch", "steps_per_graph", "timer_stride", "timeout")
     ap.add_argument("--trace-steps", type=int, default=4, help="steps of the two traced runs (0: no traced run)")
     ap.add_argument("--trace-timeout", type=int, default=240)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "surprise_weighting_ab.json"))
+    ap.add_argument("--out", default=ab.out_path("surprise_weighting_ab.json"))
     args = ap.parse_args()
     if args.line is not None:
         return worker(args)
-    keys = ("games", "sims", "size", "lam", "steps", "warmup", "preroll_cheap", "preroll_full", "stat_moves", "cache_entries", "replay_capacity",
-            "per_launch", "steps_per_graph", "timer_stride")
-
-    def child(line, **over):
-        return [sys.executable, os.path.abspath(__file__), "--line", str(line)] + [f"--{k.replace('_', '-')}={over.get(k, getattr(args, k))}" for k in keys]
-    rows = []
-    for rnd in range(args.rounds):
-        for line in (1, 2):
-            try:
-                r = subprocess.run(child(line), capture_output=True, text=True, timeout=args.timeout)
-            except subprocess.TimeoutExpired:
-                print(f"round {rnd} line {line}: no result after {args.timeout} s - stopping here", file=sys.stderr)
-                return 124
-            if r.returncode != 0:
-                print(f"round {rnd} line {line}: exit status {r.returncode} - stopping here\n{r.stderr[-4000:]}", file=sys.stderr)
-                return r.returncode
-            rows.append(dict(json.loads(r.stdout.strip().splitlines()[-1]), round=rnd))
-            print(json.dumps(rows[-1]), flush=True)
+    status, rows = ab.collect_lines(__file__, args, (1, 2), FORWARDED, rounds=args.rounds)
+    if status != 0:
+        return status
     traced = None
     if args.trace_steps > 0:
-        import csv
-        import glob
-        import tempfile
         traced = {}
         for line in (1, 2):
-            with tempfile.TemporaryDirectory() as d:
-                cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"] + child(
-                    line, steps=args.trace_steps, warmup=1, preroll_cheap=32, preroll_full=2, stat_moves=0)
-                try:
-                    r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.trace_timeout)
-                except subprocess.TimeoutExpired:
-                    print(f"traced run of line {line}: no result after {args.trace_timeout} s - stopping here", file=sys.stderr)
-                    return 124
-                if r.returncode != 0:
-                    print(f"traced run of line {line}: exit status {r.returncode}\n{r.stderr[-4000:]}", file=sys.stderr)
-                    return r.returncode
-                files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-                kernels = {}
-                for row in (csv.DictReader(open(files[0])) if files else []):
-                    for want in ("k_move_async", "k_emit_alloc", "k_emit_tuples", "k_tree"):
-                        if want in row["Name"]:
-                            k = kernels.setdefault(want, dict(calls=0, total_ns=0.0))
-                            k["calls"] += int(row["Calls"])
-                            k["total_ns"] += float(row["TotalDurationNs"])
-                for k in kernels.values():
-                    k["us_per_launch"] = 1e-3 * k.pop("total_ns") / max(1, k["calls"])
-                traced[LINES[line - 1][0]] = kernels
-                print(json.dumps({LINES[line - 1][0]: kernels}), flush=True)
-
-    def mean(line, key):
-        v = [r[key] for r in rows if r["line"] == line and r.get(key) is not None]
-        return sum(v) / len(v) if v else None
-    summary = {k: dict(off=mean(1, k), on=mean(2, k)) for k in ("ms_per_G_moves", "tuples_per_finished_ply", "mean_plies_of_finished_games", "k_tree_us_per_launch",
-                                                               "drain_us_per_call", "tree_launches_per_G_moves")}
+            child = ab.child_cmd(__file__, args, "--line", line, FORWARDED, steps=args.trace_steps, warmup=1, preroll_cheap=32, preroll_full=2, stat_moves=0)
+            status, kernels = ab.traced_kernels(child, args.trace_timeout, f"traced run of line {line}", ("k_move_async", "k_emit_alloc", "k_emit_tuples", "k_tree"))
+            if status != 0:
+                return status
+            traced[LINES[line - 1][0]] = kernels
+            print(json.dumps({LINES[line - 1][0]: kernels}), flush=True)
+    summary = {k: dict(off=ab.mean_of(rows, 1, k), on=ab.mean_of(rows, 2, k))
+               for k in ("ms_per_G_moves", "tuples_per_finished_ply", "mean_plies_of_finished_games", "k_tree_us_per_launch", "drain_us_per_call",
+                         "tree_launches_per_G_moves")}
     for k in ("share_plies_no_copy", "share_plies_two_or_more", "mean_w", "max_w", "mean_copies_per_ply"):
-        summary[k] = dict(on=mean(2, k))
-    doc = dict(what="policy surprise weighting inside the asynchronous movers at the headline workload with a replay ring attached, one box, one process after "
-                    "the other, off and on alternated (tools/surprise_weighting_ab.py); every figure is measured; kernels_traced comes from a separate short "
-                    "run of each line under rocprofv3 --kernel-trace --stats; what the option does to the strength of a trained network is not measured",
-               lines=rows, mean_of_rounds=summary, kernels_traced=traced)
-    with open(args.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+        summary[k] = dict(on=ab.mean_of(rows, 2, k))
+    ab.write_doc(args.out, what="policy surprise weighting inside the asynchronous movers at the headline workload with a replay ring attached, one box, one "
+                                "process after the other, off and on alternated (tools/surprise_weighting_ab.py); every figure is measured; kernels_traced "
+                                "comes from a separate short run of each line under rocprofv3 --kernel-trace --stats; what the option does to the strength "
+                                "of a trained network is not measured",
+                 lines=rows, mean_of_rounds=summary, kernels_traced=traced)
     return 0
 
 

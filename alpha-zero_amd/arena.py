@@ -20,19 +20,37 @@ def _game_name(game, size):
 
 
 def compete_batch(game, model1, model2, n_games, model1_mcts_iter=50, model2_mcts_iter=50, sampling=False, size=None,
-                  seed=0, first_global_game=0, device=0, leaf_dtype="float32", noise_fn=None, uniform_fn=None, cache_entries=0):
+                  seed=0, first_global_game=0, device=0, leaf_dtype="float32", noise_fn=None, uniform_fn=None, cache_entries=0,
+                  openings=None, openings_first_game=None):
     """n_games independent test.compete games at once -> (winners int array in {0, 1, -1}, final boards).
 
     cache_entries > 0 turns on the per-game eval cache, which - like the reference's process-global MCTS.cache (mcts.py:7,
     38-44: keyed by the position alone) - is shared by BOTH models: whichever model evaluated a position first also answers
     for the other.  That reproduces the reference's compete games exactly as long as no entry is evicted (direct-mapped
-    table: size it well above the positions a game visits); with 0 every model evaluates its own positions."""
+    table: size it well above the positions a game visits); with 0 every model evaluates its own positions.
+
+    openings = (max_plies, spread) (OPT-IN, selfplay.check_openings with p_open = 1): every game starts from a drawn position - 1..max_plies
+    plies inside the centred window - keyed (seed, (openings_first_game or first_global_game) + game, move 0); player 0 is still model1,
+    whoever is to move first; both models then search the same number of iterations and neither may be None (ValueError)."""
     game, size = _game_name(game, size)
+    opn = _arena_openings(openings)
     res = self_play_batch(game, (model1, model2), n_games, (model1_mcts_iter, model2_mcts_iter), size=size, seed=seed,
                           first_global_game=first_global_game, device=device, leaf_dtype=leaf_dtype,
-                          noise_fn=noise_fn, uniform_fn=uniform_fn, sample_until=20 if sampling else 0, cache_entries=cache_entries)
+                          noise_fn=noise_fn, uniform_fn=uniform_fn, sample_until=20 if sampling else 0, cache_entries=cache_entries,
+                          openings=opn, openings_first_game=openings_first_game)
     winners = np.array([r.winner for r in res], np.int64)
     return winners, res
+
+
+def _arena_openings(openings):
+    """(max_plies, spread) -> the runners' (1.0, max_plies, spread), or None."""
+    if openings is None:
+        return None
+    try:
+        max_plies, spread = openings
+    except (TypeError, ValueError):
+        raise ValueError(f"openings must be (max_plies, spread), not {openings!r}")
+    return (1.0, max_plies, spread)
 
 
 def compete(Game, model1, model2, model1_mcts_iter=50, model2_mcts_iter=50, sampling=False, display=False):
@@ -114,14 +132,22 @@ def compare_sequential(Game, best_model, contender_model, best_model_mcts_iter, 
 
 
 def compare(game, best_model, contender_model, best_model_mcts_iter, contender_model_mcts_iter, iterations, sampling,
-            early_stopping, size=None, seed=0, device=0, leaf_dtype="float32"):
+            early_stopping, size=None, seed=0, device=0, leaf_dtype="float32", openings=None):
     """test.compare(Game, best_model, contender_model, best_iter, contender_iter, iterations, sampling, early_stopping)
     (test.py:107-140) with all games of a half played at once; a model of None plays vanilla MCTS (main.py:76).
-    (compare_sequential is the game-by-game form that reproduces the reference's RNG stream and cache history.)"""
+    (compare_sequential is the game-by-game form that reproduces the reference's RNG stream and cache history.)
+    openings = (max_plies, spread) (OPT-IN): every game starts from a drawn position and the openings have a first game index of their own,
+    the same for both halves - game i of the second half starts from the position game i of the first half started from, with the models
+    swapped, so each opening is played with both colours.  An odd `iterations` has no such pairs and is refused (ValueError)."""
     game, size = _game_name(game, size)
+    if openings is not None:
+        from selfplay import check_openings
+        check_openings(_arena_openings(openings), game, size, (best_model, contender_model))
+        if iterations % 2:
+            raise ValueError(f"compare: openings pair game i of the first half with game i of the second - iterations must be even, not {iterations!r}")
     half = iterations // 2
     w1, _ = compete_batch(game, best_model, contender_model, half, best_model_mcts_iter, contender_model_mcts_iter,
-                          sampling, size, seed, 0, device, leaf_dtype) if half else (np.zeros(0, np.int64), None)
+                          sampling, size, seed, 0, device, leaf_dtype, openings=openings, openings_first_game=0) if half else (np.zeros(0, np.int64), None)
     w2, _ = compete_batch(game, contender_model, best_model, iterations - half, contender_model_mcts_iter,
-                          best_model_mcts_iter, sampling, size, seed, half, device, leaf_dtype)
+                          best_model_mcts_iter, sampling, size, seed, half, device, leaf_dtype, openings=openings, openings_first_game=0)
     return score_like_reference(w1, w2, iterations, early_stopping)

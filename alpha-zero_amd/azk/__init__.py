@@ -40,6 +40,8 @@ SYMBOLS = [
     "azk_emit_elements", "azk_replay_gather",
     "azk_set_surprise_weighting", "azk_clear_surprise_weighting", "azk_advance_keyed", "azk_get_surprise", "azk_async_surprise_columns",
     "azk_set_gumbel_root", "azk_clear_gumbel_root", "azk_gen_gumbel", "azk_gen_gumbel_uniforms",
+    "azk_set_openings", "azk_clear_openings", "azk_open_pending", "azk_get_open_plies", "azk_get_opening_stats",
+    "azk_get_opening_actions", "azk_get_leaf_flags",
 ]
 
 
@@ -209,6 +211,7 @@ class Engine:
         self.resign = None                          # (v_resign, p_never, min_ply) once set_resign has switched the option on
         self.forced_playouts = None                 # k once set_forced_playouts has switched the option on
         self.gumbel_root = None                     # (m, n_sims, c_visit, c_scale) once set_gumbel_root has switched the option on
+        self.openings = None                        # (p_open, max_plies, spread) once set_openings has switched the option on
         self.surprise_weight = None                 # lambda once set_surprise_weighting has switched the option on (0.0 is a live setting)
         self.cache_entries = int(cache_entries)
         # with the eval cache a step can have pending (cached) leaves to expand although no leaf went to the evaluator
@@ -277,6 +280,61 @@ class Engine:
             raise AzkError("search_full: no playout cap is set (set_playout_cap)")
         self._chk(self.L.azk_get_search_full(self.h, _p(self._search_full), _stream()))
         return self._search_full
+
+    def set_openings(self, p_open, max_plies, spread=-1, seed=0, first_global_game=0):
+        """OPT-IN random openings (azk_set_openings): from now on a game that starts in a slot is, with probability p_open,
+        played forward 1..max_plies uniformly drawn legal plies inside the centred window of half-width `spread` (-1: the whole board) before
+        its first search, by draws keyed (seed, first_global_game + g, move key of that search).  Lock-step drivers call open_pending(key)
+        after the games were reset (key 0) and after recycle_finished (key = the next move index); the asynchronous movers open their games
+        themselves.  Those plies are not emitted as (state, pi, z).  p_open = 0 is a live setting; clear_openings switches the option off."""
+        self._chk(self.L.azk_set_openings(self.h, float(p_open), int(max_plies), int(spread), int(seed) & ((1 << 64) - 1), int(first_global_game),
+                                          _stream()))
+        self.openings = (float(p_open), int(max_plies), int(spread))
+        if getattr(self, "_open_plies", None) is None:
+            self._open_plies = self.torch.zeros(self.G, dtype=self.torch.int32, device=self.device)
+
+    def clear_openings(self):
+        """Random openings off (azk_clear_openings): the engine launches what it launched before."""
+        self._chk(self.L.azk_clear_openings(self.h))
+        self.openings = None
+
+    def open_pending(self, key):
+        """Open the games that have just started (azk_open_pending): key = the move index of the search that follows."""
+        if self.openings is None:
+            raise AzkError("open_pending: no openings are set (set_openings)")
+        self._chk(self.L.azk_open_pending(self.h, int(key), _stream()))
+
+    def open_plies(self):
+        """int32 CUDA tensor [G]: the opening plies of each slot's current game, 0 = not opened (azk_get_open_plies; valid until the next call)."""
+        if self.openings is None:
+            raise AzkError("open_plies: no openings are set (set_openings)")
+        self._chk(self.L.azk_get_open_plies(self.h, _p(self._open_plies), _stream()))
+        return self._open_plies
+
+    def opening_actions(self):
+        """Per slot, the cells its current game's opening was played on, in order: a list of G lists (azk_get_opening_actions; host sync)."""
+        if self.openings is None:
+            raise AzkError("opening_actions: no openings are set (set_openings)")
+        acts = self.torch.zeros((self.G, self.state_dim), dtype=self.torch.int16, device=self.device)
+        self._chk(self.L.azk_get_opening_actions(self.h, _p(acts), _stream()))
+        plies, acts = self.open_plies().cpu().numpy(), acts.cpu().numpy()
+        return [[int(c) for c in acts[g, :plies[g]]] for g in range(self.G)]
+
+    def leaf_flags(self):
+        """uint8 CUDA tensor [G * K]: non-zero = the slot has a row in the evaluator batch of the step that has just selected, rows in
+        ascending slot order (azk_get_leaf_flags; valid until the next call)."""
+        if getattr(self, "_leaf_flags", None) is None:
+            self._leaf_flags = self.torch.zeros(self.slots, dtype=self.torch.uint8, device=self.device)
+        self._chk(self.L.azk_get_leaf_flags(self.h, _p(self._leaf_flags), _stream()))
+        return self._leaf_flags
+
+    def opening_stats(self):
+        """[games opened, opening plies played, openings cut short] (host sync)."""
+        if self.openings is None:
+            raise AzkError("opening_stats: no openings are set (set_openings)")
+        out = np.zeros(3, np.int64)
+        self._chk(self.L.azk_get_opening_stats(self.h, _np(out), _stream()))
+        return [int(x) for x in out]
 
     def set_resign(self, v_resign, p_never=0.0, min_ply=0, seed=0, first_global_game=0):
         """OPT-IN resignation (azk_set_resign): from now on, after a move that does not end the game, the side that has just moved concedes

@@ -179,6 +179,13 @@ def declare(L, symbols):
     L.azk_clear_gumbel_root.argtypes = [vp]
     L.azk_gen_gumbel.argtypes = [vp, u64, i64, i32, vp, vp]
     L.azk_gen_gumbel_uniforms.argtypes = [vp, u64, i64, i32, vp, vp]
+    L.azk_set_openings.argtypes = [vp, f64, i32, i32, u64, i64, vp]
+    L.azk_clear_openings.argtypes = [vp]
+    L.azk_open_pending.argtypes = [vp, i32, vp]
+    L.azk_get_open_plies.argtypes = [vp, vp, vp]
+    L.azk_get_opening_stats.argtypes = [vp, vp, vp]
+    L.azk_get_opening_actions.argtypes = [vp, vp, vp]
+    L.azk_get_leaf_flags.argtypes = [vp, vp, vp]
     L.azk_set_eval_symmetry.argtypes = [vp, i32, u64, vp]
     L.azk_get_leaf_symmetry.argtypes = [vp, vp, vp]
     L.azk_eval_symmetry_restore.argtypes = [vp, vp, vp, vp]

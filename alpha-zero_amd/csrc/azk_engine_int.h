@@ -192,6 +192,25 @@ struct SurpriseDev {
     double *rec_kl, *rec_coin; // asynchronous record ring: [record_capacity] columns, or null
 };
 
+// random openings (azk_set_openings, opt-in): a game that starts in slot g is, with probability p_open, played forward
+// 1..max_plies uniformly drawn legal moves inside a centred window before its first search, by draws keyed like the search's noise row
+// (Philox word 3 = 0xFFFFFFFA).  Those plies are ordinary plies without a search: emission leaves them out.  Its own argument block, passed
+// only to k_open_pending and to the OPEN instantiations of the kernels that start games or emit them (azk_moves.hip): every other argument
+// block - and every kernel an engine without the option launches - stays as it was
+struct OpenDev {
+    double p_open;             // share of the games that are opened
+    int max_plies;             // an opening has 1..max_plies plies (less where it is cut short)
+    int spread;                // window half-width about the board's centre, per axis; -1 = the whole board
+    unsigned long long seed;   // the draws' key: (seed, first_game + g, move key of the game's first search); the option's own, in both drivers
+    long long first_game;
+    uint8_t *pending;          // [G] 1 = the slot's game has just started and has not been through open_game_one
+    int *open_plies;           // [G] opening plies of the slot's current game (0: not opened)
+    int16_t *actions;          // [G][state_dim] the cells those plies were played on, in order (an engine without trajectories has them too)
+    long long *stats;          // [3] games opened, opening plies played, openings cut short
+};
+// ... and what emission needs of it
+struct OpenEmit { const int *open_plies; };
+
 struct LdsView {
     uint8_t *board;
     int *path;
@@ -352,6 +371,8 @@ struct azk_engine {
     SurpriseDev sp = {};                 // policy surprise weighting (azk_set_surprise_weighting); sp_on == false: off, nothing allocated
     bool sp_on = false;                  // (lambda = 0 is a live setting, so the switch is its own word)
     EmitSym emit = {};                   // emission under a mask of elements (cfg.emit_elements); emit.n == 0: off, the reference's rule
+    OpenDev op = {};                     // random openings (azk_set_openings); op_on == false: off, nothing allocated
+    bool op_on = false;                  // (p_open = 0 is a live setting, so the switch is its own word)
     bool in_search = false;              // between a search's begin and the move (or new position) that ends it: azk_set_eval_symmetry refuses
 };
 

@@ -10,8 +10,8 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// The opt-ins (playout cap, resignation, forced playouts, emission under a mask of elements, surprise weighting; DESIGN sections 18 to 20, 22 and
-// 23).  A kernel an option touches is ONE __global__ template with a bool per option, and the options' argument blocks (CapDev, ResignDev, ForcedDev, EmitSym, SurpriseDev)
+// The opt-ins (playout cap, resignation, forced playouts, emission under a mask of elements, surprise weighting, random openings; DESIGN sections
+// 18 to 20, 22, 23 and 25).  A kernel an option touches is ONE __global__ template with a bool per option, and the options' argument blocks (CapDev, ResignDev, ForcedDev, EmitSym, SurpriseDev, OpenDev)
 // ride on the block in front of them as a Pack: that block plus exactly the blocks whose flag is set.  A block that is off is an empty
 // base, which takes no room, so with every flag off the Pack IS its first block: the kernel an engine without options launches has the
 // argument layout and the instruction stream it always had, and an option costs the others nothing.  The kernels are one line each: the
@@ -33,14 +33,19 @@ template <class First, bool CAP> using CapPack = Pack<First, Opt<CapDev, CAP>>;
 template <class First, bool CAP> using CapKeyPack = Pack<First, Opt<Keyed<CapDev>, CAP>>;
 template <class First, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
 using MovePack = Pack<First, Opt<CapDev, CAP>, Opt<ResignDev, RESIGN>, Opt<ForcedDev, FORCED>, Opt<SurpriseDev, SURPRISE>>;
-template <bool CAP, bool SYM, bool SURPRISE> using EmitPack = Pack<Dev, Opt<CapDev, CAP>, Opt<EmitSym, SYM>, Opt<SurpriseDev, SURPRISE>>;
+template <bool CAP, bool SYM, bool SURPRISE, bool OPEN>
+using EmitPack = Pack<Dev, Opt<CapDev, CAP>, Opt<EmitSym, SYM>, Opt<SurpriseDev, SURPRISE>, Opt<OpenEmit, OPEN>>;
+// random openings: the kernels that start games take the option's block behind Dev
+template <bool OPEN> using OpenPack = Pack<Dev, Opt<OpenDev, OPEN>>;
+template <bool CAP, bool OPEN> using RestartPack = Pack<Dev, Opt<CapDev, CAP>, Opt<OpenDev, OPEN>>;
 // Gumbel root search combines with resignation only, and the kernels of the other options keep their names: the movers'
 // GUMBEL forms are overloads that take this pack
 template <class First, bool RESIGN> using GumbelPack = Pack<First, Opt<ResignDev, RESIGN>, Opt<GumbelDev, true>>;
-static_assert(sizeof(MovePack<Dev, false, false, false, false>) == sizeof(Dev) && sizeof(EmitPack<false, false, false>) == sizeof(Dev) &&
+static_assert(sizeof(MovePack<Dev, false, false, false, false>) == sizeof(Dev) && sizeof(EmitPack<false, false, false, false>) == sizeof(Dev) &&
+              sizeof(OpenPack<false>) == sizeof(Dev) && sizeof(RestartPack<false, false>) == sizeof(Dev) && sizeof(RestartPack<true, false>) == sizeof(CapPack<Dev, true>) &&
               sizeof(MovePack<ReuseDev, false, false, false, false>) == sizeof(ReuseDev) &&
               sizeof(MovePack<Dev, true, true, true, false>) == sizeof(Pack<Dev, Opt<CapDev, true>, Opt<ResignDev, true>, Opt<ForcedDev, true>>) &&
-              sizeof(EmitPack<true, true, false>) == sizeof(Pack<Dev, Opt<CapDev, true>, Opt<EmitSym, true>>) &&
+              sizeof(EmitPack<true, true, false, false>) == sizeof(Pack<Dev, Opt<CapDev, true>, Opt<EmitSym, true>>) &&
               sizeof(CapPack<ReuseDev, false>) == sizeof(ReuseDev) && sizeof(CapKeyPack<ReuseDev, false>) == sizeof(ReuseDev), "a pack without options is its first block");
 
 // A leaf that missed the eval cache claims its entry's key at selection and fills logits/value at expansion; if the search
@@ -313,18 +318,27 @@ __global__ __launch_bounds__(AZK_WAVE) void k_reroot(Dev d, CapKeyPack<ReuseDev,
     if (azk_lane() == 0) r.chosen_node[g] = -1;                   // one search per recorded move
 }
 
-__global__ void k_reset_games(Dev d, int first, int count, int *chosen_node) {
+// a game has just started in slot g (one lane; engines with random openings): k_open_pending, which follows, decides whether it is opened
+__device__ __forceinline__ void open_mark_one(const OpenDev &od, int g) { od.pending[g] = 1; od.open_plies[g] = 0; }
+
+// OPEN, here and in k_recycle (engines with random openings, azk_set_openings): the new games are flagged for k_open_pending
+template <bool OPEN>
+__global__ void k_reset_games(OpenPack<OPEN> a, int first, int count, int *chosen_node) {
+    const Dev d = a;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count * d.rc_pad) return;
     const int g = first + t / d.rc_pad, i = t % d.rc_pad;
     d.cells[(size_t)g * d.rc_pad + i] = 0;
     if (i == 0) drop_pending_cache_claim(d, g);
     if (i == 0) { new_game_one(d, g); clear_leaf_slots(d, g); if (chosen_node) chosen_node[g] = -1; }
+    if constexpr (OPEN) { if (i == 0) open_mark_one(opt<OpenDev>(a), g); }
 }
 
 // Continuous self-play: every finished game's slot restarts from Game() (empty board, player 0).
-// stats[0] += games recycled, stats[1] += plies those games lasted, stats[2..4] += wins of player 0 / player 1 / draws.
-__global__ void k_recycle(Dev d, long long *stats, int *chosen_node) {
+// stats[0] += games recycled, stats[1] += plies those games lasted (opening plies included), stats[2..4] += wins of player 0 / player 1 / draws.
+template <bool OPEN>
+__global__ void k_recycle(OpenPack<OPEN> a, long long *stats, int *chosen_node) {
+    const Dev d = a;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.G || !d.done[g]) return;
     atomicAdd((unsigned long long *)&stats[0], 1ull);
@@ -336,6 +350,7 @@ __global__ void k_recycle(Dev d, long long *stats, int *chosen_node) {
     new_game_one(d, g);
     clear_leaf_slots(d, g);
     if (chosen_node) chosen_node[g] = -1;
+    if constexpr (OPEN) open_mark_one(opt<OpenDev>(a), g);
 }
 
 // utils.get_probablity_distribution_of_children (utils.py:46-55), root.value / root.visit (gomoku.py:140)
@@ -509,6 +524,169 @@ __device__ __forceinline__ int gumbel_target(const Dev &d, const LdsView &L, int
     return best;
 }
 
+// make_move (gomoku.py:148) on the wave's LDS board: the mover's stone goes onto cellc, placed by lane 0; azk_check_winner follows it.  The
+// ONE copy of the placing rule, which the movers (advance_one) and the openings (open_game_one) both play their plies through.  It is text,
+// not a function: behind a call the compiler schedules the movers differently, and an engine without openings launches the device code it
+// always launched (profiles/openings_isa_vs_parent.txt).  Two statements without a wrapper, for the same reason: use it only as a full statement
+// at block scope, never as the body of an unbraced if / else / loop.
+#define AZK_PLACE_STONE(board, gd, lane, mover, cellc)                                         \
+    if ((lane) == 0) {                                                                         \
+        if ((gd).kind == AZK_KIND_C4) (board)[cellc] |= (uint8_t)(1 << (mover));               \
+        else if ((board)[cellc] == 0) (board)[cellc] = (uint8_t)(1 << (mover));                \
+    }                                                                                          \
+    __syncthreads()
+
+// ================================================================================================
+// Random openings (azk_set_openings, opt-in): a game that has just started in slot g - empty board, player 0 - is played
+// forward a few uniformly drawn plies before its first search, so that the batch's games do not all grow from one position.  One wave per
+// game, nothing waits on another wave.  key = the move key of the game's first search (the lock-step move index, the asynchronous slot's
+// move counter): the key of its noise row and of its resignation coin.  With gg = first_game + g, every draw one Philox4x32-10 block under
+// key (seed lo, seed hi) and word 3 = 0xFFFFFFFA (no other stream's), a uniform = ((hi << 32 | lo) >> 11) * 2^-53 as keyed_coin makes it:
+//   game draw   counter {gg lo, gg hi, key, tag}: c0 from words (0, 1), c1 from (2, 3); opened iff c0 < p_open,
+//               n = min(1 + floor(c1 * max_plies), max_plies) plies
+//   ply j       counter {gg lo, gg hi ^ ((j + 1) << 8), key, tag}: u from words (0, 1); with m candidates - the legal actions inside the window,
+//               ascending - the side to move plays candidate min(floor(u * m), m - 1).  m == 0 ends the opening; a ply that decides the game or
+//               fills the board is taken back and ends it (cut short): an opened position always has a legal move.
+// The window: cell (r, c) iff spread < 0 or |2r - (rows - 1)| <= 2 spread and |2c - (cols - 1)| <= 2 spread; Connect4's candidates are its
+// columns that are not full (the column condition alone) and the stone lands where the engine's rule puts it.
+// The wave holds the board in registers, four cells of a dword per lane and two dwords (512 cells >= make_game's 400): the window is a
+// 4-bit mask per dword, computed once; per ply the candidates are (window & empty), ranked by a DPP prefix sum of the lanes' popcounts, and
+// the lane whose range holds the drawn index names the cell.  The draws are wave-uniform (scalar inputs, readfirstlane on the results).  The
+// plies are ordinary plies without a search: cells, to_move, move_count and traj_action are written; no pi, no q, no record.
+// ================================================================================================
+__device__ __forceinline__ int wave_scan_incl_i32(int v) {               // inclusive prefix sum over the wave's lanes, on DPP (as azk_valid_moves_gomoku's)
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);
+    return v;
+}
+__device__ __forceinline__ double open_uniform(uint32_t hi, uint32_t lo) {
+    return (double)((((unsigned long long)hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
+}
+// bits 0..3: which of the dword's four cells are empty
+__device__ __forceinline__ unsigned open_empty4(uint32_t w) {
+    return ((w & 0xffu) == 0u ? 1u : 0u) | ((w & 0xff00u) == 0u ? 2u : 0u) | ((w & 0xff0000u) == 0u ? 4u : 0u) | ((w & 0xff000000u) == 0u ? 8u : 0u);
+}
+// position of the r-th set bit of a 4-bit mask (r < popcount)
+__device__ __forceinline__ int open_nth_bit4(unsigned m, int r) {
+    int pos = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const bool set = (m >> b) & 1u;
+        if (set && r == 0) pos = b;
+        r -= set ? 1 : 0;
+    }
+    return pos;
+}
+
+// board: the wave's LDS board (up16(rc) bytes).  All lanes of the wave call; g and key are made wave-uniform here
+__device__ __forceinline__ void open_game_one(const Dev &d, const OpenDev &od, uint8_t *board, int g_in, uint32_t key_in) {
+    const int lane = azk_lane();
+    const GameDesc &gd = d.g;
+    const int g = uniform_i32(g_in);
+    const uint32_t key = (uint32_t)uniform_i32((int)key_in);
+    const unsigned long long gg = (unsigned long long)(od.first_game + g);
+    const uint32_t k0 = (uint32_t)od.seed, k1 = (uint32_t)(od.seed >> 32), tag = 0xFFFFFFFAu;
+    int n = 0;
+    {
+        uint32_t w[4] = {(uint32_t)gg, (uint32_t)(gg >> 32), key, tag};
+        philox4x32_10(w, k0, k1);
+        const double c0 = open_uniform(w[0], w[1]), c1 = open_uniform(w[2], w[3]);
+        if (c0 < od.p_open) n = min(1 + (int)floor(c1 * (double)od.max_plies), od.max_plies);
+    }
+    n = uniform_i32(n);
+    if (n == 0) {                                                   // not opened: the game starts from the empty board, as ever
+        if (lane == 0) od.open_plies[g] = 0;
+        return;
+    }
+    // the board by dword, and the window's cells of each dword
+    const bool c4 = gd.kind == AZK_KIND_C4;
+    uint32_t *cw = (uint32_t *)(d.cells + (size_t)g * d.rc_pad);
+    uint32_t cell4[2];
+    unsigned win4[2];
+#pragma unroll
+    for (int p = 0; p < 2; p++) {
+        const int idx = p * AZK_WAVE + lane;
+        const bool in = 4 * idx < d.rc_pad;                           // (rc_pad is a multiple of 16: a dword is inside or outside as a whole)
+        cell4[p] = in ? cw[idx] : 0u;
+        win4[p] = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int e = 4 * idx + b;
+            const int r = (int)(((unsigned)(e < gd.rc ? e : 0) * gd.inv_cols) >> 16), c = (e < gd.rc ? e : 0) - r * gd.cols;
+            const bool col_ok = od.spread < 0 || abs(2 * c - (gd.cols - 1)) <= 2 * od.spread;
+            const bool row_ok = c4 ? r == 0 : (od.spread < 0 || abs(2 * r - (gd.rows - 1)) <= 2 * od.spread);   // Connect4: a column stands for its top cell
+            if (e < gd.rc && col_ok && row_ok) win4[p] |= 1u << b;
+        }
+        if (in) ((uint32_t *)board)[idx] = cell4[p];
+    }
+    __syncthreads();
+    int mc = uniform_i32(d.move_count[g]), mover = uniform_i32(d.to_move[g]);
+    int played = 0, cut = 0;
+    for (int j = 0; j < n; j++) {
+        const unsigned cm0 = win4[0] & open_empty4(cell4[0]), cm1 = win4[1] & open_empty4(cell4[1]);
+        const int n0 = __popc(cm0), n1 = __popc(cm1);
+        const int incl0 = wave_scan_incl_i32(n0), incl1 = wave_scan_incl_i32(n1);
+        const int tot0 = __builtin_amdgcn_readlane(incl0, AZK_WAVE - 1), m = tot0 + __builtin_amdgcn_readlane(incl1, AZK_WAVE - 1);
+        if (m == 0) break;                                            // no legal action inside the window
+        uint32_t w[4] = {(uint32_t)gg, (uint32_t)(gg >> 32) ^ ((uint32_t)(j + 1) << 8), key, tag};
+        philox4x32_10(w, k0, k1);
+        const int k = uniform_i32(min((int)floor(open_uniform(w[0], w[1]) * (double)m), m - 1));
+        int cell = -1;                                                // the lane whose range of candidates holds index k names the cell
+        if (k >= incl0 - n0 && k < incl0) cell = 4 * lane + open_nth_bit4(cm0, k - (incl0 - n0));
+        if (k - tot0 >= incl1 - n1 && k - tot0 < incl1) cell = 4 * (AZK_WAVE + lane) + open_nth_bit4(cm1, k - tot0 - (incl1 - n1));
+        const unsigned long long owner = __ballot(cell >= 0);
+        if (owner == 0ull) break;                                     // (cannot happen: k < m)
+        int cellc = __builtin_amdgcn_readlane(cell, __ffsll((long long)owner) - 1);
+        if (c4) {                                                     // connect4.py:44-53: the lowest empty row of the column
+            const int col = cellc;
+            const unsigned long long emp = __ballot(lane < gd.rows && board[(lane < gd.rows ? lane : 0) * gd.cols + col] == 0);
+            if (emp == 0ull) break;                                   // (cannot happen: a candidate column's top cell is empty)
+            cellc = (63 - __clzll((long long)emp)) * gd.cols + col;
+        }
+        AZK_PLACE_STONE(board, gd, lane, mover, cellc);
+        const int won = azk_check_winner(board, gd, mover, cellc);
+        if (won != -1 || mc + 1 == gd.state_dim) {                                                     // decided or full: the ply is taken back, the opening ends here
+            __syncthreads();
+            if (lane == 0) board[cellc] = 0;
+            __syncthreads();
+            cut = 1;
+            break;
+        }
+        const int idx = cellc >> 2;
+        const uint32_t stone = (1u << mover) << (8 * (cellc & 3));
+        if (lane == (idx & (AZK_WAVE - 1))) { if (idx < AZK_WAVE) cell4[0] |= stone; else cell4[1] |= stone; }
+        if (lane == 0 && d.traj_action != nullptr && mc < gd.state_dim) d.traj_action[(size_t)g * gd.state_dim + mc] = (int16_t)cellc;
+        if (lane == 0 && played < gd.state_dim) od.actions[(size_t)g * gd.state_dim + played] = (int16_t)cellc;
+        mc += 1; mover = 1 - mover; played += 1;
+    }
+    if (played > 0) {
+#pragma unroll
+        for (int p = 0; p < 2; p++) { const int idx = p * AZK_WAVE + lane; if (4 * idx < d.rc_pad) cw[idx] = cell4[p]; }
+    }
+    if (lane == 0) {
+        d.to_move[g] = mover; d.move_count[g] = mc;
+        od.open_plies[g] = played;
+        atomicAdd((unsigned long long *)&od.stats[0], 1ull);
+        if (played) atomicAdd((unsigned long long *)&od.stats[1], (unsigned long long)played);
+        if (cut) atomicAdd((unsigned long long *)&od.stats[2], 1ull);
+    }
+}
+
+// The lock-step entry (azk_open_pending): one wave per slot; a slot without a pending flag ends after one load.  k_reset_games / k_recycle
+// set the flag where a game starts; key = the move index of the search that follows
+__global__ __launch_bounds__(AZK_WAVE) void k_open_pending(Dev d, OpenDev od, int key) {
+    const int g = blockIdx.x;
+    if (uniform_i32((int)od.pending[g]) == 0) return;
+    LdsView L = carve(d.g, d.path_cap, d.table_size);
+    const bool fresh = uniform_i32(d.move_count[g]) == 0 && uniform_i32(d.done[g]) == 0;   // (a position set by hand is no new game)
+    if (fresh) open_game_one(d, od, L.board, g, (uint32_t)key);
+    if (azk_lane() == 0) { od.pending[g] = 0; if (!fresh) od.open_plies[g] = 0; }     // (not a new game: whatever plies it has were not drawn here)
+}
+
 // gomoku.py:143-162 for one game (one wave): choose (sample ~ visits | first max-visit child), record pi / the action in the
 // trajectory, make_move, check_winner, draw.  Returns the chosen cell (-1: state error, already reported); *win_out / *done_out as
 // k_advance's outputs; pi of the move is left in L.cnt / sum_out (visit counts per action and their sum).
@@ -611,11 +789,7 @@ __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool
             sp.last_kl[g] = kl; sp.last_coin[g] = coin;
         }
     }
-    if (lane == 0) {
-        if (gd.kind == AZK_KIND_C4) L.board[cellc] |= (uint8_t)(1 << mover);
-        else if (L.board[cellc] == 0) L.board[cellc] = (uint8_t)(1 << mover);
-    }
-    __syncthreads();
+    AZK_PLACE_STONE(L.board, gd, lane, mover, cellc);
     const int w = azk_check_winner(L.board, gd, mover, cellc);      // gomoku.py:150
     int win = -2, dn = 0;
     if (w != -1) { win = w; dn = 1; }
@@ -738,29 +912,35 @@ __global__ __launch_bounds__(AZK_WAVE) void k_advance(GumbelPack<Dev, RESIGN> a,
 // sequential sum of their kl in ply order) is written c_i = floor(w_i) + (coin_i < w_i - floor(w_i)) times,
 //     w_i = S > 0 ? (1 - lambda) + ((lambda * n_F) * kl_i) / S : 1      (float64)
 // copy-major at base + sum_{j<i} c_j * grp_j.  k_emit_alloc writes c into traj_copies (0 outside F) and reserves the sum; k_emit_tuples reads it.
-template <bool CAP, bool SYM, bool SURPRISE>
+// OPEN (engines with random openings): the opening's plies i < open_plies[g] had no search and are left out exactly as a
+// capped engine's fast plies are - no tuples, not in n_F or S, 0 copies, not in the sums of the tuples before a ply; `i < 2 ? 1 : grp`
+// stays keyed on the absolute ply index, and boards are rebuilt from ply 0.
+template <bool CAP, bool SYM, bool SURPRISE, bool OPEN>
 __device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full, unsigned long long *cursor, long long *game_base_out, const EmitSym &es,
-                                                const SurpriseDev &sp) {
+                                                const SurpriseDev &sp, const OpenEmit &oe) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.G) return;
     long long base = -1;                                          // the stream index stays 64-bit end to end (2^31 tuples = hours of self-play)
     if (d.done[g] == 1) {
         const int n = d.move_count[g];
         const int grp = SYM ? es.n : 8;
+        int o = 0;                                                // the first ply that had a search
+        if constexpr (OPEN) o = min(oe.open_plies[g], n);
         int tuples = n <= 2 ? n : 2 + grp * (n - 2);
+        if (OPEN) tuples -= o <= 2 ? o : 2 + grp * (o - 2);
         if (CAP) {
             tuples = 0;
-            for (int i = 0; i < n; i++) if (traj_full[(size_t)g * d.g.state_dim + i]) tuples += i < 2 ? 1 : grp;
+            for (int i = o; i < n; i++) if (traj_full[(size_t)g * d.g.state_dim + i]) tuples += i < 2 ? 1 : grp;
         }
         if constexpr (SURPRISE) {
             const size_t row = (size_t)g * d.g.state_dim;
             int n_F = 0;
             double S = 0.0;
-            for (int i = 0; i < n; i++) if (!CAP || traj_full[row + i]) { n_F += 1; S += sp.traj_kl[row + i]; }
+            for (int i = o; i < n; i++) if (!CAP || traj_full[row + i]) { n_F += 1; S += sp.traj_kl[row + i]; }
             tuples = 0;
             for (int i = 0; i < n; i++) {
                 int c = 0;
-                if (!CAP || traj_full[row + i]) {
+                if ((!OPEN || i >= o) && (!CAP || traj_full[row + i])) {
                     const double w = S > 0.0 ? (1.0 - sp.lambda) + ((sp.lambda * (double)n_F) * sp.traj_kl[row + i]) / S : 1.0;
                     const double f = floor(w);
                     c = (int)f + (sp.traj_coin[row + i] < w - f ? 1 : 0);
@@ -775,9 +955,9 @@ __device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full,
     if (game_base_out) game_base_out[g] = base;
 }
 
-template <bool CAP, bool SYM, bool SURPRISE>
-__global__ void k_emit_alloc(EmitPack<CAP, SYM, SURPRISE> a, unsigned long long *cursor, long long *game_base_out) {
-    emit_alloc_body<CAP, SYM, SURPRISE>(a, opt<CapDev>(a).traj_full, cursor, game_base_out, opt<EmitSym>(a), opt<SurpriseDev>(a));
+template <bool CAP, bool SYM, bool SURPRISE, bool OPEN>
+__global__ void k_emit_alloc(EmitPack<CAP, SYM, SURPRISE, OPEN> a, unsigned long long *cursor, long long *game_base_out) {
+    emit_alloc_body<CAP, SYM, SURPRISE, OPEN>(a, opt<CapDev>(a).traj_full, cursor, game_base_out, opt<EmitSym>(a), opt<SurpriseDev>(a), opt<OpenEmit>(a));
 }
 
 __device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
@@ -798,10 +978,11 @@ __device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
 
 // LIST: the grid walks a list of finished games (asynchronous drain) instead of covering all G.  SURPRISE: the ply's group is written
 // traj_copies[i] times, copy-major, behind the copies of the plies before it (a capped engine's fast plies have 0 copies: traj_full is not read)
-template <bool LIST, bool CAP, bool SYM, bool SURPRISE>
+// OPEN: the opening's plies are not written and do not count among the tuples before a ply (their copies are 0 under SURPRISE)
+template <bool LIST, bool CAP, bool SYM, bool SURPRISE, bool OPEN>
 __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full, float *states, double *pis, float *zs, long long capacity,
                                                  const unsigned long long *cursor, const int *list, const int *n_list, const EmitSym &es,
-                                                 const uint16_t *traj_copies) {
+                                                 const uint16_t *traj_copies, const OpenEmit &oe) {
     const int S = d.g.state_dim, A = d.g.action_dim, rc = d.g.rc, F = d.g.planes, N = d.g.rows;
     const int lane = azk_lane();
     const int nb = LIST ? *n_list * S : (int)gridDim.x;
@@ -811,6 +992,8 @@ __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full
     const int g = LIST ? list[gi] : gi;
     const long long base = d.emit_base[g];
     if (base < 0 || i >= d.move_count[g]) continue;
+    int o = 0;                                                    // the first ply that had a search
+    if constexpr (OPEN) { o = uniform_i32(oe.open_plies[g]); if (i < o) continue; }   // an opening ply: it was drawn, not searched
     if (CAP && !SURPRISE && traj_full[(size_t)g * S + i] == 0) continue;      // a fast ply: it chose the move, it is not trained on
     const int copies = SURPRISE ? (int)traj_copies[(size_t)g * S + i] : 1;
     if (SURPRISE && copies == 0) continue;                        // no copy of this ply: the coin rounded its weight down to none (or a fast ply)
@@ -827,9 +1010,10 @@ __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full
     const int grp = SYM ? es.n : 8;
     const int ntr = i < 2 ? 1 : grp;
     long long first = base + (i < 2 ? i : 2 + grp * (i - 2));
+    if (OPEN) first -= o < 2 ? o : 2 + grp * (o - 2);
     if (CAP && !SURPRISE) {                                       // tuples of the full plies before this one
         int before = 0;
-        for (int j = lane; j < i; j += AZK_WAVE) if (traj_full[(size_t)g * S + j]) before += j < 2 ? 1 : grp;
+        for (int j = o + lane; j < i; j += AZK_WAVE) if (traj_full[(size_t)g * S + j]) before += j < 2 ? 1 : grp;
         first = base + wave_sum_i32(before);
     }
     if (SURPRISE) {                                               // tuples of every copy of the plies before this one
@@ -860,11 +1044,11 @@ __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full
     }
 }
 
-template <bool LIST, bool CAP, bool SYM, bool SURPRISE>
-__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(EmitPack<CAP, SYM, SURPRISE> a, float *states, double *pis, float *zs, long long capacity,
+template <bool LIST, bool CAP, bool SYM, bool SURPRISE, bool OPEN>
+__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(EmitPack<CAP, SYM, SURPRISE, OPEN> a, float *states, double *pis, float *zs, long long capacity,
                                                             const unsigned long long *cursor, const int *list, const int *n_list) {
-    emit_tuples_body<LIST, CAP, SYM, SURPRISE>(a, opt<CapDev>(a).traj_full, states, pis, zs, capacity, cursor, list, n_list, opt<EmitSym>(a),
-                                               opt<SurpriseDev>(a).traj_copies);
+    emit_tuples_body<LIST, CAP, SYM, SURPRISE, OPEN>(a, opt<CapDev>(a).traj_full, states, pis, zs, capacity, cursor, list, n_list, opt<EmitSym>(a),
+                                                     opt<SurpriseDev>(a).traj_copies, opt<OpenEmit>(a));
 }
 
 __global__ void k_emit_mark(Dev d) {
@@ -1140,8 +1324,10 @@ __global__ void k_async_list(Dev d, AsyncDev p) {
 }
 
 // drain, step 3: statistics + Game() + the next search for every listed game
-template <bool CAP>
-__device__ __forceinline__ void async_restart_body(Dev d, AsyncDev p, int recycle, CapDev cp) {
+// OPEN (engines with random openings): the new game is opened here, where it is born - nothing on the host runs between two
+// games of a slot -, under the key of its first search (the slot's move counter), before that search begins
+template <bool CAP, bool OPEN>
+__device__ __forceinline__ void async_restart_body(Dev d, AsyncDev p, int recycle, CapDev cp, const OpenDev &od) {
     const int lane = azk_lane();
     LdsView L = carve(d.g, d.path_cap, d.table_size);
     const int n = *p.fin_count;
@@ -1158,14 +1344,20 @@ __device__ __forceinline__ void async_restart_body(Dev d, AsyncDev p, int recycl
         for (int i = lane; i < d.rc_pad; i += AZK_WAVE) d.cells[(size_t)g * d.rc_pad + i] = 0;
         if (lane == 0) new_game_one(d, g);
         __syncthreads();
+        if constexpr (OPEN) {
+            open_game_one(d, od, L.board, g, (uint32_t)p.slot_moves[g]);
+            __syncthreads();
+        }
         begin_search_one(d, p, g);
         if (CAP && lane == 0) cap_begin_fresh(d, cp, g, (int)p.slot_moves[g], true);
         __syncthreads();
     }
 }
 
-template <bool CAP>
-__global__ __launch_bounds__(AZK_WAVE) void k_async_restart(CapPack<Dev, CAP> d, AsyncDev p, int recycle) { async_restart_body<CAP>(d, p, recycle, opt<CapDev>(d)); }
+template <bool CAP, bool OPEN>
+__global__ __launch_bounds__(AZK_WAVE) void k_async_restart(RestartPack<CAP, OPEN> d, AsyncDev p, int recycle) {
+    async_restart_body<CAP, OPEN>(d, p, recycle, opt<CapDev>(d), opt<OpenDev>(d));
+}
 
 // azk_root_policy_target: the pi the next move would record - k_root_stats' counts, pruned where the game's search is a forced one
 __global__ __launch_bounds__(AZK_WAVE) void k_root_policy_target(Dev d, ForcedDev fp, double *pi) {
@@ -1222,7 +1414,7 @@ template <bool CAP, class First> CapKeyPack<First, CAP> cap_key_pack(const First
 
 int32_t azk_init_games(azk_engine *e) {
     const Dev &d = e->d;
-    k_reset_games<<<(unsigned)(((size_t)d.G * d.rc_pad + 255) / 256), 256>>>(d, 0, d.G, e->ru.chosen_node);
+    k_reset_games<false><<<(unsigned)(((size_t)d.G * d.rc_pad + 255) / 256), 256>>>(OpenPack<false>{d}, 0, d.G, e->ru.chosen_node);
     k_begin_search<false><<<(unsigned)((d.G + 255) / 256), 256>>>(cap_key_pack<false>(d, e, 0));
     HIPCHK(e, hipDeviceSynchronize());
     return AZK_OK;
@@ -1246,11 +1438,13 @@ static void launch_emit(azk_engine *e, float *states, double *pis, float *zs, lo
     const unsigned per_game = (unsigned)((d.G + 255) / 256), lds = (unsigned)up16(d.g.rc);
     const int plies = d.G * d.g.state_dim;
     const unsigned blocks = (unsigned)(list && plies > 16384 ? 16384 : plies);
-    with_flags([&](auto by_list, auto cap, auto sym, auto surprise) {   // sym: emit_elements, the mask's elements on any geometry
-        const EmitPack<cap.value, sym.value, surprise.value> a{d, on<cap.value>(e->cp), on<sym.value>(e->emit), on<surprise.value>(e->sp)};
-        k_emit_alloc<cap.value, sym.value, surprise.value><<<per_game, 256, 0, st>>>(a, cursor, game_base);
-        k_emit_tuples<by_list.value, cap.value, sym.value, surprise.value><<<blocks, AZK_WAVE, lds, st>>>(a, states, pis, zs, capacity, cursor, list, n_list);
-    }, list != nullptr, e->cp.n_fast != 0, e->emit.n != 0, e->sp_on);
+    with_flags([&](auto by_list, auto cap, auto sym, auto surprise, auto open) {   // sym: emit_elements, the mask's elements on any geometry
+        const EmitPack<cap.value, sym.value, surprise.value, open.value> a{d, on<cap.value>(e->cp), on<sym.value>(e->emit), on<surprise.value>(e->sp),
+                                                                           on<open.value>(OpenEmit{e->op.open_plies})};
+        k_emit_alloc<cap.value, sym.value, surprise.value, open.value><<<per_game, 256, 0, st>>>(a, cursor, game_base);
+        k_emit_tuples<by_list.value, cap.value, sym.value, surprise.value, open.value><<<blocks, AZK_WAVE, lds, st>>>(a, states, pis, zs, capacity, cursor, list,
+                                                                                                                     n_list);
+    }, list != nullptr, e->cp.n_fast != 0, e->emit.n != 0, e->sp_on, e->op_on);
     k_emit_mark<<<per_game, 256, 0, st>>>(d);
 }
 
@@ -1260,7 +1454,10 @@ int32_t azk_reset_games(azk_engine *e, int32_t first, int32_t count, void *strea
     if (!e || first < 0 || count < 0 || first + count > e->d.G) { if (e) e->err = "azk_reset_games: bad range"; return AZK_ERR_ARG; }
     if (count == 0) return AZK_OK;
     e->in_search = false;                  // new games: whatever search was under way is over
-    k_reset_games<<<(unsigned)(((size_t)count * e->d.rc_pad + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d, first, count, e->ru.chosen_node);
+    with_flags([&](auto open) {
+        k_reset_games<open.value><<<(unsigned)(((size_t)count * e->d.rc_pad + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+            OpenPack<open.value>{e->d, on<open.value>(e->op)}, first, count, e->ru.chosen_node);
+    }, e->op_on);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -1568,6 +1765,75 @@ int32_t azk_async_surprise_columns(azk_engine *e, double *rec_kl_dev, double *re
     return AZK_OK;
 }
 
+// ---- random openings -------------------------------------------------------------------------------------------------------
+int32_t azk_set_openings(azk_engine *e, double p_open, int32_t max_plies, int32_t spread, uint64_t seed, int64_t first_global_game, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_openings: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (!(p_open >= 0.0 && p_open <= 1.0)) { e->err = "azk_set_openings: p_open must lie in [0, 1] (azk_clear_openings switches the option off)"; return AZK_ERR_ARG; }
+    if (max_plies < 1 || max_plies > e->d.g.state_dim - 1) { e->err = "azk_set_openings: max_plies must lie in [1, state_dim - 1]"; return AZK_ERR_ARG; }
+    if (spread < -1) { e->err = "azk_set_openings: spread must be -1 (the whole board) or >= 0"; return AZK_ERR_ARG; }
+    const Dev &d = e->d;
+    OpenDev &o = e->op;
+    hipStream_t st = (hipStream_t)stream;
+    if (!o.pending) {
+        HIPCHK(e, dalloc(e, &o.pending, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &o.open_plies, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &o.stats, 3));
+        HIPCHK(e, dalloc(e, &o.actions, (size_t)d.G * d.g.state_dim));
+    }
+    // every slot is looked at by the next azk_open_pending (or azk_async_begin), which opens the games that have not started yet
+    HIPCHK(e, hipMemsetAsync(o.pending, 1, (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(o.open_plies, 0, sizeof(int) * (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(o.stats, 0, sizeof(long long) * 3, st));
+    o.p_open = p_open; o.max_plies = max_plies; o.spread = spread; o.seed = seed; o.first_game = first_global_game;
+    e->op_on = true;
+    return AZK_OK;
+}
+
+int32_t azk_clear_openings(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_openings: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    e->op_on = false;                                             // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+int32_t azk_open_pending(azk_engine *e, int32_t key, void *stream) {
+    if (!e || key < 0) { if (e) e->err = "azk_open_pending: bad argument"; return AZK_ERR_ARG; }
+    if (!e->op_on) { e->err = "azk_open_pending: no openings are set (azk_set_openings)"; return AZK_ERR_STATE; }
+    if (e->async_on) { e->err = "azk_open_pending: the asynchronous movers open their games themselves"; return AZK_ERR_STATE; }
+    k_open_pending<<<e->d.G, AZK_WAVE, e->d.lds_bytes, (hipStream_t)stream>>>(e->d, e->op, key);
+    HIPCHK(e, hipGetLastError());
+    return AZK_OK;
+}
+
+int32_t azk_get_open_plies(azk_engine *e, int32_t *open_plies_dev, void *stream) {
+    if (!e || !open_plies_dev) return AZK_ERR_ARG;
+    if (!e->op_on) { e->err = "azk_get_open_plies: no openings are set (azk_set_openings)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(open_plies_dev, e->op.open_plies, sizeof(int) * (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_get_opening_actions(azk_engine *e, int16_t *actions_dev, void *stream) {
+    if (!e || !actions_dev) return AZK_ERR_ARG;
+    if (!e->op_on) { e->err = "azk_get_opening_actions: no openings are set (azk_set_openings)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(actions_dev, e->op.actions, sizeof(int16_t) * (size_t)e->d.G * e->d.g.state_dim, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_get_leaf_flags(azk_engine *e, uint8_t *flags_dev, void *stream) {
+    if (!e || !flags_dev) return AZK_ERR_ARG;
+    HIPCHK(e, hipMemcpyAsync(flags_dev, e->d.leaf_flag, (size_t)e->d.G * e->d.K, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_get_opening_stats(azk_engine *e, int64_t *out3_host, void *stream) {
+    if (!e || !out3_host) return AZK_ERR_ARG;
+    if (!e->op_on) { e->err = "azk_get_opening_stats: no openings are set (azk_set_openings)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(out3_host, e->op.stats, sizeof(long long) * 3, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
+    return AZK_OK;
+}
+
 // ---- asynchronous self-play ---------------------------------------------------------------------------------------------
 static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *stream, bool reuse) {
     if (!e || !c || !c->stats_dev || c->n_sims < 1 || c->n_sims > e->cfg.max_sims || c->max_sims_per_launch < 1 || !(c->alpha > 0.0)) {
@@ -1628,6 +1894,7 @@ static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *strea
     if (e->sp_on) { e->sp.seed = a.seed; e->sp.first_game = a.first_game; }      // ... and the ply coins of surprise weighting
     // first search of every game: fresh roots + the Dirichlet rows of move keys 0 (this search) and 1 (the next one)
     if (e->cp.n_fast) { e->cp.seed = a.seed; e->cp.first_game = a.first_game; e->cp.stats = a.stats; }   // the coins share the noise rows' key: this run's seed and first game
+    if (e->op_on) k_open_pending<<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->op, 0);      // random openings: the first games, under move key 0
     with_flags([&](auto cap) { k_begin_search<cap.value><<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(cap_key_pack<cap.value>(d, e, 0)); }, e->cp.n_fast != 0);
     HIPCHK(e, hipMemsetAsync(a.todo_count, 0, sizeof(int), st));
     if (a.dirichlet) {
@@ -1686,8 +1953,11 @@ int32_t azk_async_drain(azk_engine *e, float *states_dev, double *pis_dev, float
         if (!pis_dev || !zs_dev || !cursor_dev || capacity < 1 || !d.traj_pi) { e->err = "azk_async_drain: bad replay arguments"; return AZK_ERR_ARG; }
         launch_emit(e, states_dev, pis_dev, zs_dev, (long long)capacity, (unsigned long long *)cursor_dev, nullptr, e->ad.fin_list, e->ad.fin_count, st);
     }
+    with_flags([&](auto cap, auto open) {
+        k_async_restart<cap.value, open.value><<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(
+            RestartPack<cap.value, open.value>{d, on<cap.value>(e->cp), on<open.value>(e->op)}, e->ad, e->async_recycle);
+    }, e->cp.n_fast != 0, e->op_on);
     with_flags([&](auto cap) {
-        k_async_restart<cap.value><<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(CapPack<Dev, cap.value>{d, on<cap.value>(e->cp)}, e->ad, e->async_recycle);
         // re-rooting engines: the next search of every game that moved since the last drain
         if (e->ru.mode) k_reroot_list<cap.value><<<(unsigned)d.G, AZK_WAVE, 0, st>>>(d, e->ad, CapPack<ReuseDev, cap.value>{e->ru, on<cap.value>(e->cp)});
     }, e->cp.n_fast != 0);
@@ -1720,7 +1990,10 @@ int32_t azk_emit_elements(const azk_engine *e, int32_t *mask_out, int32_t *group
 
 int32_t azk_recycle_finished(azk_engine *e, int64_t *stats_dev, void *stream) {
     if (!e || !stats_dev) return AZK_ERR_ARG;
-    k_recycle<<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(e->d, (long long *)stats_dev, e->ru.chosen_node);
+    with_flags([&](auto open) {
+        k_recycle<open.value><<<(unsigned)((e->d.G + 255) / 256), 256, 0, (hipStream_t)stream>>>(OpenPack<open.value>{e->d, on<open.value>(e->op)},
+                                                                                              (long long *)stats_dev, e->ru.chosen_node);
+    }, e->op_on);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }

@@ -240,6 +240,43 @@ def surprise_copies(kl, coin, lam, full=None):
     return out
 
 
+def board_cells(game, size=None):
+    """rows * cols of a game's board (its state_dim)."""
+    if game == "tictactoe":
+        return 9
+    if game == "connect4":
+        return 42
+    rows, cols = (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (int(size or 0), int(size or 0))
+    return rows * cols
+
+
+def check_openings(openings, game, size=None, evaluator=True):
+    """openings = (p_open, max_plies, spread) -> (float, int, int), or None for off.  OPT-IN random openings (include/azk.h azk_set_openings;
+    DESIGN section 25): a game that starts in a slot is, with probability p_open, played forward 1..max_plies uniformly drawn legal plies inside
+    the centred window of half-width spread (-1: the whole board) before its first search; those plies are not trained on.  Raises ValueError,
+    before any engine exists, for what the engine refuses too - p_open outside [0, 1] or NaN, max_plies outside [1, state_dim - 1], a spread
+    below -1 - and for vanilla MCTS on either side (evaluator None): its oracle is not driven from set-up positions."""
+    if openings is None:
+        return None
+    try:
+        p_open, max_plies, spread = openings
+        if isinstance(p_open, bool) or int(max_plies) != max_plies or int(spread) != spread:
+            raise ValueError
+        p_open, max_plies, spread = float(p_open), int(max_plies), int(spread)
+    except (TypeError, ValueError):
+        raise ValueError(f"openings must be (p_open, max_plies, spread), not {openings!r}")
+    if not 0.0 <= p_open <= 1.0:                                  # (NaN fails both comparisons)
+        raise ValueError(f"openings: p_open must lie in [0, 1] (None switches the option off), not {p_open!r}")
+    cells = board_cells(game, size)
+    if not 1 <= max_plies <= cells - 1:
+        raise ValueError(f"openings: max_plies must lie in [1, state_dim - 1 = {cells - 1}], not {max_plies!r}")
+    if spread < -1:
+        raise ValueError(f"openings: spread must be -1 (the whole board) or >= 0, not {spread!r}")
+    if _is_vanilla(evaluator):
+        raise ValueError("openings: vanilla MCTS (evaluator None) is refused - its rollouts are not driven from set-up positions")
+    return p_open, max_plies, spread
+
+
 def mask_elements(mask):
     """The elements of an emission mask, ascending."""
     return tuple(s for s in range(8) if (mask >> s) & 1)
@@ -251,13 +288,15 @@ def _refuse_vanilla_resign(resign, evaluator):
 
 
 class SelfPlayResult:
-    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base", "full", "resigned", "kl", "coin")
+    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base", "full", "resigned", "kl", "coin", "open_plies", "opening")
 
     def __init__(self):
         self.boards, self.actions, self.pis, self.qs, self.winner, self.cells = [], [(-1, -1)], [], [], None, []
         self.full = []               # per ply: was its search a full one (always True without playout_cap); only those plies are trained on
         self.replay_base = None      # first tuple index in the DeviceReplay stream (when a replay ring is attached)
         self.resigned = False        # the game ended by resignation (resign=...): winner is then the side that did not concede
+        self.open_plies = 0          # plies of the game's random opening (openings=...): boards[0] is the position after them, ply open_plies
+        self.opening = []            # ... and the cells they were played on, in order (the players alternate from player 0)
         self.kl, self.coin = [], []  # per ply with surprise_weight=...: KL(recorded pi || raw prior) and the ply's coin (empty without)
 
     def as_reference_tuple(self):
@@ -269,7 +308,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                     alpha=0.03, noise_fn=None, uniform_fn=None, device=0, leaf_dtype="float32", engine=None,
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
                     budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
-                    eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None):
+                    eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None,
+                    openings_first_game=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -294,8 +334,19 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     and coin (SelfPlayResult.kl / .coin) and the replay ring gets each recorded ply as often as its weight says (surprise_copies).
     gumbel_root = (m, c_visit, c_scale) (OPT-IN, check_gumbel_root): a Gumbel root search of n_sims simulations per move - the engine's Gumbel
     rows (or noise_fn's) where the Dirichlet rows go, SelfPlayResult.pis and the replay tuples carry softmax(logits + sigma(completed Q)).
+    openings = (p_open, max_plies, spread) (OPT-IN, check_openings): every game starts from a drawn position with that probability, keyed
+    (openings_seed or seed, (openings_first_game or first_global_game) + g, move 0); SelfPlayResult.open_plies counts the opening's plies,
+    SelfPlayResult.opening holds their cells in order, boards[0] is the position after them, and a replay ring does not get them.  With an
+    (evaluator0, evaluator1) pair the games of the batch are no longer at one ply, so the pair is told apart per game: every leaf of a game
+    whose root has player p to move is evaluated by evaluator p (both run over the step's batch, Engine.leaf_flags says which game a row
+    belongs to); the two sides then search the same number of simulations (ValueError otherwise).
     """
     import torch
+    opn = check_openings(openings, game, size, evaluator)
+    by_game = opn is not None and isinstance(evaluator, (tuple, list))       # the pair is told apart per game, not by the batch's ply
+    if by_game and isinstance(n_sims, (tuple, list)) and len(set(n_sims)) != 1:
+        raise ValueError(f"openings: with an (evaluator0, evaluator1) pair both sides search the same number of simulations, not {n_sims!r} - "
+                         "opened games are not all at the same ply, so one search serves movers of both sides")
     emit = check_emit_symmetry(emit_symmetry, game, size)
     if engine is not None and engine.emit_elements != emit:
         raise ValueError(f"self_play_batch: emit_symmetry={emit_symmetry!r} is mask {emit:#x}, the engine handed in was created with {engine.emit_elements:#x}")
@@ -330,6 +381,14 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     G, A = eng.G, eng.action_dim
     eng.reset_games()
     results = [SelfPlayResult() for _ in range(G)]
+    if opn is not None:
+        eng.set_openings(opn[0], opn[1], opn[2], seed if openings_seed is None else openings_seed,
+                         first_global_game if openings_first_game is None else openings_first_game)
+        eng.open_pending(0)
+        for r, n, cells in zip(results, eng.open_plies().cpu().numpy(), eng.opening_actions()):
+            r.open_plies, r.opening = int(n), cells
+    elif eng.openings is not None:                                # an engine handed in with the option still on: this batch starts from empty boards
+        eng.clear_openings()
     active = np.ones(G, bool)
     su = SAMPLE_UNTIL[game] if sample_until is None else sample_until
     evs = list(evaluator) if isinstance(evaluator, (tuple, list)) else [evaluator]
@@ -357,6 +416,15 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         # an (evaluator0, evaluator1) pair plays the two sides (test.compete, test.py:79-84); all games are at the same ply
         ev = evaluator[move & 1] if isinstance(evaluator, (tuple, list)) else evaluator
         ns = n_sims[move & 1] if isinstance(n_sims, (tuple, list)) else n_sims
+        cells_before, to_move, _ = eng.get_positions()
+        if by_game:
+            side = torch.from_numpy(np.ascontiguousarray(to_move, np.int64)).to(eng.device)
+
+            def ev(x, side=side):
+                rows = torch.nonzero(eng.leaf_flags()).reshape(-1)[: x.shape[0]] // eng.K     # the game of each row: rows are in ascending slot order
+                first = side[rows] == 0
+                (l0, v0), (l1, v1) = evaluator[0](x), evaluator[1](x)
+                return torch.where(first[:, None], l0, l1), torch.where(first, v0.reshape(-1), v1.reshape(-1))
         if ev is None:
             eng.vanilla_search(ns, chunk=vanilla_chunk)
         elif budget_stepping:
@@ -367,7 +435,6 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         pi, q, _ = eng.root_stats()
         if eng.forced_playouts is not None or eng.gumbel_root is not None:
             pi = eng.root_policy_target()                         # what advance records: pruned where the search was a forced one; a Gumbel root's target
-        cells_before, to_move, _ = eng.get_positions()
         chosen, winner, done = eng.advance(uni, su, move_index=move)
         resigned_h = eng.resigned().cpu().numpy() if eng.resign is not None else None
         kl_h, coin_h = [t.cpu().numpy() for t in eng.surprise()] if eng.surprise_weight is not None else (None, None)
@@ -529,6 +596,11 @@ class SelfPlayRunner:
     gumbel_root = (m, c_visit, c_scale) (OPT-IN, check_gumbel_root; with resign, eval_symmetry, emit_symmetry, the eval cache, plain and budget
     stepping): every search is a Gumbel root search of n_sims simulations; the groups get Gumbel rows of the same key where they get Dirichlet
     rows, the records' pi and the replay ring carry softmax(logits + sigma(completed Q)).
+
+    openings = (p_open, max_plies, spread) (OPT-IN, check_openings; with everything above): a game that starts in a slot - the first games and
+    every recycled one - is, with that probability, played forward a few drawn plies before its first search (Engine.open_pending, outside the
+    captured graphs), keyed (openings_seed or seed, (openings_first_game or first_global_game) + slot, the move counter of that search).  Records
+    start at the first searched ply; the replay ring does not get the opening's plies; finished_plies counts them, plies_played does not.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
@@ -536,8 +608,9 @@ class SelfPlayRunner:
                  use_graph=False, n_split=1, replay=None, cache_entries=0, cache_shared=False, budget_stepping=False, per_launch=8,
                  steps_per_graph=32,
                  leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None,
-                 surprise_weight=None, gumbel_root=None):
+                 surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None, openings_first_game=None):
         import torch
+        self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, playout_cap, forced_playouts,
                                              surprise_weight)
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
@@ -596,6 +669,10 @@ class SelfPlayRunner:
                 h.eng.set_surprise_weighting(self.surprise_weight, seed, first_global_game + i * per)
             if self.gumbel_root is not None:
                 h.eng.set_gumbel_root(self.gumbel_root[0], n_sims, self.gumbel_root[1], self.gumbel_root[2])
+            if self.openings is not None:                         # the first games, under the key of their first search (move 0)
+                h.eng.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
+                                   (first_global_game if openings_first_game is None else openings_first_game) + i * per)
+                h.eng.open_pending(0)
 
     # ---- one move for every slot -------------------------------------------------------------------------
     def play_move(self):
@@ -635,6 +712,8 @@ class SelfPlayRunner:
                 e.emit_finished(self.replay)              # (state, pi, z) tuples with D4 augmentation, on device
             if self.recycle:
                 e.recycle_finished(h.stats)
+                if self.openings is not None:                     # the games that have just started, under the key of the next move's search
+                    e.open_pending(self.move_idx + 1)
             h.h_stats.copy_(h.stats, non_blocking=True)
         torch.cuda.current_stream().synchronize()
         for i, h in enumerate(self.halves):
@@ -870,13 +949,18 @@ class AsyncSelfPlayRunner:
 
     gumbel_root = (m, c_visit, c_scale) (OPT-IN, check_gumbel_root; with resign, eval_symmetry, emit_symmetry and the eval cache; not with
     reroot): the games and records of SelfPlayRunner(gumbel_root=...), slot for slot - the movers make the Gumbel rows a search ahead where they
-    make Dirichlet rows, play the survivor and record the Gumbel target.  n_sims is fixed for the run."""
+    make Dirichlet rows, play the survivor and record the Gumbel target.  n_sims is fixed for the run.
+
+    openings = (p_open, max_plies, spread) (OPT-IN, check_openings; with everything above): the games of SelfPlayRunner(openings=...), slot for
+    slot - the first games are opened inside async_begin, a restarted game inside the drain's restart kernel, under the slot's move counter."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
-                 playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None):
+                 playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None,
+                 openings=None, openings_seed=None, openings_first_game=None):
         import torch
+        self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, 1, tree_reuse or reroot, playout_cap, forced_playouts, surprise_weight)
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
         self.surprise_weight = check_surprise_weight(surprise_weight, evaluator)
@@ -916,6 +1000,9 @@ class AsyncSelfPlayRunner:
             e.set_surprise_weighting(self.surprise_weight, seed, first_global_game)
         if self.gumbel_root is not None:
             e.set_gumbel_root(self.gumbel_root[0], n_sims, self.gumbel_root[1], self.gumbel_root[2])
+        if self.openings is not None:                             # async_begin opens the first games, the drain's restart every later one
+            e.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
+                           first_global_game if openings_first_game is None else openings_first_game)
         cap = (4 * n_games if record_capacity is None else record_capacity) if (on_records is not None or record_capacity) else 0
         self.stats, self.records = e.async_begin(n_sims, self.per_launch, SAMPLE_UNTIL[game], seed, first_global_game, alpha, dirichlet, recycle, cap,
                                                  young_launch_us=young_launch_us, reroot=bool(self.reroot))

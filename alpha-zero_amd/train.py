@@ -1,7 +1,7 @@
 """train.py of the reference (train.py:8-123) with its names and signatures, on the batched engine.
 
     collect_data(Game, model, buffer, iterations, mcts_iter, display=False)   train.py:54-83
-    save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=None)   train.py:30-49
+    save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=None, first_ply=0)   train.py:30-49
     rotate_data / flip_data                                                   train.py:8-27
     train(model, batch_size, buffer, train_iterations, lr, device, augment=None)   train.py:85-123
 
@@ -74,16 +74,19 @@ def _add_group(Game, buffer, canon, policy, target, i, elements):
                 buffer.add(fb, fp, target)
 
 
-def save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=None):
+def save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=None, first_ply=0):
     """train.py:30-49: z = +reward for the winner's positions, -reward for the loser's; canonical boards; positions 0 and 1
     once, every later position with its 8 dihedral images in the reference's order.  full (playout cap, SelfPlayResult.full): one flag
     per position; the positions of fast searches are left out, the others keep the group they would have had.  elements (OPT-IN; None:
     the reference's code path): a tuple of D4 elements, ascending - every later position once per element instead (element_image), on any
     board and for Connect4's column actions: what an engine created with that emit_symmetry puts into a DeviceReplay.  copies (OPT-IN surprise
     weighting; None: once each): one count per position (selfplay.surprise_copies) - the position's whole group is added that many times, copy
-    after copy, what an engine with surprise weighting puts into a DeviceReplay; a position with 0 copies is left out."""
+    after copy, what an engine with surprise weighting puts into a DeviceReplay; a position with 0 copies is left out.  first_ply (OPT-IN random
+    openings, SelfPlayResult.open_plies; 0: the reference's code path): boards[0] is the game's position at ply first_ply - the plies of its
+    opening had no search and are not in `data` - so the side to move starts at first_ply & 1 and the once-or-group rule goes by the absolute
+    ply first_ply + i: what an engine with openings puts into a DeviceReplay."""
     boards, actions, policies, qs, winner, reward = data
-    current = 0
+    current = int(first_ply) & 1
     for i in range(len(boards)):
         target = [reward] if current == winner else [-reward]
         canon = Game.get_canonical_board(boards[i], current)
@@ -91,11 +94,11 @@ def save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=Non
         if full is not None and not full[i]:
             continue
         for _ in range(1 if copies is None else int(copies[i])):
-            _add_group(Game, buffer, canon, policies[i], target, i, elements)
+            _add_group(Game, buffer, canon, policies[i], target, int(first_ply) + i, elements)
 
 
 def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed=None, batched=True, playout_cap=None, resign=None,
-                 forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None):
+                 forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None):
     """train.py:54-83: `iterations` self-play games of Game with `model` into `buffer`; returns [first, second, draw] counts.
     batched=False plays the games one after the other through Game().self_play and save_data_to_buffer exactly as the
     reference does (global np.random stream: a seeded caller gets the reference's buffer); the default plays them as one
@@ -110,13 +113,14 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     surprise_weight = lambda (OPT-IN, batched only; selfplay.check_surprise_weight): every stored position is stored as often as its policy
     surprise weight says (selfplay.surprise_copies); both buffer kinds get the same tuples.  gumbel_root = (m, c_visit, c_scale) (OPT-IN,
     batched only; selfplay.check_gumbel_root): every search is a Gumbel root search of mcts_iter simulations; both buffer kinds get
-    softmax(logits + sigma(completed Q)) as the pi of every stored position."""
+    softmax(logits + sigma(completed Q)) as the pi of every stored position.  openings = (p_open, max_plies, spread) (OPT-IN, batched only;
+    selfplay.check_openings): a game starts, with probability p_open, from a position a few drawn plies in; neither buffer kind gets those plies."""
     from azk import DeviceReplay
     from selfplay import check_emit_symmetry, check_surprise_weight, mask_elements, self_play_batch, surprise_copies
     lam = check_surprise_weight(surprise_weight, model)
     if not batched:
         for name, value in (("surprise_weight", lam), ("emit_symmetry", emit_symmetry), ("playout_cap", playout_cap), ("resign", resign),
-                            ("forced_playouts", forced_playouts), ("gumbel_root", gumbel_root),
+                            ("forced_playouts", forced_playouts), ("gumbel_root", gumbel_root), ("openings", openings),
                             ("eval_symmetry", None if eval_symmetry is False else eval_symmetry)):
             if value is not None:
                 raise ValueError(f"collect_data: {name} needs the batched engine (batched=True)")
@@ -133,7 +137,8 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     leaf_dtype = "bfloat16" if getattr(model, "dtype", None) is not None and str(model.dtype).endswith("bfloat16") else "float32"
     res = self_play_batch(Game.engine_name, model, iterations, mcts_iter, size=Game._size(), seed=seed, leaf_dtype=leaf_dtype,
                           replay=buffer if on_device else None, playout_cap=playout_cap, resign=resign, forced_playouts=forced_playouts,
-                          eval_symmetry=eval_symmetry, emit_symmetry=emit_symmetry, surprise_weight=surprise_weight, gumbel_root=gumbel_root)
+                          eval_symmetry=eval_symmetry, emit_symmetry=emit_symmetry, surprise_weight=surprise_weight, gumbel_root=gumbel_root,
+                          openings=openings)
     emit = check_emit_symmetry(emit_symmetry, Game.engine_name, Game._size())
     results = [0, 0, 0]
     for r in res:
@@ -143,7 +148,7 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
             full = r.full if playout_cap is not None else None
             save_data_to_buffer(Game, buffer, (r.boards, r.actions, r.pis, r.qs, r.winner, reward), full=full,
                                 elements=mask_elements(emit) if emit else None,
-                                copies=surprise_copies(r.kl, r.coin, lam, full) if lam is not None else None)
+                                copies=surprise_copies(r.kl, r.coin, lam, full) if lam is not None else None, first_ply=r.open_plies)
         if display:
             Game.display_board(r.boards[-1])
     return results

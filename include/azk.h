@@ -174,7 +174,7 @@ int32_t azk_search_unfinished(azk_engine *e, int32_t *count_host, void *stream);
  * as azk_config.tree_reuse describes, with n_sims = the budget as it stands at that drain, and the Dirichlet row of the game's new
  * move key mixed into the new root's children) and un-parks it.  A game idles from its move to that drain, so such an engine wants
  * the drain often (a few steps apart); azk_counters.roots_reused / nodes_carried count as in the lock-step drivers.
- *   stats_dev  int64 [16], zeroed by azk_async_begin(_reuse): [0] games finished, [1] their plies, [2] wins of player 0, [3] of player 1,
+ *   stats_dev  int64 [16], zeroed by azk_async_begin(_reuse): [0] games finished, [1] their plies (opening plies included), [2] wins of player 0, [3] of player 1,
  *              [4] draws, [5] moves played, [6] records written (ring cursor), [7] searches begun - by azk_async_begin's move kernel,
  *              by the drain's restart of a finished game, and by the drain's re-root of a parked game (carried subtree or fallback)
  *              [8] / [9] with a playout cap (azk_set_playout_cap): full / fast searches among those of [7]
@@ -430,6 +430,53 @@ int32_t azk_clear_gumbel_root(azk_engine *e);
 int32_t azk_gen_gumbel(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double *gumbel_dev, void *stream);
 int32_t azk_gen_gumbel_uniforms(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double *uniforms_dev, void *stream);
 
+/* ---- random openings (OPT-IN; off, the engine launches exactly the kernels it launched before).  Every game otherwise starts from the
+ * empty board and differs from its neighbours only through root noise and move sampling; with the option a game that starts in slot g is,
+ * with probability p_open, played forward 1..max_plies uniformly drawn legal plies inside a centred window before its first search (KataGo's
+ * and Leela's game initialisation).  The plies are drawn on the device, where the game is born - a recycled slot and an asynchronous restart
+ * never pass through the host - from a stateless key.  DESIGN section 25.
+ *   the key     gg = first_global_game + g and key = the move key of the game's first search: the lock-step move index (azk_open_pending's
+ *               argument), the slot's move counter in the asynchronous movers - the key of its noise row and of its resignation coin.
+ *   game draw   Philox4x32-10, key (seed lo, seed hi), counter {gg lo, gg hi, key, 0xFFFFFFFA}: c0 from words (0, 1), c1 from (2, 3), each
+ *               ((hi << 32 | lo) >> 11) * 2^-53.  The game is opened iff c0 < p_open, with n = min(1 + floor(c1 * max_plies), max_plies) plies.
+ *               Word 3 = 0xFFFFFFFA belongs to no other draw (0xFFFFFFFF..FC: move uniform and the option coins, ..FB: Gumbel rows; noise rows:
+ *               it < 64 and it | 0x40000000), so every other stream is what it was.
+ *   ply j < n   counter {gg lo, gg hi ^ ((j + 1) << 8), key, 0xFFFFFFFA}, u from words (0, 1) (j + 1 <= 400, global game index below 2^40: the
+ *               noise rows' bound).  Candidates: the legal actions inside the window, ascending by action index - cell (r, c) is inside iff
+ *               spread < 0, or |2r - (rows - 1)| <= 2 spread and |2c - (cols - 1)| <= 2 spread; Connect4's candidates are the columns that are
+ *               not full and meet the column condition, and the stone lands where the engine's rule puts it.  With m candidates the side to
+ *               move plays candidate min(floor(u * m), m - 1) (float64).  m == 0 ends the opening.  A ply after which the engine's winner rule
+ *               decides the game, or the board is full, is taken back and ends the opening ("cut short"): an opened position is never
+ *               terminal and always has a legal move.
+ *   the plies   are ordinary plies - cells, side to move, ply count and the trajectory's actions are written - without a search: no pi, no q,
+ *               no record, and azk_emit_finished / azk_async_drain leave them out exactly as a playout cap leaves out fast plies (no tuples,
+ *               not in the surprise weights' n and S, 0 copies; the group size stays keyed on the absolute ply index; boards are rebuilt from
+ *               ply 0).  The plies of finished games that azk_recycle_finished and stats_dev [1] count include them; moves played do not.
+ *               Resignation needs nothing: its game coin is keyed by (move counter - plies), constant over the game, and min_ply counts all plies.
+ *   statistics  int64 [3]: [0] games opened, [1] opening plies played, [2] openings cut short.
+ * azk_set_openings: 0 <= p_open <= 1 (0 is a live setting: every game is looked at and none is opened), 1 <= max_plies <= state_dim - 1,
+ * spread = -1 or >= 0, else AZK_ERR_ARG; allocates on first use, zeroes the statistics and flags every slot, so that the next
+ * azk_open_pending (or azk_async_begin) opens the games that have not started yet (ply count 0, not finished).  Call it before
+ * azk_async_begin(_reuse); seed and first_global_game are the option's own in both drivers.  azk_clear_openings switches the option off.
+ * azk_open_pending(key): lock-step drivers call it after the games were created or reset (key 0) and after azk_recycle_finished (key = the
+ * move index of the search that follows), outside any captured graph; one wave per slot, a slot whose game did not just start ends after
+ * one load.  azk_reset_games and azk_recycle_finished flag the slots they restart.  The asynchronous movers open a restarted game inside
+ * the drain's restart kernel and the first games inside azk_async_begin; azk_open_pending answers AZK_ERR_STATE there.
+ * azk_get_open_plies: int32 [G] into device memory, the opening plies of each slot's current game (0: not opened).
+ * azk_get_opening_actions: int16 [G][state_dim] into device memory, row g = the cells the opening of slot g's current game was played on, in
+ * order; entries from azk_get_open_plies' count on are not defined.
+ * azk_get_opening_stats: the three counts into host memory; synchronises.
+ * azk_get_leaf_flags (any engine): uint8 [G * leaves_per_step] into device memory, non-zero = the slot contributes a row to the evaluator batch
+ * of the step that has just selected; the rows are in ascending slot order.  It is how a host loop whose games are not all at the same ply
+ * (an arena between two models on opened games) tells which game a row belongs to. */
+int32_t azk_set_openings(azk_engine *e, double p_open, int32_t max_plies, int32_t spread, uint64_t seed, int64_t first_global_game, void *stream);
+int32_t azk_clear_openings(azk_engine *e);
+int32_t azk_open_pending(azk_engine *e, int32_t key, void *stream);
+int32_t azk_get_open_plies(azk_engine *e, int32_t *open_plies_dev, void *stream);
+int32_t azk_get_opening_actions(azk_engine *e, int16_t *actions_dev, void *stream);
+int32_t azk_get_opening_stats(azk_engine *e, int64_t *out3_host, void *stream);
+int32_t azk_get_leaf_flags(azk_engine *e, uint8_t *flags_dev, void *stream);
+
 /* One simulation per active game (ai/mcts.py:16-60), split around the evaluator:
  *   azk_step_select   - mcts.py:18-37: PUCT walk (node.py:42-47, utils.py:29-44), make_move along the
  *                       path, terminal test + immediate backup, get_valid_moves, canonical board.
@@ -454,7 +501,8 @@ int32_t azk_step_gather(azk_engine *e, void *leaf_boards_dev, int32_t *n_leaf_de
 
 /* Continuous self-play (the batched form of train.collect_data's `for iter in range(iterations): game = Game()`,
  * train.py:63-65): every finished game's slot restarts from an empty board.  stats_dev int64[8] accumulates
- * [0] games finished, [1] their total plies, [2] wins of player 0, [3] wins of player 1, [4] draws. */
+ * [0] games finished, [1] their total plies (the plies of a random opening included, azk_set_openings), [2] wins of player 0,
+ * [3] wins of player 1, [4] draws. */
 int32_t azk_recycle_finished(azk_engine *e, int64_t *stats_dev, void *stream);
 
 /* (state, pi, z) emission for every game that has just finished (train.save_data_to_buffer, train.py:30-49, with the D4

@@ -109,7 +109,8 @@ def test_embed_fold_exact_rows_against_float64():
     """k_embed_fold<EX> (azk_nnx_embed_fold: embedding + pooling from the patch bits, float32 rows) against the float64 evaluation of
     its formulas, entry by entry, and through the batched (hi, lo)-plane link against the float64 value-projected row.  Budget: the
     quadratic form and the score columns on two fp16 terms (2.4e-7 relative), float32 statistics / exp / sums: asserted at 3e-6 of
-    the largest entry.  Engine-leaf variant: the same rows, bit for bit, handed out from the stone-heavy classes down."""
+    the largest entry.  Engine-leaf variant: the same rows, bit for bit, handed out from the stone-heavy classes down.
+    (tests/test_gpu_fold_pinned.py holds every entry to a derived bound of its own, on every board shape.)"""
     import azk
     net = PolicyValueNet(CFG, seed=0, device="cuda", dtype=torch.float32, path="clsfold")
     ft = net._exact["foldu"]

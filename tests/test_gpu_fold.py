@@ -1,7 +1,8 @@
 """GPU tests of the patch-pooling embedding kernel (csrc/azk_nn.hip k_embed_fold, include/azk.h azk_nn_embed_fold): the kernel's rows
 against the float64 restatement of its formulas (pvnet.PolicyValueNet.forward_fold_u_emulated, itself checked against the plain
 forward on the CPU in tests/test_pvnet.py), the batched GEMM that turns them into the value-projected row, the engine-leaf
-variant, and the whole evaluator against the float32 forward."""
+variant, and the whole evaluator against the float32 forward.  tests/test_gpu_fold_pinned.py holds the kernel entry by entry, on
+every board shape it admits."""
 import ctypes as C
 
 import numpy as np

@@ -1,7 +1,8 @@
 // azk_engine.hip - the kernel-free part of the C ABI declared in include/azk.h: engine creation and teardown, geometry, positions in
 // and out, the eval cache's reset, tree export, counters' reset, debug stamps and the device error word.  The kernels and the calls that
-// launch them live with their families: azk_tree.hip (search step), azk_vanilla.hip, azk_moves.hip (searches begin and end, moves,
-// replay emission, noise, the asynchronous movers), azk_rules.hip (stateless rules); azk_engine_int.h is what they share.
+// launch them live with their families: azk_tree.hip (search step), azk_vanilla.hip, azk_rules.hip (stateless rules), azk_begin.hip (games and
+// searches start), azk_moves.hip (searches end: the moves, the asynchronous movers), azk_emit.hip (replay emission), azk_noise.hip; the
+// options' kernel-free state calls are azk_options.hip.  azk_engine_int.h is what they share.
 #include "azk_engine_int.h"
 #include "azk_sym_map.h"      // the elements a geometry admits (emit_elements)
 

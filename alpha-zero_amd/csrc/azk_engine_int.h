@@ -1,7 +1,7 @@
-// azk_engine_int.h - what more than one engine file needs (azk_tree.hip, azk_vanilla.hip, azk_moves.hip, azk_rules.hip and the
-// kernel-free azk_engine.hip): the device view of the engine and its LDS layout, the node-record helpers, the host
-// struct behind the opaque azk_engine, and the few host symbols that cross files.  Not part of the ABI (include/azk.h).  A __device__
-// function is here only if kernels of two files call it.
+// azk_engine_int.h - what more than one engine file needs (azk_tree.hip, azk_vanilla.hip, azk_rules.hip, azk_begin.hip, azk_moves.hip,
+// azk_emit.hip, azk_noise.hip and the kernel-free azk_engine.hip and azk_options.hip): the device view of the engine
+// and its LDS layout, the node-record helpers, the host struct behind the opaque azk_engine, and the few host symbols that cross files.
+// Not part of the ABI (include/azk.h).  A __device__ function is here only if kernels of two files call it.
 // The shared types and helpers live in namespace azk_eng, which every file that includes this header uses: struct azk_engine, a global
 // type whose members are of those types and whose pointers cross files (azk_launch_tree, azk_init_games), is then ONE type in every
 // translation unit.  The kernels themselves stay in each .hip file's unnamed namespace.  tools/compare_kernel_isa.py --strip-namespace
@@ -97,7 +97,7 @@ struct ReuseDev {
 
 // playout-cap randomisation (azk_set_playout_cap, opt-in; n_fast == 0 otherwise): a search is FULL (the budget's simulations) with probability
 // p_full and FAST (n_fast simulations) otherwise, by a coin keyed like the search's noise row.  Its own argument block, passed only to the CAP
-// instantiations of the kernels it touches (azk_moves.hip, "the opt-ins"): Dev, AsyncDev and ReuseDev - and every kernel an engine without the
+// instantiations of the kernels it touches (azk_opt_pack.h, "the opt-ins"): Dev, AsyncDev and ReuseDev - and every kernel an engine without the
 // option launches - stay as they were
 struct CapDev {
     int n_fast;                // simulations of a fast search; 0 = off
@@ -113,7 +113,7 @@ struct CapDev {
 // resignation (azk_set_resign, opt-in; v_resign == 0 otherwise): after a move that does not end the game, the side that
 // has just moved concedes when the root's q (root.value / root.visit: the outcome as the mover's OPPONENT sees it) reached v_resign.  A coin
 // per game makes it a never-resign control game, which is only marked with the side that would have conceded first and played on.  Its own
-// argument block, passed only to the RESIGN instantiations of the two movers (azk_moves.hip, "the opt-ins"): every other argument block - and
+// argument block, passed only to the RESIGN instantiations of the two movers (azk_moves.hip; azk_opt_pack.h, "the opt-ins"): every other argument block - and
 // every kernel an engine without the option launches - stays as it was
 struct ResignDev {
     double v_resign;           // threshold on q, in (0, 1]; 0 = off
@@ -169,7 +169,7 @@ struct SymDev {
 
 // (state, pi, z) emission under a mask of D4 elements (azk_config.emit_elements, opt-in; n == 0 otherwise): ply i >= 2 of
 // a finished game is emitted once per element of the mask instead of under the reference's eight.  Its own argument block, passed only to the SYM
-// instantiations of k_emit_alloc and k_emit_tuples (azk_moves.hip): every other argument block - and every kernel an engine without the option launches - stays as
+// instantiations of k_emit_alloc and k_emit_tuples (azk_emit.hip): every other argument block - and every kernel an engine without the option launches - stays as
 // it was
 struct EmitSym {
     uint32_t els;              // the mask's elements, four bits each, ascending, lowest first
@@ -179,7 +179,7 @@ struct EmitSym {
 // policy surprise weighting (azk_set_surprise_weighting, opt-in): every move records kl = KL(recorded pi || the root
 // children's raw float32 priors) and a coin keyed like the playout coin (Philox word 3 = 0xFFFFFFFC); at emission a recorded ply is written
 // c = floor(w) + (coin < frac(w)) times, w = (1 - lambda) + lambda * n_F * kl / (sum of kl over the game's recorded plies).  Its own
-// argument block, passed only to the SURPRISE instantiations of the two movers and the two emitters (azk_moves.hip): every other argument
+// argument block, passed only to the SURPRISE instantiations of the two movers (azk_moves.hip) and the two emitters (azk_emit.hip): every other argument
 // block - and every kernel an engine without the option launches - stays as it was
 struct SurpriseDev {
     double lambda;             // share of a game's weight that follows kl, in [0, 1] (0: one copy each, kl and coin still recorded)
@@ -195,7 +195,7 @@ struct SurpriseDev {
 // random openings (azk_set_openings, opt-in): a game that starts in slot g is, with probability p_open, played forward
 // 1..max_plies uniformly drawn legal moves inside a centred window before its first search, by draws keyed like the search's noise row
 // (Philox word 3 = 0xFFFFFFFA).  Those plies are ordinary plies without a search: emission leaves them out.  Its own argument block, passed
-// only to k_open_pending and to the OPEN instantiations of the kernels that start games or emit them (azk_moves.hip): every other argument
+// only to k_open_pending and to the OPEN instantiations of the kernels that start games (azk_begin.hip) or emit them (azk_emit.hip): every other argument
 // block - and every kernel an engine without the option launches - stays as it was
 struct OpenDev {
     double p_open;             // share of the games that are opened
@@ -320,6 +320,57 @@ struct AsyncDev {
     int *reroot_list, *reroot_count;   // the games parked since the last drain (k_reroot_list)
 };
 
+// ---- a search starts from a fresh root: the kernels that begin searches (azk_begin.hip) and the asynchronous mover (azk_moves.hip) ----
+// A leaf that missed the eval cache claims its entry's key at selection and fills logits/value at expansion; if the search
+// is abandoned in between (new search, reset, recycle) the half-written entry must not survive.
+__device__ __forceinline__ void drop_pending_cache_claim(const Dev &d, int g) {
+    for (int k = 0; k < d.K; k++) {
+        const int v = g * d.K + k;
+        if (d.cache_entries && !d.cache_shared && d.leaf_node[v] >= 0 && d.leaf_cache[v] < 0) {      // (shared mode claims nothing at selection)
+            unsigned long long *kp = d.cache_key + ((size_t)g * d.cache_entries + (size_t)(-(d.leaf_cache[v] + 1))) * d.key_words;
+            for (int w = 0; w < d.key_words; w++) kp[w] = ~0ull;
+        }
+    }
+}
+
+// every pending-leaf slot of game g back to "nothing pending"
+__device__ __forceinline__ void clear_leaf_slots(const Dev &d, int g) {
+    for (int k = 0; k < d.K; k++) { d.leaf_node[g * d.K + k] = -1; d.leaf_flag[g * d.K + k] = 0; d.to_move_v[g * d.K + k] = d.to_move[g]; }
+}
+
+// Node(None, None, current_player, move_count) for every game (gomoku.py:134)
+__device__ __forceinline__ void fresh_root_one(const Dev &d, int g) {
+    drop_pending_cache_claim(d, g);
+    const size_t base = (size_t)g * d.cap;
+    d.H[base] = NodeH{0, 0.f, meta_pack(0xffff, 0), -1}; d.W[base] = 0.0;
+    d.arena_top[g] = 1; d.root_f64[g] = 0;
+    clear_leaf_slots(d, g);
+    d.sims_done[g] = 0;
+}
+
+// Node(None, None, player, move_count) for one game of the asynchronous engine (one wave).  The search's Dirichlet row is NOT made here: a
+// row's key (seed, global game, slot move counter) is known a whole search before its use, so the rows are generated one search ahead, off
+// the step's chain (k_noise_ahead in the drain) - in this function the Marsaglia-Tsang chain (float64 log / cos / pow, two Philox blocks per
+// try) cost a moving game's wave ~30 us inside a launch every other wave had left after 1 us.
+__device__ __forceinline__ void begin_search_one(const Dev &d, const AsyncDev &p, int g) {
+    if (azk_lane() == 0) {
+        fresh_root_one(d, g);
+        atomicAdd((unsigned long long *)&p.stats[7], 1ull);
+    }
+}
+
+// make_move (gomoku.py:148) on the wave's LDS board: the mover's stone goes onto cellc, placed by lane 0; azk_check_winner follows it.  The
+// ONE copy of the placing rule, which the movers (advance_one, azk_moves.hip) and the openings (open_game_one, azk_begin.hip) both play
+// their plies through.  It is text, not a function: behind a call the compiler schedules the movers differently, and an engine without
+// openings launches the device code it always launched (profiles/openings_isa_vs_parent.txt).  Two statements without a wrapper, for the
+// same reason: use it only as a full statement at block scope, never as the body of an unbraced if / else / loop.
+#define AZK_PLACE_STONE(board, gd, lane, mover, cellc)                                         \
+    if ((lane) == 0) {                                                                         \
+        if ((gd).kind == AZK_KIND_C4) (board)[cellc] |= (uint8_t)(1 << (mover));               \
+        else if ((board)[cellc] == 0) (board)[cellc] = (uint8_t)(1 << (mover));                \
+    }                                                                                          \
+    __syncthreads()
+
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
@@ -395,13 +446,35 @@ static hipError_t dalloc(azk_engine *e, T **p, size_t count) {
     return hipSuccess;
 }
 
+// the simulation budget lives in device memory, so that a captured step graph keeps working when it changes: budget_host as it stands goes
+// up, and the call waits for it
+static inline int32_t upload_budget(azk_engine *e, hipStream_t st) {
+    HIPCHK(e, hipMemcpyAsync(e->d.budget, e->budget_host, sizeof e->budget_host, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    return AZK_OK;
+}
+
 // host symbols that cross engine files: hidden, not in include/azk.h
 #define AZK_INTERNAL __attribute__((visibility("hidden")))
 extern AZK_INTERNAL thread_local std::string azk_create_error;   // azk_last_error(nullptr): written by azk_create and the stateless rule calls (azk_engine.hip)
 // the k_tree instantiation for this engine and step (azk_tree.hip)
 AZK_INTERNAL int32_t azk_launch_tree(azk_engine *e, bool expand, bool select, bool multi, const float *logits, const float *values, hipStream_t st);
-// azk_create's last step: every game empty, every tree a fresh root (azk_moves.hip)
+// azk_create's last step: every game empty, every tree a fresh root (azk_begin.hip)
 AZK_INTERNAL int32_t azk_init_games(azk_engine *e);
+// what the asynchronous engine (azk_moves.hip) launches out of the other families' files; all on the stream, none waits.
+// azk_launch_first_searches: azk_async_begin - the first games opened (engines with random openings) and a fresh root for every game, under
+// move key 0 (azk_begin.hip).  azk_launch_next_searches: the drain - finished games counted and restarted, parked games re-rooted (azk_begin.hip)
+AZK_INTERNAL void azk_launch_first_searches(azk_engine *e, hipStream_t st);
+AZK_INTERNAL int32_t azk_launch_next_searches(azk_engine *e, hipStream_t st);
+// azk_launch_first_rows: azk_async_begin - every game's Dirichlet (Gumbel root: Gumbel) rows of move keys 0 and 1.  azk_launch_rows_ahead:
+// the drain - the next row of every game that moved since the last one (azk_noise.hip)
+AZK_INTERNAL void azk_launch_first_rows(azk_engine *e, hipStream_t st);
+AZK_INTERNAL void azk_launch_rows_ahead(azk_engine *e, hipStream_t st);
+// azk_launch_emit: (state, pi, z) emission of the finished games, all G or the *n_list listed ones (azk_emit.hip)
+AZK_INTERNAL void azk_launch_emit(azk_engine *e, float *states, double *pis, float *zs, long long capacity, unsigned long long *cursor, long long *game_base,
+                                  const int *list, const int *n_list, hipStream_t st);
+// azk_resign_clear: no game resigned, no mark, zero statistics (azk_options.hip)
+AZK_INTERNAL int32_t azk_resign_clear(azk_engine *e, hipStream_t st);
 // evaluation under a board symmetry (azk_sym.hip); both return at once while the option is off.  azk_sym_leaves: behind a selecting tree
 // launch - element and turned cells of every flagged slot.  azk_sym_restore: in front of an expanding one - the rows it is to expand from
 // (the engine's turned-back copy of `logits`, or `logits` itself)

@@ -1,0 +1,284 @@
+// azk_options.hip - the opt-ins' state calls (include/azk.h): set, clear and read playout cap, forced playouts, Gumbel root, resignation,
+// surprise weighting and random openings.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
+// block (azk_engine_int.h) that azk_opt_pack.h hands to the kernels of azk_begin.hip, azk_moves.hip and azk_emit.hip.
+#include "azk_engine_int.h"
+#include <algorithm>
+
+// resignation: no game resigned, no mark, zero statistics (azk_set_resign, and azk_async_begin where the slots' move counters start again at 0)
+int32_t azk_resign_clear(azk_engine *e, hipStream_t st) {
+    const ResignDev &r = e->rs;
+    HIPCHK(e, hipMemsetAsync(r.resigned, 0, (size_t)e->d.G, st));
+    HIPCHK(e, hipMemsetAsync(r.mark_start, 0, sizeof(uint32_t) * (size_t)e->d.G, st));
+    HIPCHK(e, hipMemsetAsync(r.mark_side, 0xff, sizeof(int) * (size_t)e->d.G, st));
+    HIPCHK(e, hipMemsetAsync(r.stats, 0, sizeof(long long) * 4, st));
+    return AZK_OK;
+}
+
+extern "C" {
+
+// ---- playout-cap randomisation ---------------------------------------------------------------------------------------------
+int32_t azk_set_playout_cap(azk_engine *e, double p_full, int32_t n_fast, uint64_t seed, int64_t first_global_game, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_playout_cap: set the cap before azk_async_begin"; return AZK_ERR_STATE; }
+    if (n_fast == 0) { e->cp.n_fast = 0; return AZK_OK; }         // off: the engine launches what it launched before
+    if (e->gb.m) { e->err = "azk_set_playout_cap: a Gumbel root is set - its halving table is built for one budget"; return AZK_ERR_STATE; }
+    if (!(p_full >= 0.0 && p_full <= 1.0)) { e->err = "azk_set_playout_cap: p_full must lie in [0, 1]"; return AZK_ERR_ARG; }
+    if (n_fast < 1 || n_fast > e->cfg.max_sims) { e->err = "azk_set_playout_cap: n_fast must lie in [1, max_sims]"; return AZK_ERR_ARG; }
+    if (e->d.K > 1) { e->err = "azk_set_playout_cap: a playout cap does not combine with leaves_per_step > 1 (virtual loss counts completed simulations differently)"; return AZK_ERR_ARG; }
+    const Dev &d = e->d;
+    CapDev &c = e->cp;
+    if (!c.search_full) {
+        HIPCHK(e, dalloc(e, &c.search_full, (size_t)d.G));
+        if (d.traj_pi) HIPCHK(e, dalloc(e, &c.traj_full, (size_t)d.G * d.g.state_dim));
+    }
+    HIPCHK(e, hipMemsetAsync(c.search_full, 1, (size_t)d.G, (hipStream_t)stream));
+    if (c.traj_full) HIPCHK(e, hipMemsetAsync(c.traj_full, 1, (size_t)d.G * d.g.state_dim, (hipStream_t)stream));
+    c.p_full = p_full; c.seed = seed; c.first_game = first_global_game; c.stats = nullptr; c.rec_full = nullptr;
+    c.n_fast = n_fast;
+    return AZK_OK;
+}
+
+int32_t azk_get_search_full(azk_engine *e, uint8_t *full_dev, void *stream) {
+    if (!e || !full_dev) return AZK_ERR_ARG;
+    if (!e->cp.n_fast) { e->err = "azk_get_search_full: no playout cap is set (azk_set_playout_cap)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(full_dev, e->cp.search_full, (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_async_record_flags(azk_engine *e, uint8_t *rec_full_dev) {
+    if (!e) return AZK_ERR_ARG;
+    if (!e->cp.n_fast) { e->err = "azk_async_record_flags: no playout cap is set (azk_set_playout_cap)"; return AZK_ERR_STATE; }
+    if (e->async_on) { e->err = "azk_async_record_flags: call it before azk_async_begin"; return AZK_ERR_STATE; }
+    e->cp.rec_full = rec_full_dev;
+    return AZK_OK;
+}
+
+// ---- forced playouts and policy target pruning ------------------------------------------------------------------------------
+int32_t azk_set_forced_playouts(azk_engine *e, double k, void *stream) {
+    (void)stream;
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_forced_playouts: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (!(k >= 0.0) || k - k != 0.0) { e->err = "azk_set_forced_playouts: k must be finite and not negative (0 = off)"; return AZK_ERR_ARG; }
+    if (k == 0.0) { e->forced_k = 0.0; return AZK_OK; }              // off: the engine launches what it launched before
+    if (e->gb.m) { e->err = "azk_set_forced_playouts: a Gumbel root is set - its eligibility rule needs raw root selection"; return AZK_ERR_STATE; }
+    if (e->d.K > 1) { e->err = "azk_set_forced_playouts: forced playouts do not combine with leaves_per_step > 1 (a virtual-loss search counts a visit before its value exists: the floor would be met by visits that carry nothing)"; return AZK_ERR_ARG; }
+    e->forced_k = k;
+    return AZK_OK;
+}
+
+// ---- Gumbel root search -----------------------------------------------------------------------------------------------------
+// schedule(m, n): the visit count a root child must have at each of the n root selections of a search that halves m sampled children
+static void gumbel_schedule(int m, int n, int *out) {
+    if (m <= 1) { for (int t = 0; t < n; t++) out[t] = t; return; }
+    int L = 0;
+    while ((1 << L) < m) L++;
+    std::vector<int> v((size_t)m, 0);
+    int c = m, len = 0;
+    while (len < n) {
+        const int extra = std::max(1, n / (L * c));
+        for (int x = 0; x < extra && len < n; x++)
+            for (int i = 0; i < c; i++) { if (len < n) out[len++] = v[i]; v[i] += 1; }
+        c = std::max(2, c / 2);
+    }
+}
+
+int32_t azk_set_gumbel_root(azk_engine *e, int32_t m, int32_t n_sims, double c_visit, double c_scale, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_gumbel_root: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (m < 1 || m > 64) { e->err = "azk_set_gumbel_root: m must lie in [1, 64]"; return AZK_ERR_ARG; }
+    if (n_sims < 2 || n_sims > e->cfg.max_sims) { e->err = "azk_set_gumbel_root: n_sims must lie in [2, max_sims]"; return AZK_ERR_ARG; }
+    if (!(c_visit >= 0.0) || c_visit - c_visit != 0.0) { e->err = "azk_set_gumbel_root: c_visit must be finite and not negative"; return AZK_ERR_ARG; }
+    if (!(c_scale > 0.0) || c_scale - c_scale != 0.0) { e->err = "azk_set_gumbel_root: c_scale must be finite and positive"; return AZK_ERR_ARG; }
+    if (e->d.K > 1) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with leaves_per_step > 1 (a virtual-loss search counts a visit before its value exists: eligibility by visit count would pass over it)"; return AZK_ERR_ARG; }
+    if (e->ru.mode) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with tree reuse (the eligibility rule needs a fresh root: every child at 0 visits)"; return AZK_ERR_STATE; }
+    if (e->cp.n_fast) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with a playout cap (the halving table is built for one budget)"; return AZK_ERR_STATE; }
+    if (e->forced_k != 0.0) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with forced playouts (the eligibility rule needs raw root selection)"; return AZK_ERR_STATE; }
+    if (e->sp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with surprise weighting (its recorded pi is not a visit distribution)"; return AZK_ERR_STATE; }
+    const Dev &d = e->d;
+    GumbelDev &gb = e->gb;
+    hipStream_t st = (hipStream_t)stream;
+    const int n = n_sims - 1;
+    std::vector<int> table((size_t)(m + 1) * n);
+    for (int mm = 0; mm <= m; mm++) gumbel_schedule(mm, n, table.data() + (size_t)mm * n);
+    int *tab = nullptr;                                              // (a table of its own per call: a captured step graph may still hold the last one)
+    HIPCHK(e, dalloc(e, &tab, table.size()));
+    if (!gb.logit) {
+        HIPCHK(e, dalloc(e, &gb.logit, (size_t)d.G * d.g.rc));
+        HIPCHK(e, dalloc(e, &gb.v0, (size_t)d.G));
+        HIPCHK(e, hipMemsetAsync(gb.logit, 0, sizeof(float) * (size_t)d.G * d.g.rc, st));
+        HIPCHK(e, hipMemsetAsync(gb.v0, 0, sizeof(float) * (size_t)d.G, st));
+    }
+    HIPCHK(e, hipMemcpyAsync(tab, table.data(), sizeof(int) * table.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    gb.table = tab; gb.n = n; gb.c_visit = c_visit; gb.c_scale = c_scale;
+    gb.m = m;
+    e->gumbel_sims = n_sims;
+    return AZK_OK;
+}
+
+int32_t azk_clear_gumbel_root(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_gumbel_root: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    e->gb.m = 0;                                                   // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+// ---- resignation ------------------------------------------------------------------------------------------------------
+int32_t azk_set_resign(azk_engine *e, double v_resign, int32_t min_ply, double p_never, uint64_t seed, int64_t first_global_game, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_resign: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (!(v_resign >= 0.0 && v_resign <= 1.0)) { e->err = "azk_set_resign: v_resign must lie in [0, 1] (0 = off)"; return AZK_ERR_ARG; }
+    if (!(p_never >= 0.0 && p_never <= 1.0)) { e->err = "azk_set_resign: p_never must lie in [0, 1]"; return AZK_ERR_ARG; }
+    if (min_ply < 0) { e->err = "azk_set_resign: min_ply must not be negative"; return AZK_ERR_ARG; }
+    if (v_resign == 0.0) { e->rs.v_resign = 0.0; return AZK_OK; }  // off: the engine launches what it launched before
+    if (e->d.K > 1) { e->err = "azk_set_resign: resignation does not combine with leaves_per_step > 1 (a virtual-loss search is another search: its q is not the one a threshold was set on)"; return AZK_ERR_ARG; }
+    const Dev &d = e->d;
+    ResignDev &r = e->rs;
+    if (!r.resigned) {
+        HIPCHK(e, dalloc(e, &r.resigned, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &r.mark_start, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &r.mark_side, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &r.stats, 4));
+    }
+    const int32_t rc = azk_resign_clear(e, (hipStream_t)stream);
+    if (rc != AZK_OK) return rc;
+    r.min_ply = min_ply; r.p_never = p_never; r.seed = seed; r.first_game = first_global_game; r.rec_resigned = nullptr;
+    r.v_resign = v_resign;
+    return AZK_OK;
+}
+
+int32_t azk_get_resigned(azk_engine *e, uint8_t *resigned_dev, void *stream) {
+    if (!e || !resigned_dev) return AZK_ERR_ARG;
+    if (e->rs.v_resign == 0.0) { e->err = "azk_get_resigned: no resignation is set (azk_set_resign)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(resigned_dev, e->rs.resigned, (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_get_resign_stats(azk_engine *e, int64_t *out4_host, void *stream) {
+    if (!e || !out4_host) return AZK_ERR_ARG;
+    if (e->rs.v_resign == 0.0) { e->err = "azk_get_resign_stats: no resignation is set (azk_set_resign)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(out4_host, e->rs.stats, sizeof(long long) * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_async_resign_flags(azk_engine *e, uint8_t *rec_resigned_dev) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->rs.v_resign == 0.0) { e->err = "azk_async_resign_flags: no resignation is set (azk_set_resign)"; return AZK_ERR_STATE; }
+    if (e->async_on) { e->err = "azk_async_resign_flags: call it before azk_async_begin"; return AZK_ERR_STATE; }
+    e->rs.rec_resigned = rec_resigned_dev;
+    return AZK_OK;
+}
+
+// ---- policy surprise weighting ------------------------------------------------------------------------------------------
+int32_t azk_set_surprise_weighting(azk_engine *e, double lambda, uint64_t seed, int64_t first_global_game, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_surprise_weighting: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (e->gb.m) { e->err = "azk_set_surprise_weighting: a Gumbel root is set - its recorded pi is not a visit distribution, which the weight is defined on"; return AZK_ERR_STATE; }
+    if (!(lambda >= 0.0 && lambda <= 1.0)) { e->err = "azk_set_surprise_weighting: lambda must lie in [0, 1] (azk_clear_surprise_weighting switches the option off)"; return AZK_ERR_ARG; }
+    if (e->d.K > 1) { e->err = "azk_set_surprise_weighting: surprise weighting does not combine with leaves_per_step > 1 (a virtual-loss search's visit counts are not the ones the weight was defined on)"; return AZK_ERR_ARG; }
+    const Dev &d = e->d;
+    if (!d.traj_pi) { e->err = "azk_set_surprise_weighting: the engine records no trajectories (a square board with one action per cell, or an engine created with emit_elements)"; return AZK_ERR_ARG; }
+    SurpriseDev &s = e->sp;
+    const size_t plies = (size_t)d.G * d.g.state_dim;
+    if (!s.traj_kl) {
+        HIPCHK(e, dalloc(e, &s.traj_kl, plies));
+        HIPCHK(e, dalloc(e, &s.traj_coin, plies));
+        HIPCHK(e, dalloc(e, &s.traj_copies, plies));
+        HIPCHK(e, dalloc(e, &s.last_kl, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &s.last_coin, (size_t)d.G));
+    }
+    HIPCHK(e, hipMemsetAsync(s.traj_kl, 0, sizeof(double) * plies, (hipStream_t)stream));
+    HIPCHK(e, hipMemsetAsync(s.traj_coin, 0, sizeof(double) * plies, (hipStream_t)stream));
+    HIPCHK(e, hipMemsetAsync(s.traj_copies, 0, sizeof(uint16_t) * plies, (hipStream_t)stream));
+    HIPCHK(e, hipMemsetAsync(s.last_kl, 0, sizeof(double) * (size_t)d.G, (hipStream_t)stream));
+    HIPCHK(e, hipMemsetAsync(s.last_coin, 0, sizeof(double) * (size_t)d.G, (hipStream_t)stream));
+    s.lambda = lambda; s.seed = seed; s.first_game = first_global_game; s.rec_kl = nullptr; s.rec_coin = nullptr;
+    e->sp_on = true;
+    return AZK_OK;
+}
+
+int32_t azk_clear_surprise_weighting(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_surprise_weighting: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    e->sp_on = false;                                             // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+int32_t azk_get_surprise(azk_engine *e, double *kl_dev, double *coin_dev, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (!e->sp_on) { e->err = "azk_get_surprise: no surprise weighting is set (azk_set_surprise_weighting)"; return AZK_ERR_STATE; }
+    if (kl_dev) HIPCHK(e, hipMemcpyAsync(kl_dev, e->sp.last_kl, sizeof(double) * (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (coin_dev) HIPCHK(e, hipMemcpyAsync(coin_dev, e->sp.last_coin, sizeof(double) * (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_async_surprise_columns(azk_engine *e, double *rec_kl_dev, double *rec_coin_dev) {
+    if (!e) return AZK_ERR_ARG;
+    if (!e->sp_on) { e->err = "azk_async_surprise_columns: no surprise weighting is set (azk_set_surprise_weighting)"; return AZK_ERR_STATE; }
+    if (e->async_on) { e->err = "azk_async_surprise_columns: call it before azk_async_begin"; return AZK_ERR_STATE; }
+    e->sp.rec_kl = rec_kl_dev; e->sp.rec_coin = rec_coin_dev;
+    return AZK_OK;
+}
+
+// ---- random openings -------------------------------------------------------------------------------------------------------
+int32_t azk_set_openings(azk_engine *e, double p_open, int32_t max_plies, int32_t spread, uint64_t seed, int64_t first_global_game, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_openings: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (!(p_open >= 0.0 && p_open <= 1.0)) { e->err = "azk_set_openings: p_open must lie in [0, 1] (azk_clear_openings switches the option off)"; return AZK_ERR_ARG; }
+    if (max_plies < 1 || max_plies > e->d.g.state_dim - 1) { e->err = "azk_set_openings: max_plies must lie in [1, state_dim - 1]"; return AZK_ERR_ARG; }
+    if (spread < -1) { e->err = "azk_set_openings: spread must be -1 (the whole board) or >= 0"; return AZK_ERR_ARG; }
+    const Dev &d = e->d;
+    OpenDev &o = e->op;
+    hipStream_t st = (hipStream_t)stream;
+    if (!o.pending) {
+        HIPCHK(e, dalloc(e, &o.pending, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &o.open_plies, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &o.stats, 3));
+        HIPCHK(e, dalloc(e, &o.actions, (size_t)d.G * d.g.state_dim));
+    }
+    // every slot is looked at by the next azk_open_pending (or azk_async_begin), which opens the games that have not started yet
+    HIPCHK(e, hipMemsetAsync(o.pending, 1, (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(o.open_plies, 0, sizeof(int) * (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(o.stats, 0, sizeof(long long) * 3, st));
+    o.p_open = p_open; o.max_plies = max_plies; o.spread = spread; o.seed = seed; o.first_game = first_global_game;
+    e->op_on = true;
+    return AZK_OK;
+}
+
+int32_t azk_clear_openings(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_openings: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    e->op_on = false;                                             // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+int32_t azk_get_open_plies(azk_engine *e, int32_t *open_plies_dev, void *stream) {
+    if (!e || !open_plies_dev) return AZK_ERR_ARG;
+    if (!e->op_on) { e->err = "azk_get_open_plies: no openings are set (azk_set_openings)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(open_plies_dev, e->op.open_plies, sizeof(int) * (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_get_opening_actions(azk_engine *e, int16_t *actions_dev, void *stream) {
+    if (!e || !actions_dev) return AZK_ERR_ARG;
+    if (!e->op_on) { e->err = "azk_get_opening_actions: no openings are set (azk_set_openings)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(actions_dev, e->op.actions, sizeof(int16_t) * (size_t)e->d.G * e->d.g.state_dim, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_get_leaf_flags(azk_engine *e, uint8_t *flags_dev, void *stream) {
+    if (!e || !flags_dev) return AZK_ERR_ARG;
+    HIPCHK(e, hipMemcpyAsync(flags_dev, e->d.leaf_flag, (size_t)e->d.G * e->d.K, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_get_opening_stats(azk_engine *e, int64_t *out3_host, void *stream) {
+    if (!e || !out3_host) return AZK_ERR_ARG;
+    if (!e->op_on) { e->err = "azk_get_opening_stats: no openings are set (azk_set_openings)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(out3_host, e->op.stats, sizeof(long long) * 3, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
+    return AZK_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // azk_sym_map.h - the D4 elements of a board, shared by the three places that turn one: evaluation under a symmetry (azk_sym.hip), (state,
-// pi, z) emission under a mask of elements (azk_moves.hip) and the replay batch gather (azk_replay.hip).  include/azk.h
+// pi, z) emission under a mask of elements (azk_emit.hip) and the replay batch gather (azk_replay.hip).  include/azk.h
 // (azk_set_eval_symmetry) has the numbering and src_s.  Not part of the ABI.
 #pragma once
 #include <stdint.h>
@@ -8,7 +8,7 @@
 
 namespace azk_eng {
 
-// source cell (row-major) of output cell (i, c) under element s of the emission's order (d4_source in azk_moves.hip), select-based: an
+// source cell (row-major) of output cell (i, c) under element s of the emission's order (d4_source in azk_emit.hip), select-based: an
 // element is "transpose?" then "flip the source row?" and "flip the source column?".  Elements that transpose exist on square boards only.
 __device__ __forceinline__ int sym_source_rc(int s, int i, int c, int R, int C) {
     const bool t = (0xB8u >> s) & 1u, fi = (0xD4u >> s) & 1u, fj = (0x5Au >> s) & 1u;

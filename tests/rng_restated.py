@@ -1,4 +1,4 @@
-"""The product RNG (noise_uniform / cap_coin / noise_row / k_gen_noise in csrc/azk_moves.hip), restated in float64 numpy from the
+"""The product RNG (noise_uniform / cap_coin / noise_row in csrc/azk_rng.h, k_gen_noise in csrc/azk_noise.hip), restated in float64 numpy from the
 counter layouts include/azk.h documents (azk_gen_noise, azk_set_playout_cap) and the kernel's comments.  Test infrastructure: no GPU,
 no libazk; everything is vectorised over games (and actions).
 

@@ -1,4 +1,4 @@
-"""Every instantiation of the two movers (k_advance, k_move_async; azk_moves.hip) and the emitter instantiations no other file reaches.
+"""Every instantiation of the two movers (k_advance, k_move_async; azk_moves.hip) and the emitter instantiations (azk_emit.hip) no other file reaches.
 The option files test each opt-in with the combinations it was written for; this file launches ALL sixteen (re-root, playout cap,
 resignation, forced playouts) combinations on their board - Gomoku 7 x 7, test_gpu_forced_playouts' MOVES, cap, resignation and k with
 test_gpu_playout_cap's G and helpers - and asserts per case that the asynchronous movers play the lock-step runner's games slot for slot,

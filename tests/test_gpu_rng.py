@@ -1,5 +1,5 @@
-"""The product RNG on the device - Engine.gen_noise through the C ABI as shipped (azk_gen_noise: noise_uniform, noise_row, k_gen_noise
-in csrc/azk_moves.hip) and the playout-cap coin - against the float64 restatement of tests/rng_restated.py, which test_rng_restated.py
+"""The product RNG on the device - Engine.gen_noise through the C ABI as shipped (azk_gen_noise: k_gen_noise in
+csrc/azk_noise.hip over noise_uniform and noise_row in csrc/azk_rng.h) and the playout-cap coin - against the float64 restatement of tests/rng_restated.py, which test_rng_restated.py
 pins on the CPU to the published Philox vectors and to the Gamma(alpha) law.  Uniforms and coins are integer arithmetic and one exact
 conversion: bit for bit.  Rows go through log / cos / sqrt / pow of two different libms: entry by entry within ROW_RTOL, no row and
 no entry left out; the CPU module shows that no accept / reject decision of these inputs is close enough to flip."""

@@ -7,7 +7,7 @@
     python3 tools/compare_kernel_isa.py OLD/csrc/build alpha-zero_amd/csrc/build --strip-namespace azk_eng --rename profiles/mover_options_rename.tsv
 
 Each side is a build directory (every *.o in it) or a library.  Every code object bundled in them is extracted (one per translation
-unit: csrc/azk_search.hip, azk_moves.hip, azk_nn.hip, ...), every kernel is cut at its symbol's size (llvm-readelf -s: llvm-objdump -d goes on to
+unit: csrc/azk_search.hip, azk_begin.hip, azk_moves.hip, azk_nn.hip, ...), every kernel is cut at its symbol's size (llvm-readelf -s: llvm-objdump -d goes on to
 disassemble a section's padding as if it were code) and the instruction text is compared symbol by symbol, whichever file the
 symbol lives in on either side (addresses and encodings left out; kernels in anonymous namespaces keep their mangled names when
 they move between files).  A mangled name also spells the namespaces of the kernel's parameter types, so a type that moves to

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-kernel register / LDS / scratch use as the compiler reports it (device-only assembly; no GPU needed).
-#   tools/kernel_resources.sh azk_nn.hip|azk_embed_conv.hip|...|azk_tree.hip|azk_moves.hip|azk_search.hip [name pattern]      (any file of csrc/)
+#   tools/kernel_resources.sh azk_nn.hip|azk_embed_conv.hip|...|azk_tree.hip|azk_begin.hip|azk_moves.hip|azk_emit.hip|azk_noise.hip|azk_search.hip [name pattern]      (any file of csrc/)
 # The engine files (the Makefile's ENGINE_SRCS and SEARCH_PARTS lists) get -ffp-contract=off as in the build, the network files -fno-slp-vectorize.
 cd "$(dirname "$0")/../alpha-zero_amd/csrc" || exit 1
 src=${1:-azk_nn.hip}

@@ -42,6 +42,7 @@ SYMBOLS = [
     "azk_set_gumbel_root", "azk_clear_gumbel_root", "azk_gen_gumbel", "azk_gen_gumbel_uniforms",
     "azk_set_openings", "azk_clear_openings", "azk_open_pending", "azk_get_open_plies", "azk_get_opening_stats",
     "azk_get_opening_actions", "azk_get_leaf_flags",
+    "azk_set_puct", "azk_clear_puct",
 ]
 
 
@@ -152,6 +153,57 @@ def emit_mask(emit_symmetry, game, size=None):
     return sum(1 << s for s in set(els))
 
 
+PUCT_TABLE_MAX = 65536                              # azk_set_puct's largest n_table
+FPU_MODES = {"absolute": 1, "reduction": 2}
+
+
+def puct_table(c_init, c_base, n=PUCT_TABLE_MAX):
+    """AlphaZero's exploration rate as a table over the selecting node's visit count: math.log((1 + N + c_base) / c_base) + c_init for
+    N = 0..n-1, in host float64 (the engine reads entry min(N, n - 1); it has no device log)."""
+    c_init, c_base, n = float(c_init), float(c_base), int(n)
+    if not 1 <= n <= PUCT_TABLE_MAX:
+        raise ValueError(f"puct_table: n must lie in [1, {PUCT_TABLE_MAX}], not {n!r}")
+    if not 0.0 < c_base < float("inf") or not 0.0 <= c_init < float("inf"):
+        raise ValueError(f"puct_table: c_base must be finite and positive and c_init finite and not negative, not {(c_init, c_base)!r}")
+    return np.array([math.log((1 + N + c_base) / c_base) + c_init for N in range(n)], np.float64)
+
+
+def puct_setting(c, fpu=None):
+    """(c, fpu) -> (c_table float64 [n], fpu_mode, fpu_tree, fpu_root), the arguments of azk_set_puct (include/azk.h).
+    c: a number (that constant for every visit count), a TUPLE (c_init, c_base) (puct_table over the whole 65536 entries), or a list / array of
+    table entries.  fpu: None (an unvisited child scores as the reference's), ("absolute", v_tree[, v_root]) or ("reduction", r_tree[, r_root]);
+    the root's parameter defaults to the tree's.  Raises ValueError for what the engine refuses too."""
+    try:
+        if isinstance(c, bool):
+            raise TypeError
+        if isinstance(c, tuple) and len(c) == 2:
+            table = puct_table(c[0], c[1])
+        elif isinstance(c, (int, float, np.integer, np.floating)):
+            table = np.array([float(c)], np.float64)
+        else:
+            table = np.ascontiguousarray([float(x) for x in c], np.float64)
+    except TypeError:
+        raise ValueError(f"puct: c must be a number, a tuple (c_init, c_base) or a list of table entries, not {c!r}")
+    if not 1 <= table.size <= PUCT_TABLE_MAX:
+        raise ValueError(f"puct: the table must have 1..{PUCT_TABLE_MAX} entries, not {table.size}")
+    if not (np.isfinite(table).all() and (table >= 0.0).all()):
+        raise ValueError("puct: every table entry must be finite and not negative")
+    if fpu is None:
+        return table, 0, 0.0, 0.0
+    try:
+        kind, f_tree = fpu[0], float(fpu[1])
+        f_root = float(fpu[2]) if len(fpu) == 3 else f_tree
+        if len(fpu) not in (2, 3) or kind not in FPU_MODES:
+            raise ValueError
+    except (TypeError, ValueError, IndexError, KeyError):
+        raise ValueError(f"puct: fpu must be None, ('absolute', v_tree[, v_root]) or ('reduction', r_tree[, r_root]), not {fpu!r}")
+    if not (math.isfinite(f_tree) and math.isfinite(f_root)):
+        raise ValueError(f"puct: the FPU parameters must be finite, not {fpu!r}")
+    if kind == "reduction" and (f_tree < 0.0 or f_root < 0.0):
+        raise ValueError(f"puct: a reduction must not be negative, not {fpu!r}")
+    return table, FPU_MODES[kind], f_tree, f_root
+
+
 class Engine:
     """G concurrent games + their search trees resident on one GPU (one engine per process / GPU)."""
 
@@ -212,6 +264,7 @@ class Engine:
         self.forced_playouts = None                 # k once set_forced_playouts has switched the option on
         self.gumbel_root = None                     # (m, n_sims, c_visit, c_scale) once set_gumbel_root has switched the option on
         self.openings = None                        # (p_open, max_plies, spread) once set_openings has switched the option on
+        self.puct = None                            # (c_table, fpu_mode, fpu_tree, fpu_root) once set_puct has switched the option on
         self.surprise_weight = None                 # lambda once set_surprise_weighting has switched the option on (0.0 is a live setting)
         self.cache_entries = int(cache_entries)
         # with the eval cache a step can have pending (cached) leaves to expand although no leaf went to the evaluator
@@ -369,6 +422,23 @@ class Engine:
         explains (root_policy_target shows it).  The move, root_stats, q, resignation and tree reuse keep raw visits.  k = 0 switches it off."""
         self._chk(self.L.azk_set_forced_playouts(self.h, float(k), _stream()))
         self.forced_playouts = float(k) if float(k) != 0.0 else None
+
+    def set_puct(self, c, fpu=None):
+        """OPT-IN configurable PUCT (azk_set_puct): from now on every selection scores a child
+        Q + c * P * sqrt(Np) / (N + 1), c = the table's word at the selecting node's visit count, and an unvisited child as the first-play
+        urgency says.  c: a number, a tuple (c_init, c_base) (AlphaZero's log schedule, puct_table) or a list / array of table entries;
+        fpu: None (the reference's: an unvisited child's Q counts 0), ("absolute", v_tree[, v_root]) or ("reduction", r_tree[, r_root]) - the
+        selecting node's own value minus r * sqrt(prior mass of its visited children).  set_puct(1.0) searches the trees of an engine without
+        the option.  Between searches only; not with forced playouts, a Gumbel root, leaves_per_step > 1 or vanilla_search.  clear_puct()
+        switches it off."""
+        table, mode, f_tree, f_root = puct_setting(c, fpu)
+        self._chk(self.L.azk_set_puct(self.h, _np(table), int(table.size), mode, f_tree, f_root, _stream()))
+        self.puct = (table, mode, f_tree, f_root)
+
+    def clear_puct(self):
+        """Configurable PUCT off (azk_clear_puct): the engine launches what it launched before."""
+        self._chk(self.L.azk_clear_puct(self.h))
+        self.puct = None
 
     def set_gumbel_root(self, m, n_sims, c_visit=50.0, c_scale=1.0):
         """OPT-IN Gumbel root search (azk_set_gumbel_root; Danihelka et al. 2022): every search of n_sims simulations

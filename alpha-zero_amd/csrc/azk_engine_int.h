@@ -152,6 +152,16 @@ struct GumbelDev {
     float *v0;                 // [G] the root's value as its evaluation (or the eval cache) gave it, for the side to move
 };
 
+// configurable PUCT (azk_set_puct, opt-in): the exploration rate is a table word of the selecting node's visit count, and an
+// unvisited child is worth a first-play urgency instead of the reference's 0.  Its own argument block, passed only to the PUCT instantiations
+// (k_tree<.., PUCT> in azk_tree.hip): every other argument block - and every kernel an engine without the option launches - stays as it was
+struct PuctDev {
+    const double *c_table;     // [n_table] c at a node of Np visits: c_table[min(Np, n_table - 1)], built by the host (no device log)
+    int n_table;               // 1..65536
+    int fpu_mode;              // 0 as the reference (an unvisited child scores u0), 1 absolute, 2 the node's value minus a reduction
+    double fpu_tree, fpu_root; // the value (mode 1) or the reduction r >= 0 (mode 2), below the root and at it
+};
+
 // evaluation under a board symmetry (azk_set_eval_symmetry, opt-in; mode == 0 otherwise): the evaluator is shown each pending
 // leaf in orientation s = the fixed element, or a hash of (seed, the leaf's position), and its logits row is turned back before k_tree expands
 // from it.  Its own argument of the two kernels that exist only for it (azk_sym.hip): every other argument block - and every kernel an engine
@@ -416,6 +426,8 @@ struct azk_engine {
     ForcedDev forced() const { return ForcedDev{forced_k, cp.n_fast ? cp.search_full : nullptr}; }   // the argument block as the options stand now
     GumbelDev gb = {};                   // Gumbel root search (azk_set_gumbel_root); gb.m == 0: off
     int gumbel_sims = 0;                 // ... the n_sims its table was built for
+    PuctDev pu = {};                     // configurable PUCT (azk_set_puct); puct_on == false: off, nothing allocated
+    bool puct_on = false;                // (c_table = [1.0] with mode 0 is a live setting, so the switch is its own word)
     bool async_on = false;
     int async_recycle = 1;
     SymDev sym = {};                     // evaluation under a board symmetry (azk_set_eval_symmetry); sym.mode == 0: off, nothing allocated

@@ -61,6 +61,7 @@ int32_t azk_set_forced_playouts(azk_engine *e, double k, void *stream) {
     if (!(k >= 0.0) || k - k != 0.0) { e->err = "azk_set_forced_playouts: k must be finite and not negative (0 = off)"; return AZK_ERR_ARG; }
     if (k == 0.0) { e->forced_k = 0.0; return AZK_OK; }              // off: the engine launches what it launched before
     if (e->gb.m) { e->err = "azk_set_forced_playouts: a Gumbel root is set - its eligibility rule needs raw root selection"; return AZK_ERR_STATE; }
+    if (e->puct_on) { e->err = "azk_set_forced_playouts: configurable PUCT is set (azk_set_puct) - the pruning bound restates the reference's selection formula"; return AZK_ERR_STATE; }
     if (e->d.K > 1) { e->err = "azk_set_forced_playouts: forced playouts do not combine with leaves_per_step > 1 (a virtual-loss search counts a visit before its value exists: the floor would be met by visits that carry nothing)"; return AZK_ERR_ARG; }
     e->forced_k = k;
     return AZK_OK;
@@ -94,6 +95,7 @@ int32_t azk_set_gumbel_root(azk_engine *e, int32_t m, int32_t n_sims, double c_v
     if (e->cp.n_fast) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with a playout cap (the halving table is built for one budget)"; return AZK_ERR_STATE; }
     if (e->forced_k != 0.0) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with forced playouts (the eligibility rule needs raw root selection)"; return AZK_ERR_STATE; }
     if (e->sp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with surprise weighting (its recorded pi is not a visit distribution)"; return AZK_ERR_STATE; }
+    if (e->puct_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with configurable PUCT (azk_set_puct: its root selection is not PUCT)"; return AZK_ERR_STATE; }
     const Dev &d = e->d;
     GumbelDev &gb = e->gb;
     hipStream_t st = (hipStream_t)stream;
@@ -120,6 +122,39 @@ int32_t azk_clear_gumbel_root(azk_engine *e) {
     if (!e) return AZK_ERR_ARG;
     if (e->async_on) { e->err = "azk_clear_gumbel_root: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
     e->gb.m = 0;                                                   // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+// ---- configurable PUCT ----------------------------------------------------------------------------------------------------
+int32_t azk_set_puct(azk_engine *e, const double *c_table_host, int32_t n_table, int32_t fpu_mode, double fpu_tree, double fpu_root, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_puct: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (!c_table_host) { e->err = "azk_set_puct: c_table_host is null"; return AZK_ERR_ARG; }
+    if (n_table < 1 || n_table > 65536) { e->err = "azk_set_puct: n_table must lie in [1, 65536]"; return AZK_ERR_ARG; }
+    for (int i = 0; i < n_table; i++)
+        if (!(c_table_host[i] >= 0.0) || c_table_host[i] - c_table_host[i] != 0.0) { e->err = "azk_set_puct: every table entry must be finite and not negative"; return AZK_ERR_ARG; }
+    if (fpu_mode < 0 || fpu_mode > 2) { e->err = "azk_set_puct: fpu_mode must be 0 (as the reference), 1 (absolute) or 2 (parent value minus reduction)"; return AZK_ERR_ARG; }
+    if (fpu_tree - fpu_tree != 0.0 || fpu_root - fpu_root != 0.0) { e->err = "azk_set_puct: the FPU parameters must be finite"; return AZK_ERR_ARG; }
+    if (fpu_mode == 2 && (fpu_tree < 0.0 || fpu_root < 0.0)) { e->err = "azk_set_puct: a reduction (fpu_mode 2) must not be negative"; return AZK_ERR_ARG; }
+    if (e->d.K > 1) { e->err = "azk_set_puct: configurable PUCT does not combine with leaves_per_step > 1 (a virtual-loss search leaves losses in the value sums the FPU rule reads)"; return AZK_ERR_ARG; }
+    if (e->forced_k != 0.0) { e->err = "azk_set_puct: forced playouts are set - their pruning bound restates the reference's selection formula"; return AZK_ERR_STATE; }
+    if (e->gb.m) { e->err = "azk_set_puct: a Gumbel root is set - its root selection is not PUCT"; return AZK_ERR_STATE; }
+    if (e->in_search) { e->err = "azk_set_puct: a search is under way - set the option between searches"; return AZK_ERR_STATE; }
+    hipStream_t st = (hipStream_t)stream;
+    double *tab = nullptr;                                           // (a table of its own per call: a captured step graph may still hold the last one)
+    HIPCHK(e, dalloc(e, &tab, (size_t)n_table));
+    HIPCHK(e, hipMemcpyAsync(tab, c_table_host, sizeof(double) * (size_t)n_table, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    e->pu = PuctDev{tab, n_table, fpu_mode, fpu_tree, fpu_root};
+    e->puct_on = true;
+    return AZK_OK;
+}
+
+int32_t azk_clear_puct(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_puct: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    if (e->in_search && e->puct_on) { e->err = "azk_clear_puct: a search is under way - clear the option between searches"; return AZK_ERR_STATE; }
+    e->puct_on = false;                                            // off: the engine launches what it launched before
     return AZK_OK;
 }
 

@@ -1,4 +1,4 @@
-// azk_tree.hip - the AlphaZero search step of the batched self-play engine for MI355X (gfx950): k_tree (all twenty-eight instantiations
+// azk_tree.hip - the AlphaZero search step of the batched self-play engine for MI355X (gfx950): k_tree (all thirty-four instantiations
 // live in this one translation unit), its expanding wave, the leaf gather, and the C ABI calls that launch them (include/azk.h).
 // One 64-lane wavefront owns one game (the plain k_tree gives it a helper wave); the tree is
 // a structure-of-arrays arena in HBM whose child blocks are contiguous, so a PUCT scan is a coalesced read
@@ -246,6 +246,38 @@ __device__ __forceinline__ double tree_gumbel_score(double u, int N, double q, d
     else return u;
 }
 
+// PUCT (configurable PUCT, azk_set_puct): every scan of the walk - all three forms, both precision paths - multiplies the
+// exploration term's sqrt(Np) by c = c_table[min(Np, n_table - 1)] and scores an unvisited child  qf + u0  instead of u0 (fpu_mode 1: qf = f;
+// mode 2: qf = -(Wn / Np) - f * sqrt(vm), Wn the selecting node's value sum, vm the prior mass of its visited children; f = fpu_root at the
+// root, fpu_tree below it).  The table word goes out with the children's loads; the chosen child's W comes down beside its N, meta and fc;
+// the mass is summed in mode 2 only.  Wave 1 never sees any of it.  The factor c and the unvisited child's score are plain statements under
+// `if constexpr (PUCT)` in the body, not helper templates like the two above: a call inside the scan's arithmetic, even one that folds to
+// its argument, reaches the optimiser as other IR and the 28 kernels without the option came out different (tools/compare_kernel_isa.py).
+// What only the PUCT kernels call is below.
+struct TreePuctHook { __device__ __forceinline__ void operator()() const {} };     // (wave 1's move generator: a copy of the PUCT kernels' own)
+// the wave's sum of the lanes' partial masses by the xor butterfly 32, 16, 8, 4, 2, 1 (x = x + partner; every lane ends with the sum).  Behind
+// the steps 32 and 16 the lanes of one index modulo 16 hold the same bits, behind step 8 those of one index modulo 8, so the partner of the last
+// four steps is reached inside the lane's row of 16: row_ror:8 is lane ^ 8, row_ror:4 brings a lane of the class (lane ^ 4) mod 8, and the
+// quad permutes are lane ^ 2 and lane ^ 1 - four DPP adds instead of four more trips through the LDS crossbar.
+template <typename T>
+__device__ __forceinline__ T tree_puct_mass(T part) {
+    part = part + __shfl_xor(part, 32);
+    part = part + __shfl_xor(part, 16);
+    part = part + dpp_val<0x128>(part);                           // row_ror:8
+    part = part + dpp_val<0x124>(part);                           // row_ror:4
+    part = part + dpp_val<0x4E>(part);                            // quad_perm [2,3,0,1]
+    part = part + dpp_val<0xB1>(part);                            // quad_perm [1,0,3,2]
+    return part;
+}
+// mode 2: the selecting node's value for the side that chooses (Node.backup keeps it as the player who moved INTO the node sees it), less the reduction
+__device__ __forceinline__ double tree_puct_qf2(double f, double Wn, int Np, double vm) {
+    const double qn = -(Wn / (double)Np);
+    return qn - f * sqrt(vm);
+}
+__device__ __forceinline__ double tree_readlane_f64(double v, int lane) {
+    return __builtin_bit_cast(double, azk_readlane_u64(__builtin_bit_cast(unsigned long long, v), lane));
+}
+
 // The kernels.  The fourteen instantiations without FORCED keep the name, the arguments and the device code they had before the option
 // existed (tools/compare_kernel_isa.py); the six with it - fused, select-only and MULTI, each at KSL 4 and 7 - take the extra argument block,
 // and so do the eight with GUMBEL (theirs is the GumbelDev block).
@@ -253,9 +285,12 @@ template <bool EXPAND, bool SELECT, bool DBG, bool MULTI = false, int KSL = 7>
 __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd, const float *__restrict__ logits, const float *__restrict__ values) {
     constexpr bool FORCED = false;
     constexpr bool GUMBEL = false;
+    constexpr bool PUCT = false;
 #define AZK_TREE_FORCED_ARG ForcedDev{}
 #define AZK_TREE_GUMBEL_ARG GumbelDev{}
+#define AZK_TREE_PUCT_ARG PuctDev{}
 #include "azk_tree_step.h"
+#undef AZK_TREE_PUCT_ARG
 #undef AZK_TREE_GUMBEL_ARG
 #undef AZK_TREE_FORCED_ARG
 }
@@ -264,9 +299,12 @@ template <bool EXPAND, bool SELECT, bool DBG, bool MULTI, int KSL, bool FORCED>
 __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd, const float *__restrict__ logits, const float *__restrict__ values, ForcedDev fd_arg) {
     static_assert(FORCED && SELECT && !DBG, "FORCED exists for the product kernels that select");
     constexpr bool GUMBEL = false;
+    constexpr bool PUCT = false;
 #define AZK_TREE_FORCED_ARG fd_arg
 #define AZK_TREE_GUMBEL_ARG GumbelDev{}
+#define AZK_TREE_PUCT_ARG PuctDev{}
 #include "azk_tree_step.h"
+#undef AZK_TREE_PUCT_ARG
 #undef AZK_TREE_GUMBEL_ARG
 #undef AZK_TREE_FORCED_ARG
 }
@@ -275,9 +313,25 @@ __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd
 template <bool EXPAND, bool SELECT, bool DBG, bool MULTI, int KSL, bool FORCED, bool GUMBEL>
 __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd, const float *__restrict__ logits, const float *__restrict__ values, GumbelDev gb_arg) {
     static_assert(GUMBEL && !FORCED && !DBG, "GUMBEL exists for the product kernels, without forced playouts");
+    constexpr bool PUCT = false;
 #define AZK_TREE_FORCED_ARG ForcedDev{}
 #define AZK_TREE_GUMBEL_ARG gb_arg
+#define AZK_TREE_PUCT_ARG PuctDev{}
 #include "azk_tree_step.h"
+#undef AZK_TREE_PUCT_ARG
+#undef AZK_TREE_GUMBEL_ARG
+#undef AZK_TREE_FORCED_ARG
+}
+
+// the six PUCT kernels: fused, select-only and MULTI, each at KSL 4 and 7 (an expand-only launch selects nothing: the plain kernel)
+template <bool EXPAND, bool SELECT, bool DBG, bool MULTI, int KSL, bool FORCED, bool GUMBEL, bool PUCT>
+__global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd, const float *__restrict__ logits, const float *__restrict__ values, PuctDev pu_arg) {
+    static_assert(PUCT && !FORCED && !GUMBEL && SELECT && !DBG, "PUCT exists for the product kernels that select, without forced playouts or a Gumbel root");
+#define AZK_TREE_FORCED_ARG ForcedDev{}
+#define AZK_TREE_GUMBEL_ARG GumbelDev{}
+#define AZK_TREE_PUCT_ARG pu_arg
+#include "azk_tree_step.h"
+#undef AZK_TREE_PUCT_ARG
 #undef AZK_TREE_GUMBEL_ARG
 #undef AZK_TREE_FORCED_ARG
 }
@@ -351,7 +405,15 @@ static void launch_k_tree_gumbel(const Dev &d, const float *logits, const float 
     else k_tree<E, S, false, M, 7, false, true><<<d.G, nthr, d.lds_bytes, st>>>(d, logits, values, gb);
 }
 
-// The one place that picks a k_tree instantiation: seven (EXPAND, SELECT, DBG, MULTI) forms, three FORCED ones and four GUMBEL ones, each at KSL 4 and 7.
+template <bool E, bool M>                                             // configurable PUCT: the selecting product kernels
+static void launch_k_tree_puct(const Dev &d, const float *logits, const float *values, const PuctDev &pu, hipStream_t st) {
+    const int nthr = M ? AZK_WAVE : 2 * AZK_WAVE;
+    if (d.g.rc <= 4 * AZK_WAVE && d.g.action_dim <= 4 * AZK_WAVE) k_tree<E, true, false, M, 4, false, false, true><<<d.G, nthr, d.lds_bytes, st>>>(d, logits, values, pu);
+    else k_tree<E, true, false, M, 7, false, false, true><<<d.G, nthr, d.lds_bytes, st>>>(d, logits, values, pu);
+}
+
+// The one place that picks a k_tree instantiation: seven (EXPAND, SELECT, DBG, MULTI) forms, three FORCED ones, four GUMBEL ones and three PUCT ones, each at
+// KSL 4 and 7.
 //   multi   the caller wants budget stepping.  The lock-step entry points pass `e->multi && !d.ablate` - an ablation build
 //           (AZK_TREE_ABLATE) never runs MULTI from them; azk_async_step passes true and has never looked at the ablation word.
 //           MULTI exists only with SELECT: budget stepping with `select` always launches <true, true, false, true>, whatever
@@ -362,6 +424,8 @@ static void launch_k_tree_gumbel(const Dev &d, const float *logits, const float 
 //           expand-only launches and an ablation build's DBG kernels are the plain ones (no selection / debug only).
 //   GUMBEL  an engine with a Gumbel root set (e->gb.m != 0; never together with FORCED) launches the GUMBEL sibling of every product kernel,
 //           the expand-only one included; an ablation build's DBG kernels are the plain ones.
+//   PUCT    an engine with configurable PUCT set (e->puct_on; never together with FORCED or GUMBEL) launches the PUCT sibling of whichever
+//           product kernel selects; its expand-only launches and an ablation build's DBG kernels are the plain ones.
 //   symmetry  an engine with azk_set_eval_symmetry on expands from ITS copy of the rows, turned back into each position's frame by
 //           k_sym_logits in front of the launch (the kernel is the same, it is handed another pointer); the callers run azk_sym_leaves
 //           behind a launch that selects.
@@ -370,6 +434,7 @@ int32_t azk_launch_tree(azk_engine *e, bool expand, bool select, bool multi, con
     if (expand || (multi && select)) logits = azk_sym_restore(e, logits, st);
     const bool forced = e->forced_k != 0.0 && select && (multi || !d.ablate);
     const bool gumbel = e->gb.m != 0 && (multi || !d.ablate);
+    const bool puct = e->puct_on && select && (multi || !d.ablate);
     if (gumbel && multi && select) launch_k_tree_gumbel<true, true, true>(d, logits, values, e->gb, st);
     else if (gumbel && expand && select) launch_k_tree_gumbel<true, true, false>(d, logits, values, e->gb, st);
     else if (gumbel && expand) launch_k_tree_gumbel<true, false, false>(d, logits, values, e->gb, st);
@@ -377,6 +442,9 @@ int32_t azk_launch_tree(azk_engine *e, bool expand, bool select, bool multi, con
     else if (forced && multi) launch_k_tree_forced<true, true>(d, logits, values, e->forced(), st);
     else if (forced && expand) launch_k_tree_forced<true, false>(d, logits, values, e->forced(), st);
     else if (forced) launch_k_tree_forced<false, false>(d, logits, values, e->forced(), st);
+    else if (puct && multi) launch_k_tree_puct<true, true>(d, logits, values, e->pu, st);
+    else if (puct && expand) launch_k_tree_puct<true, false>(d, logits, values, e->pu, st);
+    else if (puct) launch_k_tree_puct<false, false>(d, logits, values, e->pu, st);
     else if (multi && select) launch_k_tree<true, true, false, true>(d, logits, values, st);
     else if (d.ablate) {
         if (expand && select) launch_k_tree<true, true, true, false>(d, logits, values, st);

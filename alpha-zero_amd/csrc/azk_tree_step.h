@@ -3,7 +3,8 @@
 // existed - a body shared through a __forceinline__ function does not (the inliner hands the scheduler another instruction order;
 // tools/compare_kernel_isa.py), the same text compiled in place does.  In scope here: the template parameters EXPAND, SELECT, DBG, MULTI,
 // KSL, a constant FORCED, the kernel arguments dd, logits, values, and AZK_TREE_FORCED_ARG = the ForcedDev block (read under FORCED only);
-// a constant GUMBEL and AZK_TREE_GUMBEL_ARG = the GumbelDev block (read under GUMBEL only), the third overload's.
+// a constant GUMBEL and AZK_TREE_GUMBEL_ARG = the GumbelDev block (read under GUMBEL only), the third overload's;
+// a constant PUCT and AZK_TREE_PUCT_ARG = the PuctDev block (read under PUCT only), the fourth overload's.
     const Dev &d = dd;
     const int ablate = DBG ? dd.ablate : 0;
     const int g = blockIdx.x;
@@ -21,6 +22,7 @@
             if constexpr (EXPAND) {
                 if constexpr (GUMBEL) tree_expand_wave<DBG, KSL, TreeGumbelHook>(d, L, logits, values, ablate, AZK_TREE_GUMBEL_ARG);
                 else if constexpr (FORCED) tree_expand_wave<DBG, KSL, TreeForcedHook>(d, L, logits, values, ablate);
+                else if constexpr (PUCT) tree_expand_wave<DBG, KSL, TreePuctHook>(d, L, logits, values, ablate);
                 else tree_expand_wave<DBG, KSL>(d, L, logits, values, ablate);
             }
             // every store above has been acknowledged and the hand-off words are in LDS before the barrier (the workgroup-scope
@@ -108,6 +110,9 @@
         r_fc = SELECT ? d.H[base].fc : -1; r_N = SELECT ? d.H[base].N : 0;
         r_meta = SELECT ? d.H[base].meta : 0u;
     }
+    double r_W = 0.0;                                        // PUCT: the root's value sum, beside its N (mode 2's qn at the root)
+    bool r_W_stale = false;                                  // ... a long path's backup went through memory: read it again behind it
+    if constexpr (PUCT) r_W = d.W[base];
     unsigned long long e_key = 0ull;
     if (EXPAND && MULTI && shared) e_key = d.leaf_key[(size_t)vi * d.key_words + min(lane, d.key_words - 1)];
     // (every per-lane load below is UNCONDITIONAL with a clamped index: a load under a lane predicate - `lane < n ? p[lane] : 0` -
@@ -167,14 +172,17 @@
                     d.H[base + e_path].N = nN;
                     d.W[base + e_path] = nW;
                 }
+                if constexpr (PUCT) r_W = tree_readlane_f64(nW, 0);   // (trace node 0 is the root: lane 0 holds its new sum)
             } else {
                 backup_path(d, base, d.path + (size_t)vi * d.path_cap, depth, v, false);
+                if constexpr (PUCT) r_W_stale = true;
             }
             r_N += 1;                                                 // the root is trace node 0 of every simulation
             if (lane == 0) count_add(d, CNT_TRACE, g, depth + 1);
             // (leaf_node = -1 waits until the barrier is behind this wave: wave 1 reads the word at ITS entry)
         }
         azk_wave_sync();   // this wave's tree writes are visible to its own SELECT reads below
+        if constexpr (PUCT) { if (r_W_stale) r_W = d.W[base]; }
     }
     if constexpr (EXPAND && MULTI) {
         const int node = uniform_i32(e_node);
@@ -303,8 +311,10 @@
                     d.H[base + e_path].N = nN;
                     d.W[base + e_path] = nW;
                 }
+                if constexpr (PUCT) r_W = tree_readlane_f64(nW, 0);   // (trace node 0 is the root: lane 0 holds its new sum)
             } else {
                 backup_path(d, base, d.path + (size_t)vi * d.path_cap, depth, v, vl);
+                if constexpr (PUCT) r_W_stale = true;
             }
             if (!vl) r_N += 1;                                        // the root is trace node 0 of every simulation
             if (xst && lane == 0) {
@@ -318,6 +328,7 @@
             }
         }
         azk_wave_sync();   // this wave's tree writes are visible to its own SELECT reads below
+        if constexpr (PUCT) { if (r_W_stale) r_W = d.W[base]; }
     }
 
     if (SELECT) {
@@ -344,6 +355,7 @@
         uint32_t nmeta = (uint32_t)uniform_i32((int)r_meta);
         int node_cell = -1;
         bool root_f64 = uniform_i32(s_rootf64) != 0;
+        double Wn = r_W;                                              // PUCT: the current node's value sum, carried like Np
         long long seg_a = 0, seg_b = 0, seg_c = 0, seg_d = 0, seg_t = 0;      // debug only (ablate & 64)
         for (;;) {                                                    // mcts.py:20-23
             if (TWO && EXPAND && node == prev_leaf && !joined) {
@@ -369,6 +381,15 @@
                     gsig = (gb.c_visit + (double)gcv) * gb.c_scale;
                 }
             }
+            double pc = 1.0, qf = 0.0;                                // PUCT: c at this node's Np; an unvisited child's value (until mode 2 has it: the level's FPU parameter)
+            int pmode = 0;
+            if constexpr (PUCT) {                                     // (a uniform word of Np: its load goes out with the children's)
+                const PuctDev &pu = AZK_TREE_PUCT_ARG;
+                pc = pu.c_table[min(Np, pu.n_table - 1)];
+                qf = node == 0 ? pu.fpu_root : pu.fpu_tree;           // mode 1 as it stands; mode 2 needs the children first (each scan form below); mode 0 never reads it
+                pmode = pu.fpu_mode;
+            }
+            double bW = 0.0;                                          // PUCT: the winner's value sum, beside bN
             double bu64 = 0.0;
             float bu32 = 0.f;
             int best = 0x7fffffff, bN = 0, bfc = -1;
@@ -387,23 +408,32 @@
                 unsigned long long winners;
                 if (f64) {                                            // root after Dirichlet mixing: float64 priors => float64 UCB
                     const double P64 = d.rootP[(size_t)g * rc + (valid ? lane : 0)];
-                    const double s = sqrt((double)Np);
+                    if constexpr (PUCT) { if (pmode == 2) qf = tree_puct_qf2(qf, Wn, Np, tree_puct_mass((valid & (Nc > 0)) ? P64 : 0.0)); }
+                    double s = sqrt((double)Np);
+                    if constexpr (PUCT) s = pc * s;
                     const double u0 = P64 * s / (double)(Nc + 1);
                     const double q = Wc / (double)Nc;                 // N = 0: inf/nan, discarded by the select
-                    const double u = valid ? tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc != 0 ? q + u0 : u0, Nc, P64, fk, Np), Nc, q, P64, gcv, gsig) : -__builtin_huge_val();
+                    double un = u0;                                   // an unvisited child's score (plain text, no helper call: see the head of this file)
+                    if constexpr (PUCT) un = pmode != 0 ? qf + u0 : u0;
+                    const double u = valid ? tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc != 0 ? q + u0 : un, Nc, P64, fk, Np), Nc, q, P64, gcv, gsig) : -__builtin_huge_val();
                     const double um = wave_max_f64(u);               // (all lanes take part: never under the short-circuit below)
                     winners = __ballot(valid & (u == um));
                     if constexpr (FORCED) forced_sel = um == __builtin_huge_val();
                 } else {                                              // float32 priors => float32 UCB (numpy >= 2)
-                    const float s = (float)sqrt((double)Np);
+                    if constexpr (PUCT) { if (pmode == 2) qf = tree_puct_qf2(qf, Wn, Np, (double)tree_puct_mass((valid & (Nc > 0)) ? P32 : 0.f)); }
+                    float s = (float)sqrt((double)Np);
+                    if constexpr (PUCT) s = (float)(pc * sqrt((double)Np));
                     const float u0 = (P32 * s) / (float)(Nc + 1);
                     const float q = (float)(Wc / (double)Nc);
-                    const float u = valid ? (Nc != 0 ? q + u0 : u0) : -__builtin_huge_valf();
+                    float un = u0;
+                    if constexpr (PUCT) un = pmode != 0 ? (float)qf + u0 : u0;
+                    const float u = valid ? (Nc != 0 ? q + u0 : un) : -__builtin_huge_valf();
                     const float um = wave_max_f32(u);
                     winners = __ballot(valid & (u == um));
                 }
                 best = __ffsll((long long)winners) - 1;
                 bN = Nc; bmeta = mc; bfc = fcc;
+                if constexpr (PUCT) bW = Wc;
             } else if (nch <= 2 * AZK_WAVE && !(ablate & 2048)) {
                 // 65 .. 128 candidates (late plies: every node of the tree): two per lane, the same straight-line shape - ten loads,
                 // one round trip.  (The general loop below sinks its prior loads into per-slot branches: one more round trip per
@@ -418,27 +448,62 @@
                 unsigned long long wa, wb;
                 if (f64) {
                     const double Qa = d.rootP[(size_t)g * rc + lane], Qb = d.rootP[(size_t)g * rc + (vb ? lane + AZK_WAVE : 0)];
-                    const double s = sqrt((double)Np);
+                    if constexpr (PUCT) {
+                        if (pmode == 2) {                             // (list order inside the lane: child `lane`, then child `lane + 64`)
+                            double part = Na > 0 ? Qa : 0.0;
+                            part = (vb & (Nb > 0)) ? part + Qb : part;
+                            qf = tree_puct_qf2(qf, Wn, Np, tree_puct_mass(part));
+                        }
+                    }
+                    double s = sqrt((double)Np);
+                    if constexpr (PUCT) s = pc * s;
                     const double u0a = Qa * s / (double)(Na + 1), u0b = Qb * s / (double)(Nb + 1);
                     const double qa = Wa / (double)Na, qb = Wb / (double)Nb;
-                    const double ua = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Na != 0 ? qa + u0a : u0a, Na, Qa, fk, Np), Na, qa, Qa, gcv, gsig);
-                    const double ub = vb ? tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nb != 0 ? qb + u0b : u0b, Nb, Qb, fk, Np), Nb, qb, Qb, gcv, gsig) : -__builtin_huge_val();
+                    double una = u0a, unb = u0b;
+                    if constexpr (PUCT) { una = pmode != 0 ? qf + u0a : u0a; unb = pmode != 0 ? qf + u0b : u0b; }
+                    const double ua = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Na != 0 ? qa + u0a : una, Na, Qa, fk, Np), Na, qa, Qa, gcv, gsig);
+                    const double ub = vb ? tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nb != 0 ? qb + u0b : unb, Nb, Qb, fk, Np), Nb, qb, Qb, gcv, gsig) : -__builtin_huge_val();
                     const double um = wave_max_f64(fmax(ua, ub));
                     wa = __ballot(va & (ua == um)); wb = __ballot(vb & (ub == um));
                     if constexpr (FORCED) forced_sel = um == __builtin_huge_val();
                 } else {
-                    const float s = (float)sqrt((double)Np);
+                    if constexpr (PUCT) {
+                        if (pmode == 2) {
+                            float part = Na > 0 ? Pa : 0.f;
+                            part = (vb & (Nb > 0)) ? part + Pb : part;
+                            qf = tree_puct_qf2(qf, Wn, Np, (double)tree_puct_mass(part));
+                        }
+                    }
+                    float s = (float)sqrt((double)Np);
+                    if constexpr (PUCT) s = (float)(pc * sqrt((double)Np));
                     const float u0a = (Pa * s) / (float)(Na + 1), u0b = (Pb * s) / (float)(Nb + 1);
                     const float qa = (float)(Wa / (double)Na), qb = (float)(Wb / (double)Nb);
-                    const float ua = Na != 0 ? qa + u0a : u0a;
-                    const float ub = vb ? (Nb != 0 ? qb + u0b : u0b) : -__builtin_huge_valf();
+                    float una = u0a, unb = u0b;
+                    if constexpr (PUCT) { una = pmode != 0 ? (float)qf + u0a : u0a; unb = pmode != 0 ? (float)qf + u0b : u0b; }
+                    const float ua = Na != 0 ? qa + u0a : una;
+                    const float ub = vb ? (Nb != 0 ? qb + u0b : unb) : -__builtin_huge_valf();
                     const float um = wave_max_f32(fmaxf(ua, ub));
                     wa = __ballot(va & (ua == um)); wb = __ballot(vb & (ub == um));
                 }
                 const bool first = wa != 0ull;
                 best = first ? __ffsll((long long)wa) - 1 : AZK_WAVE + __ffsll((long long)wb) - 1;
                 bN = first ? Na : Nb; bmeta = first ? ma : mb; bfc = first ? fa : fb;
+                if constexpr (PUCT) bW = first ? Wa : Wb;
             } else {
+            if constexpr (PUCT) {
+                // mode 2 over more than one chunk (a board beyond 256 cells): the mass is needed before the first child is scored, so it takes
+                // a pass of its own over (N, P) - one more round trip on such a level; a single chunk sums the registers it has loaded anyway
+                if (pmode == 2 && nch > 4 * AZK_WAVE) {
+                    double p64 = 0.0;
+                    float p32 = 0.f;
+                    for (int i = lane; i < nch; i += AZK_WAVE) {
+                        const NodeH hk = d.H[base + fc + i];
+                        if (f64) { const double P = d.rootP[(size_t)g * rc + i]; p64 = hk.N > 0 ? p64 + P : p64; }
+                        else p32 = hk.N > 0 ? p32 + hk.P : p32;
+                    }
+                    qf = tree_puct_qf2(qf, Wn, Np, f64 ? tree_puct_mass(p64) : (double)tree_puct_mass(p32));
+                }
+            }
             // all of this level's loads are issued before any arithmetic: 4 candidates per lane per 256-child chunk
             for (int c0 = 0; c0 < nch; c0 += 4 * AZK_WAVE) {
                 int Nc[4], fcc[4];
@@ -469,31 +534,51 @@
                 }
                 // branch-free on purpose: every `if` around a division or a compare chain becomes a saveexec/branch pair on
                 // this target, and a level of the walk is a few hundred cycles of arithmetic buried under thousands of those
+                if constexpr (PUCT) {
+                    if (pmode == 2 && nch <= 4 * AZK_WAVE) {          // the one chunk: list order inside the lane is k = 0, 1, 2, 3
+                        double p64 = 0.0;
+                        float p32 = 0.f;
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            const bool in = (lane + AZK_WAVE * k < nch) & (Nc[k] > 0);
+                            p64 = in ? p64 + P64[k] : p64; p32 = in ? p32 + P32[k] : p32;
+                        }
+                        qf = tree_puct_qf2(qf, Wn, Np, f64 ? tree_puct_mass(p64) : (double)tree_puct_mass(p32));
+                    }
+                }
                 if (f64) {                                            // float64 priors => float64 UCB
-                    const double s = sqrt((double)Np);
+                    double s = sqrt((double)Np);
+                    if constexpr (PUCT) s = pc * s;
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
                         if (c0 + AZK_WAVE * k >= nch) break;             // wave-uniform: no candidate in this slot at all
                         const int i = c0 + lane + AZK_WAVE * k;
                         const double u0 = P64[k] * s / (double)(Nc[k] + 1);
                         const double q = Wc[k] / (double)Nc[k];          // N = 0: inf/nan, discarded by the select below
-                        const double u = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc[k] != 0 ? q + u0 : u0, Nc[k], P64[k], fk, Np), Nc[k], q, P64[k], gcv, gsig);
+                        double un = u0;
+                        if constexpr (PUCT) un = pmode != 0 ? qf + u0 : u0;
+                        const double u = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc[k] != 0 ? q + u0 : un, Nc[k], P64[k], fk, Np), Nc[k], q, P64[k], gcv, gsig);
                         const bool take = (i < nch) & ((best == 0x7fffffff) | (u > bu64));
                         bu64 = take ? u : bu64; best = take ? i : best; bN = take ? Nc[k] : bN;
                         bmeta = take ? mc[k] : bmeta; bfc = take ? fcc[k] : bfc;
+                        if constexpr (PUCT) bW = take ? Wc[k] : bW;
                     }
                 } else {                                              // float32 priors => float32 UCB (numpy>=2)
-                    const float s = (float)sqrt((double)Np);
+                    float s = (float)sqrt((double)Np);
+                    if constexpr (PUCT) s = (float)(pc * sqrt((double)Np));
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
                         if (c0 + AZK_WAVE * k >= nch) break;             // wave-uniform: no candidate in this slot at all
                         const int i = c0 + lane + AZK_WAVE * k;
                         const float u0 = (P32[k] * s) / (float)(Nc[k] + 1);
                         const float q = (float)(Wc[k] / (double)Nc[k]);  // N = 0: inf/nan, discarded by the select below
-                        const float u = Nc[k] != 0 ? q + u0 : u0;
+                        float un = u0;
+                        if constexpr (PUCT) un = pmode != 0 ? (float)qf + u0 : u0;
+                        const float u = Nc[k] != 0 ? q + u0 : un;
                         const bool take = (i < nch) & ((best == 0x7fffffff) | (u > bu32));
                         bu32 = take ? u : bu32; best = take ? i : best; bN = take ? Nc[k] : bN;
                         bmeta = take ? mc[k] : bmeta; bfc = take ? fcc[k] : bfc;
+                        if constexpr (PUCT) bW = take ? Wc[k] : bW;
                     }
                 }
             }
@@ -510,6 +595,7 @@
             Np = __builtin_amdgcn_readlane(bN, wl);
             nmeta = (uint32_t)__builtin_amdgcn_readlane((int)bmeta, wl);
             fc = __builtin_amdgcn_readlane(bfc, wl);
+            if constexpr (PUCT) Wn = tree_readlane_f64(bW, wl);
             if (ablate & 64) { const long long tn = clock64(); seg_c += tn - seg_t; seg_t = tn; }
             const int cellc = meta_cell(nmeta);
             const int mover = (root_player + depth) & 1;

@@ -8,12 +8,30 @@ self_play_batch returns, per game, the tuple the reference's Gomoku.self_play re
 (boards, actions, policy_distributions, qs, winner) so train.collect_data's consumer
 (train.save_data_to_buffer, train.py:30-49) can take it unchanged.
 """
+import contextlib
+import gc
+
 import numpy as np
 
-from azk import Engine, board_elements, emit_mask
+from azk import Engine, board_elements, emit_mask, puct_setting, puct_table  # noqa: F401  (puct_table: the public helper behind puct=((c_init, c_base), ...))
 
 # gomoku.py:144 samples while move_count < 8; tictactoe.py:117 / connect4.py:135 sample every move
 SAMPLE_UNTIL = {"gomoku": 8, "tictactoe": 1 << 30, "connect4": 1 << 30}
+
+
+@contextlib.contextmanager
+def capture_without_finalisers():
+    """Around a hipGraph capture: no finaliser may run inside it.  An Engine that a dead reference cycle keeps alive (a runner and the
+    closure it reports to) is destroyed whenever Python's cyclic collector next runs, and azk_destroy's hipFree inside a capture invalidates
+    the capture (torch.cuda.graph no longer collects before it begins).  So: collect now, and keep the collector off until the capture ends."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 def cells_to_board(cells, planes, rows, cols, side_to_move):
@@ -137,6 +155,31 @@ def check_gumbel_root(gumbel_root, n_sims=None, evaluator=True, dirichlet=True, 
     if surprise_weight is not None:
         raise ValueError("gumbel_root does not combine with surprise_weight (its recorded pi is not a visit distribution)")
     return m, c_visit, c_scale
+
+
+def check_puct(puct, evaluator=True, leaves_per_step=1, forced_playouts=None, gumbel_root=None):
+    """puct = (c, fpu) -> the (c_table, fpu_mode, fpu_tree, fpu_root) of azk_set_puct, or None for off.  OPT-IN configurable PUCT (include/azk.h
+    azk_set_puct): c is a number, a tuple (c_init, c_base) (puct_table) or a list of table entries indexed by the selecting
+    node's visit count; fpu is None, ("absolute", v_tree[, v_root]) or ("reduction", r_tree[, r_root]).  Raises ValueError, before any engine
+    exists, for what the engine refuses too - a table that is empty, too long or holds a negative or non-finite entry, an unknown FPU kind, a
+    non-finite FPU parameter, a negative reduction, virtual loss, forced playouts, a Gumbel root - and for vanilla MCTS (evaluator None), whose
+    UCB1 the option does not cover."""
+    if puct is None:
+        return None
+    try:
+        c, fpu = puct
+    except (TypeError, ValueError):
+        raise ValueError(f"puct must be (c, fpu), not {puct!r}")
+    setting = puct_setting(c, fpu)
+    if _is_vanilla(evaluator):
+        raise ValueError("puct: vanilla MCTS (evaluator None) is refused - it selects by UCB1, which the option does not cover")
+    if int(leaves_per_step) > 1:
+        raise ValueError("puct does not combine with leaves_per_step > 1 (a virtual-loss search leaves losses in the value sums the FPU rule reads)")
+    if forced_playouts:
+        raise ValueError("puct does not combine with forced_playouts (the pruning bound restates the reference's selection formula)")
+    if gumbel_root is not None:
+        raise ValueError("puct does not combine with gumbel_root (its root selection is not PUCT)")
+    return setting
 
 
 def eval_symmetry_elements(game, size=None):
@@ -309,7 +352,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
                     budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
                     eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None,
-                    openings_first_game=None):
+                    openings_first_game=None, puct=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -339,7 +382,10 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     SelfPlayResult.opening holds their cells in order, boards[0] is the position after them, and a replay ring does not get them.  With an
     (evaluator0, evaluator1) pair the games of the batch are no longer at one ply, so the pair is told apart per game: every leaf of a game
     whose root has player p to move is evaluated by evaluator p (both run over the step's batch, Engine.leaf_flags says which game a row
-    belongs to); the two sides then search the same number of simulations (ValueError otherwise).
+    belongs to); the two sides then search the same number of simulations (ValueError otherwise).  puct = (c, fpu) (OPT-IN, check_puct):
+    every selection of every network search scores a child with the exploration rate c - a number, a tuple (c_init, c_base) or a table over
+    the selecting node's visit count - and an unvisited child by the first-play urgency fpu (None, ("absolute", v_tree[, v_root]) or
+    ("reduction", r_tree[, r_root])); with an (evaluator0, evaluator1) pair both sides search under it.
     """
     import torch
     opn = check_openings(openings, game, size, evaluator)
@@ -356,6 +402,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     sym = check_eval_symmetry(eval_symmetry, game, size, evaluator, leaves_per_step, seed)
     lam = check_surprise_weight(surprise_weight, evaluator, leaves_per_step)
     gum = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, cap, fpk, lam)
+    pct = puct if check_puct(puct, evaluator, leaves_per_step, fpk, gum) is not None else None
     _refuse_vanilla_resign(rsg, evaluator)
     if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
@@ -375,6 +422,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         eng.set_surprise_weighting(lam, seed, first_global_game)
     if gum is not None:
         eng.set_gumbel_root(gum[0], n_sims, gum[1], gum[2])
+    if pct is not None:
+        eng.set_puct(*pct)
     # virtual-loss, top-up and capped engines are driven by the simulation budget
     budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
     assert eng.G == n_games
@@ -601,6 +650,10 @@ class SelfPlayRunner:
     every recycled one - is, with that probability, played forward a few drawn plies before its first search (Engine.open_pending, outside the
     captured graphs), keyed (openings_seed or seed, (openings_first_game or first_global_game) + slot, the move counter of that search).  Records
     start at the first searched ply; the replay ring does not get the opening's plies; finished_plies counts them, plies_played does not.
+
+    puct = (c, fpu) (OPT-IN, check_puct; with everything above except forced_playouts and gumbel_root): every selection of every search uses
+    the exploration rate c (a number, a tuple (c_init, c_base), or a table over the selecting node's visit count) and the first-play urgency
+    fpu (None, ("absolute", v_tree[, v_root]) or ("reduction", r_tree[, r_root])); set at construction, before any graph is captured.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
@@ -608,11 +661,12 @@ class SelfPlayRunner:
                  use_graph=False, n_split=1, replay=None, cache_entries=0, cache_shared=False, budget_stepping=False, per_launch=8,
                  steps_per_graph=32,
                  leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None,
-                 surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None, openings_first_game=None):
+                 surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None, openings_first_game=None, puct=None):
         import torch
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, playout_cap, forced_playouts,
                                              surprise_weight)
+        self.puct = puct if check_puct(puct, evaluator, leaves_per_step, forced_playouts, gumbel_root) is not None else None
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
         self.surprise_weight = check_surprise_weight(surprise_weight, evaluator, leaves_per_step)
         self.record_surprise = None
@@ -669,6 +723,8 @@ class SelfPlayRunner:
                 h.eng.set_surprise_weighting(self.surprise_weight, seed, first_global_game + i * per)
             if self.gumbel_root is not None:
                 h.eng.set_gumbel_root(self.gumbel_root[0], n_sims, self.gumbel_root[1], self.gumbel_root[2])
+            if self.puct is not None:
+                h.eng.set_puct(*self.puct)
             if self.openings is not None:                         # the first games, under the key of their first search (move 0)
                 h.eng.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                                    (first_global_game if openings_first_game is None else openings_first_game) + i * per)
@@ -806,14 +862,14 @@ class SelfPlayRunner:
             self._graph, self._graph_many = [], []
             for h in self.halves:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with capture_without_finalisers(), torch.cuda.graph(g):
                     self._step_body(h)
                 self._graph.append(g)
                 if self.steps_per_graph > 1:
                     # the same step `steps_per_graph` times in one graph: consecutive graph launches leave the GPU idle for ~8 us
                     # (rocprofv3 kernel trace: gap before k_tree), consecutive kernels of one graph do not
                     gm = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gm):
+                    with capture_without_finalisers(), torch.cuda.graph(gm):
                         for _ in range(self.steps_per_graph):
                             self._step_body(h)
                     self._graph_many.append(gm)
@@ -952,16 +1008,20 @@ class AsyncSelfPlayRunner:
     make Dirichlet rows, play the survivor and record the Gumbel target.  n_sims is fixed for the run.
 
     openings = (p_open, max_plies, spread) (OPT-IN, check_openings; with everything above): the games of SelfPlayRunner(openings=...), slot for
-    slot - the first games are opened inside async_begin, a restarted game inside the drain's restart kernel, under the slot's move counter."""
+    slot - the first games are opened inside async_begin, a restarted game inside the drain's restart kernel, under the slot's move counter.
+
+    puct = (c, fpu) (OPT-IN, check_puct; with everything above except forced_playouts and gumbel_root): the games of SelfPlayRunner(puct=...),
+    slot for slot - the rule reads only what the tree stores, so the movers and the re-root need nothing of it."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
                  playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None,
-                 openings=None, openings_seed=None, openings_first_game=None):
+                 openings=None, openings_seed=None, openings_first_game=None, puct=None):
         import torch
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, 1, tree_reuse or reroot, playout_cap, forced_playouts, surprise_weight)
+        self.puct = puct if check_puct(puct, evaluator, 1, forced_playouts, gumbel_root) is not None else None
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
         self.surprise_weight = check_surprise_weight(surprise_weight, evaluator)
         self.record_surprise = None
@@ -1000,6 +1060,8 @@ class AsyncSelfPlayRunner:
             e.set_surprise_weighting(self.surprise_weight, seed, first_global_game)
         if self.gumbel_root is not None:
             e.set_gumbel_root(self.gumbel_root[0], n_sims, self.gumbel_root[1], self.gumbel_root[2])
+        if self.puct is not None:
+            e.set_puct(*self.puct)
         if self.openings is not None:                             # async_begin opens the first games, the drain's restart every later one
             e.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                            first_global_game if openings_first_game is None else openings_first_game)
@@ -1054,7 +1116,7 @@ class AsyncSelfPlayRunner:
         torch.cuda.synchronize()
         self.launches += 3
         self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
+        with capture_without_finalisers(), torch.cuda.graph(self._graph):
             for _ in range(self.steps_per_graph):
                 self._step_body()
 

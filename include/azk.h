@@ -430,6 +430,41 @@ int32_t azk_clear_gumbel_root(azk_engine *e);
 int32_t azk_gen_gumbel(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double *gumbel_dev, void *stream);
 int32_t azk_gen_gumbel_uniforms(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double *uniforms_dev, void *stream);
 
+/* ---- configurable PUCT: exploration-rate schedule and first-play urgency (OPT-IN; off, the engine launches exactly the kernels it launched
+ * before).  The reference scores a child  Q + P * sqrt(Np) / (N + 1)  with no constant, and an unvisited child as if its Q were 0
+ * (utils.calcUcbOfChildrenFromParent).  With the option the selecting product kernels have PUCT siblings that follow this rule (DESIGN
+ * section 26):
+ *   state      c_table    float64 [n_table], 1 <= n_table <= 65536, built by the host (AlphaZero's log((1 + N + c_base) / c_base) + c_init is a
+ *                         table the caller fills; no device log).
+ *              fpu_mode   0 as the reference, 1 absolute, 2 the selecting node's value minus a reduction.
+ *              fpu_tree, fpu_root   the value (mode 1) or the reduction r >= 0 (mode 2); fpu_root at the root, fpu_tree below it.
+ *   per level  selection at a node of Np visits (>= 1 whenever it has children) and value sum Wn:
+ *                  c = c_table[min(Np, n_table - 1)];   f = the node is the root ? fpu_root : fpu_tree
+ *                  mode 1: qf = f.   mode 2: qn = -(Wn / (double)Np)  (the node's value for the side that chooses here: Node.backup keeps the
+ *                  sum as the player who moved INTO the node sees it);  qf = qn - f * sqrt((double)vm).
+ *              vm = the prior mass of the node's visited children, the sum of P over the children with N > 0, in a fixed order: lane l of the
+ *              wave adds its children l, l + 64, .. in list order starting from 0, then the 64 partial sums are combined by the xor butterfly
+ *              32, 16, 8, 4, 2, 1 as x = x + partner.  On the float64 root path P is the root's mixed float64 prior and the sum is float64;
+ *              elsewhere P is the float32 prior and the sum is float32, widened afterwards.
+ *   score      of a child (N, W, P).  Float64 root path (a root that got noise rows):
+ *                  s = c * sqrt((double)Np);   u0 = P * s / (double)(N + 1);   visited: W / (double)N + u0;   unvisited: mode 0 ? u0 : qf + u0
+ *              Float32 path (everything else):
+ *                  s = (float)(c * sqrt((double)Np));   u0 = (P * s) / (float)(N + 1);   visited: (float)(W / (double)N) + u0;
+ *                  unvisited: mode 0 ? u0 : (float)qf + u0
+ *              The first maximum wins, in all three forms of the scan.  c_table = {1.0} with mode 0 is the reference's formula bit for bit.
+ *   stateless  the rule reads nothing the tree does not store already: it holds on a re-rooted tree, under budget stepping and in the
+ *              asynchronous movers as it stands.  Expansion, backup, the root's noise weight (0.25), the movers and the evaluator are untouched.
+ * azk_set_puct copies the table to device memory (a table of its own per call; nothing is allocated while the option was never set).
+ * AZK_ERR_ARG: a null table, n_table outside [1, 65536], a table entry that is negative, NaN or infinite, a mode outside 0..2, a non-finite
+ * FPU parameter, a negative reduction in mode 2, an engine with leaves_per_step > 1.  AZK_ERR_STATE: with forced playouts (the pruning bound
+ * restates the selection formula) or a Gumbel root set - azk_set_forced_playouts and azk_set_gumbel_root refuse likewise while the option is
+ * set; between the begin of a search and the call that ends it (a move, new positions or a reset); after azk_async_begin; and
+ * azk_vanilla_search while the option is set (vanilla UCB1 is not covered).  azk_clear_puct switches the option off, under the same two state
+ * rules.  Combines with tree reuse, a playout cap, resignation, evaluation symmetry, emit_elements, surprise weighting, random openings, the
+ * eval cache in every mode, plain and budget stepping and the asynchronous movers with and without re-rooting. */
+int32_t azk_set_puct(azk_engine *e, const double *c_table_host, int32_t n_table, int32_t fpu_mode, double fpu_tree, double fpu_root, void *stream);
+int32_t azk_clear_puct(azk_engine *e);
+
 /* ---- random openings (OPT-IN; off, the engine launches exactly the kernels it launched before).  Every game otherwise starts from the
  * empty board and differs from its neighbours only through root noise and move sampling; with the option a game that starts in slot g is,
  * with probability p_open, played forward 1..max_plies uniformly drawn legal plies inside a centred window before its first search (KataGo's

@@ -8,6 +8,7 @@ import ctypes as C
 import math
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -43,6 +44,7 @@ SYMBOLS = [
     "azk_set_openings", "azk_clear_openings", "azk_open_pending", "azk_get_open_plies", "azk_get_opening_stats",
     "azk_get_opening_actions", "azk_get_leaf_flags",
     "azk_set_puct", "azk_clear_puct",
+    "azk_set_move_temperature", "azk_clear_move_temperature", "azk_get_move_temperature_stats",
 ]
 
 
@@ -204,6 +206,80 @@ def puct_setting(c, fpu=None):
     return table, FPU_MODES[kind], f_tree, f_root
 
 
+def _tau_schedule(tau, state_dim):
+    """tau in one of move_temperature_setting's forms -> the per-ply list of float values (0.0 = greedy); the last holds for every later ply."""
+    if isinstance(tau, bool):
+        raise TypeError
+    if isinstance(tau, (int, float, np.integer, np.floating)):
+        return [float(tau)]
+    if isinstance(tau, tuple) and len(tau) > 0 and isinstance(tau[0], str):
+        kind, rest = tau[0], tau[1:]
+        if kind == "until" and len(rest) == 2:
+            t, n = float(rest[0]), int(rest[1])
+            if n != rest[1] or n < 0:
+                raise TypeError
+            return [t] * min(n, int(state_dim)) + [0.0]
+        if kind in ("halflife", "linear") and len(rest) in (2, 3):
+            t0, span = float(rest[0]), float(rest[1])
+            t_final = float(rest[2]) if len(rest) == 3 else 0.0
+            if not (span > 0.0 and math.isfinite(span)):
+                raise TypeError
+            if kind == "halflife":
+                return [t_final + (t0 - t_final) * 0.5 ** (p / span) for p in range(int(state_dim))]
+            return [t0 + (t_final - t0) * (min(float(p), span) / span) for p in range(int(state_dim))]
+        raise TypeError
+    if isinstance(tau, (list, np.ndarray)) and len(tau) > 0:
+        return [float(t) for t in tau]
+    raise TypeError
+
+
+def move_temperature_setting(tau, max_sims, state_dim, visit_offset=0, value_cutoff=None):
+    """tau -> (row_of_ply int32 [n_plies], weights float64 [n_rows][max_sims + 1], visit_offset, value_cutoff), the arguments of
+    azk_set_move_temperature (include/azk.h).  tau: a positive number (every ply), ("until", t, n_plies) (t for the first
+    n_plies plies, then greedy), ("halflife", t0, halflife[, t_final]) (tau(p) = t_final + (t0 - t_final) * 0.5 ** (p / halflife) for
+    p < state_dim), ("linear", t0, decay_plies[, t_final]) (tau(p) = t0 + (t_final - t0) * min(p, decay_plies) / decay_plies), t_final 0
+    where it is left out, or a list of per-ply values whose last holds for every later ply.  A value of 0 is greedy (row -1); equal values share
+    one row; a row is [math.pow(float(n), 1.0 / tau) for n in range(max_sims + 1)] in host float64 (the engine has no device pow).
+    value_cutoff None (or negative) = no cutoff.  Raises ValueError for what the engine refuses too; where a row would overflow the engine's
+    bound on a weight, DBL_MAX / (rows * columns), the message names the smallest admissible tau."""
+    max_sims, state_dim = int(max_sims), int(state_dim)
+    try:
+        taus = _tau_schedule(tau, state_dim)
+    except (TypeError, ValueError):
+        raise ValueError("move_temperature: tau must be a positive number, ('until', t, n_plies), ('halflife', t0, halflife[, t_final]), "
+                         f"('linear', t0, decay_plies[, t_final]) or a list of per-ply values, not {tau!r}")
+    if max_sims < 1 or state_dim < 1:
+        raise ValueError(f"move_temperature: max_sims and state_dim must be at least 1, not {(max_sims, state_dim)!r}")
+    if not all(math.isfinite(t) and t >= 0.0 for t in taus):
+        raise ValueError(f"move_temperature: every tau must be finite and not negative (0 = greedy), not {tau!r}")
+    if isinstance(visit_offset, bool) or int(visit_offset) != visit_offset or int(visit_offset) < 0:
+        raise ValueError(f"move_temperature: visit_offset must be an integer >= 0, not {visit_offset!r}")
+    cutoff = -1.0 if value_cutoff is None else float(value_cutoff)
+    if math.isnan(cutoff):
+        raise ValueError("move_temperature: value_cutoff is NaN (None or a negative value means no cutoff)")
+    distinct = []
+    for t in taus:
+        if t > 0.0 and t not in distinct:
+            distinct.append(t)
+    if not distinct:
+        raise ValueError(f"move_temperature: no ply has a positive tau in {tau!r} - that is the engine without the option at sample_until 0")
+    n_cols = max_sims + 1
+    bound = sys.float_info.max / (len(distinct) * n_cols)
+    tau_min = math.log(max_sims) / math.log(bound) if max_sims > 1 else 0.0
+    rows = []
+    for t in distinct:
+        try:
+            row = [math.pow(float(n), 1.0 / t) for n in range(n_cols)]
+        except (OverflowError, ZeroDivisionError):
+            row = [math.inf]
+        if max(row) > bound:
+            raise ValueError(f"move_temperature: tau = {t!r} overflows the table - {max_sims} ** (1 / tau) must stay below DBL_MAX / (rows * columns) = "
+                             f"{bound:.6g}; the smallest admissible tau for {len(distinct)} row(s) of {n_cols} columns is {tau_min:.6g}")
+        rows.append(row)
+    row_of_ply = np.array([distinct.index(t) if t > 0.0 else -1 for t in taus], np.int32)
+    return row_of_ply, np.ascontiguousarray(rows, np.float64), int(visit_offset), cutoff
+
+
 class Engine:
     """G concurrent games + their search trees resident on one GPU (one engine per process / GPU)."""
 
@@ -265,6 +341,7 @@ class Engine:
         self.gumbel_root = None                     # (m, n_sims, c_visit, c_scale) once set_gumbel_root has switched the option on
         self.openings = None                        # (p_open, max_plies, spread) once set_openings has switched the option on
         self.puct = None                            # (c_table, fpu_mode, fpu_tree, fpu_root) once set_puct has switched the option on
+        self.move_temperature = None                # (row_of_ply, weights, visit_offset, value_cutoff) once set_move_temperature has switched the option on
         self.surprise_weight = None                 # lambda once set_surprise_weighting has switched the option on (0.0 is a live setting)
         self.cache_entries = int(cache_entries)
         # with the eval cache a step can have pending (cached) leaves to expand although no leaf went to the evaluator
@@ -439,6 +516,37 @@ class Engine:
         """Configurable PUCT off (azk_clear_puct): the engine launches what it launched before."""
         self._chk(self.L.azk_clear_puct(self.h))
         self.puct = None
+
+    def set_move_temperature(self, row_of_ply, weights, visit_offset=0, value_cutoff=None):
+        """OPT-IN move temperature (azk_set_move_temperature): from now on advance and the asynchronous movers ignore
+        sample_until and pick the played child by the table - at a move of a game with mc plies, row r = row_of_ply[min(mc, len - 1)]; r < 0
+        (or no uniforms) plays the first most-visited child b; otherwise child i weighs weights[r][max(0, N_i - visit_offset)], a child whose
+        W / N lies more than value_cutoff below b's weighs 0, and the child is drawn from those weights as Node.sample_child draws from the
+        counts.  move_temperature_setting builds the four arguments from a temperature schedule.  weights: float64 [n_rows][max_sims + 1].
+        value_cutoff None or negative = no cutoff.  The recorded pi stays the raw visit distribution.  Between searches only; not with a Gumbel
+        root or tree_reuse = 1.  clear_move_temperature() switches it off."""
+        rows = np.ascontiguousarray(row_of_ply, np.int32).reshape(-1)
+        wts = np.ascontiguousarray(weights, np.float64)
+        if wts.ndim != 2:
+            raise ValueError(f"set_move_temperature: weights must be [n_rows][max_sims + 1], not an array of shape {wts.shape!r}")
+        cutoff = -1.0 if value_cutoff is None else float(value_cutoff)
+        self._chk(self.L.azk_set_move_temperature(self.h, _np(rows), int(rows.size), _np(wts), int(wts.shape[0]), int(wts.shape[1]), int(visit_offset),
+                                                  cutoff, _stream()))
+        self.move_temperature = (rows, wts, int(visit_offset), cutoff)
+
+    def clear_move_temperature(self):
+        """Move temperature off (azk_clear_move_temperature): the engine launches what it launched before."""
+        self._chk(self.L.azk_clear_move_temperature(self.h))
+        self.move_temperature = None
+
+    def move_temperature_stats(self):
+        """[plies drawn by weight, of those not the most-visited child, children cut by the value cutoff, plies that fell back to the
+        most-visited child because every weight was 0] since set_move_temperature (host sync)."""
+        if self.move_temperature is None:
+            raise AzkError("move_temperature_stats: no move temperature is set (set_move_temperature)")
+        out = np.zeros(4, np.int64)
+        self._chk(self.L.azk_get_move_temperature_stats(self.h, _np(out), _stream()))
+        return [int(x) for x in out]
 
     def set_gumbel_root(self, m, n_sims, c_visit=50.0, c_scale=1.0):
         """OPT-IN Gumbel root search (azk_set_gumbel_root; Danihelka et al. 2022): every search of n_sims simulations

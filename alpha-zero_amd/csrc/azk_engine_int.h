@@ -162,6 +162,19 @@ struct PuctDev {
     double fpu_tree, fpu_root; // the value (mode 1) or the reduction r >= 0 (mode 2), below the root and at it
 };
 
+// move temperature (azk_set_move_temperature, opt-in): the played child is drawn with a weight per visit count, read from a
+// host-built table whose row is the ply's (no device pow), after a visit offset and a value cutoff; a ply whose row is -1 plays the first
+// most-visited child.  Its own argument block, passed only to the TEMP instantiations of the two movers (azk_moves.hip): every other argument
+// block - and every kernel an engine without the option launches - stays as it was
+struct TempDev {
+    const int *row_of_ply;     // [n_plies] row of `weights` for a move at that ply, -1 = greedy; the last entry holds for every later ply
+    const double *weights;     // [n_rows][n_cols] weight of a child by its visit count (less the offset); column 0 is 0
+    int n_plies, n_cols;       // n_cols = max_sims + 1
+    int visit_offset;          // >= 0: a child of N visits weighs weights[row][max(0, N - visit_offset)]
+    double value_cutoff;       // >= 0: a child whose W / N is more than this below the most-visited child's weighs 0; < 0: no cutoff
+    long long *stats;          // [4] plies drawn by weight, of those not the most-visited child, children cut, plies that fell back (all weights 0)
+};
+
 // evaluation under a board symmetry (azk_set_eval_symmetry, opt-in; mode == 0 otherwise): the evaluator is shown each pending
 // leaf in orientation s = the fixed element, or a hash of (seed, the leaf's position), and its logits row is turned back before k_tree expands
 // from it.  Its own argument of the two kernels that exist only for it (azk_sym.hip): every other argument block - and every kernel an engine
@@ -428,6 +441,8 @@ struct azk_engine {
     int gumbel_sims = 0;                 // ... the n_sims its table was built for
     PuctDev pu = {};                     // configurable PUCT (azk_set_puct); puct_on == false: off, nothing allocated
     bool puct_on = false;                // (c_table = [1.0] with mode 0 is a live setting, so the switch is its own word)
+    TempDev tp = {};                     // move temperature (azk_set_move_temperature); tp_on == false: off, nothing allocated
+    bool tp_on = false;
     bool async_on = false;
     int async_recycle = 1;
     SymDev sym = {};                     // evaluation under a board symmetry (azk_set_eval_symmetry); sym.mode == 0: off, nothing allocated

@@ -178,6 +178,85 @@ __device__ __forceinline__ int gumbel_target(const Dev &d, const LdsView &L, int
     return best;
 }
 
+// Move temperature (azk_set_move_temperature): the played child of one game's search (one wave), all float64.  With mc the
+// game's plies, r = row_of_ply[min(mc, n_plies - 1)], b = the first child with the most visits (Node.max_visit_child), qb = W_b / N_b:
+//     no uniform, or r < 0     b
+//     else, per child i        w_i = weights[r][max(0, N_i - visit_offset)];  with a cutoff >= 0, a child with w_i > 0 and
+//                              W_i / N_i < qb - cutoff gets w_i = 0 (it is cut)
+//     by action a              w[a] = its child's w_i, 0 where there is none;  S = w[0] + w[1] + ... sequentially
+//     S == 0                   b (a fallback)
+//     else                     Node.sample_child's arithmetic on w instead of the counts: acc += w[a] / S, cdf[a] = acc sequentially,
+//                              index = searchsorted(cdf / cdf[-1], u, side='right') clamped to A - 1, the first child with that action
+// The weights fill L.cdf and are accumulated in place; L.cnt keeps the raw visits, which the recorded pi is made of.  (The column is also
+// held below n_cols: no engine the option admits has a root child with more than max_sims visits, and no table is read past its end.)
+// Returns the played child's list index (wave-uniform), -1 if the drawn action has no child (a state error, as in the sampler below).
+__device__ __forceinline__ int temp_child(const Dev &d, const LdsView &L, int g, bool have_u, double u, int mc, const TempDev &tm) {
+    const int lane = azk_lane();
+    const GameDesc &gd = d.g;
+    const size_t base = (size_t)g * d.cap;
+    const int A = gd.action_dim;
+    const int fc = uniform_i32(d.H[base].fc), nch = uniform_i32(meta_nch(d.H[base].meta));
+    int best = 0x7fffffff, bn = 0;                                  // Node.max_visit_child (node.py:76-81)
+    for (int i = lane; i < nch; i += AZK_WAVE) {
+        const int n = d.H[base + fc + i].N;
+        if (best == 0x7fffffff || n > bn) { bn = n; best = i; }
+    }
+    wave_argmax_first<int>(bn, best);
+    best = uniform_i32(best); bn = uniform_i32(bn);
+    const int row = have_u ? uniform_i32(tm.row_of_ply[max(0, min(mc, tm.n_plies - 1))]) : -1;
+    if (row < 0) return best;
+    const double qb = d.W[base + fc + best] / (double)bn;
+    const double *wr = tm.weights + (size_t)row * tm.n_cols;
+    for (int a = lane; a < A; a += AZK_WAVE) L.cdf[a] = 0.0;
+    __syncthreads();
+    int cut = 0;
+    for (int i = lane; i < nch; i += AZK_WAVE) {
+        const NodeH h = d.H[base + fc + i];
+        double w = wr[min(max(h.N - tm.visit_offset, 0), tm.n_cols - 1)];
+        if (tm.value_cutoff >= 0.0 && w > 0.0 && d.W[base + fc + i] / (double)h.N < qb - tm.value_cutoff) { w = 0.0; cut += 1; }
+        L.cdf[azk_action_idx(gd, meta_cell(h.meta))] = w;
+    }
+    cut = wave_sum_i32(cut);
+    __syncthreads();
+    double S = 0.0;
+    if (lane == 0) for (int a = 0; a < A; a++) S += L.cdf[a];
+    S = __shfl(S, 0);
+    // (the quotients are elementwise: every lane divides its actions, and only the two running sums stay on lane 0's chain)
+    if (S != 0.0) for (int a = lane; a < A; a += AZK_WAVE) L.cdf[a] = L.cdf[a] / S;
+    __syncthreads();
+    if (lane == 0) {
+        int act = -1;
+        if (S != 0.0) {
+            double acc = 0.0;
+            for (int a = 0; a < A; a++) { acc += L.cdf[a]; L.cdf[a] = acc; }
+            const double lastv = L.cdf[A - 1];
+            int lo = 0, hi = A;
+            while (lo < hi) { int mid = (lo + hi) >> 1; if (u < L.cdf[mid] / lastv) hi = mid; else lo = mid + 1; }
+            act = lo < A ? lo : A - 1;
+        }
+        L.path[0] = act;                                             // action drawn, -1 = every weight is 0 (path scratch, as the sampler's)
+    }
+    __syncthreads();
+    const int act = uniform_i32(L.path[0]);
+    int found = best;
+    if (act >= 0) {
+        found = 0x7fffffff;
+        for (int i = lane; i < nch; i += AZK_WAVE)
+            if (azk_action_idx(gd, meta_cell(d.H[base + fc + i].meta)) == act && i < found) found = i;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { int o = __shfl_xor(found, off); found = o < found ? o : found; }
+    }
+    if (lane == 0) {
+        unsigned long long *st = (unsigned long long *)tm.stats;
+        if (act >= 0) {
+            atomicAdd(&st[0], 1ull);
+            if (found != best) atomicAdd(&st[1], 1ull);
+        } else atomicAdd(&st[3], 1ull);
+        if (cut) atomicAdd(&st[2], (unsigned long long)cut);
+    }
+    return found != 0x7fffffff ? found : -1;
+}
+
 // gomoku.py:143-162 for one game (one wave): choose (sample ~ visits | first max-visit child), record pi / the action in the
 // trajectory, make_move, check_winner, draw.  Returns the chosen cell (-1: state error, already reported); *win_out / *done_out as
 // k_advance's outputs; pi of the move is left in L.cnt / sum_out (visit counts per action and their sum).
@@ -194,10 +273,13 @@ __device__ __forceinline__ int gumbel_target(const Dev &d, const LdsView &L, int
 // GUMBEL (engines with a Gumbel root, azk_set_gumbel_root): the move is gumbel_target's - the uniform and sample_until are
 // not looked at, the Gumbel arg-max is the sample - and the recorded pi is its float64 row in L.cdf (the caller's record reads it there too);
 // L.cnt / sum_out still hold the raw visits.
-template <bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false>
+// TEMP (engines with a move temperature, azk_set_move_temperature): the move is temp_child's - sample_until is not looked
+// at, the ply table is - and everything after the choice works on that cell as it does on any other; the recorded pi stays the raw (or pruned)
+// visit distribution in L.cnt.
+template <bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false, bool TEMP = false>
 __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool have_u, double u, int sample_until, int *win_out, int *done_out,
                                            int *sum_out, const ResignDev &rs, int key, int *rsg_out, const ForcedDev &fp, const SurpriseDev &sp,
-                                           const GumbelDev &gb = GumbelDev{}) {
+                                           const GumbelDev &gb = GumbelDev{}, const TempDev &tm = TempDev{}) {
     const int lane = azk_lane();
     const GameDesc &gd = d.g;
     const size_t base = (size_t)g * d.cap;
@@ -223,6 +305,10 @@ __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool
     }
     if constexpr (GUMBEL) {
         cellc = meta_cell(d.H[base + fc + gumbel_target(d, L, g, gb)].meta);
+    } else
+    if constexpr (TEMP) {
+        const int child = temp_child(d, L, g, have_u, u, mc, tm);
+        cellc = child >= 0 ? meta_cell(d.H[base + fc + child].meta) : -1;
     } else
     if (have_u && mc < sample_until) {
         // Node.sample_child (node.py:83-93) -> legacy np.random.choice(p=pi): cdf = cumsum(pi); cdf /= cdf[-1];
@@ -332,11 +418,11 @@ __device__ __forceinline__ int played_child(const Dev &d, int g, int cellc) {
 }
 
 // The lock-step mover (azk_advance, azk_advance_resign): every game's move, one wave per game.  CAP: the ply's kind goes into traj_full beside its
-// pi; RESIGN, SURPRISE (move_index = the slot's move counter), FORCED: as advance_one has them
-template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false>
+// pi; RESIGN, SURPRISE (move_index = the slot's move counter), FORCED, TEMP: as advance_one has them
+template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false, bool TEMP = false>
 __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int move_index, const double *uniforms, int sample_until,
                                              int *chosen, int *winner_out, int *done_out, int *chosen_node, const ForcedDev &fp, const SurpriseDev &sp,
-                                             const GumbelDev &gb = GumbelDev{}) {
+                                             const GumbelDev &gb = GumbelDev{}, const TempDev &tm = TempDev{}) {
     const int g = blockIdx.x, lane = azk_lane();
     LdsView L = carve(d.g, d.path_cap, d.table_size);
     if (uniform_i32(d.done[g]) != 0) {
@@ -352,8 +438,8 @@ __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int
     const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
     int cellc;
     if constexpr (GUMBEL) cellc = advance_one<RESIGN, false, false, true>(d, L, g, false, 0.0, 0, &win, &dn, &sum, rs, move_index, &rsg, fp, sp, gb);
-    else cellc = advance_one<RESIGN, FORCED, SURPRISE>(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum,
-                                                            rs, move_index, &rsg, fp, sp);
+    else cellc = advance_one<RESIGN, FORCED, SURPRISE, false, TEMP>(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum,
+                                                            rs, move_index, &rsg, fp, sp, GumbelDev{}, tm);
     if (CAP && cellc >= 0 && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = cp.search_full[g];
     if (chosen_node) {
         const int child = played_child(d, g, cellc);               // tree reuse: the next search's root
@@ -371,13 +457,13 @@ __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int
 template <bool KEYED> struct Ply { int sample_until; };
 template <> struct Ply<true> { int sample_until, move_index; };
 
-template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
-__global__ __launch_bounds__(AZK_WAVE) void k_advance(MovePack<Dev, CAP, RESIGN, FORCED, SURPRISE> a, const double *uniforms, Ply<RESIGN || SURPRISE> ply,
+template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool TEMP>
+__global__ __launch_bounds__(AZK_WAVE) void k_advance(MovePack<Dev, CAP, RESIGN, FORCED, SURPRISE, TEMP> a, const double *uniforms, Ply<RESIGN || SURPRISE> ply,
                                                        int *chosen, int *winner_out, int *done_out, int *chosen_node) {
     int move_index = 0;
     if constexpr (RESIGN || SURPRISE) move_index = ply.move_index;
-    advance_body<CAP, RESIGN, FORCED, SURPRISE>(a, opt<CapDev>(a), opt<ResignDev>(a), move_index, uniforms, ply.sample_until, chosen, winner_out, done_out,
-                                                chosen_node, opt<ForcedDev>(a), opt<SurpriseDev>(a));
+    advance_body<CAP, RESIGN, FORCED, SURPRISE, false, TEMP>(a, opt<CapDev>(a), opt<ResignDev>(a), move_index, uniforms, ply.sample_until, chosen, winner_out,
+                                                             done_out, chosen_node, opt<ForcedDev>(a), opt<SurpriseDev>(a), GumbelDev{}, opt<TempDev>(a));
 }
 
 // the lock-step mover of an engine with a Gumbel root (with or without resignation)
@@ -407,10 +493,10 @@ __global__ __launch_bounds__(AZK_WAVE) void k_advance(GumbelPack<Dev, RESIGN> a,
 // ------------------------------------------------------------------------------------------------
 // The asynchronous mover.  REROOT: a re-rooting engine - the moved game is parked for the drain's k_reroot_list instead of beginning its search
 // here; CAP: the kind of the completed search goes into the record and traj_full, and the next fresh-root search flips its coin; RESIGN, FORCED:
-// SURPRISE: as advance_one has them (the move key is the slot's move counter; kl and coin go into the record's columns too)
-template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false>
+// SURPRISE, TEMP: as advance_one has them (the move key is the slot's move counter; kl and coin go into the record's columns too)
+template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false, bool TEMP = false>
 __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs, const ForcedDev &fp, const SurpriseDev &sp,
-                                                const GumbelDev &gb = GumbelDev{}) {
+                                                const GumbelDev &gb = GumbelDev{}, const TempDev &tm = TempDev{}) {
     const int g = blockIdx.x, lane = azk_lane();
     // one vector load for the three words that decide whether this game moves now (almost never: the wave then ends at once)
     const int *up = d.done + g;
@@ -437,7 +523,7 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
     const int kind = CAP ? uniform_i32((int)cp.search_full[g]) : 1;     // of the search that is complete
     int cellc;
     if constexpr (GUMBEL) cellc = advance_one<RESIGN, false, false, true>(d, L, g, false, 0.0, 0, &win, &dn, &sum, rs, (int)mv, &rsg, fp, sp, gb);
-    else cellc = advance_one<RESIGN, FORCED, SURPRISE>(d, L, g, true, u, p.sample_until, &win, &dn, &sum, rs, (int)mv, &rsg, fp, sp);
+    else cellc = advance_one<RESIGN, FORCED, SURPRISE, false, TEMP>(d, L, g, true, u, p.sample_until, &win, &dn, &sum, rs, (int)mv, &rsg, fp, sp, GumbelDev{}, tm);
     if (cellc < 0) return;
     if (CAP && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = (uint8_t)kind;
     if (p.rec_cap > 0) {                                           // the move's record: what the reference's self_play keeps per ply
@@ -479,9 +565,10 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
     }
 }
 
-template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE>
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, MovePack<ReuseDev, CAP, RESIGN, FORCED, SURPRISE> r) {
-    move_async_body<REROOT, CAP, RESIGN, FORCED, SURPRISE>(d, p, r, opt<CapDev>(r), opt<ResignDev>(r), opt<ForcedDev>(r), opt<SurpriseDev>(r));
+template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool TEMP>
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, MovePack<ReuseDev, CAP, RESIGN, FORCED, SURPRISE, TEMP> r) {
+    move_async_body<REROOT, CAP, RESIGN, FORCED, SURPRISE, false, TEMP>(d, p, r, opt<CapDev>(r), opt<ResignDev>(r), opt<ForcedDev>(r), opt<SurpriseDev>(r),
+                                                                        GumbelDev{}, opt<TempDev>(r));
 }
 
 // the asynchronous mover of an engine with a Gumbel root (no re-rooting, no cap; with or without resignation)
@@ -553,12 +640,13 @@ static int32_t advance(azk_engine *e, const double *uniforms_dev, int32_t sample
         HIPCHK(e, hipGetLastError());
         return AZK_OK;
     }
-    with_flags([&](auto cap, auto resign, auto forced, auto surprise) {
+    with_flags([&](auto cap, auto resign, auto forced, auto surprise, auto temp) {
         Ply<resign.value || surprise.value> ply{sample_until_move};
         if constexpr (resign.value || surprise.value) ply.move_index = move_index;
-        k_advance<cap.value, resign.value, forced.value, surprise.value><<<d.G, AZK_WAVE, d.lds_bytes, (hipStream_t)stream>>>(
-            move_pack<cap.value, resign.value, forced.value, surprise.value>(d, e), uniforms_dev, ply, chosen_cell_dev, winner_dev, done_dev, e->ru.chosen_node);
-    }, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0, e->sp_on);
+        k_advance<cap.value, resign.value, forced.value, surprise.value, temp.value><<<d.G, AZK_WAVE, d.lds_bytes, (hipStream_t)stream>>>(
+            move_pack<cap.value, resign.value, forced.value, surprise.value, temp.value>(d, e), uniforms_dev, ply, chosen_cell_dev, winner_dev, done_dev,
+            e->ru.chosen_node);
+    }, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0, e->sp_on, e->tp_on);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -674,10 +762,10 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
             k_move_async<resign.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, GumbelPack<ReuseDev, resign.value>{e->ru, on<resign.value>(e->rs), on<true>(e->gb)});
         }, e->rs.v_resign != 0.0);
     else if (phases & 2)
-        with_flags([&](auto reroot, auto cap, auto resign, auto forced, auto surprise) {
-            k_move_async<reroot.value, cap.value, resign.value, forced.value, surprise.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(
-                d, e->ad, move_pack<cap.value, resign.value, forced.value, surprise.value>(e->ru, e));
-        }, e->ru.mode != 0, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0, e->sp_on);
+        with_flags([&](auto reroot, auto cap, auto resign, auto forced, auto surprise, auto temp) {
+            k_move_async<reroot.value, cap.value, resign.value, forced.value, surprise.value, temp.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(
+                d, e->ad, move_pack<cap.value, resign.value, forced.value, surprise.value, temp.value>(e->ru, e));
+        }, e->ru.mode != 0, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0, e->sp_on, e->tp_on);
     HIPCHK(e, hipGetLastError());
     return azk_sym_leaves(e, st);                                 // (eval symmetry: the leaves the tree launch selected, behind the movers)
 }

@@ -1,8 +1,9 @@
 // azk_options.hip - the opt-ins' state calls (include/azk.h): set, clear and read playout cap, forced playouts, Gumbel root, resignation,
-// surprise weighting and random openings.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
+// surprise weighting, random openings and the move temperature.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
 // block (azk_engine_int.h) that azk_opt_pack.h hands to the kernels of azk_begin.hip, azk_moves.hip and azk_emit.hip.
 #include "azk_engine_int.h"
 #include <algorithm>
+#include <float.h>
 
 // resignation: no game resigned, no mark, zero statistics (azk_set_resign, and azk_async_begin where the slots' move counters start again at 0)
 int32_t azk_resign_clear(azk_engine *e, hipStream_t st) {
@@ -96,6 +97,7 @@ int32_t azk_set_gumbel_root(azk_engine *e, int32_t m, int32_t n_sims, double c_v
     if (e->forced_k != 0.0) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with forced playouts (the eligibility rule needs raw root selection)"; return AZK_ERR_STATE; }
     if (e->sp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with surprise weighting (its recorded pi is not a visit distribution)"; return AZK_ERR_STATE; }
     if (e->puct_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with configurable PUCT (azk_set_puct: its root selection is not PUCT)"; return AZK_ERR_STATE; }
+    if (e->tp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with a move temperature (azk_set_move_temperature: the Gumbel arg-max is the sample)"; return AZK_ERR_STATE; }
     const Dev &d = e->d;
     GumbelDev &gb = e->gb;
     hipStream_t st = (hipStream_t)stream;
@@ -155,6 +157,63 @@ int32_t azk_clear_puct(azk_engine *e) {
     if (e->async_on) { e->err = "azk_clear_puct: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
     if (e->in_search && e->puct_on) { e->err = "azk_clear_puct: a search is under way - clear the option between searches"; return AZK_ERR_STATE; }
     e->puct_on = false;                                            // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+// ---- move temperature -----------------------------------------------------------------------------------------------------
+int32_t azk_set_move_temperature(azk_engine *e, const int32_t *row_of_ply_host, int32_t n_plies, const double *weights_host, int32_t n_rows, int32_t n_cols,
+                                 int32_t visit_offset, double value_cutoff, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_move_temperature: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (!row_of_ply_host || !weights_host) { e->err = "azk_set_move_temperature: a table pointer is null"; return AZK_ERR_ARG; }
+    if (n_plies < 1 || n_rows < 1) { e->err = "azk_set_move_temperature: n_plies and n_rows must be at least 1"; return AZK_ERR_ARG; }
+    if (n_cols != e->cfg.max_sims + 1) { e->err = "azk_set_move_temperature: n_cols must be max_sims + 1 (a weight for every visit count a root child can have)"; return AZK_ERR_ARG; }
+    for (int p = 0; p < n_plies; p++)
+        if (row_of_ply_host[p] < -1 || row_of_ply_host[p] >= n_rows) { e->err = "azk_set_move_temperature: a row index lies outside [-1, n_rows)"; return AZK_ERR_ARG; }
+    const double wmax = DBL_MAX / ((double)n_rows * (double)n_cols);
+    for (int r = 0; r < n_rows; r++) {
+        const double *w = weights_host + (size_t)r * n_cols;
+        bool positive = false;
+        for (int c = 0; c < n_cols; c++) {
+            if (!(w[c] >= 0.0) || w[c] - w[c] != 0.0) { e->err = "azk_set_move_temperature: every weight must be finite and not negative"; return AZK_ERR_ARG; }
+            if (w[c] > wmax) { e->err = "azk_set_move_temperature: a weight exceeds DBL_MAX / (n_rows * n_cols) (the sum over a root's children must stay finite)"; return AZK_ERR_ARG; }
+            positive = positive || w[c] > 0.0;
+        }
+        if (w[0] != 0.0) { e->err = "azk_set_move_temperature: column 0 of every row must be 0 (an unvisited child is never played)"; return AZK_ERR_ARG; }
+        if (!positive) { e->err = "azk_set_move_temperature: a row has no positive weight"; return AZK_ERR_ARG; }
+    }
+    if (visit_offset < 0) { e->err = "azk_set_move_temperature: visit_offset must not be negative"; return AZK_ERR_ARG; }
+    if (value_cutoff != value_cutoff) { e->err = "azk_set_move_temperature: value_cutoff is NaN (a negative value means no cutoff)"; return AZK_ERR_ARG; }
+    if (e->in_search) { e->err = "azk_set_move_temperature: a search is under way - set the option between searches"; return AZK_ERR_STATE; }
+    if (e->gb.m) { e->err = "azk_set_move_temperature: a Gumbel root is set - the Gumbel arg-max is the sample"; return AZK_ERR_STATE; }
+    if (e->ru.mode == 1) { e->err = "azk_set_move_temperature: the engine was created with tree_reuse = 1 - a carried root child's visits are not bounded by max_sims, so the table has no column for them (top-up, tree_reuse = 2, is bounded)"; return AZK_ERR_STATE; }
+    hipStream_t st = (hipStream_t)stream;
+    int *rows = nullptr;                                             // (tables of their own per call: a captured step graph may still hold the last ones)
+    double *wts = nullptr;
+    HIPCHK(e, dalloc(e, &rows, (size_t)n_plies));
+    HIPCHK(e, dalloc(e, &wts, (size_t)n_rows * n_cols));
+    if (!e->tp.stats) HIPCHK(e, dalloc(e, &e->tp.stats, 4));
+    HIPCHK(e, hipMemcpyAsync(rows, row_of_ply_host, sizeof(int) * (size_t)n_plies, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(wts, weights_host, sizeof(double) * (size_t)n_rows * n_cols, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemsetAsync(e->tp.stats, 0, sizeof(long long) * 4, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    e->tp = TempDev{rows, wts, n_plies, n_cols, visit_offset, value_cutoff, e->tp.stats};
+    e->tp_on = true;
+    return AZK_OK;
+}
+
+int32_t azk_clear_move_temperature(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_move_temperature: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    e->tp_on = false;                                             // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+int32_t azk_get_move_temperature_stats(azk_engine *e, int64_t *out4_host, void *stream) {
+    if (!e || !out4_host) return AZK_ERR_ARG;
+    if (!e->tp_on) { e->err = "azk_get_move_temperature_stats: no move temperature is set (azk_set_move_temperature)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(out4_host, e->tp.stats, sizeof(long long) * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     return AZK_OK;
 }
 

@@ -14,6 +14,7 @@ import gc
 import numpy as np
 
 from azk import Engine, board_elements, emit_mask, puct_setting, puct_table  # noqa: F401  (puct_table: the public helper behind puct=((c_init, c_base), ...))
+from azk import move_temperature_setting
 
 # gomoku.py:144 samples while move_count < 8; tictactoe.py:117 / connect4.py:135 sample every move
 SAMPLE_UNTIL = {"gomoku": 8, "tictactoe": 1 << 30, "connect4": 1 << 30}
@@ -320,6 +321,33 @@ def check_openings(openings, game, size=None, evaluator=True):
     return p_open, max_plies, spread
 
 
+def check_move_temperature(move_temperature, n_sims, game, size=None, gumbel_root=None, tree_reuse=0):
+    """move_temperature -> the (row_of_ply, weights, visit_offset, value_cutoff) of azk_set_move_temperature, or None for off.  OPT-IN move
+    temperature (include/azk.h azk_set_move_temperature): how the played child is picked from a finished search.
+    move_temperature is a schedule tau in one of move_temperature_setting's forms - a positive number, ("until", t, n_plies), ("halflife", t0,
+    halflife[, t_final]), ("linear", t0, decay_plies[, t_final]) or a list of per-ply values - or a dict(tau=..., visit_offset=0,
+    value_cutoff=None) that adds Leela's two guards.  n_sims is the engine's max_sims (the largest of a pair).  Raises ValueError, before any
+    engine exists, for what the engine refuses too: a bad schedule, a row that overflows, a Gumbel root (its arg-max is the sample) and
+    tree_reuse = 1 (a carried root child's visits are not bounded by max_sims; top-up, 2, is)."""
+    if move_temperature is None:
+        return None
+    if isinstance(move_temperature, dict):
+        extra = set(move_temperature) - {"tau", "visit_offset", "value_cutoff"}
+        if extra or "tau" not in move_temperature:
+            raise ValueError(f"move_temperature: a dict must have tau and may have visit_offset and value_cutoff, not {move_temperature!r}")
+        tau, offset, cutoff = move_temperature["tau"], move_temperature.get("visit_offset", 0), move_temperature.get("value_cutoff")
+    else:
+        tau, offset, cutoff = move_temperature, 0, None
+    max_sims = max(n_sims) if isinstance(n_sims, (tuple, list)) else n_sims
+    setting = move_temperature_setting(tau, max_sims, board_cells(game, size), offset, cutoff)
+    if gumbel_root is not None:
+        raise ValueError("move_temperature does not combine with gumbel_root (the Gumbel arg-max is the sample)")
+    if int(tree_reuse) == 1:
+        raise ValueError("move_temperature does not combine with tree_reuse = 1 (a carried root child's visits are not bounded by max_sims, so the "
+                         "table has no column for them; top-up, tree_reuse = 2, is bounded)")
+    return setting
+
+
 def mask_elements(mask):
     """The elements of an emission mask, ascending."""
     return tuple(s for s in range(8) if (mask >> s) & 1)
@@ -352,7 +380,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
                     budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
                     eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None,
-                    openings_first_game=None, puct=None):
+                    openings_first_game=None, puct=None, move_temperature=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -385,7 +413,10 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     belongs to); the two sides then search the same number of simulations (ValueError otherwise).  puct = (c, fpu) (OPT-IN, check_puct):
     every selection of every network search scores a child with the exploration rate c - a number, a tuple (c_init, c_base) or a table over
     the selecting node's visit count - and an unvisited child by the first-play urgency fpu (None, ("absolute", v_tree[, v_root]) or
-    ("reduction", r_tree[, r_root])); with an (evaluator0, evaluator1) pair both sides search under it.
+    ("reduction", r_tree[, r_root])); with an (evaluator0, evaluator1) pair both sides search under it.  move_temperature (OPT-IN,
+    check_move_temperature): a schedule tau, or dict(tau=, visit_offset=, value_cutoff=) - every move is picked by the engine's weight table
+    instead of "sample in proportion to the visits while move_count < sample_until", which is then not looked at; the recorded pis stay the raw
+    visit distributions.  ("until", 1.0, sample_until) plays the games of a call without the option.
     """
     import torch
     opn = check_openings(openings, game, size, evaluator)
@@ -403,6 +434,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     lam = check_surprise_weight(surprise_weight, evaluator, leaves_per_step)
     gum = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, cap, fpk, lam)
     pct = puct if check_puct(puct, evaluator, leaves_per_step, fpk, gum) is not None else None
+    tmp = check_move_temperature(move_temperature, engine.max_sims if engine is not None else n_sims, game, size, gum,
+                                 engine.tree_reuse if engine is not None else tree_reuse)
     _refuse_vanilla_resign(rsg, evaluator)
     if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
@@ -424,6 +457,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         eng.set_gumbel_root(gum[0], n_sims, gum[1], gum[2])
     if pct is not None:
         eng.set_puct(*pct)
+    if tmp is not None:
+        eng.set_move_temperature(*tmp)
     # virtual-loss, top-up and capped engines are driven by the simulation budget
     budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
     assert eng.G == n_games
@@ -654,6 +689,10 @@ class SelfPlayRunner:
     puct = (c, fpu) (OPT-IN, check_puct; with everything above except forced_playouts and gumbel_root): every selection of every search uses
     the exploration rate c (a number, a tuple (c_init, c_base), or a table over the selecting node's visit count) and the first-play urgency
     fpu (None, ("absolute", v_tree[, v_root]) or ("reduction", r_tree[, r_root])); set at construction, before any graph is captured.
+
+    move_temperature (OPT-IN, check_move_temperature; with everything above except gumbel_root and tree_reuse = 1): a schedule tau or
+    dict(tau=, visit_offset=, value_cutoff=) - every move is picked by the engine's weight table instead of the reference's "sample while
+    move_count < sample_until"; the records' pis stay raw visit distributions.  move_temperature_stats() sums the groups' four counters.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
@@ -661,11 +700,13 @@ class SelfPlayRunner:
                  use_graph=False, n_split=1, replay=None, cache_entries=0, cache_shared=False, budget_stepping=False, per_launch=8,
                  steps_per_graph=32,
                  leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None,
-                 surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None, openings_first_game=None, puct=None):
+                 surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None, openings_first_game=None, puct=None,
+                 move_temperature=None):
         import torch
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, playout_cap, forced_playouts,
                                              surprise_weight)
+        self.move_temperature = check_move_temperature(move_temperature, n_sims, game, size, self.gumbel_root, tree_reuse)
         self.puct = puct if check_puct(puct, evaluator, leaves_per_step, forced_playouts, gumbel_root) is not None else None
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
         self.surprise_weight = check_surprise_weight(surprise_weight, evaluator, leaves_per_step)
@@ -725,6 +766,8 @@ class SelfPlayRunner:
                 h.eng.set_gumbel_root(self.gumbel_root[0], n_sims, self.gumbel_root[1], self.gumbel_root[2])
             if self.puct is not None:
                 h.eng.set_puct(*self.puct)
+            if self.move_temperature is not None:
+                h.eng.set_move_temperature(*self.move_temperature)
             if self.openings is not None:                         # the first games, under the key of their first search (move 0)
                 h.eng.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                                    (first_global_game if openings_first_game is None else openings_first_game) + i * per)
@@ -934,6 +977,12 @@ class SelfPlayRunner:
         for st in self.streams:
             cur.wait_stream(st)
 
+    def move_temperature_stats(self):
+        """[plies drawn by weight, of those not the most-visited child, children cut, plies that fell back] over the groups (host sync)."""
+        if self.move_temperature is None:
+            raise ValueError("move_temperature_stats: the runner was built without move_temperature")
+        return [sum(x) for x in zip(*[h.eng.move_temperature_stats() for h in self.halves])]
+
     def resign_stats(self):
         """[games ended by resignation, never-resign games ended, of those marked, of those whose marked side did not lose], all groups."""
         if self.resign is None:
@@ -1011,16 +1060,20 @@ class AsyncSelfPlayRunner:
     slot - the first games are opened inside async_begin, a restarted game inside the drain's restart kernel, under the slot's move counter.
 
     puct = (c, fpu) (OPT-IN, check_puct; with everything above except forced_playouts and gumbel_root): the games of SelfPlayRunner(puct=...),
-    slot for slot - the rule reads only what the tree stores, so the movers and the re-root need nothing of it."""
+    slot for slot - the rule reads only what the tree stores, so the movers and the re-root need nothing of it.
+
+    move_temperature (OPT-IN, check_move_temperature; with everything above except gumbel_root and reroot = 1): the games of
+    SelfPlayRunner(move_temperature=...), slot for slot - the movers draw from the same table with the same uniforms."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
                  playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None,
-                 openings=None, openings_seed=None, openings_first_game=None, puct=None):
+                 openings=None, openings_seed=None, openings_first_game=None, puct=None, move_temperature=None):
         import torch
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, 1, tree_reuse or reroot, playout_cap, forced_playouts, surprise_weight)
+        self.move_temperature = check_move_temperature(move_temperature, n_sims, game, size, self.gumbel_root, tree_reuse or reroot)
         self.puct = puct if check_puct(puct, evaluator, 1, forced_playouts, gumbel_root) is not None else None
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
         self.surprise_weight = check_surprise_weight(surprise_weight, evaluator)
@@ -1062,6 +1115,8 @@ class AsyncSelfPlayRunner:
             e.set_gumbel_root(self.gumbel_root[0], n_sims, self.gumbel_root[1], self.gumbel_root[2])
         if self.puct is not None:
             e.set_puct(*self.puct)
+        if self.move_temperature is not None:
+            e.set_move_temperature(*self.move_temperature)
         if self.openings is not None:                             # async_begin opens the first games, the drain's restart every later one
             e.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                            first_global_game if openings_first_game is None else openings_first_game)
@@ -1204,6 +1259,12 @@ class AsyncSelfPlayRunner:
     @property
     def finished_plies(self):
         return int(self._seen[1])
+
+    def move_temperature_stats(self):
+        """[plies drawn by weight, of those not the most-visited child, children cut, plies that fell back] over the groups (host sync)."""
+        if self.move_temperature is None:
+            raise ValueError("move_temperature_stats: the runner was built without move_temperature")
+        return [sum(x) for x in zip(*[h.eng.move_temperature_stats() for h in self.halves])]
 
     def resign_stats(self):
         """[games ended by resignation, never-resign games ended, of those marked, of those whose marked side did not lose] (host sync)."""

@@ -98,7 +98,8 @@ def save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=Non
 
 
 def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed=None, batched=True, playout_cap=None, resign=None,
-                 forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, puct=None):
+                 forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, puct=None,
+                 move_temperature=None):
     """train.py:54-83: `iterations` self-play games of Game with `model` into `buffer`; returns [first, second, draw] counts.
     batched=False plays the games one after the other through Game().self_play and save_data_to_buffer exactly as the
     reference does (global np.random stream: a seeded caller gets the reference's buffer); the default plays them as one
@@ -115,13 +116,16 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     batched only; selfplay.check_gumbel_root): every search is a Gumbel root search of mcts_iter simulations; both buffer kinds get
     softmax(logits + sigma(completed Q)) as the pi of every stored position.  openings = (p_open, max_plies, spread) (OPT-IN, batched only;
     selfplay.check_openings): a game starts, with probability p_open, from a position a few drawn plies in; neither buffer kind gets those plies.
-    puct = (c, fpu) (OPT-IN, batched only; selfplay.check_puct): every search selects with the exploration rate c and the first-play urgency fpu."""
+    puct = (c, fpu) (OPT-IN, batched only; selfplay.check_puct): every search selects with the exploration rate c and the first-play urgency fpu.
+    move_temperature (OPT-IN, batched only; selfplay.check_move_temperature): a schedule tau or dict(tau=, visit_offset=, value_cutoff=) picks
+    every move; both buffer kinds still get the raw visit distribution as pi."""
     from azk import DeviceReplay
     from selfplay import check_emit_symmetry, check_surprise_weight, mask_elements, self_play_batch, surprise_copies
     lam = check_surprise_weight(surprise_weight, model)
     if not batched:
         for name, value in (("surprise_weight", lam), ("emit_symmetry", emit_symmetry), ("playout_cap", playout_cap), ("resign", resign),
                             ("forced_playouts", forced_playouts), ("gumbel_root", gumbel_root), ("openings", openings), ("puct", puct),
+                            ("move_temperature", move_temperature),
                             ("eval_symmetry", None if eval_symmetry is False else eval_symmetry)):
             if value is not None:
                 raise ValueError(f"collect_data: {name} needs the batched engine (batched=True)")
@@ -139,7 +143,7 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     res = self_play_batch(Game.engine_name, model, iterations, mcts_iter, size=Game._size(), seed=seed, leaf_dtype=leaf_dtype,
                           replay=buffer if on_device else None, playout_cap=playout_cap, resign=resign, forced_playouts=forced_playouts,
                           eval_symmetry=eval_symmetry, emit_symmetry=emit_symmetry, surprise_weight=surprise_weight, gumbel_root=gumbel_root,
-                          openings=openings, puct=puct)
+                          openings=openings, puct=puct, move_temperature=move_temperature)
     emit = check_emit_symmetry(emit_symmetry, Game.engine_name, Game._size())
     results = [0, 0, 0]
     for r in res:

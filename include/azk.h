@@ -465,6 +465,46 @@ int32_t azk_gen_gumbel_uniforms(azk_engine *e, uint64_t seed, int64_t first_glob
 int32_t azk_set_puct(azk_engine *e, const double *c_table_host, int32_t n_table, int32_t fpu_mode, double fpu_tree, double fpu_root, void *stream);
 int32_t azk_clear_puct(azk_engine *e);
 
+/* ---- move temperature: per-ply schedule, visit offset, value cutoff (OPT-IN; off, the engine launches exactly the kernels it launched
+ * before).  The reference picks a move in one way: in proportion to the visits while move_count < sample_until, the first most-visited child
+ * afterwards.  With the option the movers (azk_advance*, the asynchronous movers) ignore sample_until_move - the argument and
+ * azk_async_config.sample_until_move alike - and follow this rule, all float64.  The engine knows no temperature, only a
+ * weight per visit count that the host puts into a table (no device pow):
+ *   state      row_of_ply   int32 [n_plies]: entry p is a row of `weights` or -1 (greedy); the last entry holds for every later ply.
+ *              weights      float64 [n_rows][n_cols], n_cols = max_sims + 1.  A temperature tau is the row pow(n, 1 / tau).
+ *              visit_offset >= 0 (Leela's temp-visit-offset).   value_cutoff: >= 0 (Leela's temp-value-cutoff), negative = none.
+ *   per move   of a game with mc plies played:  r = row_of_ply[min(mc, n_plies - 1)].
+ *              b = the first root child with the most visits (Node.max_visit_child), qb = W_b / N_b.
+ *              No uniforms (uniforms_dev == NULL) or r < 0: b is played.  Otherwise, for every root child i in list order,
+ *                  w_i = weights[r][max(0, N_i - visit_offset)];
+ *                  if value_cutoff >= 0 and w_i > 0 and W_i / N_i < qb - value_cutoff:  w_i = 0, the child is cut
+ *              (W / N of a child: the outcome as the side choosing at the root sees it).  w[a] = w_i of the child with action a, 0 where there
+ *              is none;  S = w[0] + w[1] + .. + w[A - 1], added in that order.  S == 0: b is played (a fallback).  Otherwise what the sampler
+ *              does with the counts:  acc += w[a] / S, cdf[a] = acc in that order;  index = the first a with u < cdf[a] / cdf[A - 1]
+ *              (searchsorted side='right'), A - 1 if there is none;  the first child with that action is played.
+ *   identity   a row w[n] = n with offset 0 and no cutoff makes every intermediate the sampler's own (integer sums are exact in float64): the
+ *              table {0, .., 0 (sample_until entries), -1} plays the games of an engine without the option.
+ *   unchanged  what is recorded as pi (traj_pi, the asynchronous record ring, azk_root_stats, azk_root_policy_target): raw visits, pruned
+ *              where a forced search prunes them - KataGo's and Leela's convention, not AlphaGo Zero's tempered target.  Surprise kl, q,
+ *              resignation, pruning and the played-child note of tree reuse work on whatever cell was chosen.
+ *   stats      four counters since azk_set_move_temperature: plies chosen by the weighted path, those among them whose played child is
+ *              not b, children cut by the value cutoff, plies that fell back because S == 0.
+ * azk_set_move_temperature takes HOST pointers, copies both tables to device memory (tables of their own per call; nothing is allocated
+ * while the option was never set) and zeroes the stats.  AZK_ERR_ARG: a null table, n_plies < 1 or n_rows < 1, n_cols != max_sims + 1, a row
+ * index outside [-1, n_rows), a weight that is negative, NaN or infinite, weights[r][0] != 0 (an unvisited child is never played), a row
+ * without a positive weight, a weight above DBL_MAX / (n_rows * n_cols) (S must stay finite), visit_offset < 0, a NaN cutoff.
+ * AZK_ERR_STATE: between the begin of a search and the call that ends it (a move, new positions or a reset); after azk_async_begin; with a
+ * Gumbel root set (its arg-max is the sample) - azk_set_gumbel_root refuses likewise while the option is set; on an engine created with
+ * tree_reuse = 1 (a carried root child's visits are not bounded by max_sims, so the table has no column for them; top-up, tree_reuse = 2, is
+ * bounded and allowed).  azk_clear_move_temperature makes the engine launch what it launched before (AZK_ERR_STATE after azk_async_begin).
+ * azk_get_move_temperature_stats copies the four counters to out4_host and waits (AZK_ERR_STATE while the option is off).  Combines with a
+ * playout cap, resignation, forced playouts, surprise weighting, configurable PUCT, evaluation symmetry, emit_elements, random openings,
+ * top-up tree reuse and the asynchronous movers with and without top-up re-rooting. */
+int32_t azk_set_move_temperature(azk_engine *e, const int32_t *row_of_ply_host, int32_t n_plies, const double *weights_host, int32_t n_rows,
+                                 int32_t n_cols, int32_t visit_offset, double value_cutoff, void *stream);
+int32_t azk_clear_move_temperature(azk_engine *e);
+int32_t azk_get_move_temperature_stats(azk_engine *e, int64_t *out4_host, void *stream);
+
 /* ---- random openings (OPT-IN; off, the engine launches exactly the kernels it launched before).  Every game otherwise starts from the
  * empty board and differs from its neighbours only through root noise and move sampling; with the option a game that starts in slot g is,
  * with probability p_open, played forward 1..max_plies uniformly drawn legal plies inside a centred window before its first search (KataGo's

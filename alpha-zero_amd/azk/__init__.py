@@ -45,6 +45,7 @@ SYMBOLS = [
     "azk_get_opening_actions", "azk_get_leaf_flags",
     "azk_set_puct", "azk_clear_puct",
     "azk_set_move_temperature", "azk_clear_move_temperature", "azk_get_move_temperature_stats",
+    "azk_set_value_target", "azk_clear_value_target", "azk_get_value_record",
 ]
 
 
@@ -343,6 +344,7 @@ class Engine:
         self.puct = None                            # (c_table, fpu_mode, fpu_tree, fpu_root) once set_puct has switched the option on
         self.move_temperature = None                # (row_of_ply, weights, visit_offset, value_cutoff) once set_move_temperature has switched the option on
         self.surprise_weight = None                 # lambda once set_surprise_weighting has switched the option on (0.0 is a live setting)
+        self.value_target = None                    # (r, lam) once set_value_target has switched the option on (r = 0.0 is a live setting)
         self.cache_entries = int(cache_entries)
         # with the eval cache a step can have pending (cached) leaves to expand although no leaf went to the evaluator
         need = cache_entries or self.K > 1
@@ -592,6 +594,29 @@ class Engine:
             raise AzkError("surprise: no surprise weighting is set (set_surprise_weighting)")
         self._chk(self.L.azk_get_surprise(self.h, _p(self._surprise[0]), _p(self._surprise[1]), _stream()))
         return self._surprise
+
+    def set_value_target(self, r, lam=0.0):
+        """OPT-IN value targets (azk_set_value_target): from now on every move keeps the root's q = W / N beside its pi
+        (value_record shows it) and emission - emit_finished, the asynchronous drain - writes t_i = (1 - r) * z_i + r * G_i in place of z_i,
+        G the horizon-lam return over the game's own search values v_i = -q_i that ends in z:  G_{n-1} = (1 - lam) * v_{n-1} + lam * z_{n-1},
+        G_i = (1 - lam) * v_i + lam * (-G_{i+1}).  r, lam in [0, 1]: (r, 0) is Leela's q-ratio, (1, lam) a TD(lambda) return; (0, lam) and
+        (1, 1) write the option-off ring byte for byte.  States and pis do not change.  Not with a Gumbel root or leaves_per_step > 1;
+        before async_begin.  r = None switches it off (azk_clear_value_target)."""
+        if r is None:
+            self._chk(self.L.azk_clear_value_target(self.h))
+            self.value_target = None
+            return
+        self._chk(self.L.azk_set_value_target(self.h, float(r), float(lam), _stream()))
+        self.value_target = (float(r), float(lam))
+
+    def value_record(self):
+        """float64 CUDA tensor [G, state_dim]: q of the plies of each slot's current game, as the movers kept them (azk_get_value_record);
+        row g is valid up to the game's move count (entries before its first searched ply, and beyond its last, are older games' or 0)."""
+        if self.value_target is None:
+            raise AzkError("value_record: no value target is set (set_value_target)")
+        out = self.torch.empty((self.G, self.state_dim), dtype=self.torch.float64, device=self.device)
+        self._chk(self.L.azk_get_value_record(self.h, _p(out), _stream()))
+        return out
 
     def set_eval_symmetry(self, mode, value=0):
         """OPT-IN evaluation under a board symmetry (azk_set_eval_symmetry): the evaluator sees every pending leaf turned by a D4 element

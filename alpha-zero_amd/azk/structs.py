@@ -184,6 +184,9 @@ def declare(L, symbols):
     L.azk_set_move_temperature.argtypes = [vp, vp, i32, vp, i32, i32, i32, f64, vp]
     L.azk_clear_move_temperature.argtypes = [vp]
     L.azk_get_move_temperature_stats.argtypes = [vp, vp, vp]
+    L.azk_set_value_target.argtypes = [vp, f64, f64, vp]
+    L.azk_clear_value_target.argtypes = [vp]
+    L.azk_get_value_record.argtypes = [vp, vp, vp]
     L.azk_set_openings.argtypes = [vp, f64, i32, i32, u64, i64, vp]
     L.azk_clear_openings.argtypes = [vp]
     L.azk_open_pending.argtypes = [vp, i32, vp]

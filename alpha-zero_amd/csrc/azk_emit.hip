@@ -23,9 +23,15 @@ namespace {
 // OPEN (engines with random openings): the opening's plies i < open_plies[g] had no search and are left out exactly as a
 // capped engine's fast plies are - no tuples, not in n_F or S, 0 copies, not in the sums of the tuples before a ply; `i < 2 ? 1 : grp`
 // stays keyed on the absolute ply index, and boards are rebuilt from ply 0.
-template <bool CAP, bool SYM, bool SURPRISE, bool OPEN>
+// VALUE (engines with value targets): the tuples of ply i carry t_i instead of z_i.  With o the first searched ply, q_i =
+// traj_q (the root's W / N at the move of ply i: the value for the mover's opponent), v_i = -q_i, z_i the outcome from ply i's mover's view:
+//     G_{n-1} = (1 - lam) * v_{n-1} + lam * z_{n-1};    G_i = (1 - lam) * v_i + lam * (-G_{i+1})  for i = n-2 .. o;    t_i = (1 - r) * z_i + r * G_i
+// in float64, one ply after the other from the last one down (the side to move alternates, hence the sign).  Every searched ply takes part,
+// a capped engine's fast plies too; k_emit_alloc's thread of the game writes t into traj_vt, k_emit_tuples writes (float)t_i into every tuple
+// of ply i - every element of the group, every copy.  r = 0, and r = lam = 1, write z bit for bit (a draw keeps +0.0: the last sum has a +0.0 term).
+template <bool CAP, bool SYM, bool SURPRISE, bool OPEN, bool VALUE>
 __device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full, unsigned long long *cursor, long long *game_base_out, const EmitSym &es,
-                                                const SurpriseDev &sp, const OpenEmit &oe) {
+                                                const SurpriseDev &sp, const OpenEmit &oe, const ValueDev &vt) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.G) return;
     long long base = -1;                                          // the stream index stays 64-bit end to end (2^31 tuples = hours of self-play)
@@ -57,15 +63,27 @@ __device__ __forceinline__ void emit_alloc_body(Dev d, const uint8_t *traj_full,
                 tuples += c * (i < 2 ? 1 : grp);
             }
         }
+        if constexpr (VALUE) {
+            const size_t row = (size_t)g * d.g.state_dim;
+            const int winner = d.winner[g];
+            double G = 0.0;
+            for (int i = n - 1; i >= o; i--) {
+                const double z = winner == -1 ? 0.0 : ((i & 1) == winner ? 1.0 : -1.0);
+                const double v = -vt.traj_q[row + i];
+                G = (1.0 - vt.lam) * v + vt.lam * (i == n - 1 ? z : -G);
+                vt.traj_vt[row + i] = (1.0 - vt.r) * z + vt.r * G;
+            }
+        }
         base = (long long)atomicAdd(cursor, (unsigned long long)tuples);
     }
     d.emit_base[g] = base;
     if (game_base_out) game_base_out[g] = base;
 }
 
-template <bool CAP, bool SYM, bool SURPRISE, bool OPEN>
-__global__ void k_emit_alloc(EmitPack<CAP, SYM, SURPRISE, OPEN> a, unsigned long long *cursor, long long *game_base_out) {
-    emit_alloc_body<CAP, SYM, SURPRISE, OPEN>(a, opt<CapDev>(a).traj_full, cursor, game_base_out, opt<EmitSym>(a), opt<SurpriseDev>(a), opt<OpenEmit>(a));
+template <bool CAP, bool SYM, bool SURPRISE, bool OPEN, bool VALUE>
+__global__ void k_emit_alloc(EmitPack<CAP, SYM, SURPRISE, OPEN, VALUE> a, unsigned long long *cursor, long long *game_base_out) {
+    emit_alloc_body<CAP, SYM, SURPRISE, OPEN, VALUE>(a, opt<CapDev>(a).traj_full, cursor, game_base_out, opt<EmitSym>(a), opt<SurpriseDev>(a), opt<OpenEmit>(a),
+                                                     opt<ValueDev>(a));
 }
 
 __device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
@@ -87,10 +105,11 @@ __device__ __forceinline__ int d4_source(int t, int i, int j, int N) {
 // LIST: the grid walks a list of finished games (asynchronous drain) instead of covering all G.  SURPRISE: the ply's group is written
 // traj_copies[i] times, copy-major, behind the copies of the plies before it (a capped engine's fast plies have 0 copies: traj_full is not read)
 // OPEN: the opening's plies are not written and do not count among the tuples before a ply (their copies are 0 under SURPRISE)
-template <bool LIST, bool CAP, bool SYM, bool SURPRISE, bool OPEN>
+// VALUE: the z of a tuple is the ply's target out of traj_vt, rounded to float32, instead of the outcome
+template <bool LIST, bool CAP, bool SYM, bool SURPRISE, bool OPEN, bool VALUE>
 __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full, float *states, double *pis, float *zs, long long capacity,
                                                  const unsigned long long *cursor, const int *list, const int *n_list, const EmitSym &es,
-                                                 const uint16_t *traj_copies, const OpenEmit &oe) {
+                                                 const uint16_t *traj_copies, const OpenEmit &oe, const double *traj_vt) {
     const int S = d.g.state_dim, A = d.g.action_dim, rc = d.g.rc, F = d.g.planes, N = d.g.rows;
     const int lane = azk_lane();
     const int nb = LIST ? *n_list * S : (int)gridDim.x;
@@ -113,7 +132,8 @@ __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full
     for (int j = lane; j < i; j += AZK_WAVE) cells[acts[j]] = (uint8_t)(1 << (j & 1));
     __syncthreads();
     const int side = i & 1, winner = d.winner[g];
-    const float z = winner == -1 ? 0.0f : (side == winner ? 1.0f : -1.0f);
+    float z = winner == -1 ? 0.0f : (side == winner ? 1.0f : -1.0f);
+    if constexpr (VALUE) z = (float)traj_vt[(size_t)g * S + i];
     const double *pi = d.traj_pi + ((size_t)g * S + i) * A;
     const int grp = SYM ? es.n : 8;
     const int ntr = i < 2 ? 1 : grp;
@@ -152,11 +172,11 @@ __device__ __forceinline__ void emit_tuples_body(Dev d, const uint8_t *traj_full
     }
 }
 
-template <bool LIST, bool CAP, bool SYM, bool SURPRISE, bool OPEN>
-__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(EmitPack<CAP, SYM, SURPRISE, OPEN> a, float *states, double *pis, float *zs, long long capacity,
+template <bool LIST, bool CAP, bool SYM, bool SURPRISE, bool OPEN, bool VALUE>
+__global__ __launch_bounds__(AZK_WAVE) void k_emit_tuples(EmitPack<CAP, SYM, SURPRISE, OPEN, VALUE> a, float *states, double *pis, float *zs, long long capacity,
                                                             const unsigned long long *cursor, const int *list, const int *n_list) {
-    emit_tuples_body<LIST, CAP, SYM, SURPRISE, OPEN>(a, opt<CapDev>(a).traj_full, states, pis, zs, capacity, cursor, list, n_list, opt<EmitSym>(a),
-                                                     opt<SurpriseDev>(a).traj_copies, opt<OpenEmit>(a));
+    emit_tuples_body<LIST, CAP, SYM, SURPRISE, OPEN, VALUE>(a, opt<CapDev>(a).traj_full, states, pis, zs, capacity, cursor, list, n_list, opt<EmitSym>(a),
+                                                            opt<SurpriseDev>(a).traj_copies, opt<OpenEmit>(a), opt<ValueDev>(a).traj_vt);
 }
 
 __global__ void k_emit_mark(Dev d) {
@@ -174,13 +194,13 @@ void azk_launch_emit(azk_engine *e, float *states, double *pis, float *zs, long 
     const unsigned per_game = (unsigned)((d.G + 255) / 256), lds = (unsigned)up16(d.g.rc);
     const int plies = d.G * d.g.state_dim;
     const unsigned blocks = (unsigned)(list && plies > 16384 ? 16384 : plies);
-    with_flags([&](auto by_list, auto cap, auto sym, auto surprise, auto open) {   // sym: emit_elements, the mask's elements on any geometry
-        const EmitPack<cap.value, sym.value, surprise.value, open.value> a{d, on<cap.value>(e->cp), on<sym.value>(e->emit), on<surprise.value>(e->sp),
-                                                                           on<open.value>(OpenEmit{e->op.open_plies})};
-        k_emit_alloc<cap.value, sym.value, surprise.value, open.value><<<per_game, 256, 0, st>>>(a, cursor, game_base);
-        k_emit_tuples<by_list.value, cap.value, sym.value, surprise.value, open.value><<<blocks, AZK_WAVE, lds, st>>>(a, states, pis, zs, capacity, cursor, list,
-                                                                                                                     n_list);
-    }, list != nullptr, e->cp.n_fast != 0, e->emit.n != 0, e->sp_on, e->op_on);
+    with_flags([&](auto by_list, auto cap, auto sym, auto surprise, auto open, auto value) {   // sym: emit_elements, the mask's elements on any geometry
+        const EmitPack<cap.value, sym.value, surprise.value, open.value, value.value> a{d, on<cap.value>(e->cp), on<sym.value>(e->emit), on<surprise.value>(e->sp),
+                                                                                        on<open.value>(OpenEmit{e->op.open_plies}), on<value.value>(e->vt)};
+        k_emit_alloc<cap.value, sym.value, surprise.value, open.value, value.value><<<per_game, 256, 0, st>>>(a, cursor, game_base);
+        k_emit_tuples<by_list.value, cap.value, sym.value, surprise.value, open.value, value.value><<<blocks, AZK_WAVE, lds, st>>>(a, states, pis, zs, capacity,
+                                                                                                                                  cursor, list, n_list);
+    }, list != nullptr, e->cp.n_fast != 0, e->emit.n != 0, e->sp_on, e->op_on, e->vt_on);
     k_emit_mark<<<per_game, 256, 0, st>>>(d);
 }
 

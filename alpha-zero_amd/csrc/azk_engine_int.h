@@ -175,6 +175,17 @@ struct TempDev {
     long long *stats;          // [4] plies drawn by weight, of those not the most-visited child, children cut, plies that fell back (all weights 0)
 };
 
+// value targets (azk_set_value_target, opt-in): every move keeps the root's q = W / N beside traj_pi, and emission writes
+// t_i = (1 - r) * z_i + r * G_i in place of z_i, G the lam-horizon return over the game's own search values (v_i = -q_i), ending in z.  Its own
+// argument block, passed only to the VALUE instantiations of the two movers (azk_moves.hip) and the two emitters (azk_emit.hip): every other
+// argument block - and every kernel an engine without the option launches - stays as it was
+struct ValueDev {
+    double r;                  // weight of the search-based part G in the target, in [0, 1] (0: today's z, q still recorded)
+    double lam;                // horizon of G in [0, 1]: 0 = the ply's own search value (Leela's q-ratio), 1 = z
+    double *traj_q;            // [G][state_dim] q of each ply of the current game, beside traj_pi (the value for the mover's OPPONENT)
+    double *traj_vt;           // [G][state_dim] the plies' targets: written by k_emit_alloc, read by k_emit_tuples
+};
+
 // evaluation under a board symmetry (azk_set_eval_symmetry, opt-in; mode == 0 otherwise): the evaluator is shown each pending
 // leaf in orientation s = the fixed element, or a hash of (seed, the leaf's position), and its logits row is turned back before k_tree expands
 // from it.  Its own argument of the two kernels that exist only for it (azk_sym.hip): every other argument block - and every kernel an engine
@@ -443,6 +454,8 @@ struct azk_engine {
     bool puct_on = false;                // (c_table = [1.0] with mode 0 is a live setting, so the switch is its own word)
     TempDev tp = {};                     // move temperature (azk_set_move_temperature); tp_on == false: off, nothing allocated
     bool tp_on = false;
+    ValueDev vt = {};                    // value targets (azk_set_value_target); vt_on == false: off, nothing allocated
+    bool vt_on = false;                  // (r = 0 is a live setting, so the switch is its own word)
     bool async_on = false;
     int async_recycle = 1;
     SymDev sym = {};                     // evaluation under a board symmetry (azk_set_eval_symmetry); sym.mode == 0: off, nothing allocated

@@ -276,10 +276,13 @@ __device__ __forceinline__ int temp_child(const Dev &d, const LdsView &L, int g,
 // TEMP (engines with a move temperature, azk_set_move_temperature): the move is temp_child's - sample_until is not looked
 // at, the ply table is - and everything after the choice works on that cell as it does on any other; the recorded pi stays the raw (or pruned)
 // visit distribution in L.cnt.
-template <bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false, bool TEMP = false>
+// VALUE (engines with value targets, azk_set_value_target): the root's q = W / N - the expression of k_root_stats, the
+// asynchronous record and resignation, the value for the mover's opponent - goes into traj_q beside traj_pi (lane 0 writes it); the move itself
+// and everything else recorded are what they are without the option.
+template <bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false, bool TEMP = false, bool VALUE = false>
 __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool have_u, double u, int sample_until, int *win_out, int *done_out,
                                            int *sum_out, const ResignDev &rs, int key, int *rsg_out, const ForcedDev &fp, const SurpriseDev &sp,
-                                           const GumbelDev &gb = GumbelDev{}, const TempDev &tm = TempDev{}) {
+                                           const GumbelDev &gb = GumbelDev{}, const TempDev &tm = TempDev{}, const ValueDev &vt = ValueDev{}) {
     const int lane = azk_lane();
     const GameDesc &gd = d.g;
     const size_t base = (size_t)g * d.cap;
@@ -358,6 +361,7 @@ __device__ __forceinline__ int advance_one(const Dev &d, LdsView &L, int g, bool
         else
         for (int a = lane; a < A; a += AZK_WAVE) tp[a] = (double)L.cnt[a] / (double)sum;
         if (lane == 0) d.traj_action[(size_t)g * gd.state_dim + mc] = (int16_t)cellc;
+        if constexpr (VALUE) { if (lane == 0) vt.traj_q[(size_t)g * gd.state_dim + mc] = d.W[base] / (double)d.H[base].N; }
     }
     if constexpr (SURPRISE) {
         const double kl = surprise_kl(d, L, g, sum), coin = surprise_coin(sp, g, key);
@@ -418,11 +422,11 @@ __device__ __forceinline__ int played_child(const Dev &d, int g, int cellc) {
 }
 
 // The lock-step mover (azk_advance, azk_advance_resign): every game's move, one wave per game.  CAP: the ply's kind goes into traj_full beside its
-// pi; RESIGN, SURPRISE (move_index = the slot's move counter), FORCED, TEMP: as advance_one has them
-template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false, bool TEMP = false>
+// pi; RESIGN, SURPRISE (move_index = the slot's move counter), FORCED, TEMP, VALUE: as advance_one has them
+template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false, bool TEMP = false, bool VALUE = false>
 __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int move_index, const double *uniforms, int sample_until,
                                              int *chosen, int *winner_out, int *done_out, int *chosen_node, const ForcedDev &fp, const SurpriseDev &sp,
-                                             const GumbelDev &gb = GumbelDev{}, const TempDev &tm = TempDev{}) {
+                                             const GumbelDev &gb = GumbelDev{}, const TempDev &tm = TempDev{}, const ValueDev &vt = ValueDev{}) {
     const int g = blockIdx.x, lane = azk_lane();
     LdsView L = carve(d.g, d.path_cap, d.table_size);
     if (uniform_i32(d.done[g]) != 0) {
@@ -438,8 +442,8 @@ __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int
     const int mc = CAP ? uniform_i32(d.move_count[g]) : 0;
     int cellc;
     if constexpr (GUMBEL) cellc = advance_one<RESIGN, false, false, true>(d, L, g, false, 0.0, 0, &win, &dn, &sum, rs, move_index, &rsg, fp, sp, gb);
-    else cellc = advance_one<RESIGN, FORCED, SURPRISE, false, TEMP>(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum,
-                                                            rs, move_index, &rsg, fp, sp, GumbelDev{}, tm);
+    else cellc = advance_one<RESIGN, FORCED, SURPRISE, false, TEMP, VALUE>(d, L, g, uniforms != nullptr, uniforms != nullptr ? uniforms[g] : 0.0, sample_until, &win, &dn, &sum,
+                                                            rs, move_index, &rsg, fp, sp, GumbelDev{}, tm, vt);
     if (CAP && cellc >= 0 && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = cp.search_full[g];
     if (chosen_node) {
         const int child = played_child(d, g, cellc);               // tree reuse: the next search's root
@@ -457,13 +461,14 @@ __device__ __forceinline__ void advance_body(Dev d, CapDev cp, ResignDev rs, int
 template <bool KEYED> struct Ply { int sample_until; };
 template <> struct Ply<true> { int sample_until, move_index; };
 
-template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool TEMP>
-__global__ __launch_bounds__(AZK_WAVE) void k_advance(MovePack<Dev, CAP, RESIGN, FORCED, SURPRISE, TEMP> a, const double *uniforms, Ply<RESIGN || SURPRISE> ply,
+template <bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool TEMP, bool VALUE>
+__global__ __launch_bounds__(AZK_WAVE) void k_advance(MovePack<Dev, CAP, RESIGN, FORCED, SURPRISE, TEMP, VALUE> a, const double *uniforms, Ply<RESIGN || SURPRISE> ply,
                                                        int *chosen, int *winner_out, int *done_out, int *chosen_node) {
     int move_index = 0;
     if constexpr (RESIGN || SURPRISE) move_index = ply.move_index;
-    advance_body<CAP, RESIGN, FORCED, SURPRISE, false, TEMP>(a, opt<CapDev>(a), opt<ResignDev>(a), move_index, uniforms, ply.sample_until, chosen, winner_out,
-                                                             done_out, chosen_node, opt<ForcedDev>(a), opt<SurpriseDev>(a), GumbelDev{}, opt<TempDev>(a));
+    advance_body<CAP, RESIGN, FORCED, SURPRISE, false, TEMP, VALUE>(a, opt<CapDev>(a), opt<ResignDev>(a), move_index, uniforms, ply.sample_until, chosen, winner_out,
+                                                                    done_out, chosen_node, opt<ForcedDev>(a), opt<SurpriseDev>(a), GumbelDev{}, opt<TempDev>(a),
+                                                                    opt<ValueDev>(a));
 }
 
 // the lock-step mover of an engine with a Gumbel root (with or without resignation)
@@ -493,10 +498,10 @@ __global__ __launch_bounds__(AZK_WAVE) void k_advance(GumbelPack<Dev, RESIGN> a,
 // ------------------------------------------------------------------------------------------------
 // The asynchronous mover.  REROOT: a re-rooting engine - the moved game is parked for the drain's k_reroot_list instead of beginning its search
 // here; CAP: the kind of the completed search goes into the record and traj_full, and the next fresh-root search flips its coin; RESIGN, FORCED:
-// SURPRISE, TEMP: as advance_one has them (the move key is the slot's move counter; kl and coin go into the record's columns too)
-template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false, bool TEMP = false>
+// SURPRISE, TEMP, VALUE: as advance_one has them (the move key is the slot's move counter; kl and coin go into the record's columns too)
+template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool GUMBEL = false, bool TEMP = false, bool VALUE = false>
 __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, CapDev cp, ResignDev rs, const ForcedDev &fp, const SurpriseDev &sp,
-                                                const GumbelDev &gb = GumbelDev{}, const TempDev &tm = TempDev{}) {
+                                                const GumbelDev &gb = GumbelDev{}, const TempDev &tm = TempDev{}, const ValueDev &vt = ValueDev{}) {
     const int g = blockIdx.x, lane = azk_lane();
     // one vector load for the three words that decide whether this game moves now (almost never: the wave then ends at once)
     const int *up = d.done + g;
@@ -523,7 +528,7 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
     const int kind = CAP ? uniform_i32((int)cp.search_full[g]) : 1;     // of the search that is complete
     int cellc;
     if constexpr (GUMBEL) cellc = advance_one<RESIGN, false, false, true>(d, L, g, false, 0.0, 0, &win, &dn, &sum, rs, (int)mv, &rsg, fp, sp, gb);
-    else cellc = advance_one<RESIGN, FORCED, SURPRISE, false, TEMP>(d, L, g, true, u, p.sample_until, &win, &dn, &sum, rs, (int)mv, &rsg, fp, sp, GumbelDev{}, tm);
+    else cellc = advance_one<RESIGN, FORCED, SURPRISE, false, TEMP, VALUE>(d, L, g, true, u, p.sample_until, &win, &dn, &sum, rs, (int)mv, &rsg, fp, sp, GumbelDev{}, tm, vt);
     if (cellc < 0) return;
     if (CAP && lane == 0 && cp.traj_full != nullptr && mc < d.g.state_dim) cp.traj_full[(size_t)g * d.g.state_dim + mc] = (uint8_t)kind;
     if (p.rec_cap > 0) {                                           // the move's record: what the reference's self_play keeps per ply
@@ -565,10 +570,10 @@ __device__ __forceinline__ void move_async_body(Dev d, AsyncDev p, ReuseDev r, C
     }
 }
 
-template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool TEMP>
-__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, MovePack<ReuseDev, CAP, RESIGN, FORCED, SURPRISE, TEMP> r) {
-    move_async_body<REROOT, CAP, RESIGN, FORCED, SURPRISE, false, TEMP>(d, p, r, opt<CapDev>(r), opt<ResignDev>(r), opt<ForcedDev>(r), opt<SurpriseDev>(r),
-                                                                        GumbelDev{}, opt<TempDev>(r));
+template <bool REROOT, bool CAP, bool RESIGN, bool FORCED, bool SURPRISE, bool TEMP, bool VALUE>
+__global__ __launch_bounds__(AZK_WAVE) void k_move_async(Dev d, AsyncDev p, MovePack<ReuseDev, CAP, RESIGN, FORCED, SURPRISE, TEMP, VALUE> r) {
+    move_async_body<REROOT, CAP, RESIGN, FORCED, SURPRISE, false, TEMP, VALUE>(d, p, r, opt<CapDev>(r), opt<ResignDev>(r), opt<ForcedDev>(r), opt<SurpriseDev>(r),
+                                                                               GumbelDev{}, opt<TempDev>(r), opt<ValueDev>(r));
 }
 
 // the asynchronous mover of an engine with a Gumbel root (no re-rooting, no cap; with or without resignation)
@@ -640,13 +645,13 @@ static int32_t advance(azk_engine *e, const double *uniforms_dev, int32_t sample
         HIPCHK(e, hipGetLastError());
         return AZK_OK;
     }
-    with_flags([&](auto cap, auto resign, auto forced, auto surprise, auto temp) {
+    with_flags([&](auto cap, auto resign, auto forced, auto surprise, auto temp, auto value) {
         Ply<resign.value || surprise.value> ply{sample_until_move};
         if constexpr (resign.value || surprise.value) ply.move_index = move_index;
-        k_advance<cap.value, resign.value, forced.value, surprise.value, temp.value><<<d.G, AZK_WAVE, d.lds_bytes, (hipStream_t)stream>>>(
-            move_pack<cap.value, resign.value, forced.value, surprise.value, temp.value>(d, e), uniforms_dev, ply, chosen_cell_dev, winner_dev, done_dev,
-            e->ru.chosen_node);
-    }, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0, e->sp_on, e->tp_on);
+        k_advance<cap.value, resign.value, forced.value, surprise.value, temp.value, value.value><<<d.G, AZK_WAVE, d.lds_bytes, (hipStream_t)stream>>>(
+            move_pack<cap.value, resign.value, forced.value, surprise.value, temp.value, value.value>(d, e), uniforms_dev, ply, chosen_cell_dev, winner_dev,
+            done_dev, e->ru.chosen_node);
+    }, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0, e->sp_on, e->tp_on, e->vt_on);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -762,10 +767,10 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
             k_move_async<resign.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, GumbelPack<ReuseDev, resign.value>{e->ru, on<resign.value>(e->rs), on<true>(e->gb)});
         }, e->rs.v_resign != 0.0);
     else if (phases & 2)
-        with_flags([&](auto reroot, auto cap, auto resign, auto forced, auto surprise, auto temp) {
-            k_move_async<reroot.value, cap.value, resign.value, forced.value, surprise.value, temp.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(
-                d, e->ad, move_pack<cap.value, resign.value, forced.value, surprise.value, temp.value>(e->ru, e));
-        }, e->ru.mode != 0, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0, e->sp_on, e->tp_on);
+        with_flags([&](auto reroot, auto cap, auto resign, auto forced, auto surprise, auto temp, auto value) {
+            k_move_async<reroot.value, cap.value, resign.value, forced.value, surprise.value, temp.value, value.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(
+                d, e->ad, move_pack<cap.value, resign.value, forced.value, surprise.value, temp.value, value.value>(e->ru, e));
+        }, e->ru.mode != 0, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0, e->sp_on, e->tp_on, e->vt_on);
     HIPCHK(e, hipGetLastError());
     return azk_sym_leaves(e, st);                                 // (eval symmetry: the leaves the tree launch selected, behind the movers)
 }

@@ -1,5 +1,5 @@
 // azk_options.hip - the opt-ins' state calls (include/azk.h): set, clear and read playout cap, forced playouts, Gumbel root, resignation,
-// surprise weighting, random openings and the move temperature.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
+// surprise weighting, random openings, the move temperature and value targets.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
 // block (azk_engine_int.h) that azk_opt_pack.h hands to the kernels of azk_begin.hip, azk_moves.hip and azk_emit.hip.
 #include "azk_engine_int.h"
 #include <algorithm>
@@ -98,6 +98,7 @@ int32_t azk_set_gumbel_root(azk_engine *e, int32_t m, int32_t n_sims, double c_v
     if (e->sp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with surprise weighting (its recorded pi is not a visit distribution)"; return AZK_ERR_STATE; }
     if (e->puct_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with configurable PUCT (azk_set_puct: its root selection is not PUCT)"; return AZK_ERR_STATE; }
     if (e->tp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with a move temperature (azk_set_move_temperature: the Gumbel arg-max is the sample)"; return AZK_ERR_STATE; }
+    if (e->vt_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with value targets (azk_set_value_target: the Gumbel movers do not keep the per-ply q)"; return AZK_ERR_STATE; }
     const Dev &d = e->d;
     GumbelDev &gb = e->gb;
     hipStream_t st = (hipStream_t)stream;
@@ -312,6 +313,43 @@ int32_t azk_async_surprise_columns(azk_engine *e, double *rec_kl_dev, double *re
     if (!e->sp_on) { e->err = "azk_async_surprise_columns: no surprise weighting is set (azk_set_surprise_weighting)"; return AZK_ERR_STATE; }
     if (e->async_on) { e->err = "azk_async_surprise_columns: call it before azk_async_begin"; return AZK_ERR_STATE; }
     e->sp.rec_kl = rec_kl_dev; e->sp.rec_coin = rec_coin_dev;
+    return AZK_OK;
+}
+
+// ---- value targets ---------------------------------------------------------------------------------------------------------
+int32_t azk_set_value_target(azk_engine *e, double r, double lam, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_value_target: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (e->gb.m) { e->err = "azk_set_value_target: a Gumbel root is set - its movers do not keep the per-ply q (a follow-up, DESIGN section 28)"; return AZK_ERR_STATE; }
+    if (!(r >= 0.0 && r <= 1.0)) { e->err = "azk_set_value_target: r must lie in [0, 1] (azk_clear_value_target switches the option off)"; return AZK_ERR_ARG; }
+    if (!(lam >= 0.0 && lam <= 1.0)) { e->err = "azk_set_value_target: lam must lie in [0, 1]"; return AZK_ERR_ARG; }
+    if (e->d.K > 1) { e->err = "azk_set_value_target: value targets do not combine with leaves_per_step > 1 (a virtual-loss search is another search: its q is not the one the target was defined on)"; return AZK_ERR_ARG; }
+    const Dev &d = e->d;
+    if (!d.traj_pi) { e->err = "azk_set_value_target: the engine records no trajectories (a square board with one action per cell, or an engine created with emit_elements)"; return AZK_ERR_ARG; }
+    ValueDev &v = e->vt;
+    const size_t plies = (size_t)d.G * d.g.state_dim;
+    if (!v.traj_q) {
+        HIPCHK(e, dalloc(e, &v.traj_q, plies));
+        HIPCHK(e, dalloc(e, &v.traj_vt, plies));
+    }
+    HIPCHK(e, hipMemsetAsync(v.traj_q, 0, sizeof(double) * plies, (hipStream_t)stream));
+    HIPCHK(e, hipMemsetAsync(v.traj_vt, 0, sizeof(double) * plies, (hipStream_t)stream));
+    v.r = r; v.lam = lam;
+    e->vt_on = true;
+    return AZK_OK;
+}
+
+int32_t azk_clear_value_target(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_value_target: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    e->vt_on = false;                                             // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+int32_t azk_get_value_record(azk_engine *e, double *q_out_dev, void *stream) {
+    if (!e || !q_out_dev) return AZK_ERR_ARG;
+    if (!e->vt_on) { e->err = "azk_get_value_record: no value target is set (azk_set_value_target)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(q_out_dev, e->vt.traj_q, sizeof(double) * (size_t)e->d.G * e->d.g.state_dim, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return AZK_OK;
 }
 

@@ -284,6 +284,58 @@ def surprise_copies(kl, coin, lam, full=None):
     return out
 
 
+def check_value_target(value_target, evaluator=True, leaves_per_step=1, gumbel_root=None):
+    """value_target = r | (r, lam) -> (r, lam), floats in [0, 1], or None for off.  OPT-IN value targets (include/azk.h azk_set_value_target;
+    DESIGN section 28): the z of every emitted tuple becomes (1 - r) * z + r * G, G the horizon-lam return over the game's own search values
+    that ends in z (value_targets).  A number r means (r, 0.0), Leela's q-ratio; (1, lam) is a TD(lambda) return; r = 0 is a live setting
+    (today's ring; q is still recorded).  Raises ValueError, before any engine exists, for what the engine refuses too - r or lam outside
+    [0, 1] or NaN, virtual loss, a Gumbel root (its movers do not keep q) - and for vanilla MCTS (evaluator None), whose q is a rollout mean."""
+    if value_target is None:
+        return None
+    try:
+        if isinstance(value_target, bool):
+            raise TypeError
+        if isinstance(value_target, (tuple, list)):
+            r, lam = value_target
+            if isinstance(r, bool) or isinstance(lam, bool):
+                raise TypeError
+            r, lam = float(r), float(lam)
+        else:
+            r, lam = float(value_target), 0.0
+    except (TypeError, ValueError):
+        raise ValueError(f"value_target must be a number r or a pair (r, lam), both in [0, 1], not {value_target!r}")
+    if not (0.0 <= r <= 1.0 and 0.0 <= lam <= 1.0):             # (NaN fails every comparison)
+        raise ValueError(f"value_target: r and lam must lie in [0, 1] (None switches the option off), not {value_target!r}")
+    if _is_vanilla(evaluator):
+        raise ValueError("value_target: vanilla MCTS (evaluator None) is refused - its q is a rollout mean, not a search value to train on")
+    if int(leaves_per_step) > 1:
+        raise ValueError("value_target does not combine with leaves_per_step > 1 (a virtual-loss search is another search: its q is not the one the target was defined on)")
+    if gumbel_root is not None:
+        raise ValueError("value_target does not combine with gumbel_root (the Gumbel movers do not keep the per-ply q)")
+    return r, lam
+
+
+def value_targets(qs, winner, first_ply, r, lam):
+    """The emission rule of value targets for one finished game, for host buffers (train.save_data_to_buffer(values=...)): qs = the game's
+    per-ply q (SelfPlayResult.qs: root W / N at each move, the value for the mover's OPPONENT), the game's first searched ply first_ply
+    (SelfPlayResult.open_plies), winner 0 / 1 / -1.  -> float64 array, one target per ply of qs: with v_i = -q_i and z_i the outcome from the
+    mover's view (ply first_ply + i is moved by side (first_ply + i) & 1),
+        G_last = (1 - lam) * v_last + lam * z_last,    G_i = (1 - lam) * v_i + lam * (-G_{i+1}),    t_i = (1 - r) * z_i + r * G_i
+    in float64, operation for operation what k_emit_alloc computes (the ring stores np.float32(t_i))."""
+    qs = np.asarray(qs, np.float64)
+    r, lam = np.float64(r), np.float64(lam)
+    one = np.float64(1.0)
+    out = np.zeros(len(qs), np.float64)
+    G = np.float64(0.0)
+    for i in range(len(qs) - 1, -1, -1):
+        side = (int(first_ply) + i) & 1
+        z = np.float64(0.0 if winner == -1 else (1.0 if side == winner else -1.0))
+        v = -qs[i]
+        G = (one - lam) * v + lam * (z if i == len(qs) - 1 else -G)
+        out[i] = (one - r) * z + r * G
+    return out
+
+
 def board_cells(game, size=None):
     """rows * cols of a game's board (its state_dim)."""
     if game == "tictactoe":
@@ -380,7 +432,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
                     budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
                     eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None,
-                    openings_first_game=None, puct=None, move_temperature=None):
+                    openings_first_game=None, puct=None, move_temperature=None, value_target=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -416,7 +468,9 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     ("reduction", r_tree[, r_root])); with an (evaluator0, evaluator1) pair both sides search under it.  move_temperature (OPT-IN,
     check_move_temperature): a schedule tau, or dict(tau=, visit_offset=, value_cutoff=) - every move is picked by the engine's weight table
     instead of "sample in proportion to the visits while move_count < sample_until", which is then not looked at; the recorded pis stay the raw
-    visit distributions.  ("until", 1.0, sample_until) plays the games of a call without the option.
+    visit distributions.  ("until", 1.0, sample_until) plays the games of a call without the option.  value_target = r | (r, lam) (OPT-IN,
+    check_value_target): the replay ring gets (1 - r) * z + r * G as the z of every tuple, G the horizon-lam return over the game's own search
+    values (value_targets(SelfPlayResult.qs, ...) is the same rule on the host); the games, states and pis do not change.
     """
     import torch
     opn = check_openings(openings, game, size, evaluator)
@@ -436,6 +490,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     pct = puct if check_puct(puct, evaluator, leaves_per_step, fpk, gum) is not None else None
     tmp = check_move_temperature(move_temperature, engine.max_sims if engine is not None else n_sims, game, size, gum,
                                  engine.tree_reuse if engine is not None else tree_reuse)
+    vtg = check_value_target(value_target, evaluator, leaves_per_step, gum)
     _refuse_vanilla_resign(rsg, evaluator)
     if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
@@ -459,6 +514,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         eng.set_puct(*pct)
     if tmp is not None:
         eng.set_move_temperature(*tmp)
+    if vtg is not None:
+        eng.set_value_target(*vtg)
     # virtual-loss, top-up and capped engines are driven by the simulation budget
     budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
     assert eng.G == n_games
@@ -693,6 +750,10 @@ class SelfPlayRunner:
     move_temperature (OPT-IN, check_move_temperature; with everything above except gumbel_root and tree_reuse = 1): a schedule tau or
     dict(tau=, visit_offset=, value_cutoff=) - every move is picked by the engine's weight table instead of the reference's "sample while
     move_count < sample_until"; the records' pis stay raw visit distributions.  move_temperature_stats() sums the groups' four counters.
+
+    value_target = r | (r, lam) (OPT-IN, check_value_target; with everything above except gumbel_root and leaves_per_step > 1): the replay ring
+    gets (1 - r) * z + r * G as the z of every tuple, G the horizon-lam return over the game's own search values (value_targets); the games,
+    the records, states and pis do not change.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
@@ -701,11 +762,12 @@ class SelfPlayRunner:
                  steps_per_graph=32,
                  leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None,
                  surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None, openings_first_game=None, puct=None,
-                 move_temperature=None):
+                 move_temperature=None, value_target=None):
         import torch
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, playout_cap, forced_playouts,
                                              surprise_weight)
+        self.value_target = check_value_target(value_target, evaluator, leaves_per_step, self.gumbel_root)
         self.move_temperature = check_move_temperature(move_temperature, n_sims, game, size, self.gumbel_root, tree_reuse)
         self.puct = puct if check_puct(puct, evaluator, leaves_per_step, forced_playouts, gumbel_root) is not None else None
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
@@ -768,6 +830,8 @@ class SelfPlayRunner:
                 h.eng.set_puct(*self.puct)
             if self.move_temperature is not None:
                 h.eng.set_move_temperature(*self.move_temperature)
+            if self.value_target is not None:
+                h.eng.set_value_target(*self.value_target)
             if self.openings is not None:                         # the first games, under the key of their first search (move 0)
                 h.eng.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                                    (first_global_game if openings_first_game is None else openings_first_game) + i * per)
@@ -1063,16 +1127,21 @@ class AsyncSelfPlayRunner:
     slot for slot - the rule reads only what the tree stores, so the movers and the re-root need nothing of it.
 
     move_temperature (OPT-IN, check_move_temperature; with everything above except gumbel_root and reroot = 1): the games of
-    SelfPlayRunner(move_temperature=...), slot for slot - the movers draw from the same table with the same uniforms."""
+    SelfPlayRunner(move_temperature=...), slot for slot - the movers draw from the same table with the same uniforms.
+
+    value_target = r | (r, lam) (OPT-IN, check_value_target; with everything above except gumbel_root): the games of SelfPlayRunner, slot for
+    slot, and the drain writes (1 - r) * z + r * G as the z of every tuple - the mover keeps each ply's q beside its pi, with re-rooting the
+    carried root's W / N as it stands; the record ring's q column holds the same numbers."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
                  playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None,
-                 openings=None, openings_seed=None, openings_first_game=None, puct=None, move_temperature=None):
+                 openings=None, openings_seed=None, openings_first_game=None, puct=None, move_temperature=None, value_target=None):
         import torch
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, 1, tree_reuse or reroot, playout_cap, forced_playouts, surprise_weight)
+        self.value_target = check_value_target(value_target, evaluator, 1, self.gumbel_root)
         self.move_temperature = check_move_temperature(move_temperature, n_sims, game, size, self.gumbel_root, tree_reuse or reroot)
         self.puct = puct if check_puct(puct, evaluator, 1, forced_playouts, gumbel_root) is not None else None
         self.emit_elements = check_emit_symmetry(emit_symmetry, game, size)
@@ -1117,6 +1186,8 @@ class AsyncSelfPlayRunner:
             e.set_puct(*self.puct)
         if self.move_temperature is not None:
             e.set_move_temperature(*self.move_temperature)
+        if self.value_target is not None:
+            e.set_value_target(*self.value_target)
         if self.openings is not None:                             # async_begin opens the first games, the drain's restart every later one
             e.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                            first_global_game if openings_first_game is None else openings_first_game)

@@ -74,7 +74,7 @@ def _add_group(Game, buffer, canon, policy, target, i, elements):
                 buffer.add(fb, fp, target)
 
 
-def save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=None, first_ply=0):
+def save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=None, first_ply=0, values=None):
     """train.py:30-49: z = +reward for the winner's positions, -reward for the loser's; canonical boards; positions 0 and 1
     once, every later position with its 8 dihedral images in the reference's order.  full (playout cap, SelfPlayResult.full): one flag
     per position; the positions of fast searches are left out, the others keep the group they would have had.  elements (OPT-IN; None:
@@ -84,11 +84,15 @@ def save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=Non
     after copy, what an engine with surprise weighting puts into a DeviceReplay; a position with 0 copies is left out.  first_ply (OPT-IN random
     openings, SelfPlayResult.open_plies; 0: the reference's code path): boards[0] is the game's position at ply first_ply - the plies of its
     opening had no search and are not in `data` - so the side to move starts at first_ply & 1 and the once-or-group rule goes by the absolute
-    ply first_ply + i: what an engine with openings puts into a DeviceReplay."""
+    ply first_ply + i: what an engine with openings puts into a DeviceReplay.  values (OPT-IN value targets; None: the reference's code path):
+    one float64 target per position (selfplay.value_targets) that replaces [+-reward] in every tuple of the position - each image, each copy:
+    what an engine with value targets puts into a DeviceReplay, which keeps it as float32."""
     boards, actions, policies, qs, winner, reward = data
     current = int(first_ply) & 1
     for i in range(len(boards)):
         target = [reward] if current == winner else [-reward]
+        if values is not None:
+            target = [float(values[i])]
         canon = Game.get_canonical_board(boards[i], current)
         current = 1 - current
         if full is not None and not full[i]:
@@ -99,7 +103,7 @@ def save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=Non
 
 def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed=None, batched=True, playout_cap=None, resign=None,
                  forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, puct=None,
-                 move_temperature=None):
+                 move_temperature=None, value_target=None):
     """train.py:54-83: `iterations` self-play games of Game with `model` into `buffer`; returns [first, second, draw] counts.
     batched=False plays the games one after the other through Game().self_play and save_data_to_buffer exactly as the
     reference does (global np.random stream: a seeded caller gets the reference's buffer); the default plays them as one
@@ -118,14 +122,18 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     selfplay.check_openings): a game starts, with probability p_open, from a position a few drawn plies in; neither buffer kind gets those plies.
     puct = (c, fpu) (OPT-IN, batched only; selfplay.check_puct): every search selects with the exploration rate c and the first-play urgency fpu.
     move_temperature (OPT-IN, batched only; selfplay.check_move_temperature): a schedule tau or dict(tau=, visit_offset=, value_cutoff=) picks
-    every move; both buffer kinds still get the raw visit distribution as pi."""
+    every move; both buffer kinds still get the raw visit distribution as pi.  value_target = r | (r, lam) (OPT-IN, batched only;
+    selfplay.check_value_target): the z of every stored position is (1 - r) * z + r * G, G the horizon-lam return over the game's search
+    values (selfplay.value_targets); both buffer kinds get the same targets, and the trainer's mse loss takes them as they are."""
     from azk import DeviceReplay
-    from selfplay import check_emit_symmetry, check_surprise_weight, mask_elements, self_play_batch, surprise_copies
+    from selfplay import (check_emit_symmetry, check_surprise_weight, check_value_target, mask_elements, self_play_batch, surprise_copies,
+                          value_targets)
     lam = check_surprise_weight(surprise_weight, model)
+    vtg = check_value_target(value_target, model)
     if not batched:
         for name, value in (("surprise_weight", lam), ("emit_symmetry", emit_symmetry), ("playout_cap", playout_cap), ("resign", resign),
                             ("forced_playouts", forced_playouts), ("gumbel_root", gumbel_root), ("openings", openings), ("puct", puct),
-                            ("move_temperature", move_temperature),
+                            ("move_temperature", move_temperature), ("value_target", vtg),
                             ("eval_symmetry", None if eval_symmetry is False else eval_symmetry)):
             if value is not None:
                 raise ValueError(f"collect_data: {name} needs the batched engine (batched=True)")
@@ -143,7 +151,7 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     res = self_play_batch(Game.engine_name, model, iterations, mcts_iter, size=Game._size(), seed=seed, leaf_dtype=leaf_dtype,
                           replay=buffer if on_device else None, playout_cap=playout_cap, resign=resign, forced_playouts=forced_playouts,
                           eval_symmetry=eval_symmetry, emit_symmetry=emit_symmetry, surprise_weight=surprise_weight, gumbel_root=gumbel_root,
-                          openings=openings, puct=puct, move_temperature=move_temperature)
+                          openings=openings, puct=puct, move_temperature=move_temperature, value_target=value_target)
     emit = check_emit_symmetry(emit_symmetry, Game.engine_name, Game._size())
     results = [0, 0, 0]
     for r in res:
@@ -153,7 +161,8 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
             full = r.full if playout_cap is not None else None
             save_data_to_buffer(Game, buffer, (r.boards, r.actions, r.pis, r.qs, r.winner, reward), full=full,
                                 elements=mask_elements(emit) if emit else None,
-                                copies=surprise_copies(r.kl, r.coin, lam, full) if lam is not None else None, first_ply=r.open_plies)
+                                copies=surprise_copies(r.kl, r.coin, lam, full) if lam is not None else None, first_ply=r.open_plies,
+                                values=value_targets(r.qs, r.winner, r.open_plies, *vtg) if vtg is not None else None)
         if display:
             Game.display_board(r.boards[-1])
     return results

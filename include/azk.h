@@ -505,6 +505,32 @@ int32_t azk_set_move_temperature(azk_engine *e, const int32_t *row_of_ply_host, 
 int32_t azk_clear_move_temperature(azk_engine *e);
 int32_t azk_get_move_temperature_stats(azk_engine *e, int64_t *out4_host, void *stream);
 
+/* ---- value targets: the outcome blended with the game's own search values at emission (OPT-IN; off, the engine launches exactly the
+ * kernels it launched before).  azk_emit_finished and azk_async_drain otherwise write z = +1 / -1 / 0 by the final winner into every tuple
+ * of a game.  With the option the movers (azk_advance*, the asynchronous movers) keep q = W[root] / (double)N[root] of every move beside
+ * its pi - the expression of azk_root_stats, the asynchronous record's q and resignation: the value for the OPPONENT of the side to move -
+ * and emission writes a target t in place of z, all float64.  For a finished game of n plies whose first searched ply
+ * is o (its opening plies with random openings, else 0), and i = o .. n - 1:
+ *   v_i = -q_i                                     the mover's own search value
+ *   z_i = +1 / -1 / 0                              what emission writes without the option: the final winner from ply i's mover's view
+ *   G_{n-1} = (1 - lam) * v_{n-1} + lam * z_{n-1}
+ *   G_i     = (1 - lam) * v_i + lam * (-G_{i+1})   from the last ply down; the side to move alternates, hence the sign
+ *   t_i     = (1 - r) * z_i + r * G_i              written to zs as (float)t_i
+ * r in [0, 1] is the weight of the search-based part, lam in [0, 1] its horizon: (r, 0) is Leela's q-ratio, (1, lam) a TD(lambda) return
+ * over search values that ends in z, and (0, any lam) and (1, 1) write today's ring byte for byte (a draw keeps +0.0).  Every searched ply
+ * takes part in the recurrence, a capped engine's fast plies too; opening plies had no search and are never reached.  Every tuple of a ply -
+ * each element of its group, each copy under surprise weighting - carries the same target; states and pis do not change.  With tree reuse
+ * and re-rooting q is the carried root's W / N as it stands; a resigned game is an ordinary finished game.
+ * azk_set_value_target allocates the two [n_games][state_dim] float64 arrays on first use and zero-fills them.  AZK_ERR_ARG: r or lam NaN or
+ * outside [0, 1]; an engine that records no trajectories; leaves_per_step > 1 (a virtual-loss search is another search).  AZK_ERR_STATE:
+ * after azk_async_begin; with a Gumbel root set (its movers do not keep q) - azk_set_gumbel_root refuses likewise while the option is set.
+ * azk_clear_value_target makes the engine launch what it launched before (AZK_ERR_STATE after azk_async_begin).  azk_get_value_record
+ * copies the q of the current games' plies, float64 [n_games][state_dim], to q_out_dev on the stream: row g holds game g's plies up to its
+ * move count, older entries are what earlier games in the slot left (AZK_ERR_STATE while the option is off). */
+int32_t azk_set_value_target(azk_engine *e, double r, double lam, void *stream);
+int32_t azk_clear_value_target(azk_engine *e);
+int32_t azk_get_value_record(azk_engine *e, double *q_out_dev, void *stream);
+
 /* ---- random openings (OPT-IN; off, the engine launches exactly the kernels it launched before).  Every game otherwise starts from the
  * empty board and differs from its neighbours only through root noise and move sampling; with the option a game that starts in slot g is,
  * with probability p_open, played forward 1..max_plies uniformly drawn legal plies inside a centred window before its first search (KataGo's

@@ -107,7 +107,8 @@ def test_cls_attention_kernel_vs_torch():
 def test_layernorm_rows_and_heads_finalize_vs_torch_fp32(D):
     """azk_nn_layernorm_rows / azk_nn_heads_finalize against the plain fp32 ops on the same bf16 inputs.
     Tolerance: outputs are rounded once to bf16 (2^-8 relative) -> 1e-2 absolute on O(1) values.
-    k_ln_rows to half a bf16 ulp of float64, constant / large-mean / one-hot rows, n < 4: tests/test_gpu_block_pinned.py."""
+    k_ln_rows to half a bf16 ulp of float64, constant / large-mean / one-hot rows, n < 4: tests/test_gpu_block_pinned.py.
+    k_heads_finalize bit for bit with ld = A + 1, live counts and the grid-stride loop's second trip: tests/test_gpu_rows_pinned.py."""
     import azk
     torch.manual_seed(D)
     n = 301
@@ -183,7 +184,8 @@ def test_fused_embed_pool_vs_torch_fp32(static_ref):
 
 def test_fused_final_norm_and_heads_vs_torch_fp32():
     """azk_nn_ln_heads (final LayerNorm + merged policy/value head + tanh in one launch, the default cls tail) against
-    fp32 PyTorch on the same bf16 input: logits to 2e-2 (bf16 operands, scale ~0.5), value to 5e-3; honours the row count."""
+    fp32 PyTorch on the same bf16 input: logits to 2e-2 (bf16 operands, scale ~0.5), value to 5e-3; honours the row count.
+    Exact probes, D = 256, every action_dim and row edge, the second grid-stride trip and float64 bounds: tests/test_gpu_rows_pinned.py."""
     import azk
     cfg = NetConfig(15, 15, 2, 225, 5, 512, 8, 1)
     net = PolicyValueNet(cfg, seed=4, device="cuda", dtype=torch.bfloat16, path="clsfold")

@@ -46,6 +46,7 @@ SYMBOLS = [
     "azk_set_puct", "azk_clear_puct",
     "azk_set_move_temperature", "azk_clear_move_temperature", "azk_get_move_temperature_stats",
     "azk_set_value_target", "azk_clear_value_target", "azk_get_value_record",
+    "azk_export_tree_quotients", "azk_debug_fill_quotients",
 ]
 
 
@@ -876,13 +877,25 @@ class Engine:
         n = self._chk(self.L.azk_root_children(self.h, int(game), cap, _np(cells), _np(visits), _np(values), _np(priors), _stream()))
         return dict(cell=cells[:n].copy(), visit=visits[:n].astype(np.int64), value=values[:n].copy(), prior=priors[:n].copy())
 
-    def export_tree(self, game, cap=None):
+    def export_tree(self, game, cap=None, quotient=False):
+        """The game's tree, DFS pre-order.  quotient=True adds the engine's quotient column (value / visit where visit > 0, bit for bit;
+        unspecified where visit == 0)."""
         cap = cap or (1 + (2 if self.tree_reuse == 1 else 1) * self.max_sims * self.rows * self.cols)   # (a carry engine's default arena is twice the size)
         depth = np.empty(cap, np.int32); cell = np.empty(cap, np.int32); visit = np.empty(cap, np.int32)
         value = np.empty(cap, np.float64); prior = np.empty(cap, np.float64)
+        if quotient:
+            quot = np.empty(cap, np.float64)
+            n = self._chk(self.L.azk_export_tree_quotients(self.h, int(game), cap, _np(depth), _np(cell), _np(visit), _np(value), _np(prior),
+                                                           _np(quot), _stream()))
+            n = min(n, cap)
+            return dict(depth=depth[:n], cell=cell[:n], visit=visit[:n].astype(np.int64), value=value[:n], prior=prior[:n], quotient=quot[:n])
         n = self._chk(self.L.azk_export_tree(self.h, int(game), cap, _np(depth), _np(cell), _np(visit), _np(value), _np(prior), _stream()))
         n = min(n, cap)
         return dict(depth=depth[:n], cell=cell[:n], visit=visit[:n].astype(np.int64), value=value[:n], prior=prior[:n])
+
+    def fill_quotients(self, byte):
+        """Tests only: every byte of the quotient column becomes `byte` (0: zeros, 255: NaNs).  For engines whose trees are fresh roots."""
+        self._chk(self.L.azk_debug_fill_quotients(self.h, int(byte), _stream()))
 
     def counters(self):
         c = Counters()

@@ -109,6 +109,8 @@ def declare(L, symbols):
     L.azk_root_stats.argtypes = [vp, vp, vp, vp, vp]
     L.azk_root_children.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.azk_export_tree.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.azk_export_tree_quotients.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.azk_debug_fill_quotients.argtypes = [vp, i32, vp]
     L.azk_advance.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.azk_get_positions.argtypes = [vp, vp, vp, vp, vp]
     L.azk_get_counters.argtypes = [vp, C.POINTER(Counters), vp]

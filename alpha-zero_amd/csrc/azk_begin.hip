@@ -146,13 +146,13 @@ __device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_
             for (int j = 0; j < 4; j++) { wd[j] = azk_readlane_u64(wreg, k0 + j); pk[j] = __builtin_amdgcn_readlane(preg, k0 + j); }
             if ((wd[0] | wd[1] | wd[2] | wd[3]) == 0ull) continue;
             NodeH h[4];
-            double wv[4];
+            double wv[4], qv[4];                                              // (Q travels with W: a kept node's N and W do not change, so neither does their quotient)
             bool has[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) {                                     // every record of the round, before any store
                 has[j] = (wd[j] >> lane) & 1ull;
                 const size_t src = base + (has[j] ? (wb + k0 + j) * AZK_WAVE + lane : c);
-                h[j] = d.H[src]; wv[j] = d.W[src];
+                h[j] = d.H[src]; wv[j] = d.W[src]; qv[j] = d.Q[src];
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) if (has[j] && h[j].fc >= 0) h[j].fc = rr_rank(bm, pre, h[j].fc);
@@ -161,7 +161,7 @@ __device__ void reroot_one(const Dev &d, const ReuseDev &r, int g, int c, int n_
                 if (!has[j]) continue;
                 const int dst = pk[j] + __popcll(wd[j] & rr_below(lane));
                 if ((wb + k0 + j) * AZK_WAVE + lane == c) { h[j].P = 0.f; h[j].meta = meta_pack(0xffff, root_nch); }   // the root: no prevAction
-                d.H[base + dst] = h[j]; d.W[base + dst] = wv[j];
+                d.H[base + dst] = h[j]; d.W[base + dst] = wv[j]; d.Q[base + dst] = qv[j];
             }
         }
     }

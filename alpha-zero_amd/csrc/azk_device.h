@@ -142,13 +142,22 @@ __device__ __forceinline__ double dpp_keep_f64(double v) {
     const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(b >> 32), (int)(unsigned)(b >> 32), CTRL, ROWMASK, 0xF, false);
     return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
+// float32: each step is ONE v_max_f32 whose first source comes through DPP.  Written as fmaxf(v, dpp_keep_f32(v)) a step was five
+// instructions - a copy for the DPP move's `old`, the move, a canonicalising v_max of each operand (fmaxf quiets a signalling NaN), the
+// max - thirty per reduction, on every level of the walk.  No NaN comes in (above), the maximum of two numbers is exact, and the callers
+// compare the result with == (so a zero's sign does not matter): the same winner, bit for bit.  A lane outside a step's row mask, or
+// whose source lane is not executing, keeps its value (the destination is the operand).  s_nop 1: a DPP read of a register needs two
+// wait states behind the VALU write of it, and the hazard pass does not look inside an asm statement.
+// (one asm statement for the six steps: between separate ones the compiler puts a wait state of its own)
 __device__ __forceinline__ float wave_max_f32(float v) {
-    v = fmaxf(v, dpp_keep_f32<0xB1, 0xF>(v));
-    v = fmaxf(v, dpp_keep_f32<0x4E, 0xF>(v));
-    v = fmaxf(v, dpp_keep_f32<0x141, 0xF>(v));
-    v = fmaxf(v, dpp_keep_f32<0x140, 0xF>(v));
-    v = fmaxf(v, dpp_keep_f32<0x142, 0xA>(v));
-    v = fmaxf(v, dpp_keep_f32<0x143, 0xC>(v));
+    asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "s_nop 1"                                                     // (... and the readlane below reads what the last step wrote)
+        : "+v"(v));
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 __device__ __forceinline__ double wave_max_f64(double v) {

@@ -59,7 +59,7 @@ int32_t azk_create(const azk_config *cfg, azk_engine **out) {
     hipError_t s = hipSuccess;
 #define DA(ptr, count) if (s == hipSuccess) s = dalloc(e, &ptr, (count))
     DA(d.cells, G * d.rc_pad); DA(d.to_move, G); DA(d.move_count, G); DA(d.done, G); DA(d.winner, G);
-    DA(d.H, nodes); DA(d.W, nodes);
+    DA(d.H, nodes); DA(d.W, nodes); DA(d.Q, nodes);
     DA(d.rootP, G * g.rc); DA(d.root_f64, G); DA(d.arena_top, G);
     e->ru.mode = tree_reuse;
     if (tree_reuse) {
@@ -168,7 +168,7 @@ int32_t azk_clear_cache(azk_engine *e, void *stream) {
 // copy one game's used arena to the host
 struct HostTree {
     std::vector<int> N, first_child;
-    std::vector<double> W, rootP;
+    std::vector<double> W, Q, rootP;
     std::vector<float> P;
     std::vector<uint32_t> meta;
     std::vector<int> cell, nch;
@@ -182,11 +182,12 @@ static int32_t fetch_tree(azk_engine *e, int game, HostTree *t, hipStream_t st) 
     HIPCHK(e, hipMemcpyAsync(&t->root_f64, d.root_f64 + game, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
     const size_t n = (size_t)t->top, base = (size_t)game * d.cap;
-    t->N.resize(n); t->first_child.resize(n); t->W.resize(n); t->P.resize(n); t->cell.resize(n); t->nch.resize(n); t->meta.resize(n);
+    t->N.resize(n); t->first_child.resize(n); t->W.resize(n); t->Q.resize(n); t->P.resize(n); t->cell.resize(n); t->nch.resize(n); t->meta.resize(n);
     t->rootP.resize(d.g.rc);
     std::vector<NodeH> recs(n);
     HIPCHK(e, hipMemcpyAsync(recs.data(), d.H + base, n * sizeof(NodeH), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(t->W.data(), d.W + base, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(t->Q.data(), d.Q + base, n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(t->rootP.data(), d.rootP + (size_t)game * d.g.rc, d.g.rc * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
     for (size_t i = 0; i < n; i++) { t->N[i] = recs[i].N; t->first_child[i] = recs[i].fc; t->P[i] = recs[i].P; t->meta[i] = recs[i].meta; }
@@ -214,8 +215,9 @@ int32_t azk_root_children(azk_engine *e, int32_t game, int32_t cap, int32_t *cel
     return n;
 }
 
-int32_t azk_export_tree(azk_engine *e, int32_t game, int32_t cap, int32_t *depth_host, int32_t *cell_host,
-                        int32_t *visit_host, double *value_host, double *prior_host, void *stream) {
+// azk_export_tree and azk_export_tree_quotients: one walk, the second with the Q column beside the others
+static int32_t export_tree_rows(azk_engine *e, int32_t game, int32_t cap, int32_t *depth_host, int32_t *cell_host,
+                                int32_t *visit_host, double *value_host, double *prior_host, double *quotient_host, void *stream) {
     if (!e) return AZK_ERR_ARG;
     HostTree t;
     int32_t rc = fetch_tree(e, game, &t, (hipStream_t)stream);
@@ -232,6 +234,7 @@ int32_t azk_export_tree(azk_engine *e, int32_t game, int32_t cap, int32_t *depth
             if (cell_host) cell_host[m] = t.cell[node];
             if (visit_host) visit_host[m] = t.N[node];
             if (value_host) value_host[m] = t.W[node];
+            if (quotient_host) quotient_host[m] = t.Q[node];
             if (prior_host) {
                 const bool root_child = dep == 1 && t.root_f64;
                 prior_host[m] = root_child ? t.rootP[node - rfc] : (double)t.P[node];
@@ -241,6 +244,22 @@ int32_t azk_export_tree(azk_engine *e, int32_t game, int32_t cap, int32_t *depth
         for (int i = t.nch[node] - 1; i >= 0; i--) stack.push_back({t.first_child[node] + i, dep + 1});
     }
     return m;
+}
+
+int32_t azk_export_tree(azk_engine *e, int32_t game, int32_t cap, int32_t *depth_host, int32_t *cell_host,
+                        int32_t *visit_host, double *value_host, double *prior_host, void *stream) {
+    return export_tree_rows(e, game, cap, depth_host, cell_host, visit_host, value_host, prior_host, nullptr, stream);
+}
+
+int32_t azk_export_tree_quotients(azk_engine *e, int32_t game, int32_t cap, int32_t *depth_host, int32_t *cell_host,
+                                  int32_t *visit_host, double *value_host, double *prior_host, double *quotient_host, void *stream) {
+    return export_tree_rows(e, game, cap, depth_host, cell_host, visit_host, value_host, prior_host, quotient_host, stream);
+}
+
+int32_t azk_debug_fill_quotients(azk_engine *e, int32_t byte, void *stream) {
+    if (!e || byte < 0 || byte > 255) { if (e) e->err = "azk_debug_fill_quotients: bad argument"; return AZK_ERR_ARG; }
+    HIPCHK(e, hipMemsetAsync(e->d.Q, byte, sizeof(double) * (size_t)e->d.G * (size_t)e->d.cap, (hipStream_t)stream));
+    return AZK_OK;
 }
 
 int32_t azk_get_positions(azk_engine *e, int8_t *cells_host, int32_t *to_move_host, int32_t *move_count_host, void *stream) {

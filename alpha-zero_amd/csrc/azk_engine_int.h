@@ -45,6 +45,9 @@ struct Dev {               // device view of the engine, passed to kernels by va
                            // r*cols+c) << 16 | len(Node.children) (cell 0xFFFF = root), fc = index of children[0] in this game's arena
                            // (-1 = not expanded): a PUCT candidate costs one 16-byte load + W instead of five column loads
     double *W;             // Node.value (running sum)
+    double *Q;             // W / (double)N of every node with N > 0, bit for bit the quotient the walk used to compute per child and level: kept by
+                           // node_store_wq(), the one writer of a visited node's W.  UNSPECIFIED where N = 0 (never written there: fresh roots,
+                           // new children), and every reader discards it there
     double *rootP;         // [G][rc] float64 root priors after Dirichlet mixing (utils.py:24-25), by child position
     int *root_f64;         // [G] root children use rootP (float64 UCB) instead of P (float32 UCB)
     int *arena_top;        // [G] bump allocator
@@ -322,14 +325,27 @@ __device__ __forceinline__ void count_add(const Dev &d, int which, int g, long l
     atomicAdd((unsigned long long *)&d.counters[(size_t)which * d.G + g], (unsigned long long)v);
 }
 
+// The ONE copy of "a visited node's statistics change": every store of a node's N or W after its creation goes through these two, so that
+// Q[node] == W[node] / (double)H[node].N holds bit for bit wherever N > 0 (the walk reads Q and divides nothing; the division is the one the
+// walk's scan made, on the same operands).  N: the node's visit count as it stands behind the change, >= 1.
+__device__ __forceinline__ void node_store_wq(const Dev &d, size_t idx, int N, double W) {       // the count itself stays as it is in memory
+    d.W[idx] = W;
+    d.Q[idx] = W / (double)N;
+}
+__device__ __forceinline__ void node_store(const Dev &d, size_t idx, int N, double W) {
+    d.H[idx].N = N;
+    node_store_wq(d, idx, N, W);
+}
+
 // Node.backup (node.py:62-74): the node at trace index i gets value * (-1)^(depth - i); lanes take one node each.
 __device__ __forceinline__ void backup_path(const Dev &d, size_t base, const int *path, int depth, double value, bool undo_virtual_loss = false) {
     for (int i = azk_lane(); i <= depth; i += AZK_WAVE) {
         int nd = path[i];
         double sv = ((depth - i) & 1) ? -value : value;
-        if (undo_virtual_loss) { d.W[base + nd] = (d.W[base + nd] + sv) + 1.0; continue; }      // the visit was counted at selection (same association as the short-path form)
-        d.H[base + nd].N += 1;
-        d.W[base + nd] += sv;
+        const int N = d.H[base + nd].N;
+        const double W = d.W[base + nd];
+        if (undo_virtual_loss) { node_store_wq(d, base + nd, N, (W + sv) + 1.0); continue; }     // the visit was counted at selection (same association as the short-path form)
+        node_store(d, base + nd, N + 1, W + sv);
     }
 }
 
@@ -376,7 +392,7 @@ __device__ __forceinline__ void clear_leaf_slots(const Dev &d, int g) {
 __device__ __forceinline__ void fresh_root_one(const Dev &d, int g) {
     drop_pending_cache_claim(d, g);
     const size_t base = (size_t)g * d.cap;
-    d.H[base] = NodeH{0, 0.f, meta_pack(0xffff, 0), -1}; d.W[base] = 0.0;
+    d.H[base] = NodeH{0, 0.f, meta_pack(0xffff, 0), -1}; d.W[base] = 0.0;   // (N = 0: Q[base] is unspecified until the first backup)
     d.arena_top[g] = 1; d.root_f64[g] = 0;
     clear_leaf_slots(d, g);
     d.sims_done[g] = 0;

@@ -2,7 +2,7 @@
 // live in this one translation unit), its expanding wave, the leaf gather, and the C ABI calls that launch them (include/azk.h).
 // One 64-lane wavefront owns one game (the plain k_tree gives it a helper wave); the tree is
 // a structure-of-arrays arena in HBM whose child blocks are contiguous, so a PUCT scan is a coalesced read
-// of the N / W / P columns; per-wave scratch (board, path, move list, emulated CPython set) lives in LDS.
+// of the header records and the Q column (W / N, kept at backup: the walk divides nothing); per-wave scratch (board, path, move list, emulated CPython set) lives in LDS.
 // Built with -ffp-contract=off: every float result is the same sequence of IEEE operations the oracle runs.
 // Reference lines cited as file:line relative to the reference root.
 #include "azk_engine_int.h"
@@ -163,7 +163,7 @@ __device__ __forceinline__ void tree_expand_wave(const Dev &d, const LdsView &L,
                 const int a = azk_action_idx(gd, cell);
                 const float p = L.e[a] / s;
                 const size_t idx = base + fc + i;
-                d.H[idx] = NodeH{0, p, meta_pack(cell, 0), -1}; d.W[idx] = 0.0;
+                d.H[idx] = NodeH{0, p, meta_pack(cell, 0), -1}; d.W[idx] = 0.0;       // (N = 0: Q[idx] stays unwritten - unspecified until the first backup)
                 if constexpr (GUMBEL) {                               // the child's base score: its raw logit + the game's Gumbel draw for its action
                     if (mix) { const float lga = lg[a]; d.rootP[(size_t)g * rc + i] = (double)lga + nzv[k4]; gb.logit[(size_t)g * rc + i] = lga; }
                 } else

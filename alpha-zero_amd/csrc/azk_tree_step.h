@@ -168,10 +168,7 @@
             if (shortpath) {                                          // Node.backup (node.py:62-74) on the operands fetched above
                 const int nN = bN + 1;
                 const double nW = bW + (((depth - lane) & 1) ? -v : v);
-                if (lane <= depth) {
-                    d.H[base + e_path].N = nN;
-                    d.W[base + e_path] = nW;
-                }
+                if (lane <= depth) node_store(d, base + e_path, nN, nW);
                 if constexpr (PUCT) r_W = tree_readlane_f64(nW, 0);   // (trace node 0 is the root: lane 0 holds its new sum)
             } else {
                 backup_path(d, base, d.path + (size_t)vi * d.path_cap, depth, v, false);
@@ -284,7 +281,7 @@
                     const int a = azk_action_idx(gd, cell);
                     const float p = L.e[a] / s;
                     const size_t idx = base + fc + i;
-                    d.H[idx] = NodeH{0, p, meta_pack(cell, 0), -1}; d.W[idx] = 0.0;
+                    d.H[idx] = NodeH{0, p, meta_pack(cell, 0), -1}; d.W[idx] = 0.0;   // (N = 0: Q[idx] stays unwritten - unspecified until the first backup)
                     if constexpr (GUMBEL) {                           // the child's base score: its raw logit + the game's Gumbel draw for its action
                         if (mix) { const float lga = lg[a]; d.rootP[(size_t)g * rc + i] = (double)lga + nzv[k4]; AZK_TREE_GUMBEL_ARG.logit[(size_t)g * rc + i] = lga; }
                     } else
@@ -307,10 +304,7 @@
                 // virtual-loss mode: the visit was already counted at selection and the value carries the loss (-1) left there
                 const int nN = vl ? bN : bN + 1;
                 const double nW = bW + (((depth - lane) & 1) ? -v : v) + (vl ? 1.0 : 0.0);
-                if (lane <= depth) {
-                    d.H[base + e_path].N = nN;
-                    d.W[base + e_path] = nW;
-                }
+                if (lane <= depth) node_store(d, base + e_path, nN, nW);
                 if constexpr (PUCT) r_W = tree_readlane_f64(nW, 0);   // (trace node 0 is the root: lane 0 holds its new sum)
             } else {
                 backup_path(d, base, d.path + (size_t)vi * d.path_cap, depth, v, vl);
@@ -395,13 +389,18 @@
             int best = 0x7fffffff, bN = 0, bfc = -1;
             uint32_t bmeta = 0;
             bool forced_sel = false;                                  // FORCED: the child taken at the root was a forced one (counted, nothing else)
+            // a child's q = W / (double)N comes from the Q column, where the backup that last changed W left it (node_store_wq: the same division
+            // on the same operands, once per backup instead of once per scanned child and level).  Where N = 0 the word is unspecified, and every
+            // use of q there is discarded: by the `Nc != 0 ? .. : un` select below, which is all tree_forced_score sees of it, and by
+            // tree_gumbel_score's own `N != 0` select.  The PUCT kernels need the winner's W beside its N (bW): they load W and divide, as before.
+            const double *const qcol = PUCT ? d.W : d.Q;
             if (nch <= AZK_WAVE && !(ablate & 2048)) {
                 // the common case (a Gomoku position has ~50 candidate moves): one candidate per lane, one load per column, the
                 // argmax as a DPP maximum + ballot - "first maximum wins" (node.py:47) is the lowest lane holding the maximum
                 const bool valid = lane < nch;
                 const size_t ci = base + fc + (valid ? lane : 0);
                 const NodeH hc = d.H[ci];                             // one 16-byte load: N, P, meta, first_child
-                const double Wc = d.W[ci];
+                const double Vc = qcol[ci];                           // the child's quotient (PUCT: its value sum)
                 const int Nc = hc.N, fcc = hc.fc;
                 const uint32_t mc = hc.meta;
                 const float P32 = hc.P;
@@ -412,7 +411,7 @@
                     double s = sqrt((double)Np);
                     if constexpr (PUCT) s = pc * s;
                     const double u0 = P64 * s / (double)(Nc + 1);
-                    const double q = Wc / (double)Nc;                 // N = 0: inf/nan, discarded by the select
+                    const double q = PUCT ? Vc / (double)Nc : Vc;     // N = 0: unspecified (PUCT: inf/nan), discarded by the select
                     double un = u0;                                   // an unvisited child's score (plain text, no helper call: see the head of this file)
                     if constexpr (PUCT) un = pmode != 0 ? qf + u0 : u0;
                     const double u = valid ? tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc != 0 ? q + u0 : un, Nc, P64, fk, Np), Nc, q, P64, gcv, gsig) : -__builtin_huge_val();
@@ -424,7 +423,7 @@
                     float s = (float)sqrt((double)Np);
                     if constexpr (PUCT) s = (float)(pc * sqrt((double)Np));
                     const float u0 = (P32 * s) / (float)(Nc + 1);
-                    const float q = (float)(Wc / (double)Nc);
+                    const float q = (float)(PUCT ? Vc / (double)Nc : Vc);
                     float un = u0;
                     if constexpr (PUCT) un = pmode != 0 ? (float)qf + u0 : u0;
                     const float u = valid ? (Nc != 0 ? q + u0 : un) : -__builtin_huge_valf();
@@ -433,7 +432,7 @@
                 }
                 best = __ffsll((long long)winners) - 1;
                 bN = Nc; bmeta = mc; bfc = fcc;
-                if constexpr (PUCT) bW = Wc;
+                if constexpr (PUCT) bW = Vc;
             } else if (nch <= 2 * AZK_WAVE && !(ablate & 2048)) {
                 // 65 .. 128 candidates (late plies: every node of the tree): two per lane, the same straight-line shape - ten loads,
                 // one round trip.  (The general loop below sinks its prior loads into per-slot branches: one more round trip per
@@ -441,7 +440,7 @@
                 const bool va = true, vb = lane + AZK_WAVE < nch;
                 const size_t ca = base + fc + lane, cb = base + fc + (vb ? lane + AZK_WAVE : 0);
                 const NodeH ha = d.H[ca], hb = d.H[cb];
-                const double Wa = d.W[ca], Wb = d.W[cb];
+                const double Va = qcol[ca], Vb = qcol[cb];            // quotients (PUCT: value sums)
                 const int Na = ha.N, Nb = hb.N, fa = ha.fc, fb = hb.fc;
                 const uint32_t ma = ha.meta, mb = hb.meta;
                 const float Pa = ha.P, Pb = hb.P;
@@ -458,7 +457,7 @@
                     double s = sqrt((double)Np);
                     if constexpr (PUCT) s = pc * s;
                     const double u0a = Qa * s / (double)(Na + 1), u0b = Qb * s / (double)(Nb + 1);
-                    const double qa = Wa / (double)Na, qb = Wb / (double)Nb;
+                    const double qa = PUCT ? Va / (double)Na : Va, qb = PUCT ? Vb / (double)Nb : Vb;
                     double una = u0a, unb = u0b;
                     if constexpr (PUCT) { una = pmode != 0 ? qf + u0a : u0a; unb = pmode != 0 ? qf + u0b : u0b; }
                     const double ua = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Na != 0 ? qa + u0a : una, Na, Qa, fk, Np), Na, qa, Qa, gcv, gsig);
@@ -477,7 +476,7 @@
                     float s = (float)sqrt((double)Np);
                     if constexpr (PUCT) s = (float)(pc * sqrt((double)Np));
                     const float u0a = (Pa * s) / (float)(Na + 1), u0b = (Pb * s) / (float)(Nb + 1);
-                    const float qa = (float)(Wa / (double)Na), qb = (float)(Wb / (double)Nb);
+                    const float qa = (float)(PUCT ? Va / (double)Na : Va), qb = (float)(PUCT ? Vb / (double)Nb : Vb);
                     float una = u0a, unb = u0b;
                     if constexpr (PUCT) { una = pmode != 0 ? (float)qf + u0a : u0a; unb = pmode != 0 ? (float)qf + u0b : u0b; }
                     const float ua = Na != 0 ? qa + u0a : una;
@@ -488,7 +487,7 @@
                 const bool first = wa != 0ull;
                 best = first ? __ffsll((long long)wa) - 1 : AZK_WAVE + __ffsll((long long)wb) - 1;
                 bN = first ? Na : Nb; bmeta = first ? ma : mb; bfc = first ? fa : fb;
-                if constexpr (PUCT) bW = first ? Wa : Wb;
+                if constexpr (PUCT) bW = first ? Va : Vb;
             } else {
             if constexpr (PUCT) {
                 // mode 2 over more than one chunk (a board beyond 256 cells): the mass is needed before the first child is scored, so it takes
@@ -507,7 +506,7 @@
             // all of this level's loads are issued before any arithmetic: 4 candidates per lane per 256-child chunk
             for (int c0 = 0; c0 < nch; c0 += 4 * AZK_WAVE) {
                 int Nc[4], fcc[4];
-                double Wc[4], P64[4] = {0.0, 0.0, 0.0, 0.0};
+                double Vc[4], P64[4] = {0.0, 0.0, 0.0, 0.0};                  // Vc: quotients (PUCT: value sums)
                 float P32[4];
                 uint32_t mc[4];
                 // straight-line loads, no per-slot control flow: a branch inside this loop makes the compiler wait for each
@@ -517,7 +516,7 @@
                     const int i = c0 + lane + AZK_WAVE * k;
                     const size_t ci = base + fc + (i < nch ? i : 0);
                     const NodeH hk = d.H[ci];
-                    Nc[k] = hk.N; Wc[k] = d.W[ci]; mc[k] = hk.meta; fcc[k] = hk.fc; P32[k] = hk.P;
+                    Nc[k] = hk.N; Vc[k] = qcol[ci]; mc[k] = hk.meta; fcc[k] = hk.fc; P32[k] = hk.P;
                 }
                 if (f64) {                                            // root after Dirichlet mixing: float64 priors by child position
 #pragma unroll
@@ -554,14 +553,14 @@
                         if (c0 + AZK_WAVE * k >= nch) break;             // wave-uniform: no candidate in this slot at all
                         const int i = c0 + lane + AZK_WAVE * k;
                         const double u0 = P64[k] * s / (double)(Nc[k] + 1);
-                        const double q = Wc[k] / (double)Nc[k];          // N = 0: inf/nan, discarded by the select below
+                        const double q = PUCT ? Vc[k] / (double)Nc[k] : Vc[k];   // N = 0: unspecified (PUCT: inf/nan), discarded by the select below
                         double un = u0;
                         if constexpr (PUCT) un = pmode != 0 ? qf + u0 : u0;
                         const double u = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc[k] != 0 ? q + u0 : un, Nc[k], P64[k], fk, Np), Nc[k], q, P64[k], gcv, gsig);
                         const bool take = (i < nch) & ((best == 0x7fffffff) | (u > bu64));
                         bu64 = take ? u : bu64; best = take ? i : best; bN = take ? Nc[k] : bN;
                         bmeta = take ? mc[k] : bmeta; bfc = take ? fcc[k] : bfc;
-                        if constexpr (PUCT) bW = take ? Wc[k] : bW;
+                        if constexpr (PUCT) bW = take ? Vc[k] : bW;
                     }
                 } else {                                              // float32 priors => float32 UCB (numpy>=2)
                     float s = (float)sqrt((double)Np);
@@ -571,14 +570,14 @@
                         if (c0 + AZK_WAVE * k >= nch) break;             // wave-uniform: no candidate in this slot at all
                         const int i = c0 + lane + AZK_WAVE * k;
                         const float u0 = (P32[k] * s) / (float)(Nc[k] + 1);
-                        const float q = (float)(Wc[k] / (double)Nc[k]);  // N = 0: inf/nan, discarded by the select below
+                        const float q = (float)(PUCT ? Vc[k] / (double)Nc[k] : Vc[k]);   // N = 0: unspecified (PUCT: inf/nan), discarded by the select below
                         float un = u0;
                         if constexpr (PUCT) un = pmode != 0 ? (float)qf + u0 : u0;
                         const float u = Nc[k] != 0 ? q + u0 : un;
                         const bool take = (i < nch) & ((best == 0x7fffffff) | (u > bu32));
                         bu32 = take ? u : bu32; best = take ? i : best; bN = take ? Nc[k] : bN;
                         bmeta = take ? mc[k] : bmeta; bfc = take ? fcc[k] : bfc;
-                        if constexpr (PUCT) bW = take ? Wc[k] : bW;
+                        if constexpr (PUCT) bW = take ? Vc[k] : bW;
                     }
                 }
             }
@@ -745,7 +744,7 @@
         }
         for (int i = lane; i <= depth; i += AZK_WAVE) d.path[(size_t)vi * d.path_cap + i] = L.path[i];
         if (vl) {                                                     // virtual loss: the path counts a visit now and a lost game until its value arrives
-            for (int i = lane; i <= depth; i += AZK_WAVE) { const int nd = L.path[i]; d.H[base + nd].N += 1; d.W[base + nd] -= 1.0; }
+            for (int i = lane; i <= depth; i += AZK_WAVE) { const int nd = L.path[i]; node_store(d, base + nd, d.H[base + nd].N + 1, d.W[base + nd] - 1.0); }
             if (lane == 0) d.H[base + node].fc = -2;           // "expansion pending": a second slot arriving here gives up
         }
         if (lane == 0) {

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(AZK_WAVE) void k_vanilla(Dev d, int n_sims, uint32_
             if (afc + nv > d.cap) { if (lane == 0) atomicExch(d.err, AZK_ERR_ARENA_FULL); return; }
             for (int i = lane; i < nv; i += AZK_WAVE) {               // node.expand(valid_moves, None, Game): node.py:50-59
                 const size_t idx = base + afc + i;
-                d.H[idx] = NodeH{0, 0.f, meta_pack(L.moves[i], 0), -1}; d.W[idx] = 0.0;
+                d.H[idx] = NodeH{0, 0.f, meta_pack(L.moves[i], 0), -1}; d.W[idx] = 0.0;   // (N = 0: Q[idx] unspecified)
             }
             if (lane == 0) {
                 d.H[base + node].fc = afc;

@@ -670,6 +670,16 @@ int32_t azk_root_children(azk_engine *e, int32_t game, int32_t cap, int32_t *cel
  * Returns the node count (may exceed cap: only the first cap rows are written).  Synchronises. */
 int32_t azk_export_tree(azk_engine *e, int32_t game, int32_t cap, int32_t *depth_host, int32_t *cell_host,
                         int32_t *visit_host, double *value_host, double *prior_host, void *stream);
+/* The same rows with one more column (any output may be NULL): quotient_host[m] = the node's word of the engine's quotient column, which
+ * holds value / visit (IEEE float64 division of the two numbers azk_export_tree reports) bit for bit for every node with visit > 0 - the
+ * search keeps it at backup and the walk reads it instead of dividing.  For a node with visit == 0 the word is unspecified (whatever the
+ * memory held) and nothing reads it. */
+int32_t azk_export_tree_quotients(azk_engine *e, int32_t game, int32_t cap, int32_t *depth_host, int32_t *cell_host,
+                                  int32_t *visit_host, double *value_host, double *prior_host, double *quotient_host, void *stream);
+/* Debug / tests only: every byte of the quotient column of every game becomes `byte` (0: +0.0 everywhere, 255: a NaN everywhere).  It
+ * breaks the column for visited nodes, so it is for engines whose trees are fresh roots (after azk_create / azk_reset_games, before the
+ * first search, no tree reuse pending): a search that follows must come out the same whatever was filled in.  Asynchronous on the stream. */
+int32_t azk_debug_fill_quotients(azk_engine *e, int32_t byte, void *stream);
 
 /* Move selection + state advance for all active games (gomoku.py:143-162; a tree_reuse engine also notes the played child as the
  * next search's root - forgotten again by azk_reset_games, azk_set_positions, azk_recycle_finished and for finished games):

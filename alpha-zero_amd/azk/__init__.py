@@ -47,6 +47,8 @@ SYMBOLS = [
     "azk_set_move_temperature", "azk_clear_move_temperature", "azk_get_move_temperature_stats",
     "azk_set_value_target", "azk_clear_value_target", "azk_get_value_record",
     "azk_export_tree_quotients", "azk_debug_fill_quotients",
+    "azk_set_solver", "azk_clear_solver", "azk_get_solver_status", "azk_export_tree_status", "azk_get_solver_stats",
+    "azk_debug_fill_solver_status",
 ]
 
 
@@ -343,6 +345,7 @@ class Engine:
         self.gumbel_root = None                     # (m, n_sims, c_visit, c_scale) once set_gumbel_root has switched the option on
         self.openings = None                        # (p_open, max_plies, spread) once set_openings has switched the option on
         self.puct = None                            # (c_table, fpu_mode, fpu_tree, fpu_root) once set_puct has switched the option on
+        self.solver = False                         # True once set_solver has switched the option on
         self.move_temperature = None                # (row_of_ply, weights, visit_offset, value_cutoff) once set_move_temperature has switched the option on
         self.surprise_weight = None                 # lambda once set_surprise_weighting has switched the option on (0.0 is a live setting)
         self.value_target = None                    # (r, lam) once set_value_target has switched the option on (r = 0.0 is a live setting)
@@ -519,6 +522,42 @@ class Engine:
         """Configurable PUCT off (azk_clear_puct): the engine launches what it launched before."""
         self._chk(self.L.azk_clear_puct(self.h))
         self.puct = None
+
+    def set_solver(self, on=True):
+        """OPT-IN exact game-end proofs in the search (azk_set_solver): every node keeps a status - unknown, won, lost,
+        draw for the player who moved into it - proven from terminal leaves up the path of the simulation that found them; the walk stops on
+        proven nodes below the root and selection shuts out children proven lost.  Between searches only; not with forced playouts, a Gumbel
+        root, configurable PUCT, tree reuse, leaves_per_step > 1 or vanilla_search.  set_solver(False) switches it off (azk_clear_solver)."""
+        if on:
+            self._chk(self.L.azk_set_solver(self.h, _stream()))
+        else:
+            self._chk(self.L.azk_clear_solver(self.h))
+        self.solver = bool(on)
+
+    def solver_status(self):
+        """int8 [G]: every root's status as the side to move there sees it - 0 unknown, 1 wins, 2 loses, 3 draw (azk_get_solver_status)."""
+        out = np.empty(self.G, np.int8)
+        self._chk(self.L.azk_get_solver_status(self.h, _np(out), _stream()))
+        return out
+
+    def export_tree_status(self, game, cap=None):
+        """uint8 [nodes]: the stored statuses (0 unknown, 1 won, 2 lost, 3 draw for the player who moved INTO the node) in export_tree's row order."""
+        cap = cap or (1 + self.max_sims * self.rows * self.cols)
+        out = np.empty(cap, np.uint8)
+        n = self._chk(self.L.azk_export_tree_status(self.h, int(game), cap, _np(out), _stream()))
+        return out[:min(n, cap)]
+
+    def solver_stats(self):
+        """The six counters since set_solver (azk_get_solver_stats): terminal leaves marked, nodes proven by one won child, nodes proven by
+        all their children, simulations ended on a proven node with children, selections that shut a child out, roots that took a status."""
+        out = np.zeros(6, np.int64)
+        self._chk(self.L.azk_get_solver_stats(self.h, _np(out), _stream()))
+        keys = ("terminal_marked", "proven_by_won_child", "proven_by_all_children", "stopped_on_proven", "selections_excluding", "roots_proven")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def fill_solver_status(self, byte):
+        """Tests only: every byte of the status column becomes `byte`.  For engines whose trees are fresh roots."""
+        self._chk(self.L.azk_debug_fill_solver_status(self.h, int(byte), _stream()))
 
     def set_move_temperature(self, row_of_ply, weights, visit_offset=0, value_cutoff=None):
         """OPT-IN move temperature (azk_set_move_temperature): from now on advance and the asynchronous movers ignore

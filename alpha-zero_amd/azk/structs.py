@@ -183,6 +183,12 @@ def declare(L, symbols):
     L.azk_gen_gumbel_uniforms.argtypes = [vp, u64, i64, i32, vp, vp]
     L.azk_set_puct.argtypes = [vp, vp, i32, i32, f64, f64, vp]
     L.azk_clear_puct.argtypes = [vp]
+    L.azk_set_solver.argtypes = [vp, vp]
+    L.azk_clear_solver.argtypes = [vp]
+    L.azk_get_solver_status.argtypes = [vp, vp, vp]
+    L.azk_export_tree_status.argtypes = [vp, i32, i32, vp, vp]
+    L.azk_get_solver_stats.argtypes = [vp, vp, vp]
+    L.azk_debug_fill_solver_status.argtypes = [vp, i32, vp]
     L.azk_set_move_temperature.argtypes = [vp, vp, i32, vp, i32, i32, i32, f64, vp]
     L.azk_clear_move_temperature.argtypes = [vp]
     L.azk_get_move_temperature_stats.argtypes = [vp, vp, vp]

@@ -256,6 +256,29 @@ int32_t azk_export_tree_quotients(azk_engine *e, int32_t game, int32_t cap, int3
     return export_tree_rows(e, game, cap, depth_host, cell_host, visit_host, value_host, prior_host, quotient_host, stream);
 }
 
+// the solver's status column in the same row order (azk_set_solver)
+int32_t azk_export_tree_status(azk_engine *e, int32_t game, int32_t cap, uint8_t *status_host, void *stream) {
+    if (!e || !status_host) return AZK_ERR_ARG;
+    if (!e->sv_on) { e->err = "azk_export_tree_status: no solver is set (azk_set_solver)"; return AZK_ERR_STATE; }
+    HostTree t;
+    int32_t rc = fetch_tree(e, game, &t, (hipStream_t)stream);
+    if (rc != AZK_OK) return rc;
+    std::vector<uint8_t> col((size_t)t.top);
+    HIPCHK(e, hipMemcpyAsync(col.data(), e->sv.status + (size_t)game * e->d.cap, col.size(), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
+    std::vector<int> stack;
+    stack.push_back(0);
+    int m = 0;
+    while (!stack.empty()) {
+        const int node = stack.back();
+        stack.pop_back();
+        if (m < cap) status_host[m] = col[node];
+        m++;
+        for (int i = t.nch[node] - 1; i >= 0; i--) stack.push_back(t.first_child[node] + i);
+    }
+    return m;
+}
+
 int32_t azk_debug_fill_quotients(azk_engine *e, int32_t byte, void *stream) {
     if (!e || byte < 0 || byte > 255) { if (e) e->err = "azk_debug_fill_quotients: bad argument"; return AZK_ERR_ARG; }
     HIPCHK(e, hipMemsetAsync(e->d.Q, byte, sizeof(double) * (size_t)e->d.G * (size_t)e->d.cap, (hipStream_t)stream));

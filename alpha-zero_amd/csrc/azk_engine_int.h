@@ -165,6 +165,17 @@ struct PuctDev {
     double fpu_tree, fpu_root; // the value (mode 1) or the reduction r >= 0 (mode 2), below the root and at it
 };
 
+// exact game-end proofs (azk_set_solver, opt-in): a status byte per node, seen by the player who moved INTO the node - proofs
+// start at terminal leaves and move up the path of the simulation that found them, the walk stops on proven nodes below the root, and selection
+// shuts out children proven LOST.  Its own argument block, passed only to the SOLVER instantiations (k_tree<.., SOLVER> in azk_tree.hip): every
+// other argument block - and every kernel an engine without the option launches - stays as it was
+enum { SOLVER_UNKNOWN = 0, SOLVER_WON = 1, SOLVER_LOST = 2, SOLVER_DRAW = 3 };
+enum { SST_TERMINAL = 0, SST_BY_WON_CHILD, SST_BY_ALL_CHILDREN, SST_STOPPED, SST_EXCLUDING, SST_ROOTS, SST_N };
+struct SolverDev {
+    uint8_t *status;           // [G][cap] beside the tree arena's columns; written UNKNOWN wherever a node is created and when the root is expanded
+    long long *stats;          // [SST_N] the counters of azk_get_solver_stats
+};
+
 // move temperature (azk_set_move_temperature, opt-in): the played child is drawn with a weight per visit count, read from a
 // host-built table whose row is the ply's (no device pow), after a visit offset and a value cutoff; a ply whose row is -1 plays the first
 // most-visited child.  Its own argument block, passed only to the TEMP instantiations of the two movers (azk_moves.hip): every other argument
@@ -480,6 +491,8 @@ struct azk_engine {
     EmitSym emit = {};                   // emission under a mask of elements (cfg.emit_elements); emit.n == 0: off, the reference's rule
     OpenDev op = {};                     // random openings (azk_set_openings); op_on == false: off, nothing allocated
     bool op_on = false;                  // (p_open = 0 is a live setting, so the switch is its own word)
+    SolverDev sv = {};                   // exact game-end proofs (azk_set_solver); sv_on == false: off, nothing allocated
+    bool sv_on = false;
     bool in_search = false;              // between a search's begin and the move (or new position) that ends it: azk_set_eval_symmetry refuses
 };
 

@@ -695,6 +695,7 @@ static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *strea
         return AZK_ERR_ARG;
     }
     if (e->ru.mode && !reuse) { e->err = "azk_async_begin: a tree_reuse engine begins with azk_async_begin_reuse (games are parked and re-rooted in the drain)"; return AZK_ERR_STATE; }
+    if (e->sv_on && reuse) { e->err = "azk_async_begin_reuse: the solver is set (azk_set_solver) - the status column is not carried through a re-rooting"; return AZK_ERR_STATE; }
     if (!e->ru.mode && reuse) { e->err = "azk_async_begin_reuse: the engine was created with tree_reuse = 0 (use azk_async_begin)"; return AZK_ERR_STATE; }
     if (c->record_capacity < 0 || (c->record_capacity > 0 && (!c->rec_meta_dev || !c->rec_q_dev || !c->rec_pi_dev))) { e->err = "azk_async_begin: record ring pointers missing"; return AZK_ERR_ARG; }
     if (e->cp.n_fast > c->n_sims) { e->err = "azk_async_begin: the playout cap's n_fast exceeds n_sims"; return AZK_ERR_ARG; }

@@ -1,5 +1,5 @@
 // azk_options.hip - the opt-ins' state calls (include/azk.h): set, clear and read playout cap, forced playouts, Gumbel root, resignation,
-// surprise weighting, random openings, the move temperature and value targets.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
+// surprise weighting, random openings, the move temperature, value targets and the solver.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
 // block (azk_engine_int.h) that azk_opt_pack.h hands to the kernels of azk_begin.hip, azk_moves.hip and azk_emit.hip.
 #include "azk_engine_int.h"
 #include <algorithm>
@@ -62,6 +62,7 @@ int32_t azk_set_forced_playouts(azk_engine *e, double k, void *stream) {
     if (!(k >= 0.0) || k - k != 0.0) { e->err = "azk_set_forced_playouts: k must be finite and not negative (0 = off)"; return AZK_ERR_ARG; }
     if (k == 0.0) { e->forced_k = 0.0; return AZK_OK; }              // off: the engine launches what it launched before
     if (e->gb.m) { e->err = "azk_set_forced_playouts: a Gumbel root is set - its eligibility rule needs raw root selection"; return AZK_ERR_STATE; }
+    if (e->sv_on) { e->err = "azk_set_forced_playouts: the solver is set (azk_set_solver) - a forced child and a child shut out would claim the same selection"; return AZK_ERR_STATE; }
     if (e->puct_on) { e->err = "azk_set_forced_playouts: configurable PUCT is set (azk_set_puct) - the pruning bound restates the reference's selection formula"; return AZK_ERR_STATE; }
     if (e->d.K > 1) { e->err = "azk_set_forced_playouts: forced playouts do not combine with leaves_per_step > 1 (a virtual-loss search counts a visit before its value exists: the floor would be met by visits that carry nothing)"; return AZK_ERR_ARG; }
     e->forced_k = k;
@@ -96,6 +97,7 @@ int32_t azk_set_gumbel_root(azk_engine *e, int32_t m, int32_t n_sims, double c_v
     if (e->cp.n_fast) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with a playout cap (the halving table is built for one budget)"; return AZK_ERR_STATE; }
     if (e->forced_k != 0.0) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with forced playouts (the eligibility rule needs raw root selection)"; return AZK_ERR_STATE; }
     if (e->sp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with surprise weighting (its recorded pi is not a visit distribution)"; return AZK_ERR_STATE; }
+    if (e->sv_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with the solver (azk_set_solver: the eligibility rule needs raw root selection)"; return AZK_ERR_STATE; }
     if (e->puct_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with configurable PUCT (azk_set_puct: its root selection is not PUCT)"; return AZK_ERR_STATE; }
     if (e->tp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with a move temperature (azk_set_move_temperature: the Gumbel arg-max is the sample)"; return AZK_ERR_STATE; }
     if (e->vt_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with value targets (azk_set_value_target: the Gumbel movers do not keep the per-ply q)"; return AZK_ERR_STATE; }
@@ -142,6 +144,7 @@ int32_t azk_set_puct(azk_engine *e, const double *c_table_host, int32_t n_table,
     if (e->d.K > 1) { e->err = "azk_set_puct: configurable PUCT does not combine with leaves_per_step > 1 (a virtual-loss search leaves losses in the value sums the FPU rule reads)"; return AZK_ERR_ARG; }
     if (e->forced_k != 0.0) { e->err = "azk_set_puct: forced playouts are set - their pruning bound restates the reference's selection formula"; return AZK_ERR_STATE; }
     if (e->gb.m) { e->err = "azk_set_puct: a Gumbel root is set - its root selection is not PUCT"; return AZK_ERR_STATE; }
+    if (e->sv_on) { e->err = "azk_set_puct: the solver is set (azk_set_solver) - the two options' kernels are not combined (a follow-up, DESIGN section 29)"; return AZK_ERR_STATE; }
     if (e->in_search) { e->err = "azk_set_puct: a search is under way - set the option between searches"; return AZK_ERR_STATE; }
     hipStream_t st = (hipStream_t)stream;
     double *tab = nullptr;                                           // (a table of its own per call: a captured step graph may still hold the last one)
@@ -158,6 +161,67 @@ int32_t azk_clear_puct(azk_engine *e) {
     if (e->async_on) { e->err = "azk_clear_puct: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
     if (e->in_search && e->puct_on) { e->err = "azk_clear_puct: a search is under way - clear the option between searches"; return AZK_ERR_STATE; }
     e->puct_on = false;                                            // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+// ---- exact game-end proofs ------------------------------------------------------------------------------------------------
+int32_t azk_set_solver(azk_engine *e, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_solver: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (e->d.K > 1) { e->err = "azk_set_solver: the solver does not combine with leaves_per_step > 1 (a virtual-loss search leaves losses on paths a proof would end)"; return AZK_ERR_ARG; }
+    if (e->forced_k != 0.0) { e->err = "azk_set_solver: forced playouts are set - a forced child and a child shut out would claim the same selection"; return AZK_ERR_STATE; }
+    if (e->gb.m) { e->err = "azk_set_solver: a Gumbel root is set - its eligibility rule needs raw root selection"; return AZK_ERR_STATE; }
+    if (e->puct_on) { e->err = "azk_set_solver: configurable PUCT is set (azk_set_puct) - the two options' kernels are not combined (a follow-up, DESIGN section 29)"; return AZK_ERR_STATE; }
+    if (e->ru.mode) { e->err = "azk_set_solver: the engine was created with tree_reuse != 0 - the status column is not carried through a re-rooting (a follow-up, DESIGN section 29)"; return AZK_ERR_STATE; }
+    if (e->in_search) { e->err = "azk_set_solver: a search is under way - set the option between searches"; return AZK_ERR_STATE; }
+    const Dev &d = e->d;
+    SolverDev &s = e->sv;
+    hipStream_t st = (hipStream_t)stream;
+    if (!s.status) {
+        HIPCHK(e, dalloc(e, &s.status, (size_t)d.G * (size_t)d.cap));
+        HIPCHK(e, dalloc(e, &s.stats, (size_t)SST_N));
+    }
+    HIPCHK(e, hipMemsetAsync(s.status, 0, (size_t)d.G * (size_t)d.cap, st));
+    HIPCHK(e, hipMemsetAsync(s.stats, 0, sizeof(long long) * SST_N, st));
+    e->sv_on = true;
+    return AZK_OK;
+}
+
+int32_t azk_clear_solver(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_solver: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    if (e->in_search && e->sv_on) { e->err = "azk_clear_solver: a search is under way - clear the option between searches"; return AZK_ERR_STATE; }
+    e->sv_on = false;                                             // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+int32_t azk_get_solver_status(azk_engine *e, int8_t *root_status_host, void *stream) {
+    if (!e || !root_status_host) return AZK_ERR_ARG;
+    if (!e->sv_on) { e->err = "azk_get_solver_status: no solver is set (azk_set_solver)"; return AZK_ERR_STATE; }
+    const Dev &d = e->d;
+    hipStream_t st = (hipStream_t)stream;
+    // one byte per game, a row of the column apart: the roots are node 0 of every arena
+    HIPCHK(e, hipMemcpy2DAsync(root_status_host, 1, e->sv.status, (size_t)d.cap, 1, (size_t)d.G, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    for (int g = 0; g < d.G; g++) {                                // stored: as the player who moved INTO the root sees it; reported: as the side to move does
+        const int s = (uint8_t)root_status_host[g];
+        root_status_host[g] = (int8_t)(s == SOLVER_WON ? 2 : s == SOLVER_LOST ? 1 : s == SOLVER_DRAW ? 3 : 0);
+    }
+    return AZK_OK;
+}
+
+int32_t azk_get_solver_stats(azk_engine *e, int64_t *out6_host, void *stream) {
+    if (!e || !out6_host) return AZK_ERR_ARG;
+    if (!e->sv_on) { e->err = "azk_get_solver_stats: no solver is set (azk_set_solver)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(out6_host, e->sv.stats, sizeof(long long) * SST_N, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_debug_fill_solver_status(azk_engine *e, int32_t byte, void *stream) {
+    if (!e || byte < 0 || byte > 255) { if (e) e->err = "azk_debug_fill_solver_status: bad argument"; return AZK_ERR_ARG; }
+    if (!e->sv_on) { e->err = "azk_debug_fill_solver_status: no solver is set (azk_set_solver)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemsetAsync(e->sv.status, byte, (size_t)e->d.G * (size_t)e->d.cap, (hipStream_t)stream));
     return AZK_OK;
 }
 

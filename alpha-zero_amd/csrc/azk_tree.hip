@@ -1,4 +1,4 @@
-// azk_tree.hip - the AlphaZero search step of the batched self-play engine for MI355X (gfx950): k_tree (all thirty-four instantiations
+// azk_tree.hip - the AlphaZero search step of the batched self-play engine for MI355X (gfx950): k_tree (all forty-two instantiations
 // live in this one translation unit), its expanding wave, the leaf gather, and the C ABI calls that launch them (include/azk.h).
 // One 64-lane wavefront owns one game (the plain k_tree gives it a helper wave); the tree is
 // a structure-of-arrays arena in HBM whose child blocks are contiguous, so a PUCT scan is a coalesced read
@@ -40,10 +40,14 @@ struct TreeForcedHook { __device__ __forceinline__ void operator()() const {} };
 // The GUMBEL kernels' hook type says more: their wave 1 writes a root's children as a Gumbel search wants them (gb, read under that type only) -
 // rootP = the child's raw logit + the game's Gumbel draw for its action, the logit and the root's value kept in the GumbelDev block.
 struct TreeGumbelHook { __device__ __forceinline__ void operator()() const {} };
+// The SOLVER kernels' hook type: their wave 1 writes the status byte of every child it creates - and the root's, when it expands the root -
+// as UNKNOWN (sv, read under that type only), whatever the arena slot held before.
+struct TreeSolverHook { __device__ __forceinline__ void operator()() const {} };
 template <bool DBG, int KSL, typename Hook = AzkNoHook>
 __device__ __forceinline__ void tree_expand_wave(const Dev &d, const LdsView &L, const float *__restrict__ logits, const float *__restrict__ values, int ablate,
-                                                 const GumbelDev &gb = GumbelDev{}) {
+                                                 const GumbelDev &gb = GumbelDev{}, const SolverDev &sv = SolverDev{}) {
     constexpr bool GUMBEL = std::is_same_v<Hook, TreeGumbelHook>;
+    constexpr bool SOLVER = std::is_same_v<Hook, TreeSolverHook>;
     const int g = blockIdx.x, vi = g * d.K, lane = azk_lane();        // (slot 0 of the game, as in wave 0)
     const GameDesc &gd = d.g;
     const int A = gd.action_dim, rc = gd.rc;
@@ -164,12 +168,14 @@ __device__ __forceinline__ void tree_expand_wave(const Dev &d, const LdsView &L,
                 const float p = L.e[a] / s;
                 const size_t idx = base + fc + i;
                 d.H[idx] = NodeH{0, p, meta_pack(cell, 0), -1}; d.W[idx] = 0.0;       // (N = 0: Q[idx] stays unwritten - unspecified until the first backup)
+                if constexpr (SOLVER) sv.status[idx] = (uint8_t)SOLVER_UNKNOWN;       // a new node is UNKNOWN whatever the slot held (idx < base + cap: `fits`)
                 if constexpr (GUMBEL) {                               // the child's base score: its raw logit + the game's Gumbel draw for its action
                     if (mix) { const float lga = lg[a]; d.rootP[(size_t)g * rc + i] = (double)lga + nzv[k4]; gb.logit[(size_t)g * rc + i] = lga; }
                 } else
                 if (mix) d.rootP[(size_t)g * rc + i] = (double)(0.75f * p) + 0.25 * nzv[k4];   // utils.py:24-25
             }
             if constexpr (GUMBEL) { if (mix && lane == 0) gb.v0[g] = vraw; }
+            if constexpr (SOLVER) { if (depth == 0 && lane == 0) sv.status[base + node] = (uint8_t)SOLVER_UNKNOWN; }   // the root becomes UNKNOWN when it is expanded
             if (lane == 0) {
                 d.H[base + node].fc = fc;
                 d.H[base + node].meta = (node_meta & 0xffff0000u) | (uint32_t)nv;
@@ -289,7 +295,10 @@ __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd
 #define AZK_TREE_FORCED_ARG ForcedDev{}
 #define AZK_TREE_GUMBEL_ARG GumbelDev{}
 #define AZK_TREE_PUCT_ARG PuctDev{}
+    constexpr bool SOLVER = false;
+#define AZK_TREE_SOLVER_ARG SolverDev{}
 #include "azk_tree_step.h"
+#undef AZK_TREE_SOLVER_ARG
 #undef AZK_TREE_PUCT_ARG
 #undef AZK_TREE_GUMBEL_ARG
 #undef AZK_TREE_FORCED_ARG
@@ -303,7 +312,10 @@ __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd
 #define AZK_TREE_FORCED_ARG fd_arg
 #define AZK_TREE_GUMBEL_ARG GumbelDev{}
 #define AZK_TREE_PUCT_ARG PuctDev{}
+    constexpr bool SOLVER = false;
+#define AZK_TREE_SOLVER_ARG SolverDev{}
 #include "azk_tree_step.h"
+#undef AZK_TREE_SOLVER_ARG
 #undef AZK_TREE_PUCT_ARG
 #undef AZK_TREE_GUMBEL_ARG
 #undef AZK_TREE_FORCED_ARG
@@ -317,7 +329,10 @@ __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd
 #define AZK_TREE_FORCED_ARG ForcedDev{}
 #define AZK_TREE_GUMBEL_ARG gb_arg
 #define AZK_TREE_PUCT_ARG PuctDev{}
+    constexpr bool SOLVER = false;
+#define AZK_TREE_SOLVER_ARG SolverDev{}
 #include "azk_tree_step.h"
+#undef AZK_TREE_SOLVER_ARG
 #undef AZK_TREE_PUCT_ARG
 #undef AZK_TREE_GUMBEL_ARG
 #undef AZK_TREE_FORCED_ARG
@@ -330,7 +345,25 @@ __global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd
 #define AZK_TREE_FORCED_ARG ForcedDev{}
 #define AZK_TREE_GUMBEL_ARG GumbelDev{}
 #define AZK_TREE_PUCT_ARG pu_arg
+    constexpr bool SOLVER = false;
+#define AZK_TREE_SOLVER_ARG SolverDev{}
 #include "azk_tree_step.h"
+#undef AZK_TREE_SOLVER_ARG
+#undef AZK_TREE_PUCT_ARG
+#undef AZK_TREE_GUMBEL_ARG
+#undef AZK_TREE_FORCED_ARG
+}
+
+// the eight SOLVER kernels: fused, select-only, expand-only (expansion writes the new nodes' UNKNOWN bytes) and MULTI, each at KSL 4 and 7
+template <bool EXPAND, bool SELECT, bool DBG, bool MULTI, int KSL, bool FORCED, bool GUMBEL, bool PUCT, bool SOLVER>
+__global__ __launch_bounds__(MULTI ? AZK_WAVE : 2 * AZK_WAVE) void k_tree(Dev dd, const float *__restrict__ logits, const float *__restrict__ values, SolverDev sv_arg) {
+    static_assert(SOLVER && !FORCED && !GUMBEL && !PUCT && !DBG, "SOLVER exists for the product kernels, without forced playouts, a Gumbel root or configurable PUCT");
+#define AZK_TREE_FORCED_ARG ForcedDev{}
+#define AZK_TREE_GUMBEL_ARG GumbelDev{}
+#define AZK_TREE_PUCT_ARG PuctDev{}
+#define AZK_TREE_SOLVER_ARG sv_arg
+#include "azk_tree_step.h"
+#undef AZK_TREE_SOLVER_ARG
 #undef AZK_TREE_PUCT_ARG
 #undef AZK_TREE_GUMBEL_ARG
 #undef AZK_TREE_FORCED_ARG
@@ -412,8 +445,15 @@ static void launch_k_tree_puct(const Dev &d, const float *logits, const float *v
     else k_tree<E, true, false, M, 7, false, false, true><<<d.G, nthr, d.lds_bytes, st>>>(d, logits, values, pu);
 }
 
-// The one place that picks a k_tree instantiation: seven (EXPAND, SELECT, DBG, MULTI) forms, three FORCED ones, four GUMBEL ones and three PUCT ones, each at
-// KSL 4 and 7.
+template <bool E, bool S, bool M>                                     // exact game-end proofs: the product kernels
+static void launch_k_tree_solver(const Dev &d, const float *logits, const float *values, const SolverDev &sv, hipStream_t st) {
+    const int nthr = M ? AZK_WAVE : 2 * AZK_WAVE;
+    if (d.g.rc <= 4 * AZK_WAVE && d.g.action_dim <= 4 * AZK_WAVE) k_tree<E, S, false, M, 4, false, false, false, true><<<d.G, nthr, d.lds_bytes, st>>>(d, logits, values, sv);
+    else k_tree<E, S, false, M, 7, false, false, false, true><<<d.G, nthr, d.lds_bytes, st>>>(d, logits, values, sv);
+}
+
+// The one place that picks a k_tree instantiation: seven (EXPAND, SELECT, DBG, MULTI) forms, three FORCED ones, four GUMBEL ones, three PUCT ones and four
+// SOLVER ones, each at KSL 4 and 7.
 //   multi   the caller wants budget stepping.  The lock-step entry points pass `e->multi && !d.ablate` - an ablation build
 //           (AZK_TREE_ABLATE) never runs MULTI from them; azk_async_step passes true and has never looked at the ablation word.
 //           MULTI exists only with SELECT: budget stepping with `select` always launches <true, true, false, true>, whatever
@@ -426,7 +466,9 @@ static void launch_k_tree_puct(const Dev &d, const float *logits, const float *v
 //           the expand-only one included; an ablation build's DBG kernels are the plain ones.
 //   PUCT    an engine with configurable PUCT set (e->puct_on; never together with FORCED or GUMBEL) launches the PUCT sibling of whichever
 //           product kernel selects; its expand-only launches and an ablation build's DBG kernels are the plain ones.
-//   symmetry  an engine with azk_set_eval_symmetry on expands from ITS copy of the rows, turned back into each position's frame by
+//   SOLVER  an engine with the solver set (e->sv_on; never together with FORCED, GUMBEL or PUCT) launches the SOLVER sibling of every product
+//           kernel, the expand-only one included (expansion writes the new nodes' status bytes); an ablation build's DBG kernels are the plain ones.
+//   symmetry an engine with azk_set_eval_symmetry on expands from ITS copy of the rows, turned back into each position's frame by
 //           k_sym_logits in front of the launch (the kernel is the same, it is handed another pointer); the callers run azk_sym_leaves
 //           behind a launch that selects.
 int32_t azk_launch_tree(azk_engine *e, bool expand, bool select, bool multi, const float *logits, const float *values, hipStream_t st) {
@@ -435,6 +477,7 @@ int32_t azk_launch_tree(azk_engine *e, bool expand, bool select, bool multi, con
     const bool forced = e->forced_k != 0.0 && select && (multi || !d.ablate);
     const bool gumbel = e->gb.m != 0 && (multi || !d.ablate);
     const bool puct = e->puct_on && select && (multi || !d.ablate);
+    const bool solver = e->sv_on && (multi || !d.ablate);
     if (gumbel && multi && select) launch_k_tree_gumbel<true, true, true>(d, logits, values, e->gb, st);
     else if (gumbel && expand && select) launch_k_tree_gumbel<true, true, false>(d, logits, values, e->gb, st);
     else if (gumbel && expand) launch_k_tree_gumbel<true, false, false>(d, logits, values, e->gb, st);
@@ -445,6 +488,10 @@ int32_t azk_launch_tree(azk_engine *e, bool expand, bool select, bool multi, con
     else if (puct && multi) launch_k_tree_puct<true, true>(d, logits, values, e->pu, st);
     else if (puct && expand) launch_k_tree_puct<true, false>(d, logits, values, e->pu, st);
     else if (puct) launch_k_tree_puct<false, false>(d, logits, values, e->pu, st);
+    else if (solver && multi && select) launch_k_tree_solver<true, true, true>(d, logits, values, e->sv, st);
+    else if (solver && expand && select) launch_k_tree_solver<true, true, false>(d, logits, values, e->sv, st);
+    else if (solver && expand) launch_k_tree_solver<true, false, false>(d, logits, values, e->sv, st);
+    else if (solver) launch_k_tree_solver<false, true, false>(d, logits, values, e->sv, st);
     else if (multi && select) launch_k_tree<true, true, false, true>(d, logits, values, st);
     else if (d.ablate) {
         if (expand && select) launch_k_tree<true, true, true, false>(d, logits, values, st);

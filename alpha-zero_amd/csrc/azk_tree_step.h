@@ -4,7 +4,8 @@
 // tools/compare_kernel_isa.py), the same text compiled in place does.  In scope here: the template parameters EXPAND, SELECT, DBG, MULTI,
 // KSL, a constant FORCED, the kernel arguments dd, logits, values, and AZK_TREE_FORCED_ARG = the ForcedDev block (read under FORCED only);
 // a constant GUMBEL and AZK_TREE_GUMBEL_ARG = the GumbelDev block (read under GUMBEL only), the third overload's;
-// a constant PUCT and AZK_TREE_PUCT_ARG = the PuctDev block (read under PUCT only), the fourth overload's.
+// a constant PUCT and AZK_TREE_PUCT_ARG = the PuctDev block (read under PUCT only), the fourth overload's;
+// a constant SOLVER and AZK_TREE_SOLVER_ARG = the SolverDev block (read under SOLVER only), the fifth overload's.
     const Dev &d = dd;
     const int ablate = DBG ? dd.ablate : 0;
     const int g = blockIdx.x;
@@ -23,6 +24,7 @@
                 if constexpr (GUMBEL) tree_expand_wave<DBG, KSL, TreeGumbelHook>(d, L, logits, values, ablate, AZK_TREE_GUMBEL_ARG);
                 else if constexpr (FORCED) tree_expand_wave<DBG, KSL, TreeForcedHook>(d, L, logits, values, ablate);
                 else if constexpr (PUCT) tree_expand_wave<DBG, KSL, TreePuctHook>(d, L, logits, values, ablate);
+                else if constexpr (SOLVER) tree_expand_wave<DBG, KSL, TreeSolverHook>(d, L, logits, values, ablate, GumbelDev{}, AZK_TREE_SOLVER_ARG);
                 else tree_expand_wave<DBG, KSL>(d, L, logits, values, ablate);
             }
             // every store above has been acknowledged and the hand-off words are in LDS before the barrier (the workgroup-scope
@@ -282,12 +284,14 @@
                     const float p = L.e[a] / s;
                     const size_t idx = base + fc + i;
                     d.H[idx] = NodeH{0, p, meta_pack(cell, 0), -1}; d.W[idx] = 0.0;   // (N = 0: Q[idx] stays unwritten - unspecified until the first backup)
+                    if constexpr (SOLVER) AZK_TREE_SOLVER_ARG.status[idx] = (uint8_t)SOLVER_UNKNOWN;   // a new node is UNKNOWN whatever the slot held (idx < base + cap: `fits`)
                     if constexpr (GUMBEL) {                           // the child's base score: its raw logit + the game's Gumbel draw for its action
                         if (mix) { const float lga = lg[a]; d.rootP[(size_t)g * rc + i] = (double)lga + nzv[k4]; AZK_TREE_GUMBEL_ARG.logit[(size_t)g * rc + i] = lga; }
                     } else
                     if (mix) d.rootP[(size_t)g * rc + i] = (double)(0.75f * p) + 0.25 * nzv[k4];   // utils.py:24-25
                 }
                 if constexpr (GUMBEL) { if (mix && lane == 0) AZK_TREE_GUMBEL_ARG.v0[g] = vraw; }
+                if constexpr (SOLVER) { if (depth == 0 && lane == 0) AZK_TREE_SOLVER_ARG.status[base + node] = (uint8_t)SOLVER_UNKNOWN; }   // the root becomes UNKNOWN when it is expanded
                 if (lane == 0) {
                     d.H[base + node].fc = fc;
                     d.H[base + node].meta = (node_meta & 0xffff0000u) | (uint32_t)nv;
@@ -351,6 +355,12 @@
         bool root_f64 = uniform_i32(s_rootf64) != 0;
         double Wn = r_W;                                              // PUCT: the current node's value sum, carried like Np
         long long seg_a = 0, seg_b = 0, seg_c = 0, seg_d = 0, seg_t = 0;      // debug only (ablate & 64)
+        int nst = 0;                                                  // SOLVER: the current node's status, carried like Np (the root's is never looked at)
+        int shut_sels = 0;                                            // SOLVER: selections of this simulation that shut a child out (counted below)
+        int bst = 0;                                                  // SOLVER, per level: the winner's status, beside bN
+        bool open_any = true;                                         // SOLVER, general form of the scan: some child of this node is not LOST
+        bool shut_any = false;                                        // ... and this lane shut one of its candidates out
+        int stc[4];                                                   // ... and the statuses of the lane's four candidates of a chunk
         for (;;) {                                                    // mcts.py:20-23
             if (TWO && EXPAND && node == prev_leaf && !joined) {
                 // the walk stands on the node wave 1 is expanding (the root: at once): the one barrier, then the node's children from
@@ -362,6 +372,7 @@
                     if (node == 0) root_f64 = uniform_i32(L.ho[HO_ROOTF64]) != 0;
                 }
             }
+            if constexpr (SOLVER) { if (depth > 0 && nst != SOLVER_UNKNOWN) break; }   // a proven node below the root: the simulation ends here
             const int nch = meta_nch(nmeta);
             if (nch <= 0 || (ablate & 2)) break;
             if (ablate & 64) seg_t = clock64();
@@ -389,6 +400,9 @@
             int best = 0x7fffffff, bN = 0, bfc = -1;
             uint32_t bmeta = 0;
             bool forced_sel = false;                                  // FORCED: the child taken at the root was a forced one (counted, nothing else)
+            if constexpr (SOLVER) { bst = 0; open_any = true; shut_any = false; }
+            // SOLVER: a child's status byte is loaded beside its header and quotient (unconditional, clamped index: the same round trip).  After
+            // the scores: WON -> +inf, LOST -> -inf provided some child is not LOST (one ballot per level), then the argmax as it stands.
             // a child's q = W / (double)N comes from the Q column, where the backup that last changed W left it (node_store_wq: the same division
             // on the same operands, once per backup instead of once per scanned child and level).  Where N = 0 the word is unspecified, and every
             // use of q there is discarded: by the `Nc != 0 ? .. : un` select below, which is all tree_forced_score sees of it, and by
@@ -401,6 +415,14 @@
                 const size_t ci = base + fc + (valid ? lane : 0);
                 const NodeH hc = d.H[ci];                             // one 16-byte load: N, P, meta, first_child
                 const double Vc = qcol[ci];                           // the child's quotient (PUCT: its value sum)
+                int st1 = 0;
+                bool s_shut = false;
+                if constexpr (SOLVER) {
+                    st1 = AZK_TREE_SOLVER_ARG.status[ci];
+                    const bool open1 = __ballot(valid & (st1 != SOLVER_LOST)) != 0ull;
+                    s_shut = valid & (st1 == SOLVER_LOST) & open1;
+                    shut_sels += __ballot(s_shut) != 0ull ? 1 : 0;
+                }
                 const int Nc = hc.N, fcc = hc.fc;
                 const uint32_t mc = hc.meta;
                 const float P32 = hc.P;
@@ -414,7 +436,8 @@
                     const double q = PUCT ? Vc / (double)Nc : Vc;     // N = 0: unspecified (PUCT: inf/nan), discarded by the select
                     double un = u0;                                   // an unvisited child's score (plain text, no helper call: see the head of this file)
                     if constexpr (PUCT) un = pmode != 0 ? qf + u0 : u0;
-                    const double u = valid ? tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc != 0 ? q + u0 : un, Nc, P64, fk, Np), Nc, q, P64, gcv, gsig) : -__builtin_huge_val();
+                    double u = valid ? tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc != 0 ? q + u0 : un, Nc, P64, fk, Np), Nc, q, P64, gcv, gsig) : -__builtin_huge_val();
+                    if constexpr (SOLVER) u = (valid & (st1 == SOLVER_WON)) ? __builtin_huge_val() : (s_shut ? -__builtin_huge_val() : u);
                     const double um = wave_max_f64(u);               // (all lanes take part: never under the short-circuit below)
                     winners = __ballot(valid & (u == um));
                     if constexpr (FORCED) forced_sel = um == __builtin_huge_val();
@@ -426,13 +449,15 @@
                     const float q = (float)(PUCT ? Vc / (double)Nc : Vc);
                     float un = u0;
                     if constexpr (PUCT) un = pmode != 0 ? (float)qf + u0 : u0;
-                    const float u = valid ? (Nc != 0 ? q + u0 : un) : -__builtin_huge_valf();
+                    float u = valid ? (Nc != 0 ? q + u0 : un) : -__builtin_huge_valf();
+                    if constexpr (SOLVER) u = (valid & (st1 == SOLVER_WON)) ? __builtin_huge_valf() : (s_shut ? -__builtin_huge_valf() : u);
                     const float um = wave_max_f32(u);
                     winners = __ballot(valid & (u == um));
                 }
                 best = __ffsll((long long)winners) - 1;
                 bN = Nc; bmeta = mc; bfc = fcc;
                 if constexpr (PUCT) bW = Vc;
+                if constexpr (SOLVER) bst = st1;
             } else if (nch <= 2 * AZK_WAVE && !(ablate & 2048)) {
                 // 65 .. 128 candidates (late plies: every node of the tree): two per lane, the same straight-line shape - ten loads,
                 // one round trip.  (The general loop below sinks its prior loads into per-slot branches: one more round trip per
@@ -441,6 +466,14 @@
                 const size_t ca = base + fc + lane, cb = base + fc + (vb ? lane + AZK_WAVE : 0);
                 const NodeH ha = d.H[ca], hb = d.H[cb];
                 const double Va = qcol[ca], Vb = qcol[cb];            // quotients (PUCT: value sums)
+                int sta = 0, stb = 0;
+                bool shut_a = false, shut_b = false;
+                if constexpr (SOLVER) {
+                    sta = AZK_TREE_SOLVER_ARG.status[ca]; stb = AZK_TREE_SOLVER_ARG.status[cb];
+                    const bool open2 = __ballot((sta != SOLVER_LOST) | (vb & (stb != SOLVER_LOST))) != 0ull;
+                    shut_a = (sta == SOLVER_LOST) & open2; shut_b = vb & (stb == SOLVER_LOST) & open2;
+                    shut_sels += __ballot(shut_a | shut_b) != 0ull ? 1 : 0;
+                }
                 const int Na = ha.N, Nb = hb.N, fa = ha.fc, fb = hb.fc;
                 const uint32_t ma = ha.meta, mb = hb.meta;
                 const float Pa = ha.P, Pb = hb.P;
@@ -460,8 +493,12 @@
                     const double qa = PUCT ? Va / (double)Na : Va, qb = PUCT ? Vb / (double)Nb : Vb;
                     double una = u0a, unb = u0b;
                     if constexpr (PUCT) { una = pmode != 0 ? qf + u0a : u0a; unb = pmode != 0 ? qf + u0b : u0b; }
-                    const double ua = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Na != 0 ? qa + u0a : una, Na, Qa, fk, Np), Na, qa, Qa, gcv, gsig);
-                    const double ub = vb ? tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nb != 0 ? qb + u0b : unb, Nb, Qb, fk, Np), Nb, qb, Qb, gcv, gsig) : -__builtin_huge_val();
+                    double ua = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Na != 0 ? qa + u0a : una, Na, Qa, fk, Np), Na, qa, Qa, gcv, gsig);
+                    double ub = vb ? tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nb != 0 ? qb + u0b : unb, Nb, Qb, fk, Np), Nb, qb, Qb, gcv, gsig) : -__builtin_huge_val();
+                    if constexpr (SOLVER) {
+                        ua = sta == SOLVER_WON ? __builtin_huge_val() : (shut_a ? -__builtin_huge_val() : ua);
+                        ub = (vb & (stb == SOLVER_WON)) ? __builtin_huge_val() : (shut_b ? -__builtin_huge_val() : ub);
+                    }
                     const double um = wave_max_f64(fmax(ua, ub));
                     wa = __ballot(va & (ua == um)); wb = __ballot(vb & (ub == um));
                     if constexpr (FORCED) forced_sel = um == __builtin_huge_val();
@@ -479,8 +516,12 @@
                     const float qa = (float)(PUCT ? Va / (double)Na : Va), qb = (float)(PUCT ? Vb / (double)Nb : Vb);
                     float una = u0a, unb = u0b;
                     if constexpr (PUCT) { una = pmode != 0 ? (float)qf + u0a : u0a; unb = pmode != 0 ? (float)qf + u0b : u0b; }
-                    const float ua = Na != 0 ? qa + u0a : una;
-                    const float ub = vb ? (Nb != 0 ? qb + u0b : unb) : -__builtin_huge_valf();
+                    float ua = Na != 0 ? qa + u0a : una;
+                    float ub = vb ? (Nb != 0 ? qb + u0b : unb) : -__builtin_huge_valf();
+                    if constexpr (SOLVER) {
+                        ua = sta == SOLVER_WON ? __builtin_huge_valf() : (shut_a ? -__builtin_huge_valf() : ua);
+                        ub = (vb & (stb == SOLVER_WON)) ? __builtin_huge_valf() : (shut_b ? -__builtin_huge_valf() : ub);
+                    }
                     const float um = wave_max_f32(fmaxf(ua, ub));
                     wa = __ballot(va & (ua == um)); wb = __ballot(vb & (ub == um));
                 }
@@ -488,6 +529,7 @@
                 best = first ? __ffsll((long long)wa) - 1 : AZK_WAVE + __ffsll((long long)wb) - 1;
                 bN = first ? Na : Nb; bmeta = first ? ma : mb; bfc = first ? fa : fb;
                 if constexpr (PUCT) bW = first ? Va : Vb;
+                if constexpr (SOLVER) bst = first ? sta : stb;
             } else {
             if constexpr (PUCT) {
                 // mode 2 over more than one chunk (a board beyond 256 cells): the mass is needed before the first child is scored, so it takes
@@ -501,6 +543,15 @@
                         else p32 = hk.N > 0 ? p32 + hk.P : p32;
                     }
                     qf = tree_puct_qf2(qf, Wn, Np, f64 ? tree_puct_mass(p64) : (double)tree_puct_mass(p32));
+                }
+            }
+            if constexpr (SOLVER) {
+                // more than one chunk (a board beyond 256 cells): "some child is not LOST" is needed before the first child is scored, so it takes a
+                // pass of its own over the status bytes; a single chunk asks the registers it has loaded anyway
+                if (nch > 4 * AZK_WAVE) {
+                    bool mine = false;
+                    for (int i = lane; i < nch; i += AZK_WAVE) mine = mine | (AZK_TREE_SOLVER_ARG.status[base + fc + i] != SOLVER_LOST);
+                    open_any = __ballot(mine) != 0ull;
                 }
             }
             // all of this level's loads are issued before any arithmetic: 4 candidates per lane per 256-child chunk
@@ -517,6 +568,15 @@
                     const size_t ci = base + fc + (i < nch ? i : 0);
                     const NodeH hk = d.H[ci];
                     Nc[k] = hk.N; Vc[k] = qcol[ci]; mc[k] = hk.meta; fcc[k] = hk.fc; P32[k] = hk.P;
+                    if constexpr (SOLVER) stc[k] = AZK_TREE_SOLVER_ARG.status[ci];
+                }
+                if constexpr (SOLVER) {
+                    if (nch <= 4 * AZK_WAVE) {                        // the one chunk
+                        bool mine = false;
+#pragma unroll
+                        for (int k = 0; k < 4; k++) mine = mine | ((lane + AZK_WAVE * k < nch) & (stc[k] != SOLVER_LOST));
+                        open_any = __ballot(mine) != 0ull;
+                    }
                 }
                 if (f64) {                                            // root after Dirichlet mixing: float64 priors by child position
 #pragma unroll
@@ -556,11 +616,17 @@
                         const double q = PUCT ? Vc[k] / (double)Nc[k] : Vc[k];   // N = 0: unspecified (PUCT: inf/nan), discarded by the select below
                         double un = u0;
                         if constexpr (PUCT) un = pmode != 0 ? qf + u0 : u0;
-                        const double u = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc[k] != 0 ? q + u0 : un, Nc[k], P64[k], fk, Np), Nc[k], q, P64[k], gcv, gsig);
+                        double u = tree_gumbel_score<GUMBEL>(tree_forced_score<FORCED>(Nc[k] != 0 ? q + u0 : un, Nc[k], P64[k], fk, Np), Nc[k], q, P64[k], gcv, gsig);
+                        if constexpr (SOLVER) {
+                            const bool sh = (i < nch) & (stc[k] == SOLVER_LOST) & open_any;
+                            shut_any = shut_any | sh;
+                            u = stc[k] == SOLVER_WON ? __builtin_huge_val() : (sh ? -__builtin_huge_val() : u);
+                        }
                         const bool take = (i < nch) & ((best == 0x7fffffff) | (u > bu64));
                         bu64 = take ? u : bu64; best = take ? i : best; bN = take ? Nc[k] : bN;
                         bmeta = take ? mc[k] : bmeta; bfc = take ? fcc[k] : bfc;
                         if constexpr (PUCT) bW = take ? Vc[k] : bW;
+                        if constexpr (SOLVER) bst = take ? stc[k] : bst;
                     }
                 } else {                                              // float32 priors => float32 UCB (numpy>=2)
                     float s = (float)sqrt((double)Np);
@@ -573,16 +639,23 @@
                         const float q = (float)(PUCT ? Vc[k] / (double)Nc[k] : Vc[k]);   // N = 0: unspecified (PUCT: inf/nan), discarded by the select below
                         float un = u0;
                         if constexpr (PUCT) un = pmode != 0 ? (float)qf + u0 : u0;
-                        const float u = Nc[k] != 0 ? q + u0 : un;
+                        float u = Nc[k] != 0 ? q + u0 : un;
+                        if constexpr (SOLVER) {
+                            const bool sh = (i < nch) & (stc[k] == SOLVER_LOST) & open_any;
+                            shut_any = shut_any | sh;
+                            u = stc[k] == SOLVER_WON ? __builtin_huge_valf() : (sh ? -__builtin_huge_valf() : u);
+                        }
                         const bool take = (i < nch) & ((best == 0x7fffffff) | (u > bu32));
                         bu32 = take ? u : bu32; best = take ? i : best; bN = take ? Nc[k] : bN;
                         bmeta = take ? mc[k] : bmeta; bfc = take ? fcc[k] : bfc;
                         if constexpr (PUCT) bW = take ? Vc[k] : bW;
+                        if constexpr (SOLVER) bst = take ? stc[k] : bst;
                     }
                 }
             }
             if (ablate & 64) { const long long tn = clock64(); seg_b += tn - seg_t; seg_t = tn; }
             if constexpr (FORCED) forced_sel = f64 && __ballot(bu64 == __builtin_huge_val()) != 0ull;   // (+inf is the maximum: the winner is one of them)
+            if constexpr (SOLVER) shut_sels += __ballot(shut_any) != 0ull ? 1 : 0;
             if (f64) wave_argmax_first_lane63<double>(bu64, best);
             else wave_argmax_first_lane63<float>(bu32, best);
             best = __builtin_amdgcn_readlane(best, 63);               // DPP reduction: the wave's result lives in lane 63
@@ -595,6 +668,7 @@
             nmeta = (uint32_t)__builtin_amdgcn_readlane((int)bmeta, wl);
             fc = __builtin_amdgcn_readlane(bfc, wl);
             if constexpr (PUCT) Wn = tree_readlane_f64(bW, wl);
+            if constexpr (SOLVER) nst = __builtin_amdgcn_readlane(bst, wl);
             if (ablate & 64) { const long long tn = clock64(); seg_c += tn - seg_t; seg_t = tn; }
             const int cellc = meta_cell(nmeta);
             const int mover = (root_player + depth) & 1;
@@ -665,8 +739,19 @@
                 kw = d.cache_key[((size_t)g * d.cache_entries + entry) * KW + min(lane, KW - 1)];
             }
         };
-        if (TWO) probe_issue();
+        // SOLVER: a walk that stopped on a proven node (depth > 0 && nst != SOLVER_UNKNOWN) looks at nothing below - no probe, no terminal test.
+        // (Its two conditions are spelled out under `if constexpr`, and the terminal test stands twice: a flag declared here for every kernel,
+        // even one that folds away, gave the fused PUCT kernels another instruction order - tools/compare_kernel_isa.py.)
+        if constexpr (SOLVER) { if (TWO && !(depth > 0 && nst != SOLVER_UNKNOWN)) probe_issue(); }
+        else if (TWO) probe_issue();
         int term = -1;
+        if constexpr (SOLVER) {
+            if (depth > 0 && nst == SOLVER_UNKNOWN) {                 // mcts.py:25-32 (root is never tested)
+                const int w = azk_check_winner(L.board, gd, 1 - node_player, node_cell);
+                if (w != -1) term = 1;
+                else if (node_mc == gd.state_dim) term = 0;
+            }
+        } else
         if (depth > 0) {                                              // mcts.py:25-32 (root is never tested)
             const int w = azk_check_winner(L.board, gd, 1 - node_player, node_cell);
             if (w != -1) term = 1;
@@ -678,6 +763,64 @@
             if constexpr (FORCED) { if (forced_root) count_add(d, CNT_FORCED, g, 1); }   // (with the simulation's other counters, off the walk)
         }
         if (wrec) rec_depth = depth;
+        if constexpr (SOLVER) {
+            if (lane == 0 && shut_sels) atomicAdd((unsigned long long *)&AZK_TREE_SOLVER_ARG.stats[SST_EXCLUDING], (unsigned long long)shut_sels);
+            const bool sstop = depth > 0 && nst != SOLVER_UNKNOWN;   // the walk stopped on a proven node
+            if (sstop || term >= 0) {
+                const SolverDev &sv = AZK_TREE_SOLVER_ARG;
+                const bool has_children = meta_nch(nmeta) > 0;
+                double bv = (double)term;
+                int n_by_won = 0, n_by_all = 0, root_proven = 0;
+                if (sstop) {
+                    bv = nst == SOLVER_WON ? 1.0 : (nst == SOLVER_LOST ? -1.0 : 0.0);
+                } else {
+                    // the first arrival at this terminal leaf marks it, and the proof runs from it up the path: cs = the status the node at
+                    // trace index ci has just taken.  Wave 0 reads the children of PATH nodes only; the one path node whose children wave 1 may be
+                    // writing is prev_leaf, and the walk stands on it only behind join(1) - every byte read here was stored before the barrier or
+                    // by this wave.  The child that has just been proven is taken from the register, not from the byte stored a moment ago.
+                    int cs = term == 1 ? SOLVER_WON : SOLVER_DRAW, cnode = node;
+                    if (lane == 0) sv.status[base + node] = (uint8_t)cs;
+                    for (int ci = depth; ci > 0; ci--) {
+                        const int p = uniform_i32(L.path[ci - 1]);
+                        if (uniform_i32((int)sv.status[base + p]) != SOLVER_UNKNOWN) break;       // already proven (only the root can be): stop
+                        int ns = SOLVER_LOST;                                                     // c WON: p is LOST
+                        if (cs == SOLVER_WON) n_by_won++;
+                        else {                                                                    // one wave-wide pass over all of p's children
+                            const NodeH hp = d.H[base + p];
+                            const int pfc = uniform_i32(hp.fc), pn = meta_nch((uint32_t)uniform_i32((int)hp.meta));
+                            bool unk = false, open = false;
+                            for (int i = lane; i < pn; i += AZK_WAVE) {
+                                const int ch = pfc + i;
+                                const int st = ch == cnode ? cs : (int)sv.status[base + ch];
+                                unk = unk | (st == SOLVER_UNKNOWN); open = open | (st != SOLVER_LOST);
+                            }
+                            if (__ballot(unk) != 0ull) break;
+                            ns = __ballot(open) != 0ull ? SOLVER_DRAW : SOLVER_WON;              // all LOST: WON; LOST and DRAW: DRAW
+                            n_by_all++;
+                        }
+                        if (lane == 0) sv.status[base + p] = (uint8_t)ns;
+                        if (ci == 1) root_proven = 1;
+                        cs = ns; cnode = p;
+                    }
+                }
+                backup_path(d, base, L.path, depth, bv);
+                if (lane == 0) {
+                    d.leaf_flag[vi] = 0;
+                    if (!has_children) count_add(d, CNT_TERMINAL, g, 1);
+                    count_add(d, CNT_TRACE, g, depth + 1);
+                    unsigned long long *ss = (unsigned long long *)sv.stats;
+                    if (sstop) { if (has_children) atomicAdd(ss + SST_STOPPED, 1ull); }
+                    else {
+                        atomicAdd(ss + SST_TERMINAL, 1ull);
+                        if (n_by_won) atomicAdd(ss + SST_BY_WON_CHILD, (unsigned long long)n_by_won);
+                        if (n_by_all) atomicAdd(ss + SST_BY_ALL_CHILDREN, (unsigned long long)n_by_all);
+                        if (root_proven) atomicAdd(ss + SST_ROOTS, 1ull);
+                    }
+                }
+                if (MULTI && (vl || still_young())) continue;
+                break;
+            }
+        } else
         if (term >= 0) {
             if (wrec) { rec_type = 0; t3 = t4 = clock64(); }
             backup_path(d, base, L.path, depth, (double)term);

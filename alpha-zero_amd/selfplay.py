@@ -183,6 +183,30 @@ def check_puct(puct, evaluator=True, leaves_per_step=1, forced_playouts=None, gu
     return setting
 
 
+def check_solver(solver, evaluator=True, leaves_per_step=1, forced_playouts=None, gumbel_root=None, puct=None, tree_reuse=0):
+    """solver = True -> True, or None for off (None or False).  OPT-IN exact game-end proofs in the search (include/azk.h azk_set_solver; DESIGN
+    section 29): every node keeps a status proven from terminal leaves up the simulation's path, the walk stops on proven nodes below the
+    root and selection shuts out children proven lost.  Raises ValueError, before any engine exists, for what the engine refuses too - virtual
+    loss, forced playouts, a Gumbel root, configurable PUCT, tree reuse - and for vanilla MCTS (evaluator None), which keeps no status."""
+    if solver is None or solver is False:
+        return None
+    if solver is not True:
+        raise ValueError(f"solver must be True, False or None, not {solver!r}")
+    if _is_vanilla(evaluator):
+        raise ValueError("solver: vanilla MCTS (evaluator None) is refused - its search keeps no status column")
+    if int(leaves_per_step) > 1:
+        raise ValueError("solver does not combine with leaves_per_step > 1 (a virtual-loss search leaves losses on paths a proof would end)")
+    if forced_playouts:
+        raise ValueError("solver does not combine with forced_playouts (a forced child and a child shut out would claim the same selection)")
+    if gumbel_root is not None:
+        raise ValueError("solver does not combine with gumbel_root (the eligibility rule needs raw root selection)")
+    if puct is not None:
+        raise ValueError("solver does not combine with puct (the two options' kernels are not combined)")
+    if int(tree_reuse) != 0:
+        raise ValueError("solver does not combine with tree_reuse (the status column is not carried through a re-rooting)")
+    return True
+
+
 def eval_symmetry_elements(game, size=None):
     """The D4 elements (the emission's numbering: rot0, lr, tb, rot90, lr(rot90), tb(rot90), rot180, rot270) a game's geometry admits
     (include/azk.h azk_set_eval_symmetry): all eight on a square board with one action per cell, {0, 1, 2, 6} on a Gomoku board with
@@ -411,7 +435,7 @@ def _refuse_vanilla_resign(resign, evaluator):
 
 
 class SelfPlayResult:
-    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base", "full", "resigned", "kl", "coin", "open_plies", "opening")
+    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base", "full", "resigned", "kl", "coin", "open_plies", "opening", "root_status")
 
     def __init__(self):
         self.boards, self.actions, self.pis, self.qs, self.winner, self.cells = [], [(-1, -1)], [], [], None, []
@@ -420,6 +444,7 @@ class SelfPlayResult:
         self.resigned = False        # the game ended by resignation (resign=...): winner is then the side that did not concede
         self.open_plies = 0          # plies of the game's random opening (openings=...): boards[0] is the position after them, ply open_plies
         self.opening = []            # ... and the cells they were played on, in order (the players alternate from player 0)
+        self.root_status = []        # per ply with solver=True: the root's proven status as the mover sees it (0 unknown, 1 wins, 2 loses, 3 draw)
         self.kl, self.coin = [], []  # per ply with surprise_weight=...: KL(recorded pi || raw prior) and the ply's coin (empty without)
 
     def as_reference_tuple(self):
@@ -432,7 +457,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
                     budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
                     eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None,
-                    openings_first_game=None, puct=None, move_temperature=None, value_target=None):
+                    openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -470,7 +495,9 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     instead of "sample in proportion to the visits while move_count < sample_until", which is then not looked at; the recorded pis stay the raw
     visit distributions.  ("until", 1.0, sample_until) plays the games of a call without the option.  value_target = r | (r, lam) (OPT-IN,
     check_value_target): the replay ring gets (1 - r) * z + r * G as the z of every tuple, G the horizon-lam return over the game's own search
-    values (value_targets(SelfPlayResult.qs, ...) is the same rule on the host); the games, states and pis do not change.
+    values (value_targets(SelfPlayResult.qs, ...) is the same rule on the host); the games, states and pis do not change.  solver = True
+    (OPT-IN, check_solver): every search keeps exact game-end proofs (Engine.set_solver); SelfPlayResult.root_status gets each move's root
+    status as the mover sees it (0 unknown, 1 wins, 2 loses, 3 draw).
     """
     import torch
     opn = check_openings(openings, game, size, evaluator)
@@ -491,6 +518,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     tmp = check_move_temperature(move_temperature, engine.max_sims if engine is not None else n_sims, game, size, gum,
                                  engine.tree_reuse if engine is not None else tree_reuse)
     vtg = check_value_target(value_target, evaluator, leaves_per_step, gum)
+    slv = check_solver(solver, evaluator, leaves_per_step, fpk, gum, pct, engine.tree_reuse if engine is not None else tree_reuse)
     _refuse_vanilla_resign(rsg, evaluator)
     if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
@@ -516,6 +544,10 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         eng.set_move_temperature(*tmp)
     if vtg is not None:
         eng.set_value_target(*vtg)
+    if slv is not None:
+        eng.set_solver(True)
+    elif eng.solver:                                              # an engine handed in with the option still on
+        eng.set_solver(False)
     # virtual-loss, top-up and capped engines are driven by the simulation budget
     budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
     assert eng.G == n_games
@@ -573,6 +605,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         else:
             eng.search(ev, ns, noise if dirichlet else None)
         full_h = eng.search_full().cpu().numpy() if eng.playout_cap is not None else None
+        status_h = eng.solver_status() if eng.solver else None
         pi, q, _ = eng.root_stats()
         if eng.forced_playouts is not None or eng.gumbel_root is not None:
             pi = eng.root_policy_target()                         # what advance records: pruned where the search was a forced one; a Gumbel root's target
@@ -588,6 +621,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
             r.pis.append(pi_h[g].copy())
             r.qs.append(float(q_h[g]))
             r.full.append(True if full_h is None else bool(full_h[g]))
+            if status_h is not None:
+                r.root_status.append(int(status_h[g]))
             if kl_h is not None:
                 r.kl.append(float(kl_h[g]))
                 r.coin.append(float(coin_h[g]))
@@ -754,6 +789,9 @@ class SelfPlayRunner:
     value_target = r | (r, lam) (OPT-IN, check_value_target; with everything above except gumbel_root and leaves_per_step > 1): the replay ring
     gets (1 - r) * z + r * G as the z of every tuple, G the horizon-lam return over the game's own search values (value_targets); the games,
     the records, states and pis do not change.
+
+    solver = True (OPT-IN, check_solver; with everything above except forced_playouts, gumbel_root, puct, tree_reuse and leaves_per_step > 1):
+    every search keeps exact game-end proofs (Engine.set_solver); solver_stats() sums the groups' six counters.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
@@ -762,11 +800,12 @@ class SelfPlayRunner:
                  steps_per_graph=32,
                  leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None,
                  surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None, openings_first_game=None, puct=None,
-                 move_temperature=None, value_target=None):
+                 move_temperature=None, value_target=None, solver=None):
         import torch
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, playout_cap, forced_playouts,
                                              surprise_weight)
+        self.solver = check_solver(solver, evaluator, leaves_per_step, forced_playouts, gumbel_root, puct, tree_reuse)
         self.value_target = check_value_target(value_target, evaluator, leaves_per_step, self.gumbel_root)
         self.move_temperature = check_move_temperature(move_temperature, n_sims, game, size, self.gumbel_root, tree_reuse)
         self.puct = puct if check_puct(puct, evaluator, leaves_per_step, forced_playouts, gumbel_root) is not None else None
@@ -832,6 +871,8 @@ class SelfPlayRunner:
                 h.eng.set_move_temperature(*self.move_temperature)
             if self.value_target is not None:
                 h.eng.set_value_target(*self.value_target)
+            if self.solver is not None:
+                h.eng.set_solver(True)
             if self.openings is not None:                         # the first games, under the key of their first search (move 0)
                 h.eng.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                                    (first_global_game if openings_first_game is None else openings_first_game) + i * per)
@@ -1047,6 +1088,16 @@ class SelfPlayRunner:
             raise ValueError("move_temperature_stats: the runner was built without move_temperature")
         return [sum(x) for x in zip(*[h.eng.move_temperature_stats() for h in self.halves])]
 
+    def solver_stats(self):
+        """The six counters of Engine.solver_stats summed over the groups (host sync)."""
+        if self.solver is None:
+            raise ValueError("solver_stats: the runner was built without solver=True")
+        out = {}
+        for h in self.halves:
+            for k, v in h.eng.solver_stats().items():
+                out[k] = out.get(k, 0) + v
+        return out
+
     def resign_stats(self):
         """[games ended by resignation, never-resign games ended, of those marked, of those whose marked side did not lose], all groups."""
         if self.resign is None:
@@ -1131,16 +1182,20 @@ class AsyncSelfPlayRunner:
 
     value_target = r | (r, lam) (OPT-IN, check_value_target; with everything above except gumbel_root): the games of SelfPlayRunner, slot for
     slot, and the drain writes (1 - r) * z + r * G as the z of every tuple - the mover keeps each ply's q beside its pi, with re-rooting the
-    carried root's W / N as it stands; the record ring's q column holds the same numbers."""
+    carried root's W / N as it stands; the record ring's q column holds the same numbers.
+
+    solver = True (OPT-IN, check_solver; with everything above except forced_playouts, gumbel_root, puct and reroot): the games of
+    SelfPlayRunner(solver=True), slot for slot - the option lives in k_tree alone, the movers do not know it."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
                  playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None,
-                 openings=None, openings_seed=None, openings_first_game=None, puct=None, move_temperature=None, value_target=None):
+                 openings=None, openings_seed=None, openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None):
         import torch
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, 1, tree_reuse or reroot, playout_cap, forced_playouts, surprise_weight)
+        self.solver = check_solver(solver, evaluator, 1, forced_playouts, gumbel_root, puct, tree_reuse or reroot)
         self.value_target = check_value_target(value_target, evaluator, 1, self.gumbel_root)
         self.move_temperature = check_move_temperature(move_temperature, n_sims, game, size, self.gumbel_root, tree_reuse or reroot)
         self.puct = puct if check_puct(puct, evaluator, 1, forced_playouts, gumbel_root) is not None else None
@@ -1188,6 +1243,8 @@ class AsyncSelfPlayRunner:
             e.set_move_temperature(*self.move_temperature)
         if self.value_target is not None:
             e.set_value_target(*self.value_target)
+        if self.solver is not None:
+            e.set_solver(True)
         if self.openings is not None:                             # async_begin opens the first games, the drain's restart every later one
             e.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                            first_global_game if openings_first_game is None else openings_first_game)
@@ -1336,6 +1393,16 @@ class AsyncSelfPlayRunner:
         if self.move_temperature is None:
             raise ValueError("move_temperature_stats: the runner was built without move_temperature")
         return [sum(x) for x in zip(*[h.eng.move_temperature_stats() for h in self.halves])]
+
+    def solver_stats(self):
+        """The six counters of Engine.solver_stats summed over the groups (host sync)."""
+        if self.solver is None:
+            raise ValueError("solver_stats: the runner was built without solver=True")
+        out = {}
+        for h in self.halves:
+            for k, v in h.eng.solver_stats().items():
+                out[k] = out.get(k, 0) + v
+        return out
 
     def resign_stats(self):
         """[games ended by resignation, never-resign games ended, of those marked, of those whose marked side did not lose] (host sync)."""

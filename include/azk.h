@@ -465,6 +465,53 @@ int32_t azk_gen_gumbel_uniforms(azk_engine *e, uint64_t seed, int64_t first_glob
 int32_t azk_set_puct(azk_engine *e, const double *c_table_host, int32_t n_table, int32_t fpu_mode, double fpu_tree, double fpu_root, void *stream);
 int32_t azk_clear_puct(azk_engine *e);
 
+/* ---- exact game-end proofs in the search: a solver for k_tree (OPT-IN; off, the engine launches exactly the kernels it launched before).
+ * A simulation that walks into a decided position learns nothing new, and the reference's search never writes a decided result down.  With
+ * the option every node keeps a STATUS byte, seen by the player who moved INTO the node - the view Node.value has (node.py:34) - as in
+ * Winands' MCTS-Solver and Leela's certainty propagation:
+ *   status     0 UNKNOWN;  1 WON, backed up as +1;  2 LOST, backed up as -1;  3 DRAW, backed up as 0.  A new node is UNKNOWN whatever the
+ *              arena slot held before (recycled, restarted and re-positioned games); the root becomes UNKNOWN when it is expanded.
+ *   walk       descends while the node has children and is either the root or UNKNOWN.  If it stops on a proven node other than the root
+ *              the simulation ends there: check_winner, the eval-cache probe, the move list and the evaluator are skipped and the status's
+ *              value is backed up along the path exactly as a terminal value is.  The root is never stopped on: it keeps selecting, so
+ *              N[root] = 1 + sum N[child] still holds and the movers, pi, q and resignation read what they read without the option.
+ *   terminal   the first arrival at a terminal leaf (mcts.py:25-32) marks it - WON for a win, DRAW for a full board - and the proof runs
+ *              from it; later arrivals find it proven.
+ *   proof      after a node c on the path has just become proven, its parent p on the path is examined, from the leaf upwards: p already
+ *              proven: stop.  c WON: p becomes LOST.  Otherwise the statuses of ALL of p's children are read in list order: any UNKNOWN:
+ *              stop; all LOST: p becomes WON; otherwise (LOST and DRAW) p becomes DRAW.  If p was newly proven the proof goes on to its
+ *              parent; the root takes a status like any node.  The backup of the simulation's value does not change.
+ *   selection  at the root or an UNKNOWN node the scores are computed as without the option, on both precision paths and in all three forms
+ *              of the scan; then a WON child scores +infinity (possible only at a proven root) and a LOST child -infinity provided at least
+ *              one child of the node is not LOST (if every child is LOST the scores stay as they were).  The first maximum wins; a DRAW
+ *              child is an ordinary candidate.
+ *   hence      an UNKNOWN node never has a WON child and has at least one UNKNOWN child.  At a root proven for its mover every further
+ *              simulation goes to the first WON child, whose visits then dominate pi and the move without the movers knowing the option.
+ *              Every W is still a sum of float32 network values and of +1, -1 and 0.  With the option on and no terminal reached, the tree
+ *              is the option-off tree bit for bit.
+ * azk_set_solver allocates the status column (uint8 [G][cap]) and six counters on first use and zeroes both (nothing is allocated while the
+ * option was never set); azk_clear_solver makes the engine launch what it launched before.  AZK_ERR_ARG: an engine with leaves_per_step > 1.
+ * AZK_ERR_STATE: with forced playouts, a Gumbel root or configurable PUCT set - azk_set_forced_playouts, azk_set_gumbel_root and
+ * azk_set_puct refuse likewise while the solver is set; on an engine created with tree_reuse != 0 (the status column is not carried through
+ * a re-rooting; azk_async_begin_reuse refuses likewise); between the begin of a search and the call that ends it; after azk_async_begin;
+ * and azk_vanilla_search while the option is set.  Combines with a playout cap, resignation, evaluation symmetry, emit_elements, surprise
+ * weighting, random openings, a move temperature, value targets, the eval cache in both modes, plain and budget stepping and the
+ * asynchronous movers without re-rooting.
+ * azk_get_solver_status: root_status_host int8 [G], each root's status as the side TO MOVE at the root sees it - 0 unknown, 1 wins, 2 loses,
+ * 3 draw: the flip of the stored WON and LOST.  Meaningful from the root's expansion (a search's first simulation) on.  Waits.
+ * azk_export_tree_status: status_host uint8 [cap], the stored statuses of one game's nodes in azk_export_tree's row order; returns the node
+ * count.  azk_get_solver_stats: out6_host int64 [6] since azk_set_solver - terminal leaves marked; nodes proven by one WON child; nodes proven
+ * by all their children; simulations ended on a proven node that has children; selections that shut at least one child out; roots that took
+ * a status.  All three: AZK_ERR_STATE while the option is off.
+ * azk_debug_fill_solver_status (debug / tests only): every byte of the status column becomes `byte`; for engines whose trees are fresh
+ * roots - a search that follows must come out the same whatever was filled in. */
+int32_t azk_set_solver(azk_engine *e, void *stream);
+int32_t azk_clear_solver(azk_engine *e);
+int32_t azk_get_solver_status(azk_engine *e, int8_t *root_status_host, void *stream);
+int32_t azk_export_tree_status(azk_engine *e, int32_t game, int32_t cap, uint8_t *status_host, void *stream);
+int32_t azk_get_solver_stats(azk_engine *e, int64_t *out6_host, void *stream);
+int32_t azk_debug_fill_solver_status(azk_engine *e, int32_t byte, void *stream);
+
 /* ---- move temperature: per-ply schedule, visit offset, value cutoff (OPT-IN; off, the engine launches exactly the kernels it launched
  * before).  The reference picks a move in one way: in proportion to the visits while move_count < sample_until, the first most-visited child
  * afterwards.  With the option the movers (azk_advance*, the asynchronous movers) ignore sample_until_move - the argument and

@@ -49,6 +49,7 @@ SYMBOLS = [
     "azk_export_tree_quotients", "azk_debug_fill_quotients",
     "azk_set_solver", "azk_clear_solver", "azk_get_solver_status", "azk_export_tree_status", "azk_get_solver_stats",
     "azk_debug_fill_solver_status",
+    "azk_set_root_noise", "azk_clear_root_noise", "azk_gen_root_noise", "azk_get_root_noise",
 ]
 
 
@@ -344,6 +345,7 @@ class Engine:
         self.forced_playouts = None                 # k once set_forced_playouts has switched the option on
         self.gumbel_root = None                     # (m, n_sims, c_visit, c_scale) once set_gumbel_root has switched the option on
         self.openings = None                        # (p_open, max_plies, spread) once set_openings has switched the option on
+        self.root_noise = None                      # ("legal" | "total", alpha) once set_root_noise has switched the option on
         self.puct = None                            # (c_table, fpu_mode, fpu_tree, fpu_root) once set_puct has switched the option on
         self.solver = False                         # True once set_solver has switched the option on
         self.move_temperature = None                # (row_of_ply, weights, visit_offset, value_cutoff) once set_move_temperature has switched the option on
@@ -907,6 +909,44 @@ class Engine:
         self._chk(self.L.azk_gen_noise(self.h, int(seed), int(first_global_game), int(move_index), float(alpha),
                                        _p(noise), _p(uni), _stream()))
         return noise, uni
+
+    def set_root_noise(self, mode, alpha):
+        """OPT-IN root noise on the legal moves (azk_set_root_noise): from now on a search's Dirichlet row is drawn over the
+        actions that are legal in the position the search starts from - the root's children - and is 0 elsewhere.  mode "legal": Gamma(alpha)
+        per legal action (gen_noise's row restricted to them and renormalised); "total": Gamma(alpha / n) for n legal actions, so the row's total
+        concentration is alpha whatever n is (KataGo: 10.83).  Lock-step drivers make the rows with gen_root_noise where they called gen_noise;
+        the asynchronous movers make them themselves (alpha takes the place of async_begin's).  Not with a Gumbel root; before async_begin and
+        outside a search.  clear_root_noise switches it off."""
+        modes = {"legal": 1, "total": 2}
+        if mode not in modes:
+            raise AzkError(f"set_root_noise: mode must be 'legal' or 'total', not {mode!r}")
+        self._chk(self.L.azk_set_root_noise(self.h, modes[mode], float(alpha), _stream()))
+        self.root_noise = (mode, float(alpha))
+
+    def clear_root_noise(self):
+        """Root noise on the legal moves off (azk_clear_root_noise): the engine launches what it launched before."""
+        self._chk(self.L.azk_clear_root_noise(self.h))
+        self.root_noise = None
+
+    def gen_root_noise(self, seed, first_global_game, move_index, want_noise=True, want_uniforms=True):
+        """gen_noise's (rows, uniforms) with the rows drawn over each game's legal moves, from the engine's positions as they stand
+        (azk_gen_root_noise): call it after open_pending / advance and before begin_search*.  The uniforms are gen_noise's bit for bit."""
+        if self.root_noise is None:
+            raise AzkError("gen_root_noise: no root noise is set (set_root_noise)")
+        torch = self.torch
+        noise = torch.empty((self.G, self.action_dim), dtype=torch.float64, device=self.device) if want_noise else None
+        uni = torch.empty(self.G, dtype=torch.float64, device=self.device) if want_uniforms else None
+        self._chk(self.L.azk_gen_root_noise(self.h, int(seed) & ((1 << 64) - 1), int(first_global_game), int(move_index), _p(noise), _p(uni), _stream()))
+        return noise, uni
+
+    def root_noise_rows(self):
+        """float64 CUDA tensor [G, A]: the row each game's current search reads (azk_get_root_noise; an asynchronous engine: the row of the slot's
+        move counter)."""
+        if self.root_noise is None:
+            raise AzkError("root_noise_rows: no root noise is set (set_root_noise)")
+        rows = self.torch.empty((self.G, self.action_dim), dtype=self.torch.float64, device=self.device)
+        self._chk(self.L.azk_get_root_noise(self.h, _p(rows), _stream()))
+        return rows
 
     # ---- inspection -----------------------------------------------------------------------------
     def root_children(self, game):

@@ -202,6 +202,10 @@ def declare(L, symbols):
     L.azk_get_opening_stats.argtypes = [vp, vp, vp]
     L.azk_get_opening_actions.argtypes = [vp, vp, vp]
     L.azk_get_leaf_flags.argtypes = [vp, vp, vp]
+    L.azk_set_root_noise.argtypes = [vp, i32, f64, vp]
+    L.azk_clear_root_noise.argtypes = [vp]
+    L.azk_gen_root_noise.argtypes = [vp, u64, i64, i32, vp, vp, vp]
+    L.azk_get_root_noise.argtypes = [vp, vp, vp]
     L.azk_set_eval_symmetry.argtypes = [vp, i32, u64, vp]
     L.azk_get_leaf_symmetry.argtypes = [vp, vp, vp]
     L.azk_eval_symmetry_restore.argtypes = [vp, vp, vp, vp]

@@ -486,6 +486,9 @@ int32_t azk_launch_next_searches(azk_engine *e, hipStream_t st) {
         k_async_restart<cap.value, open.value><<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(
             RestartPack<cap.value, open.value>{d, on<cap.value>(e->cp), on<open.value>(e->op)}, e->ad, e->async_recycle);
     }, e->cp.n_fast != 0, e->op_on);
+    // root noise on the legal moves: the rows of the restarted games (opened or empty boards) and of the parked ones, whose positions stand
+    // since their move - in front of k_reroot_list, which mixes a parked game's row into its carried root
+    if (e->rn.mode && e->ad.dirichlet) azk_launch_root_noise_due(e, st);
     if (!e->ru.mode) return AZK_OK;
     with_flags([&](auto cap) {
         k_reroot_list<cap.value><<<(unsigned)d.G, AZK_WAVE, 0, st>>>(d, e->ad, CapPack<ReuseDev, cap.value>{e->ru, on<cap.value>(e->cp)});

@@ -259,6 +259,16 @@ struct OpenDev {
 // ... and what emission needs of it
 struct OpenEmit { const int *open_plies; };
 
+// root noise on the legal moves (azk_set_root_noise, opt-in; mode == 0 otherwise): a search's Dirichlet row is drawn over the
+// actions that are legal in the position it starts from - the root's children - and is +0.0 elsewhere; k_tree and reroot_one read it as they read
+// any row.  Its own argument of the two kernels that exist only for it (azk_noise.hip: k_root_noise, k_root_noise_due): every other argument
+// block - and every kernel an engine without the option launches - stays as it was
+struct RootNoiseDev {
+    int mode;                  // 0 off, 1 "legal": Gamma(alpha) per legal action, 2 "total": Gamma(alpha / n) for n legal actions
+    double alpha;              // replaces azk_async_config.alpha while the option is set
+    int *row_key;              // asynchronous engines: [G] the move key the game's row pair last got a row for, -1 = none; null otherwise
+};
+
 struct LdsView {
     uint8_t *board;
     int *path;
@@ -493,7 +503,8 @@ struct azk_engine {
     bool op_on = false;                  // (p_open = 0 is a live setting, so the switch is its own word)
     SolverDev sv = {};                   // exact game-end proofs (azk_set_solver); sv_on == false: off, nothing allocated
     bool sv_on = false;
-    bool in_search = false;              // between a search's begin and the move (or new position) that ends it: azk_set_eval_symmetry refuses
+    RootNoiseDev rn = {};                // root noise on the legal moves (azk_set_root_noise); rn.mode == 0: off, nothing allocated
+    bool in_search = false;             // between a search's begin and the move (or new position) that ends it: azk_set_eval_symmetry refuses
 };
 
 #define HIPCHK(e, call)                                                                 \
@@ -539,6 +550,11 @@ AZK_INTERNAL int32_t azk_launch_next_searches(azk_engine *e, hipStream_t st);
 // the drain - the next row of every game that moved since the last one (azk_noise.hip)
 AZK_INTERNAL void azk_launch_first_rows(azk_engine *e, hipStream_t st);
 AZK_INTERNAL void azk_launch_rows_ahead(azk_engine *e, hipStream_t st);
+// root noise on the legal moves (azk_set_root_noise), asynchronous engines: the rows are made where the position is known, not a search ahead.
+// azk_root_noise_begin: azk_async_begin, behind the first searches - row_key allocated and cleared, noise_key at the largest int (the movers'
+// "row exists" test holds), every game's first row.  azk_launch_root_noise_due: the row of every game whose key moved (azk_noise.hip)
+AZK_INTERNAL int32_t azk_root_noise_begin(azk_engine *e, hipStream_t st);
+AZK_INTERNAL void azk_launch_root_noise_due(azk_engine *e, hipStream_t st);
 // azk_launch_emit: (state, pi, z) emission of the finished games, all G or the *n_list listed ones (azk_emit.hip)
 AZK_INTERNAL void azk_launch_emit(azk_engine *e, float *states, double *pis, float *zs, long long capacity, unsigned long long *cursor, long long *game_base,
                                   const int *list, const int *n_list, hipStream_t st);

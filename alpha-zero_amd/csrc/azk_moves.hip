@@ -749,7 +749,9 @@ static int32_t async_begin(azk_engine *e, const azk_async_config *c, void *strea
     if (e->cp.n_fast) { e->cp.seed = a.seed; e->cp.first_game = a.first_game; e->cp.stats = a.stats; }   // the coins share the noise rows' key: this run's seed and first game
     azk_launch_first_searches(e, st);
     HIPCHK(e, hipMemsetAsync(a.todo_count, 0, sizeof(int), st));
-    if (a.dirichlet) azk_launch_first_rows(e, st);
+    if (a.dirichlet && e->rn.mode) {                              // root noise on the legal moves: the rows come from the positions, none is made ahead
+        if (const int32_t rc = azk_root_noise_begin(e, st); rc != AZK_OK) return rc;
+    } else if (a.dirichlet) azk_launch_first_rows(e, st);
     HIPCHK(e, hipGetLastError());
     return AZK_OK;
 }
@@ -772,8 +774,11 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
             k_move_async<reroot.value, cap.value, resign.value, forced.value, surprise.value, temp.value, value.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(
                 d, e->ad, move_pack<cap.value, resign.value, forced.value, surprise.value, temp.value, value.value>(e->ru, e));
         }, e->ru.mode != 0, e->cp.n_fast != 0, e->rs.v_resign != 0.0, e->forced_k != 0.0, e->sp_on, e->tp_on, e->vt_on);
+    // root noise on the legal moves: a game that has just moved began its next search in the mover - its row, from the new position, before the
+    // next tree launch; one more node of the linear chain.  (A re-rooting engine's moved games are parked: their rows are the drain's.)
+    if ((phases & 2) && e->rn.mode && e->ad.dirichlet && !e->ru.mode) azk_launch_root_noise_due(e, st);
     HIPCHK(e, hipGetLastError());
-    return azk_sym_leaves(e, st);                                 // (eval symmetry: the leaves the tree launch selected, behind the movers)
+    return azk_sym_leaves(e, st);                                // (eval symmetry: the leaves the tree launch selected, behind the movers)
 }
 
 int32_t azk_async_set_budget(azk_engine *e, int32_t n_sims, int32_t max_sims_per_launch, void *stream) {
@@ -795,7 +800,7 @@ int32_t azk_async_drain(azk_engine *e, float *states_dev, double *pis_dev, float
     }
     if (const int32_t rc = azk_launch_next_searches(e, st); rc != AZK_OK) return rc;      // finished games restarted, parked games re-rooted
     if (e->ad.dirichlet) {                                        // the rows of the searches AFTER the ones begun since the last drain
-        azk_launch_rows_ahead(e, st);
+        if (!e->rn.mode) azk_launch_rows_ahead(e, st);            // (root noise on the legal moves: azk_launch_next_searches has made the rows that are due)
         HIPCHK(e, hipMemsetAsync(e->ad.todo_count, 0, sizeof(int), st));
     }
     HIPCHK(e, hipGetLastError());

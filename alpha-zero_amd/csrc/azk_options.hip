@@ -1,5 +1,5 @@
 // azk_options.hip - the opt-ins' state calls (include/azk.h): set, clear and read playout cap, forced playouts, Gumbel root, resignation,
-// surprise weighting, random openings, the move temperature, value targets and the solver.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
+// surprise weighting, random openings, root noise on the legal moves, the move temperature, value targets and the solver.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
 // block (azk_engine_int.h) that azk_opt_pack.h hands to the kernels of azk_begin.hip, azk_moves.hip and azk_emit.hip.
 #include "azk_engine_int.h"
 #include <algorithm>
@@ -101,6 +101,7 @@ int32_t azk_set_gumbel_root(azk_engine *e, int32_t m, int32_t n_sims, double c_v
     if (e->puct_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with configurable PUCT (azk_set_puct: its root selection is not PUCT)"; return AZK_ERR_STATE; }
     if (e->tp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with a move temperature (azk_set_move_temperature: the Gumbel arg-max is the sample)"; return AZK_ERR_STATE; }
     if (e->vt_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with value targets (azk_set_value_target: the Gumbel movers do not keep the per-ply q)"; return AZK_ERR_STATE; }
+    if (e->rn.mode) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with root noise on the legal moves (azk_set_root_noise: its rows are Dirichlet rows)"; return AZK_ERR_STATE; }
     const Dev &d = e->d;
     GumbelDev &gb = e->gb;
     hipStream_t st = (hipStream_t)stream;
@@ -446,6 +447,27 @@ int32_t azk_clear_openings(azk_engine *e) {
     if (!e) return AZK_ERR_ARG;
     if (e->async_on) { e->err = "azk_clear_openings: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
     e->op_on = false;                                             // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+// ---- root noise on the legal moves ------------------------------------------------------------------------------------------
+int32_t azk_set_root_noise(azk_engine *e, int32_t mode, double alpha, void *stream) {
+    (void)stream;                                                 // (nothing is allocated or written here: an asynchronous engine's row_key at azk_async_begin)
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_root_noise: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (e->in_search) { e->err = "azk_set_root_noise: a search is under way - its row was made under the setting as it stood"; return AZK_ERR_STATE; }
+    if (mode != 1 && mode != 2) { e->err = "azk_set_root_noise: mode must be 1 (legal: alpha per legal move) or 2 (total: alpha / legal moves)"; return AZK_ERR_ARG; }
+    if (!(alpha > 0.0) || alpha - alpha != 0.0) { e->err = "azk_set_root_noise: alpha must be finite and positive"; return AZK_ERR_ARG; }
+    if (e->gb.m) { e->err = "azk_set_root_noise: a Gumbel root is set - its rows are Gumbel rows, not Dirichlet rows"; return AZK_ERR_STATE; }
+    e->rn.mode = mode; e->rn.alpha = alpha;
+    return AZK_OK;
+}
+
+int32_t azk_clear_root_noise(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_root_noise: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    if (e->in_search) { e->err = "azk_clear_root_noise: a search is under way"; return AZK_ERR_STATE; }
+    e->rn.mode = 0;                                               // off: the engine launches what it launched before
     return AZK_OK;
 }
 

@@ -71,27 +71,35 @@ __device__ __forceinline__ double noise_uniform(unsigned long long seed, unsigne
     return u53_incl0(c[0], c[1]);
 }
 
+// the Gamma(alpha) draw `gam` of entry a of the row of (key k0 k1, global game, move): Gamma(alpha) = Gamma(alpha + 1) * U^(1/alpha) (Marsaglia-
+// Tsang for the shape > 1 part), two Philox blocks per try - {gg lo, gg hi ^ (a << 8), move, it} and it | 0x40000000 -, at most 64 tries (0 then).
+// The ONE copy of the recipe: noise_row draws every entry of the action vector with it, root_noise_row (azk_noise.hip) the legal ones.  It is
+// text, not a function: behind a call the compiler schedules k_gen_noise and k_noise_ahead differently, and an engine without root noise on
+// the legal moves launches the device code it always launched (profiles/root_noise_isa_vs_parent.txt).  Declarations and a loop without a
+// wrapper: use it only as full statements at block scope; it declares `gam`.
+#define AZK_GAMMA_ENTRY(gam, k0, k1, gg, a, move, alpha)                                                                              \
+    const double gm_d = (alpha) + 1.0 - 1.0 / 3.0, gm_cc = 1.0 / sqrt(9.0 * gm_d);                                                    \
+    double gam = 0.0;                                                                                                                 \
+    for (uint32_t it = 0; it < 64; it++) {                                                                                            \
+        uint32_t c[4] = {(uint32_t)(gg), (uint32_t)((gg) >> 32) ^ ((uint32_t)(a) << 8), (uint32_t)(move), it};                        \
+        philox4x32_10(c, k0, k1);                                                                                                     \
+        uint32_t c2[4] = {(uint32_t)(gg), (uint32_t)((gg) >> 32) ^ ((uint32_t)(a) << 8), (uint32_t)(move), it | 0x40000000u};         \
+        philox4x32_10(c2, k0, k1);                                                                                                    \
+        const double u1 = u53(c[0], c[1]), u2 = u53(c[2], c[3]), u3 = u53(c2[0], c2[1]), u4 = u53(c2[2], c2[3]);                      \
+        const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);                                                          \
+        const double t = 1.0 + gm_cc * x;                                                                                             \
+        if (t <= 0.0) continue;                                                                                                       \
+        const double v = t * t * t;                                                                                                   \
+        if (log(u3) < 0.5 * x * x + gm_d - gm_d * v + gm_d * log(v)) { gam = gm_d * v * pow(u4, 1.0 / (alpha)); break; }              \
+    }
+
 // the Dirichlet(alpha) row of (seed, global game, move), by one wave; red: 64 doubles of LDS scratch.
-// Dirichlet(alpha) via Gamma(alpha) = Gamma(alpha + 1) * U^(1/alpha) (Marsaglia-Tsang for the shape > 1 part).
 __device__ __forceinline__ void noise_row(int A, unsigned long long seed, unsigned long long gg, int move, double alpha, double *row, double *red) {
     const int lane = azk_lane();
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     double part = 0.0;
     for (int a = lane; a < A; a += AZK_WAVE) {
-        const double d = alpha + 1.0 - 1.0 / 3.0, cc = 1.0 / sqrt(9.0 * d);
-        double gam = 0.0;
-        for (uint32_t it = 0; it < 64; it++) {
-            uint32_t c[4] = {(uint32_t)gg, (uint32_t)(gg >> 32) ^ ((uint32_t)a << 8), (uint32_t)move, it};
-            philox4x32_10(c, k0, k1);
-            uint32_t c2[4] = {(uint32_t)gg, (uint32_t)(gg >> 32) ^ ((uint32_t)a << 8), (uint32_t)move, it | 0x40000000u};
-            philox4x32_10(c2, k0, k1);
-            const double u1 = u53(c[0], c[1]), u2 = u53(c[2], c[3]), u3 = u53(c2[0], c2[1]), u4 = u53(c2[2], c2[3]);
-            const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-            const double t = 1.0 + cc * x;
-            if (t <= 0.0) continue;
-            const double v = t * t * t;
-            if (log(u3) < 0.5 * x * x + d - d * v + d * log(v)) { gam = d * v * pow(u4, 1.0 / alpha); break; }
-        }
+        AZK_GAMMA_ENTRY(gam, k0, k1, gg, a, move, alpha)
         row[a] = gam;
         part += gam;
     }

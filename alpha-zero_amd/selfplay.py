@@ -10,6 +10,7 @@ self_play_batch returns, per game, the tuple the reference's Gomoku.self_play re
 """
 import contextlib
 import gc
+import math
 
 import numpy as np
 
@@ -397,6 +398,37 @@ def check_openings(openings, game, size=None, evaluator=True):
     return p_open, max_plies, spread
 
 
+def check_root_noise(root_noise, dirichlet=True, evaluator=True, gumbel_root=None, noise_fn=None):
+    """root_noise = ("legal", alpha) | ("total", alpha_total) -> (str, float), or None for off.  OPT-IN root noise on the legal moves
+    (include/azk.h azk_set_root_noise): a search's Dirichlet row is drawn over the actions that are legal in the position it
+    starts from - "legal": Gamma(alpha) each, "total": Gamma(alpha_total / n) for n legal actions - instead of over the whole action vector.
+    Raises ValueError, before any engine exists, for what the engine refuses too - an unknown mode, an alpha that is not finite and positive, a
+    Gumbel root (its rows are Gumbel rows) - and for dirichlet=False (there is no row), vanilla MCTS on either side (evaluator None: it mixes no
+    row in) and a caller-supplied noise_fn (its rows are the caller's)."""
+    if root_noise is None:
+        return None
+    try:
+        mode, alpha = root_noise
+        if isinstance(alpha, bool) or not isinstance(mode, str):
+            raise ValueError
+        alpha = float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"root_noise must be ('legal', alpha) or ('total', alpha_total), not {root_noise!r}")
+    if mode not in ("legal", "total"):
+        raise ValueError(f"root_noise: the mode must be 'legal' or 'total', not {mode!r}")
+    if not (alpha > 0.0 and math.isfinite(alpha)):                # (NaN fails the comparison)
+        raise ValueError(f"root_noise: alpha must be finite and positive, not {alpha!r}")
+    if not dirichlet:
+        raise ValueError("root_noise shapes the root's Dirichlet row: dirichlet=False has none")
+    if _is_vanilla(evaluator):
+        raise ValueError("root_noise: vanilla MCTS (evaluator None) is refused - its searches mix no noise row in")
+    if gumbel_root is not None:
+        raise ValueError("root_noise does not combine with gumbel_root (its rows are Gumbel rows, not Dirichlet rows)")
+    if noise_fn is not None:
+        raise ValueError("root_noise does not combine with a caller-supplied noise_fn (the rows are then the caller's)")
+    return mode, alpha
+
+
 def check_move_temperature(move_temperature, n_sims, game, size=None, gumbel_root=None, tree_reuse=0):
     """move_temperature -> the (row_of_ply, weights, visit_offset, value_cutoff) of azk_set_move_temperature, or None for off.  OPT-IN move
     temperature (include/azk.h azk_set_move_temperature): how the played child is picked from a finished search.
@@ -457,7 +489,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
                     budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
                     eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None,
-                    openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None):
+                    openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None, root_noise=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -497,9 +529,12 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     check_value_target): the replay ring gets (1 - r) * z + r * G as the z of every tuple, G the horizon-lam return over the game's own search
     values (value_targets(SelfPlayResult.qs, ...) is the same rule on the host); the games, states and pis do not change.  solver = True
     (OPT-IN, check_solver): every search keeps exact game-end proofs (Engine.set_solver); SelfPlayResult.root_status gets each move's root
-    status as the mover sees it (0 unknown, 1 wins, 2 loses, 3 draw).
+    status as the mover sees it (0 unknown, 1 wins, 2 loses, 3 draw).  root_noise = ("legal", alpha) | ("total", alpha_total) (OPT-IN,
+    check_root_noise): every search's Dirichlet row is drawn over the legal moves of the position it starts from (Engine.gen_root_noise where
+    gen_noise is called); `alpha` is then not looked at.
     """
     import torch
+    rnz = check_root_noise(root_noise, dirichlet, evaluator, gumbel_root, noise_fn)
     opn = check_openings(openings, game, size, evaluator)
     by_game = opn is not None and isinstance(evaluator, (tuple, list))       # the pair is told apart per game, not by the batch's ply
     if by_game and isinstance(n_sims, (tuple, list)) and len(set(n_sims)) != 1:
@@ -548,6 +583,10 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         eng.set_solver(True)
     elif eng.solver:                                              # an engine handed in with the option still on
         eng.set_solver(False)
+    if rnz is not None:
+        eng.set_root_noise(*rnz)
+    elif eng.root_noise is not None:
+        eng.clear_root_noise()
     # virtual-loss, top-up and capped engines are driven by the simulation budget
     budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
     assert eng.G == n_games
@@ -582,6 +621,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
             uni = None
         elif gum is not None:
             noise, uni = eng.gen_gumbel(seed, first_global_game, move), None
+        elif rnz is not None:                                     # rows over the legal moves of the positions as they stand
+            noise, uni = eng.gen_root_noise(seed, first_global_game, move)
         else:
             noise, uni = eng.gen_noise(seed, first_global_game, move, alpha, want_noise=dirichlet)
         if uniform_fn is not None:
@@ -792,6 +833,10 @@ class SelfPlayRunner:
 
     solver = True (OPT-IN, check_solver; with everything above except forced_playouts, gumbel_root, puct, tree_reuse and leaves_per_step > 1):
     every search keeps exact game-end proofs (Engine.set_solver); solver_stats() sums the groups' six counters.
+
+    root_noise = ("legal", alpha) | ("total", alpha_total) (OPT-IN, check_root_noise; with everything above except gumbel_root): every search's
+    Dirichlet row is drawn over the legal moves of the position it starts from - gen_root_noise where gen_noise is called, behind the recycle and
+    the openings of the move before; `alpha` is then not looked at.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
@@ -800,8 +845,9 @@ class SelfPlayRunner:
                  steps_per_graph=32,
                  leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None,
                  surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None, openings_first_game=None, puct=None,
-                 move_temperature=None, value_target=None, solver=None):
+                 move_temperature=None, value_target=None, solver=None, root_noise=None):
         import torch
+        self.root_noise = check_root_noise(root_noise, dirichlet, evaluator, gumbel_root)
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, playout_cap, forced_playouts,
                                              surprise_weight)
@@ -873,6 +919,8 @@ class SelfPlayRunner:
                 h.eng.set_value_target(*self.value_target)
             if self.solver is not None:
                 h.eng.set_solver(True)
+            if self.root_noise is not None:
+                h.eng.set_root_noise(*self.root_noise)
             if self.openings is not None:                         # the first games, under the key of their first search (move 0)
                 h.eng.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                                    (first_global_game if openings_first_game is None else openings_first_game) + i * per)
@@ -885,6 +933,8 @@ class SelfPlayRunner:
         for i, h in enumerate(self.halves):
             if self.gumbel_root is not None:                  # Gumbel rows where the Dirichlet rows go; the move needs no uniform
                 noise, h.uni = h.eng.gen_gumbel(self.seed, self.first + i * per, self.move_idx), None
+            elif self.root_noise is not None:                 # rows over the legal moves of the positions as they stand
+                noise, h.uni = h.eng.gen_root_noise(self.seed, self.first + i * per, self.move_idx)
             else:
                 noise, h.uni = h.eng.gen_noise(self.seed, self.first + i * per, self.move_idx, self.alpha, want_noise=self.dirichlet)
             if self.dirichlet:
@@ -1185,14 +1235,21 @@ class AsyncSelfPlayRunner:
     carried root's W / N as it stands; the record ring's q column holds the same numbers.
 
     solver = True (OPT-IN, check_solver; with everything above except forced_playouts, gumbel_root, puct and reroot): the games of
-    SelfPlayRunner(solver=True), slot for slot - the option lives in k_tree alone, the movers do not know it."""
+    SelfPlayRunner(solver=True), slot for slot - the option lives in k_tree alone, the movers do not know it.
+
+    root_noise = ("legal", alpha) | ("total", alpha_total) (OPT-IN, check_root_noise; with everything above except gumbel_root): the games of
+    SelfPlayRunner(root_noise=...), slot for slot - a row cannot be made a search ahead (the position is not known then), so the row of a game
+    that has just moved is made behind the movers, inside the step chain, and a parked or restarted game's in the drain; `alpha` is then not
+    looked at."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
                  playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None,
-                 openings=None, openings_seed=None, openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None):
+                 openings=None, openings_seed=None, openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None,
+                 root_noise=None):
         import torch
+        self.root_noise = check_root_noise(root_noise, dirichlet, evaluator, gumbel_root)
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, 1, tree_reuse or reroot, playout_cap, forced_playouts, surprise_weight)
         self.solver = check_solver(solver, evaluator, 1, forced_playouts, gumbel_root, puct, tree_reuse or reroot)
@@ -1245,6 +1302,8 @@ class AsyncSelfPlayRunner:
             e.set_value_target(*self.value_target)
         if self.solver is not None:
             e.set_solver(True)
+        if self.root_noise is not None:                           # the movers make the rows themselves, from each game's position
+            e.set_root_noise(*self.root_noise)
         if self.openings is not None:                             # async_begin opens the first games, the drain's restart every later one
             e.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                            first_global_game if openings_first_game is None else openings_first_game)

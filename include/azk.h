@@ -764,6 +764,36 @@ int32_t azk_check_device_error(azk_engine *e, void *stream);
 int32_t azk_gen_noise(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double alpha,
                       double *noise_dev, double *uniforms_dev, void *stream);
 
+/* ---- OPT-IN root noise on the legal moves ----
+ * azk_gen_noise keeps the reference's law: utils.add_dirichlet_noise is handed the whole softmax vector (mcts.py:43,53), so a row is
+ * Dirichlet(alpha) over all A = action_dim entries and only the part that falls on the root's children acts.  With this option a search's row
+ * is drawn over the actions that are legal in the position the search starts from - exactly the children its root gets:
+ *   L           TicTacToe: the empty cells; Connect4: the columns that are not full; Gomoku: the empty cells next to a stone, the centre cell
+ *               (rows / 2, cols / 2) where there is none (get_valid_moves as a set).  n = |L|.
+ *   alpha_eff   alpha (mode 1, "legal") or alpha / n (mode 2, "total": the row's total concentration stays alpha whatever n is)
+ *   a in L      gam[a] = the Gamma(alpha_eff) draw of azk_gen_noise's recipe at azk_gen_noise's counters for entry a - Philox4x32-10, key
+ *               (seed lo, seed hi), tries it = 0..63 from {game lo, game hi ^ (a << 8), move key, it} and it | 0x40000000 -, and
+ *               row[a] = gam[a] / sum over L of gam, or 1 / n where that sum is 0.  n == 1 gives exactly 1.0.
+ *   a not in L  row[a] = +0.0.  (A full TicTacToe or Connect4 board - a finished game that waits in the batch - has n == 0: a row of zeros.)
+ * In mode 1 the row is azk_gen_noise's row of the same (seed, game, move key, alpha) restricted to L and renormalised, from the same Philox
+ * blocks; no new word-3 tag exists and the move uniform (word 3 = 0xFFFFFFFF) is what it was.  A row depends on (seed, global game, move key,
+ * position) only - not on the engine's game count or on sharding.  The root mix (0.75 prior + 0.25 row, k_tree and the re-rooting kernels) is
+ * not part of the option: it reads a row that was made differently.
+ * azk_set_root_noise: mode 1 | 2 and a finite alpha > 0, else AZK_ERR_ARG; AZK_ERR_STATE with a Gumbel root set (and azk_set_gumbel_root
+ * with this option set), after azk_async_begin(_reuse), and between a search's begin and its move.  azk_clear_root_noise switches it off.
+ * azk_gen_root_noise (lock-step): azk_gen_noise's buffers and NULL conventions, its uniforms bit for bit, the rows from the engine's cells as
+ * they stand: call it after azk_open_pending / azk_advance and before azk_begin_search*; one wave per game.  AZK_ERR_STATE without the option.
+ * The asynchronous movers: while the option is set its alpha replaces azk_async_config.alpha, no row is made a search ahead (the position is
+ * not known then), and the row of a game whose move key has moved is made from its position - behind the movers in every azk_async_step
+ * (engines that do not re-root), and in azk_async_drain behind the restart of finished games and in front of the re-rooting of parked ones.
+ * azk_get_root_noise: float64 [G][A] into device memory, the row each game's current search reads (an asynchronous engine: row
+ * (move counter & 1) of the game's pair); AZK_ERR_STATE before the first search with rows. */
+int32_t azk_set_root_noise(azk_engine *e, int32_t mode, double alpha, void *stream);
+int32_t azk_clear_root_noise(azk_engine *e);
+int32_t azk_gen_root_noise(azk_engine *e, uint64_t seed, int64_t first_global_game, int32_t move_index, double *noise_dev, double *uniforms_dev,
+                           void *stream);
+int32_t azk_get_root_noise(azk_engine *e, double *rows_dev, void *stream);
+
 /* ---- stateless board-rule kernels over caller boards (float32 [n][F][R][C], the reference's layout) ----
  * game/rows/cols as in azk_config.  These replace the Game statics (games/game.py:4-38):
  *   azk_rules_legal_moves : get_valid_moves - cells in the reference's LIST ORDER (tictactoe.py:82-83,

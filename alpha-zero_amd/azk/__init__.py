@@ -1074,15 +1074,24 @@ def softmax_rows(logits):
     return out
 
 
-def nn_patch_embed(boards, wt, cpos, ln_w, ln_b, rows, cols, ksize, embed_dim, want_x=True, want_xhat=False, eps=1e-5):
+def nn_patch_embed(boards, wt, cpos, ln_w, ln_b, rows, cols, ksize, embed_dim, want_x=True, want_xhat=False, eps=1e-5,
+                   x_out=None, xhat_out=None):
     """Token embedding on the matrix cores (azk_nn_patch_embed).  boards [n,C,R,Cc] bf16|f32 CUDA;
-    wt [D,kp] bf16; cpos [T,D] f32.  Returns (x, xhat) bf16 [n,T,D] (None where not requested)."""
+    wt [D,kp] bf16; cpos [T,D] f32.  Returns (x, xhat) bf16 [n,T,D] (None where not requested).
+    x_out / xhat_out: buffers to write into (contiguous bf16 [n,T,D]) where that output is requested."""
     torch = _torch()
     assert boards.is_cuda and boards.is_contiguous() and boards.dtype in (torch.bfloat16, torch.float32)
     n, C = boards.shape[0], boards.shape[1]
     T = rows * cols + 1
-    x = torch.empty((n, T, embed_dim), dtype=torch.bfloat16, device=boards.device) if want_x else None
-    xh = torch.empty((n, T, embed_dim), dtype=torch.bfloat16, device=boards.device) if want_xhat else None
+
+    def out(want, buf):
+        if not want:
+            return None
+        if buf is None:
+            return torch.empty((n, T, embed_dim), dtype=torch.bfloat16, device=boards.device)
+        assert buf.shape == (n, T, embed_dim) and buf.dtype == torch.bfloat16 and buf.is_contiguous()
+        return buf
+    x, xh = out(want_x, x_out), out(want_xhat, xhat_out)
     rc = lib().azk_nn_patch_embed(_p(boards), 1 if boards.dtype == torch.float32 else 0, _p(wt), _p(cpos), _p(ln_w), _p(ln_b),
                                   _p(x), _p(xh), n, C, rows, cols, ksize, wt.shape[1], embed_dim, float(eps), _stream())
     _ok(rc, "azk_nn_patch_embed")
@@ -1108,28 +1117,59 @@ def nn_embed_scores_pool(boards, wt_ext, cpos, score_cpos, score_msum, c, rows, 
     """Depth-1 folded cls attention in two launches: azk_nn_patch_embed_scores (normalised tokens + per-token head scores,
     the scores as 16 extra MFMA output columns: wt_ext [D+16, kp]) then azk_nn_cls_pool (softmax + weighted token sum).
     Returns z bf16 [n, H, D]."""
-    torch = _torch()
-    assert boards.is_cuda and boards.is_contiguous() and boards.dtype in (torch.bfloat16, torch.float32)
-    n, C = boards.shape[0], boards.shape[1]
-    T = rows * cols + 1
-    Tp = (T + 15) // 16 * 16
-    xh = torch.empty((n, T, embed_dim), dtype=torch.bfloat16, device=boards.device)
-    sc = torch.empty((n, num_heads, Tp), dtype=torch.float32, device=boards.device)
-    # with a device-side count the rows past it are never written; every later op is row-wise, so they cannot leak
-    z = torch.empty((n, num_heads, embed_dim), dtype=torch.bfloat16, device=boards.device)
-    L = lib()
     if timers is not None:
         timers[0].start()
-    rc = L.azk_nn_patch_embed_scores(_p(boards), 1 if boards.dtype == torch.float32 else 0, _p(wt_ext), _p(cpos), None, None,
-                                     _p(xh), _p(score_cpos), _p(score_msum), _p(sc), num_heads, n, C, rows, cols, ksize,
-                                     wt_ext.shape[1], embed_dim, float(eps), _p(count), _stream())
+    xh, sc = nn_patch_embed_scores(boards, wt_ext, cpos, score_cpos, score_msum, rows, cols, ksize, embed_dim, num_heads, eps=eps,
+                                   count=count)
     if timers is not None:
         timers[0].stop()
         timers[1].start()
-    _ok(rc, "azk_nn_patch_embed_scores")
-    rc = L.azk_nn_cls_pool(_p(xh), _p(sc), _p(c), _p(z), n, T, embed_dim, num_heads, _p(count), _stream())
+    z = nn_cls_pool(xh, sc, c, num_heads, count=count)
     if timers is not None:
         timers[1].stop()
+    return z
+
+
+def nn_patch_embed_scores(boards, wt_ext, cpos, score_cpos, score_msum, rows, cols, ksize, embed_dim, num_heads, eps=1e-5,
+                          count=None, xhat=None, scores=None):
+    """k_embed's score variant (azk_nn_patch_embed_scores): the normalised tokens without the LayerNorm affine, and per token the
+    folded head scores rstd (x . m'_h - mean msum[h]), the x . m'_h as 16 extra MFMA output columns (wt_ext [D+16, kp] bf16,
+    score_cpos [T, 16] f32 their per-token additive term, score_msum [16] f32).  Returns (xhat bf16 [n, T, D], scores f32
+    [n, H, Tp]), Tp = T rounded up to 16; with a device-side count the rows past it are not written.  xhat / scores: buffers to
+    write into (contiguous, of those shapes)."""
+    torch = _torch()
+    assert boards.is_cuda and boards.is_contiguous() and boards.dtype in (torch.bfloat16, torch.float32)
+    assert wt_ext.dtype == torch.bfloat16 and wt_ext.is_contiguous() and wt_ext.shape[0] == embed_dim + 16
+    n, C = boards.shape[0], boards.shape[1]
+    T = rows * cols + 1
+    Tp = (T + 15) // 16 * 16
+    assert cpos.numel() == T * embed_dim and score_cpos.numel() == T * 16 and score_msum.numel() == 16
+    xh = torch.empty((n, T, embed_dim), dtype=torch.bfloat16, device=boards.device) if xhat is None else xhat
+    sc = torch.empty((n, num_heads, Tp), dtype=torch.float32, device=boards.device) if scores is None else scores
+    assert xh.shape == (n, T, embed_dim) and xh.dtype == torch.bfloat16 and xh.is_contiguous()
+    assert sc.shape == (n, num_heads, Tp) and sc.dtype == torch.float32 and sc.is_contiguous()
+    rc = lib().azk_nn_patch_embed_scores(_p(boards), 1 if boards.dtype == torch.float32 else 0, _p(wt_ext), _p(cpos), None, None,
+                                         _p(xh), _p(score_cpos), _p(score_msum), _p(sc), num_heads, n, C, rows, cols, ksize,
+                                         wt_ext.shape[1], embed_dim, float(eps), _p(count), _stream())
+    _ok(rc, "azk_nn_patch_embed_scores")
+    return xh, sc
+
+
+def nn_cls_pool(xhat, scores, c, num_heads, count=None, z=None):
+    """k_cls_pool (azk_nn_cls_pool): z[b, h, :] = sum_t softmax_t(scores[b, h, :T] + c[h])[t] xhat[b, t, :].  xhat bf16 [n, T, D];
+    scores f32 [n, H, Tp] (Tp = T rounded up to 16; the entries from T on are not read); c f32 [H].  Returns z bf16 [n, H, D];
+    with a device-side count the boards past it are not written.  z: a buffer to write into."""
+    torch = _torch()
+    assert xhat.is_cuda and xhat.dtype == torch.bfloat16 and xhat.is_contiguous()
+    n, T, D = xhat.shape
+    Tp = (T + 15) // 16 * 16
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.shape == (n, num_heads, Tp)
+    assert c.dtype == torch.float32 and c.is_contiguous() and c.numel() == num_heads
+    # with a device-side count the rows past it are never written; every later op is row-wise, so they cannot leak
+    if z is None:
+        z = torch.empty((n, num_heads, D), dtype=torch.bfloat16, device=xhat.device)
+    assert z.shape == (n, num_heads, D) and z.dtype == torch.bfloat16 and z.is_contiguous()
+    rc = lib().azk_nn_cls_pool(_p(xhat), _p(scores), _p(c), _p(z), n, T, D, num_heads, _p(count), _stream())
     _ok(rc, "azk_nn_cls_pool")
     return z
 

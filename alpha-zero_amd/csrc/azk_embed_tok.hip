@@ -444,6 +444,7 @@ extern "C" int32_t azk_nn_cls_attention(const void *xhat_bf16_dev, const float *
 // z[b][h][:] = sum_t a[h][t] * xhat[b][t][:].  No cross-lane reduction in the token loop: each lane owns 8 (CPL)
 // columns, reads its 16 bytes of every token row and the token's NH weights (one broadcast LDS read).
 // One workgroup per board, 4 waves interleave tokens, 4 tokens in flight per wave.  HBM-read-bound.
+// Any token count whose weights [Tp][NH] and two partial rows [NH][D] fit 64 KB of LDS (the entry point refuses the others).
 // =====================================================================================================
 namespace {
 
@@ -486,26 +487,32 @@ __global__ __launch_bounds__(256) void k_cls_pool(ClsPoolArgs a) {
     float *zpart = aw + (size_t)a.Tp * NH;                   // [2][NH][D] partial sums handed between waves
     const float *sp = a.scores + (size_t)b * NH * a.Tp;
     // ---- softmax over tokens: wave w handles heads w, w + 4 (scores are tiny: NH * T floats) ----
+    // Lane l takes the tokens l + 64 k for every k < ceil(Tp / 64), in rising k: maximum, sum and weights each walk the same
+    // chunks, so a lane's order of operations does not depend on how many chunks there are.  Between the passes a token's value
+    // waits in its own aw slot, which only this lane touches before the barrier.
     if (!(a.ablate & 1)) {
+        const int nchunk = (a.Tp + 63) >> 6;
         for (int h = wave; h < NH; h += 4) {
             const float ch = a.c[h];
-            float e[4], mx = -3.0e38f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
+            float mx = -3.0e38f;
+            for (int k = 0; k < nchunk; k++) {
                 const int t = lane + 64 * k;
-                e[k] = t < a.T ? sp[h * a.Tp + t] + ch : -3.0e38f;
-                mx = fmaxf(mx, e[k]);
+                if (t < a.T) { const float e = sp[h * a.Tp + t] + ch; aw[t * NH + h] = e; mx = fmaxf(mx, e); }
             }
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
             float sum = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) { e[k] = (lane + 64 * k) < a.T ? __expf(e[k] - mx) : 0.f; sum += e[k]; }
+            for (int k = 0; k < nchunk; k++) {
+                const int t = lane + 64 * k;
+                if (t < a.T) { const float e = __expf(aw[t * NH + h] - mx); aw[t * NH + h] = e; sum += e; }
+            }
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
             const float inv = 1.0f / sum;
-#pragma unroll
-            for (int k = 0; k < 4; k++) { const int t = lane + 64 * k; if (t < a.Tp) aw[t * NH + h] = e[k] * inv; }
+            for (int k = 0; k < nchunk; k++) {
+                const int t = lane + 64 * k;
+                if (t < a.Tp) aw[t * NH + h] = t < a.T ? aw[t * NH + h] * inv : 0.f;      // the Tp padding weighs exactly 0
+            }
         }
     }
     __syncthreads();

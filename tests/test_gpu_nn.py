@@ -27,6 +27,9 @@ def random_boards(n, C, R, Cc, seed):
 @pytest.mark.parametrize("R,Cc,C,k,D,heads", [(15, 15, 2, 5, 512, 8), (7, 7, 2, 5, 256, 8), (6, 7, 3, 5, 128, 4),
                                               (3, 3, 3, 3, 128, 4), (15, 15, 2, 3, 256, 4)])
 def test_patch_embed_kernel_vs_torch_fp32(R, Cc, C, k, D, heads):
+    """k_embed on a network's own operands against the torch float32 embedding, at bf16-level tolerances.
+    The patch assembly bit for bit on fourteen geometries up to 31 x 32, the column map as an integer GEMM, LayerNorm and the score
+    columns against float64, the live count and the refusals: tests/test_gpu_embed_tok_pinned.py."""
     cfg = NetConfig(R, Cc, C, R * Cc if C == 2 else (7 if R == 6 else 9), k, D, heads, 1)
     net32 = PolicyValueNet(cfg, seed=3, device="cuda", dtype=torch.float32, path="full")
     net16 = PolicyValueNet(cfg, weights=net32.state_dict(), device="cuda", dtype=torch.bfloat16, path="full")
@@ -67,14 +70,20 @@ def test_evaluator_paths_agree_and_match_reference_kat():
     np.testing.assert_allclose(l32.cpu().numpy(), z["full_logits"], rtol=0, atol=1e-4)
 
 
-@pytest.mark.parametrize("R,D,heads,depth,k", [(15, 512, 8, 1, 5), (7, 256, 8, 2, 5), (7, 128, 4, 1, 3), (15, 256, 4, 2, 5)])
+@pytest.mark.parametrize("R,D,heads,depth,k", [(15, 512, 8, 1, 5), (7, 256, 8, 2, 5), (7, 128, 4, 1, 3), (15, 256, 4, 2, 5),
+                                               (16, 256, 8, 1, 5), (20, 128, 4, 1, 3)])
 def test_folded_cls_attention_matches_full_forward(R, D, heads, depth, k):
     """path='clsfold' (hand-written embed + folded cls attention, K/V never formed) computes the same function as
-    the plain fp32 full forward: logits within 3e-2 absolute (bf16 activations), value within 2e-2."""
+    the plain fp32 full forward: logits within 3e-2 absolute (bf16 activations), value within 2e-2.
+    16 x 16 (257 tokens) and 20 x 20 (401 tokens) are depth-1 networks beyond the 256 tokens the full-token block kernels take: they
+    run k_embed with the score columns and k_cls_pool ("two-kernel"), whose softmax once stopped at 256 tokens (logits then off by
+    0.099 and 2.45 on these two).  The two kernels on their own: tests/test_gpu_embed_tok_pinned.py."""
     cfg = NetConfig(R, R, 2, R * R, k, D, heads, depth)
     net32 = PolicyValueNet(cfg, seed=5, device="cuda", dtype=torch.float32, path="full")
     net16 = PolicyValueNet(cfg, weights=net32.state_dict(), device="cuda", dtype=torch.bfloat16, path="clsfold")
     assert net16._fold is not None
+    if R > 15:
+        assert net16._blocks is None and net16.embed_choice() == "two-kernel"
     x = random_boards(64, 2, R, R, 9).cuda()
     l32, v32 = net32(x)
     l16, v16 = net16(x.to(torch.bfloat16))
@@ -148,7 +157,9 @@ def test_fused_embed_pool_vs_torch_fp32(static_ref):
     """azk_nn_embed_pool (embedding + LayerNorm1 + folded cls attention in one launch) against the same computation in plain
     fp32 PyTorch on the operands the kernel sees (bf16-rounded weights): z = softmax_t(xn . m') @ xn.
     Tolerance: xn and the softmax weights are rounded to bf16 for the second MFMA, z to bf16 on output: 1e-2 absolute
-    (values are O(0.1)); the two-launch path is checked against the same reference at 6e-2 (its bf16 token round trip)."""
+    (values are O(0.1)); the two-launch path is checked against the same reference at 6e-2 (its bf16 token round trip).
+    The two launches of that path (k_embed's score variant, k_cls_pool) each on its own, bit for bit and against float64, every
+    (D, heads) and up to 993 tokens: tests/test_gpu_embed_tok_pinned.py."""
     import azk
     cfg = NetConfig(15, 15, 2, 225, 5, 512, 8, 1)
     net = PolicyValueNet(cfg, seed=5, device="cuda", dtype=torch.bfloat16, path="clsfold")

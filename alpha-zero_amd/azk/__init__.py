@@ -50,6 +50,8 @@ SYMBOLS = [
     "azk_set_solver", "azk_clear_solver", "azk_get_solver_status", "azk_export_tree_status", "azk_get_solver_stats",
     "azk_debug_fill_solver_status",
     "azk_set_root_noise", "azk_clear_root_noise", "azk_gen_root_noise", "azk_get_root_noise",
+    "azk_set_kld_stop", "azk_clear_kld_stop", "azk_kld_checkpoint", "azk_get_search_sims", "azk_get_kld_rate", "azk_get_kld_stats",
+    "azk_async_sims_column",
 ]
 
 
@@ -351,6 +353,7 @@ class Engine:
         self.move_temperature = None                # (row_of_ply, weights, visit_offset, value_cutoff) once set_move_temperature has switched the option on
         self.surprise_weight = None                 # lambda once set_surprise_weighting has switched the option on (0.0 is a live setting)
         self.value_target = None                    # (r, lam) once set_value_target has switched the option on (r = 0.0 is a live setting)
+        self.kld_stop = None                        # (interval, min_gain, min_sims) once set_kld_stop has switched the option on
         self.cache_entries = int(cache_entries)
         # with the eval cache a step can have pending (cached) leaves to expand although no leaf went to the evaluator
         need = cache_entries or self.K > 1
@@ -700,6 +703,55 @@ class Engine:
         self._chk(self.L.azk_root_policy_target(self.h, _p(self._pi_target), _stream()))
         return self._pi_target
 
+    def set_kld_stop(self, interval, min_gain, min_sims=0):
+        """OPT-IN adaptive search budgets (azk_set_kld_stop): from now on a search runs in segments of `interval` simulations
+        and ends at the first checkpoint between two segments at which the KL divergence its root's visit distribution gained per simulation
+        since the last checkpoint is below min_gain (not before it has run min_sims new simulations), or when its allowance is used up.  The
+        lock-step search is search_budget (plain stepping is refused); the asynchronous movers judge their games themselves.  Not with a
+        Gumbel root or leaves_per_step > 1; before async_begin and outside a search.  clear_kld_stop switches it off."""
+        self._chk(self.L.azk_set_kld_stop(self.h, int(interval), float(min_gain), int(min_sims), _stream()))
+        self.kld_stop = (int(interval), float(min_gain), int(min_sims))
+
+    def clear_kld_stop(self):
+        """Adaptive search budgets off (azk_clear_kld_stop): the engine launches what it launched before."""
+        self._chk(self.L.azk_clear_kld_stop(self.h))
+        self.kld_stop = None
+
+    def kld_checkpoint(self):
+        """Judge every game whose segment is complete (azk_kld_checkpoint; host sync): returns how many games were released for another
+        segment - 0: every search is over, move."""
+        out = C.c_int32(0)
+        self._chk(self.L.azk_kld_checkpoint(self.h, C.byref(out), _stream()))
+        return int(out.value)
+
+    def search_sims(self):
+        """int32 CUDA tensor [G]: the new simulations each game's current or last-judged search has run (azk_get_search_sims; valid until
+        the next call)."""
+        if self.kld_stop is None:
+            raise AzkError("search_sims: no adaptive search budget is set (set_kld_stop)")
+        if getattr(self, "_search_sims", None) is None:
+            self._search_sims = self.torch.zeros(self.G, dtype=self.torch.int32, device=self.device)
+        self._chk(self.L.azk_get_search_sims(self.h, _p(self._search_sims), _stream()))
+        return self._search_sims
+
+    def kld_rate(self):
+        """float64 CUDA tensor [G]: the rate of each game's last judged checkpoint (azk_get_kld_rate; valid until the next call)."""
+        if self.kld_stop is None:
+            raise AzkError("kld_rate: no adaptive search budget is set (set_kld_stop)")
+        if getattr(self, "_kld_rate", None) is None:
+            self._kld_rate = self.torch.zeros(self.G, dtype=self.torch.float64, device=self.device)
+        self._chk(self.L.azk_get_kld_rate(self.h, _p(self._kld_rate), _stream()))
+        return self._kld_rate
+
+    def kld_stats(self):
+        """The four counters since set_kld_stop (azk_get_kld_stats): checkpoints judged, searches ended early, simulations those searches
+        left unrun, searches that ran their allowance."""
+        if self.kld_stop is None:
+            raise AzkError("kld_stats: no adaptive search budget is set (set_kld_stop)")
+        out = np.zeros(4, np.int64)
+        self._chk(self.L.azk_get_kld_stats(self.h, _np(out), _stream()))
+        return dict(judged=int(out[0]), ended_early=int(out[1]), sims_unrun=int(out[2]), ran_allowance=int(out[3]))
+
     def begin_search_budget(self, noise, n_sims, per_launch=8, move_index=None):
         """begin_search + a simulation budget: afterwards every step lets a game run on inside the launch while its simulations
         need no evaluator (terminal leaves, eval-cache hits); step until unfinished() == 0, then step_expand_backup once.
@@ -793,23 +845,31 @@ class Engine:
     def search_budget(self, evaluator, n_sims, noise=None, per_launch=8, move_index=None):
         """The same search as `search` - bit-identical trees - with budget stepping: a game runs on inside a launch while its
         simulations need no evaluator, so n_sims simulations take about (share of simulations that miss the cache) * n_sims
-        launches, each with a fuller evaluator batch.  Returns the number of launches."""
+        launches, each with a fuller evaluator batch.  Returns the number of launches.
+        With adaptive search budgets set (set_kld_stop) the search runs segment by segment: when every game's segment is complete,
+        kld_checkpoint judges the games, and the stepping goes on while it released one."""
         self.begin_search_budget(noise, n_sims, per_launch, move_index)
-        logits = values = None
         launches = 0
-        while True:
-            self.step(logits, values)
-            launches += 1
-            n = int(self.n_leaf.item())
-            if n > 0:
-                logits, values = self.evaluate_leaves(evaluator, n)
-            else:
-                logits, values = (self._no_logits, self._no_values) if self._no_logits is not None else (None, None)
-                if self.unfinished() == 0:
-                    break
-            assert launches <= 2 * n_sims + 8, "budget stepping does not terminate"
-        if self.cache_entries and self.K == 1:
-            self.step_expand_backup(self._no_logits, self._no_values)       # leaves served by the cache in the last launch
+        segments = 0
+        while True:     # one round per segment of the search (adaptive search budgets, set_kld_stop); without the option there is one
+            logits = values = None
+            segments += 1
+            while True:
+                self.step(logits, values)
+                launches += 1
+                n = int(self.n_leaf.item())
+                if n > 0:
+                    logits, values = self.evaluate_leaves(evaluator, n)
+                else:
+                    logits, values = (self._no_logits, self._no_values) if self._no_logits is not None else (None, None)
+                    if self.unfinished() == 0:
+                        break
+                assert launches <= 2 * n_sims + 8 * segments, "budget stepping does not terminate"
+            if self.cache_entries and self.K == 1:
+                self.step_expand_backup(self._no_logits, self._no_values)       # leaves served by the cache in the last launch
+            if self.kld_stop is None or self.kld_checkpoint() == 0:             # every game at a checkpoint: released for another segment, or over
+                break
+            assert segments <= n_sims, "the checkpoints do not terminate"
         return launches
 
     # ---- asynchronous self-play (azk_async_*) -----------------------------------------------------
@@ -835,6 +895,9 @@ class Engine:
                 rec["kl"] = torch.zeros(record_capacity, dtype=torch.float64, device=self.device)
                 rec["coin"] = torch.zeros(record_capacity, dtype=torch.float64, device=self.device)
                 self._chk(self.L.azk_async_surprise_columns(self.h, _p(rec["kl"]), _p(rec["coin"])))
+            if self.kld_stop is not None:                     # ... and its sims column: the new simulations the record's search ran
+                rec["sims"] = torch.zeros(record_capacity, dtype=torch.int32, device=self.device)
+                self._chk(self.L.azk_async_sims_column(self.h, _p(rec["sims"])))
         self.async_records = rec
         c = AsyncConfig()
         c.n_sims, c.max_sims_per_launch, c.sample_until_move = int(n_sims), int(per_launch), int(min(sample_until, 1 << 30))

@@ -206,6 +206,13 @@ def declare(L, symbols):
     L.azk_clear_root_noise.argtypes = [vp]
     L.azk_gen_root_noise.argtypes = [vp, u64, i64, i32, vp, vp, vp]
     L.azk_get_root_noise.argtypes = [vp, vp, vp]
+    L.azk_set_kld_stop.argtypes = [vp, i32, f64, i32, vp]
+    L.azk_clear_kld_stop.argtypes = [vp]
+    L.azk_kld_checkpoint.argtypes = [vp, vp, vp]
+    L.azk_get_search_sims.argtypes = [vp, vp, vp]
+    L.azk_get_kld_rate.argtypes = [vp, vp, vp]
+    L.azk_get_kld_stats.argtypes = [vp, vp, vp]
+    L.azk_async_sims_column.argtypes = [vp, vp]
     L.azk_set_eval_symmetry.argtypes = [vp, i32, u64, vp]
     L.azk_get_leaf_symmetry.argtypes = [vp, vp, vp]
     L.azk_eval_symmetry_restore.argtypes = [vp, vp, vp, vp]

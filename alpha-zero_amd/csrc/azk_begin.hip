@@ -452,7 +452,24 @@ __global__ __launch_bounds__(AZK_WAVE) void k_async_restart(RestartPack<CAP, OPE
     async_restart_body<CAP, OPEN>(d, p, recycle, opt<CapDev>(d), opt<OpenDev>(d));
 }
 
+// Adaptive search budgets (azk_set_kld_stop): the searches that have just begun are armed (kld_arm_one), one thread per game -
+// every game (list == nullptr: the lock-step begin, azk_async_begin) or the listed ones (the drain: the games k_async_restart restarted, the
+// games k_reroot_list re-rooted).  It follows the kernel that began the searches on the same stream: sims_done is what that kernel left.
+__global__ void k_kld_arm(Dev d, KldDev kd, const int *list, const int *n_list) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = list != nullptr ? min(*n_list, d.G) : d.G;
+    if (t >= n) return;
+    const int g = list != nullptr ? list[t] : t;
+    if ((unsigned)g >= (unsigned)d.G) return;
+    kld_arm_one(d, kd, g);
+}
+
 }  // namespace
+
+void azk_launch_kld_arm(azk_engine *e, const int *list, const int *n_list, hipStream_t st) {
+    if (!e->kld_on) return;
+    k_kld_arm<<<(unsigned)((e->d.G + 255) / 256), 256, 0, st>>>(e->d, e->kd, list, n_list);
+}
 
 int32_t azk_init_games(azk_engine *e) {
     const Dev &d = e->d;
@@ -470,12 +487,14 @@ static void launch_begin_search(azk_engine *e, int n_sims, int move_index, hipSt
         if (e->ru.mode) k_reroot<cap.value><<<d.G, AZK_WAVE, 0, st>>>(d, cap_key_pack<cap.value>(e->ru, e, move_index), n_sims);
         else k_begin_search<cap.value><<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(cap_key_pack<cap.value>(d, e, move_index));
     }, e->cp.n_fast != 0);
+    azk_launch_kld_arm(e, nullptr, nullptr, st);                   // adaptive search budgets: every game's first segment
 }
 
 void azk_launch_first_searches(azk_engine *e, hipStream_t st) {
     const Dev &d = e->d;
     if (e->op_on) k_open_pending<<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->op, 0);      // random openings: the first games, under move key 0
     with_flags([&](auto cap) { k_begin_search<cap.value><<<(unsigned)((d.G + 255) / 256), 256, 0, st>>>(cap_key_pack<cap.value>(d, e, 0)); }, e->cp.n_fast != 0);
+    azk_launch_kld_arm(e, nullptr, nullptr, st);                   // adaptive search budgets: every game's first segment
 }
 
 // the drain's steps 3 and 4: every listed game counted and, with recycling on, restarted; re-rooting engines: the next search of every game
@@ -486,6 +505,7 @@ int32_t azk_launch_next_searches(azk_engine *e, hipStream_t st) {
         k_async_restart<cap.value, open.value><<<(unsigned)(d.G < 256 ? d.G : 256), AZK_WAVE, d.lds_bytes, st>>>(
             RestartPack<cap.value, open.value>{d, on<cap.value>(e->cp), on<open.value>(e->op)}, e->ad, e->async_recycle);
     }, e->cp.n_fast != 0, e->op_on);
+    azk_launch_kld_arm(e, e->ad.fin_list, e->ad.fin_count, st);    // adaptive search budgets: the restarted games (a slot that stays finished is not armed)
     // root noise on the legal moves: the rows of the restarted games (opened or empty boards) and of the parked ones, whose positions stand
     // since their move - in front of k_reroot_list, which mixes a parked game's row into its carried root
     if (e->rn.mode && e->ad.dirichlet) azk_launch_root_noise_due(e, st);
@@ -493,6 +513,7 @@ int32_t azk_launch_next_searches(azk_engine *e, hipStream_t st) {
     with_flags([&](auto cap) {
         k_reroot_list<cap.value><<<(unsigned)d.G, AZK_WAVE, 0, st>>>(d, e->ad, CapPack<ReuseDev, cap.value>{e->ru, on<cap.value>(e->cp)});
     }, e->cp.n_fast != 0);
+    azk_launch_kld_arm(e, e->ad.reroot_list, e->ad.reroot_count, st);   // adaptive search budgets: the re-rooted games, behind reroot_one's sims_done
     HIPCHK(e, hipMemsetAsync(e->ad.reroot_count, 0, sizeof(int), st));
     return AZK_OK;
 }
@@ -530,6 +551,7 @@ int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
     if (gumbel_refuses(e, noise_dev, 0, "azk_begin_search")) return AZK_ERR_STATE;
     if (forced_needs_noise(e, noise_dev, "azk_begin_search")) return AZK_ERR_STATE;
+    if (e->kld_on) { e->err = "azk_begin_search: adaptive search budgets are set (azk_set_kld_stop) - their searches run under budget stepping (azk_begin_search_budget / _capped)"; return AZK_ERR_STATE; }
     if (e->cp.n_fast) { e->err = "azk_begin_search: a playout cap is set - its searches begin with azk_begin_search_capped (budget + move index)"; return AZK_ERR_STATE; }
     e->d.noise = noise_dev; e->d.noise_sel = nullptr;
     if (e->ru.mode == 2) { e->err = "azk_begin_search: top-up tree reuse needs the budget (azk_begin_search_budget)"; return AZK_ERR_STATE; }

@@ -1,5 +1,5 @@
 // azk_options.hip - the opt-ins' state calls (include/azk.h): set, clear and read playout cap, forced playouts, Gumbel root, resignation,
-// surprise weighting, random openings, root noise on the legal moves, the move temperature, value targets and the solver.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
+// surprise weighting, random openings, root noise on the legal moves, the move temperature, value targets, the solver and adaptive search budgets.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
 // block (azk_engine_int.h) that azk_opt_pack.h hands to the kernels of azk_begin.hip, azk_moves.hip and azk_emit.hip.
 #include "azk_engine_int.h"
 #include <algorithm>
@@ -102,6 +102,7 @@ int32_t azk_set_gumbel_root(azk_engine *e, int32_t m, int32_t n_sims, double c_v
     if (e->tp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with a move temperature (azk_set_move_temperature: the Gumbel arg-max is the sample)"; return AZK_ERR_STATE; }
     if (e->vt_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with value targets (azk_set_value_target: the Gumbel movers do not keep the per-ply q)"; return AZK_ERR_STATE; }
     if (e->rn.mode) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with root noise on the legal moves (azk_set_root_noise: its rows are Dirichlet rows)"; return AZK_ERR_STATE; }
+    if (e->kld_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with adaptive search budgets (azk_set_kld_stop: the halving table needs a fixed number of simulations)"; return AZK_ERR_STATE; }
     const Dev &d = e->d;
     GumbelDev &gb = e->gb;
     hipStream_t st = (hipStream_t)stream;
@@ -468,6 +469,79 @@ int32_t azk_clear_root_noise(azk_engine *e) {
     if (e->async_on) { e->err = "azk_clear_root_noise: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
     if (e->in_search) { e->err = "azk_clear_root_noise: a search is under way"; return AZK_ERR_STATE; }
     e->rn.mode = 0;                                               // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+// ---- adaptive search budgets ------------------------------------------------------------------------------------------------
+int32_t azk_set_kld_stop(azk_engine *e, int32_t interval, double min_gain, int32_t min_sims, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_kld_stop: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (e->in_search) { e->err = "azk_set_kld_stop: a search is under way - set the option between searches"; return AZK_ERR_STATE; }
+    if (interval < 1 || interval > e->cfg.max_sims) { e->err = "azk_set_kld_stop: interval must lie in [1, max_sims]"; return AZK_ERR_ARG; }
+    if (!(min_gain > 0.0) || min_gain - min_gain != 0.0) { e->err = "azk_set_kld_stop: min_gain must be finite and positive"; return AZK_ERR_ARG; }
+    if (min_sims < 0) { e->err = "azk_set_kld_stop: min_sims must not be negative"; return AZK_ERR_ARG; }
+    if (e->d.K > 1) { e->err = "azk_set_kld_stop: adaptive search budgets do not combine with leaves_per_step > 1 (a virtual-loss search has several leaves in flight: no checkpoint finds its tree complete)"; return AZK_ERR_ARG; }
+    if (e->gb.m) { e->err = "azk_set_kld_stop: a Gumbel root is set - its halving table needs a fixed number of simulations"; return AZK_ERR_STATE; }
+    const Dev &d = e->d;
+    KldDev &k = e->kd;
+    hipStream_t st = (hipStream_t)stream;
+    if (!k.left) {
+        HIPCHK(e, dalloc(e, &k.left, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &k.run, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &k.ckpt, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &k.snap_sum, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &k.snap, (size_t)d.G * d.g.rc));
+        HIPCHK(e, dalloc(e, &k.rate, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &k.stats, (size_t)KST_N));
+    }
+    // no search is armed: a game counts as over (ckpt < 0) until its next search begins
+    HIPCHK(e, hipMemsetAsync(k.left, 0, sizeof(int) * (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(k.run, 0, sizeof(int) * (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(k.ckpt, 0xff, sizeof(int) * (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(k.snap_sum, 0, sizeof(int) * (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(k.snap, 0, sizeof(int) * (size_t)d.G * d.g.rc, st));
+    HIPCHK(e, hipMemsetAsync(k.rate, 0, sizeof(double) * (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(k.stats, 0, sizeof(long long) * KST_N, st));
+    k.interval = interval; k.min_gain = min_gain; k.min_sims = min_sims; k.max_children = d.g.rc; k.rec_sims = nullptr;
+    e->kld_on = true;
+    return AZK_OK;
+}
+
+int32_t azk_clear_kld_stop(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_kld_stop: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    if (e->in_search && e->kld_on) { e->err = "azk_clear_kld_stop: a search is under way - clear the option between searches"; return AZK_ERR_STATE; }
+    e->kld_on = false;                                            // off: the engine launches what it launched before
+    return AZK_OK;
+}
+
+int32_t azk_get_search_sims(azk_engine *e, int32_t *sims_dev, void *stream) {
+    if (!e || !sims_dev) return AZK_ERR_ARG;
+    if (!e->kld_on) { e->err = "azk_get_search_sims: no adaptive search budget is set (azk_set_kld_stop)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(sims_dev, e->kd.run, sizeof(int) * (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_get_kld_rate(azk_engine *e, double *rate_dev, void *stream) {
+    if (!e || !rate_dev) return AZK_ERR_ARG;
+    if (!e->kld_on) { e->err = "azk_get_kld_rate: no adaptive search budget is set (azk_set_kld_stop)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(rate_dev, e->kd.rate, sizeof(double) * (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_get_kld_stats(azk_engine *e, int64_t *out4_host, void *stream) {
+    if (!e || !out4_host) return AZK_ERR_ARG;
+    if (!e->kld_on) { e->err = "azk_get_kld_stats: no adaptive search budget is set (azk_set_kld_stop)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(out4_host, e->kd.stats, sizeof(long long) * KST_N, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_async_sims_column(azk_engine *e, int32_t *rec_sims_dev) {
+    if (!e) return AZK_ERR_ARG;
+    if (!e->kld_on) { e->err = "azk_async_sims_column: no adaptive search budget is set (azk_set_kld_stop)"; return AZK_ERR_STATE; }
+    if (e->async_on) { e->err = "azk_async_sims_column: call it before azk_async_begin"; return AZK_ERR_STATE; }
+    e->kd.rec_sims = rec_sims_dev;
     return AZK_OK;
 }
 

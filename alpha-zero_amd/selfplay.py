@@ -456,6 +456,39 @@ def check_move_temperature(move_temperature, n_sims, game, size=None, gumbel_roo
     return setting
 
 
+def check_kld_stop(kld_stop, n_sims, evaluator=True, leaves_per_step=1, gumbel_root=None):
+    """kld_stop = (interval, min_gain[, min_sims]) -> (int, float, int), or None for off.  OPT-IN adaptive search budgets (include/azk.h
+    azk_set_kld_stop): a search runs in segments of `interval` simulations and ends at the first checkpoint between two
+    segments at which the KL divergence its root's visit distribution gained per simulation since the last checkpoint is below min_gain, not
+    before it has run min_sims new simulations.  n_sims is the engine's max_sims (the largest of a pair).  Raises ValueError, before any engine
+    exists, for what the engine refuses too - an interval outside [1, n_sims], a min_gain that is not finite and positive, a negative min_sims,
+    virtual loss, a Gumbel root (its halving table needs a fixed number of simulations) - and for vanilla MCTS on either side (evaluator None:
+    it runs whole searches inside one launch, without checkpoints)."""
+    if kld_stop is None:
+        return None
+    try:
+        interval, min_gain, min_sims = kld_stop if len(kld_stop) == 3 else (kld_stop[0], kld_stop[1], 0) if len(kld_stop) == 2 else (None, None, None)
+        if isinstance(interval, bool) or isinstance(min_sims, bool) or int(interval) != interval or int(min_sims) != min_sims:
+            raise ValueError
+        interval, min_gain, min_sims = int(interval), float(min_gain), int(min_sims)
+    except (TypeError, ValueError):
+        raise ValueError(f"kld_stop must be (interval, min_gain) or (interval, min_gain, min_sims), not {kld_stop!r}")
+    max_sims = max(n_sims) if isinstance(n_sims, (tuple, list)) else n_sims
+    if not 1 <= interval <= max_sims:
+        raise ValueError(f"kld_stop: interval must lie in [1, n_sims = {max_sims}], not {interval!r}")
+    if not (min_gain > 0.0 and math.isfinite(min_gain)):          # (NaN fails the comparison)
+        raise ValueError(f"kld_stop: min_gain must be finite and positive, not {min_gain!r}")
+    if min_sims < 0:
+        raise ValueError(f"kld_stop: min_sims must not be negative, not {min_sims!r}")
+    if _is_vanilla(evaluator):
+        raise ValueError("kld_stop: vanilla MCTS (evaluator None) is refused - it runs whole searches inside one launch, without checkpoints")
+    if int(leaves_per_step) > 1:
+        raise ValueError("kld_stop does not combine with leaves_per_step > 1 (a virtual-loss search has several leaves in flight: no checkpoint finds its tree complete)")
+    if gumbel_root is not None:
+        raise ValueError("kld_stop does not combine with gumbel_root (the halving table needs a fixed number of simulations)")
+    return interval, min_gain, min_sims
+
+
 def mask_elements(mask):
     """The elements of an emission mask, ascending."""
     return tuple(s for s in range(8) if (mask >> s) & 1)
@@ -467,7 +500,7 @@ def _refuse_vanilla_resign(resign, evaluator):
 
 
 class SelfPlayResult:
-    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base", "full", "resigned", "kl", "coin", "open_plies", "opening", "root_status")
+    __slots__ = ("boards", "actions", "pis", "qs", "winner", "cells", "replay_base", "full", "resigned", "kl", "coin", "open_plies", "opening", "root_status", "sims")
 
     def __init__(self):
         self.boards, self.actions, self.pis, self.qs, self.winner, self.cells = [], [(-1, -1)], [], [], None, []
@@ -478,6 +511,7 @@ class SelfPlayResult:
         self.opening = []            # ... and the cells they were played on, in order (the players alternate from player 0)
         self.root_status = []        # per ply with solver=True: the root's proven status as the mover sees it (0 unknown, 1 wins, 2 loses, 3 draw)
         self.kl, self.coin = [], []  # per ply with surprise_weight=...: KL(recorded pi || raw prior) and the ply's coin (empty without)
+        self.sims = []               # per ply with kld_stop=...: the new simulations the ply's search ran (empty without)
 
     def as_reference_tuple(self):
         """(boards, actions, policy_distributions, qs, winner) - gomoku.py:164"""
@@ -489,7 +523,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
                     budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
                     eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None,
-                    openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None, root_noise=None):
+                    openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None, root_noise=None, kld_stop=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -531,7 +565,9 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     (OPT-IN, check_solver): every search keeps exact game-end proofs (Engine.set_solver); SelfPlayResult.root_status gets each move's root
     status as the mover sees it (0 unknown, 1 wins, 2 loses, 3 draw).  root_noise = ("legal", alpha) | ("total", alpha_total) (OPT-IN,
     check_root_noise): every search's Dirichlet row is drawn over the legal moves of the position it starts from (Engine.gen_root_noise where
-    gen_noise is called); `alpha` is then not looked at.
+    gen_noise is called); `alpha` is then not looked at.  kld_stop = (interval, min_gain[, min_sims]) (OPT-IN, check_kld_stop): every search runs in
+    segments and ends when its root's visit distribution stops changing (Engine.search_budget's checkpoints; budget stepping is switched on);
+    SelfPlayResult.sims gets the new simulations each ply's search ran.
     """
     import torch
     rnz = check_root_noise(root_noise, dirichlet, evaluator, gumbel_root, noise_fn)
@@ -554,6 +590,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                                  engine.tree_reuse if engine is not None else tree_reuse)
     vtg = check_value_target(value_target, evaluator, leaves_per_step, gum)
     slv = check_solver(solver, evaluator, leaves_per_step, fpk, gum, pct, engine.tree_reuse if engine is not None else tree_reuse)
+    kls = check_kld_stop(kld_stop, engine.max_sims if engine is not None else n_sims, evaluator, leaves_per_step, gum)
     _refuse_vanilla_resign(rsg, evaluator)
     if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
@@ -587,8 +624,12 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         eng.set_root_noise(*rnz)
     elif eng.root_noise is not None:
         eng.clear_root_noise()
-    # virtual-loss, top-up and capped engines are driven by the simulation budget
-    budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None
+    if kls is not None:
+        eng.set_kld_stop(*kls)
+    elif eng.kld_stop is not None:                                # an engine handed in with the option still on
+        eng.clear_kld_stop()
+    # virtual-loss, top-up and capped engines, and engines with adaptive search budgets, are driven by the simulation budget
+    budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None or eng.kld_stop is not None
     assert eng.G == n_games
     G, A = eng.G, eng.action_dim
     eng.reset_games()
@@ -647,6 +688,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
             eng.search(ev, ns, noise if dirichlet else None)
         full_h = eng.search_full().cpu().numpy() if eng.playout_cap is not None else None
         status_h = eng.solver_status() if eng.solver else None
+        sims_h = eng.search_sims().cpu().numpy() if eng.kld_stop is not None else None
         pi, q, _ = eng.root_stats()
         if eng.forced_playouts is not None or eng.gumbel_root is not None:
             pi = eng.root_policy_target()                         # what advance records: pruned where the search was a forced one; a Gumbel root's target
@@ -667,6 +709,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
             if kl_h is not None:
                 r.kl.append(float(kl_h[g]))
                 r.coin.append(float(coin_h[g]))
+            if sims_h is not None:
+                r.sims.append(int(sims_h[g]))
             c = int(chosen_h[g])
             r.cells.append(c)
             r.actions.append((c // eng.cols, c % eng.cols))
@@ -704,6 +748,7 @@ class _Half:
         self.h_resigned = torch.zeros(e.G, dtype=torch.uint8, **pin)  # resignation: 1 = the slot's move conceded the game; all zeros without
         self.h_kl = torch.zeros(e.G, dtype=torch.float64, **pin)      # surprise weighting: kl and coin of each slot's move; zeros without
         self.h_coin = torch.zeros(e.G, dtype=torch.float64, **pin)
+        self.h_sims = torch.zeros(e.G, dtype=torch.int32, **pin)      # adaptive search budgets: new simulations of each slot's search; zeros without
         # static buffers so a captured step graph always sees the same addresses
         self.noise_buf = torch.zeros((e.G, e.action_dim), dtype=torch.float64, device=e.device) if dirichlet else None
         self.logits_buf = torch.zeros((e.slots, e.action_dim), dtype=torch.float32, device=e.device)
@@ -837,6 +882,12 @@ class SelfPlayRunner:
     root_noise = ("legal", alpha) | ("total", alpha_total) (OPT-IN, check_root_noise; with everything above except gumbel_root): every search's
     Dirichlet row is drawn over the legal moves of the position it starts from - gen_root_noise where gen_noise is called, behind the recycle and
     the openings of the move before; `alpha` is then not looked at.
+
+    kld_stop = (interval, min_gain[, min_sims]) (OPT-IN, check_kld_stop; with everything above except gumbel_root and leaves_per_step > 1): every
+    search runs in segments of `interval` simulations and ends at the first checkpoint at which its root's visit distribution gained less than
+    min_gain of KL divergence per simulation (Engine.kld_checkpoint between the segments, outside the captured graphs).  It turns budget stepping
+    on, like top-up.  `record_sims` (int32 [group size], valid inside on_records) holds the new simulations each record's search ran;
+    kld_stats() sums the groups' four counters.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
@@ -845,12 +896,14 @@ class SelfPlayRunner:
                  steps_per_graph=32,
                  leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None,
                  surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None, openings_first_game=None, puct=None,
-                 move_temperature=None, value_target=None, solver=None, root_noise=None):
+                 move_temperature=None, value_target=None, solver=None, root_noise=None, kld_stop=None):
         import torch
         self.root_noise = check_root_noise(root_noise, dirichlet, evaluator, gumbel_root)
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, playout_cap, forced_playouts,
                                              surprise_weight)
+        self.kld_stop = check_kld_stop(kld_stop, n_sims, evaluator, leaves_per_step, self.gumbel_root)
+        self.record_sims = None
         self.solver = check_solver(solver, evaluator, leaves_per_step, forced_playouts, gumbel_root, puct, tree_reuse)
         self.value_target = check_value_target(value_target, evaluator, leaves_per_step, self.gumbel_root)
         self.move_temperature = check_move_temperature(move_temperature, n_sims, game, size, self.gumbel_root, tree_reuse)
@@ -872,7 +925,8 @@ class SelfPlayRunner:
         # tree_reuse: OPT-IN tree reuse across moves (azk.h azk_config.tree_reuse; changes search results): 1 = carry, 2 = top-up.  Top-up
         # stops a game at n_sims root visits through the simulation budget, so it turns budget stepping on (eager runner: Engine.search_budget)
         self.tree_reuse = int(tree_reuse)
-        self.budget_stepping = (budget_stepping or self.leaves_per_step > 1 or self.tree_reuse == 2 or self.playout_cap is not None) and use_graph
+        self.budget_stepping = (budget_stepping or self.leaves_per_step > 1 or self.tree_reuse == 2 or self.playout_cap is not None
+                                or self.kld_stop is not None) and use_graph
         self.per_launch = per_launch
         assert self.leaves_per_step == 1 or use_graph, "virtual-loss mode runs on the graph runner"
         self.launches = 0               # simulation-step launches issued (per game group) since construction
@@ -921,6 +975,8 @@ class SelfPlayRunner:
                 h.eng.set_solver(True)
             if self.root_noise is not None:
                 h.eng.set_root_noise(*self.root_noise)
+            if self.kld_stop is not None:
+                h.eng.set_kld_stop(*self.kld_stop)
             if self.openings is not None:                         # the first games, under the key of their first search (move 0)
                 h.eng.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                                    (first_global_game if openings_first_game is None else openings_first_game) + i * per)
@@ -947,6 +1003,8 @@ class SelfPlayRunner:
             e = h.eng
             if self.playout_cap is not None:
                 h.h_full.copy_(e.search_full(), non_blocking=True)
+            if self.kld_stop is not None:
+                h.h_sims.copy_(e.search_sims(), non_blocking=True)
             pi, q, _ = e.root_stats()
             if self.forced_playouts is not None or self.gumbel_root is not None:
                 pi = e.root_policy_target()                   # what advance records: pruned where the search was a forced one; a Gumbel root's target
@@ -975,13 +1033,14 @@ class SelfPlayRunner:
             if self.on_records is not None:
                 self.record_full, self.record_resigned = h.h_full, h.h_resigned
                 self.record_surprise = (h.h_kl, h.h_coin) if self.surprise_weight is not None else None
+                self.record_sims = h.h_sims if self.kld_stop is not None else None
                 self.on_records(self.move_idx, i * per, h.h_pi, h.h_q, h.h_chosen, h.h_winner, h.h_done)
         self.move_idx += 1
 
     def search(self, noise):
         """Eager stepping (host sync per simulation, n_leaf-sized evaluator batches); optional k_tree event timing."""
         e, kt = self.eng, self.kernel_timer
-        if self.tree_reuse == 2 or self.playout_cap is not None:
+        if self.tree_reuse == 2 or self.playout_cap is not None or self.kld_stop is not None:
             e.search_budget(self.evaluator, self.n_sims, noise if self.dirichlet else None, self.per_launch, move_index=self.move_idx)
             return
         e.begin_search(noise)
@@ -1112,20 +1171,43 @@ class SelfPlayRunner:
             # no game can finish before its budget's worth of cache misses: a first stretch without looking, then a look (one
             # 4-byte read-back) every few launches
             longest = self.playout_cap[1] if self.playout_cap is not None and self.playout_cap[0] == 0.0 else self.n_sims   # (all searches fast)
-            s, first = done, max(done, int(0.36 * longest / self.leaves_per_step))
+            # adaptive search budgets (kld_stop): the same loop once per segment - when every game's segment is complete and its last leaf
+            # expanded, the groups' checkpoints judge the games (outside the graphs), and the stepping goes on while one was released
+            if self.kld_stop is not None:
+                longest = min(longest, self.kld_stop[0])
+            s, first, segments = done, max(done, int(0.36 * longest / self.leaves_per_step)), 1
             while True:
-                stop = first if s < first else s + 8
-                while s < stop:
-                    replay(s)
-                    s += 1
-                for st in self.streams:
-                    cur.wait_stream(st)
-                if all(h.eng.unfinished() == 0 for h in self.halves):
+                while True:
+                    stop = first if s < first else s + 8
+                    while s < stop:
+                        replay(s)
+                        s += 1
+                    for st in self.streams:
+                        cur.wait_stream(st)
+                    if all(h.eng.unfinished() == 0 for h in self.halves):
+                        break
+                    if s > 2 * self.n_sims + 16 * segments:
+                        raise RuntimeError("budget stepping does not terminate")
+                if self.kld_stop is None:
                     break
-                if s > 2 * self.n_sims + 16:
-                    raise RuntimeError("budget stepping does not terminate")
+                self._expand_last_leaves(streams)
+                if sum(h.eng.kld_checkpoint() for h in self.halves) == 0:
+                    break
+                if segments > self.n_sims:
+                    raise RuntimeError("the checkpoints do not terminate")
+                segments += 1
+                first = s + int(0.36 * longest)
+                for st in self.streams:
+                    st.wait_stream(cur)
             self.launches += s
-        if self.leaves_per_step == 1:            # (K > 1: the loop above only ends once nothing is pending)
+        if self.kld_stop is None:
+            self._expand_last_leaves(streams)
+
+    def _expand_last_leaves(self, streams):
+        """The closing expand + backup of a search (or of one of its segments): the leaves the last launch selected."""
+        torch = self.torch
+        cur = torch.cuda.current_stream()
+        if self.leaves_per_step == 1:            # (K > 1: the stepping loop only ends once nothing is pending)
             for h, st in zip(self.halves, streams):
                 with torch.cuda.stream(st):
                     h.eng.step_expand_backup(h.logits_buf, h.values_buf)
@@ -1145,6 +1227,16 @@ class SelfPlayRunner:
         out = {}
         for h in self.halves:
             for k, v in h.eng.solver_stats().items():
+                out[k] = out.get(k, 0) + v
+        return out
+
+    def kld_stats(self):
+        """The four counters of Engine.kld_stats summed over the groups (host sync)."""
+        if self.kld_stop is None:
+            raise ValueError("kld_stats: the runner was built without kld_stop=...")
+        out = {}
+        for h in self.halves:
+            for k, v in h.eng.kld_stats().items():
                 out[k] = out.get(k, 0) + v
         return out
 
@@ -1240,18 +1332,26 @@ class AsyncSelfPlayRunner:
     root_noise = ("legal", alpha) | ("total", alpha_total) (OPT-IN, check_root_noise; with everything above except gumbel_root): the games of
     SelfPlayRunner(root_noise=...), slot for slot - a row cannot be made a search ahead (the position is not known then), so the row of a game
     that has just moved is made behind the movers, inside the step chain, and a parked or restarted game's in the drain; `alpha` is then not
-    looked at."""
+    looked at.
+
+    kld_stop = (interval, min_gain[, min_sims]) (OPT-IN, check_kld_stop; with everything above except gumbel_root): the games of
+    SelfPlayRunner(kld_stop=...), slot for slot - the move kernel judges a game whose segment is complete and either releases it for the next
+    segment or moves it, so a game whose root has settled moves without waiting for its allowance.  `record_sims` (int32 numpy, one per record,
+    valid inside on_records) holds the new simulations each record's search ran; kld_stats() reads the four counters.  n_sims is fixed for
+    the run (the segments are cut against the budget)."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
                  playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None,
                  openings=None, openings_seed=None, openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None,
-                 root_noise=None):
+                 root_noise=None, kld_stop=None):
         import torch
         self.root_noise = check_root_noise(root_noise, dirichlet, evaluator, gumbel_root)
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, 1, tree_reuse or reroot, playout_cap, forced_playouts, surprise_weight)
+        self.kld_stop = check_kld_stop(kld_stop, n_sims, evaluator, 1, self.gumbel_root)
+        self.record_sims = None
         self.solver = check_solver(solver, evaluator, 1, forced_playouts, gumbel_root, puct, tree_reuse or reroot)
         self.value_target = check_value_target(value_target, evaluator, 1, self.gumbel_root)
         self.move_temperature = check_move_temperature(move_temperature, n_sims, game, size, self.gumbel_root, tree_reuse or reroot)
@@ -1304,6 +1404,8 @@ class AsyncSelfPlayRunner:
             e.set_solver(True)
         if self.root_noise is not None:                           # the movers make the rows themselves, from each game's position
             e.set_root_noise(*self.root_noise)
+        if self.kld_stop is not None:                             # async_begin arms the first searches, the movers and the drain every later one
+            e.set_kld_stop(*self.kld_stop)
         if self.openings is not None:                             # async_begin opens the first games, the drain's restart every later one
             e.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                            first_global_game if openings_first_game is None else openings_first_game)
@@ -1413,6 +1515,8 @@ class AsyncSelfPlayRunner:
                 self.record_resigned = self.records["resigned"][idx].cpu().numpy()
             if "kl" in self.records:
                 self.record_surprise = (self.records["kl"][idx].cpu().numpy(), self.records["coin"][idx].cpu().numpy())
+            if "sims" in self.records:
+                self.record_sims = self.records["sims"][idx].cpu().numpy()
         self.rec_read = cursor
         self.on_records(meta, q, pi)
 
@@ -1462,6 +1566,12 @@ class AsyncSelfPlayRunner:
             for k, v in h.eng.solver_stats().items():
                 out[k] = out.get(k, 0) + v
         return out
+
+    def kld_stats(self):
+        """The four counters of Engine.kld_stats (host sync)."""
+        if self.kld_stop is None:
+            raise ValueError("kld_stats: the runner was built without kld_stop=...")
+        return self.eng.kld_stats()
 
     def resign_stats(self):
         """[games ended by resignation, never-resign games ended, of those marked, of those whose marked side did not lose] (host sync)."""

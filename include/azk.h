@@ -794,6 +794,62 @@ int32_t azk_gen_root_noise(azk_engine *e, uint64_t seed, int64_t first_global_ga
                            void *stream);
 int32_t azk_get_root_noise(azk_engine *e, double *rows_dev, void *stream);
 
+/* ---- adaptive search budgets: a search ends when its root stops changing (OPT-IN; off, the engine launches exactly the kernels it launched
+ * before).  The reference runs a fixed number of simulations whether the position is a forced recapture or a real decision.  With the option a
+ * search runs in SEGMENTS of `interval` simulations and, between two segments, compares the root's visit distribution with the one a segment
+ * earlier: once the KL divergence gained per simulation falls below min_gain the game moves (Lc0's KLD-gain stopper, minimum-kldgain-per-node
+ * and kldgain-average-interval).  k_tree does not change: a segment is a preset of sims_done, the word budget stepping
+ * already counts a game's simulations in, so a checkpoint is a point where the game looks complete to the mover.  All arithmetic is float64.
+ *   state      interval I, 1 <= I <= max_sims;  min_gain, finite and > 0;  min_sims >= 0.  Per game: left, run, the snapshot o (int32 per root
+ *              child, list order) and its sum So.
+ *   arming     wherever a search begins - azk_begin_search_budget / _capped on a fresh root or a re-rooted one, azk_async_begin, the
+ *              asynchronous mover's own next search, the drain's restarted, opened and re-rooted games - behind the begin code's own write of
+ *              sims_done, for every game that is not done:  T = budget - sims_done  is the search's own allowance of new simulations (n_sims,
+ *              or the playout cap's target, or top-up's n_new);  seg = min(I, T);  sims_done = budget - seg;  left = T - seg;  run = seg;
+ *              So = 0 (no snapshot).
+ *   checkpoint a game that is not done, with sims_done >= budget and no pending leaf (the asynchronous movers' test).  n_i = the root
+ *              children's N in list order, S = their sum.
+ *                1  left == 0: the search is over, it ran its allowance.
+ *                2  otherwise, if So > 0 and run >= min_sims:  gain = sum over i with o_i > 0 of  po_i * log(po_i / pn_i),
+ *                   po_i = (double)o_i / (double)So,  pn_i = (double)n_i / (double)S - each lane sums its children i, i + 64, ... in list
+ *                   order, then the xor butterfly 32 ... 1 combines the lanes (surprise weighting's convention);
+ *                   rate = gain / (double)(S - So);  rate < min_gain: the search is over, it ended early with `left` simulations unrun.
+ *                3  otherwise the game is RELEASED:  o = n, So = S;  seg = min(I, left);  sims_done = budget - seg;  left -= seg;  run += seg;
+ *                   nothing else about the game changes.
+ *   hence      a search that is over is moved exactly as without the option, on the tree as it stands: pi, q, resignation, policy target
+ *              pruning, surprise kl, the temperature table, the value record and re-rooting read the root as it is.  The tree at every
+ *              checkpoint is the tree a plain search of `run` simulations holds, and with a min_gain so small that it never fires the games
+ *              are the option-off games bit for bit.
+ *   zero       a rate of exactly 0 - a root with one child (Gomoku's empty board), or visits that grew in exact proportion - is below every
+ *              positive min_gain: such a search ends at its first judged checkpoint, a forced move moving early; min_sims holds it back.
+ * azk_set_kld_stop allocates left, run, the checkpoint count, So (int32 [G] each), the snapshot (int32 [G][cells]), the last rate (float64 [G])
+ * and four counters on first use and clears them (nothing is allocated, and no new kernel is launched, while the option was never set);
+ * azk_clear_kld_stop makes the engine launch what it launched before.  AZK_ERR_ARG: a parameter out of range, or an engine with
+ * leaves_per_step > 1.  AZK_ERR_STATE: with a Gumbel root set (its halving table needs a fixed n; azk_set_gumbel_root refuses likewise while
+ * this option is set); between the begin of a search and the call that ends it; after azk_async_begin; and, while the option is set,
+ * azk_begin_search (plain stepping), azk_vanilla_search and azk_async_set_budget (the running searches' segments are cut against the budget
+ * as it stood).  Combines with everything else: playout cap, resignation, forced playouts, surprise weighting, configurable PUCT, the solver,
+ * a move temperature, value targets, openings, both kinds of root noise, evaluation symmetry, the eval cache and both tree-reuse modes.
+ * Lock-step drivers: begin with azk_begin_search_budget / _capped, step until azk_search_unfinished reports 0, run the closing
+ * azk_step_expand_backup where the eval cache needs one, then azk_kld_checkpoint - one wave per game judges every game at a checkpoint and
+ * *released_host is the number of games released - and step on while it released a game; then move.  Waits, like azk_search_unfinished.
+ * AZK_ERR_STATE while the option is off or after azk_async_begin.  The asynchronous movers judge a game themselves, behind their "search
+ * complete" test and in front of the move; nothing is launched that an azk_async_step did not launch before, the drain arms the searches it
+ * begins with one small launch per list.
+ * azk_get_search_sims: int32 [G] into device memory, the new simulations each game's current or last-judged search has run once its current
+ * segment is complete (`run`).  azk_get_kld_rate: float64 [G] into device memory, the rate of each game's last judged checkpoint (0 before
+ * the first).  azk_get_kld_stats: out4_host int64 [4] since azk_set_kld_stop - checkpoints judged (step 2 reached), searches ended early,
+ * simulations those searches left unrun, searches that ran their allowance; waits.  azk_async_sims_column (optional, before azk_async_begin):
+ * an int32 [record_capacity] column of the record ring, entry r % capacity = `run` of the record's search.  All AZK_ERR_STATE while the option
+ * is off. */
+int32_t azk_set_kld_stop(azk_engine *e, int32_t interval, double min_gain, int32_t min_sims, void *stream);
+int32_t azk_clear_kld_stop(azk_engine *e);
+int32_t azk_kld_checkpoint(azk_engine *e, int32_t *released_host, void *stream);
+int32_t azk_get_search_sims(azk_engine *e, int32_t *sims_dev, void *stream);
+int32_t azk_get_kld_rate(azk_engine *e, double *rate_dev, void *stream);
+int32_t azk_get_kld_stats(azk_engine *e, int64_t *out4_host, void *stream);
+int32_t azk_async_sims_column(azk_engine *e, int32_t *rec_sims_dev);
+
 /* ---- stateless board-rule kernels over caller boards (float32 [n][F][R][C], the reference's layout) ----
  * game/rows/cols as in azk_config.  These replace the Game statics (games/game.py:4-38):
  *   azk_rules_legal_moves : get_valid_moves - cells in the reference's LIST ORDER (tictactoe.py:82-83,

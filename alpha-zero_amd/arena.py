@@ -21,7 +21,7 @@ def _game_name(game, size):
 
 def compete_batch(game, model1, model2, n_games, model1_mcts_iter=50, model2_mcts_iter=50, sampling=False, size=None,
                   seed=0, first_global_game=0, device=0, leaf_dtype="float32", noise_fn=None, uniform_fn=None, cache_entries=0,
-                  openings=None, openings_first_game=None, puct=None, move_temperature=None, solver=None):
+                  openings=None, openings_first_game=None, puct=None, move_temperature=None, solver=None, lead_stop=None):
     """n_games independent test.compete games at once -> (winners int array in {0, 1, -1}, final boards).
 
     cache_entries > 0 turns on the per-game eval cache, which - like the reference's process-global MCTS.cache (mcts.py:7,
@@ -40,13 +40,19 @@ def compete_batch(game, model1, model2, n_games, model1_mcts_iter=50, model2_mct
     their moves by it, and it replaces what `sampling` would do (sampling is then not looked at).
 
     solver = True (OPT-IN, selfplay.check_solver): BOTH sides search with exact game-end proofs (Engine.set_solver) - a side that has seen a
-    forced win plays it; each result's root_status holds the movers' proven statuses.  Neither model may be None (ValueError)."""
+    forced win plays it; each result's root_status holds the movers' proven statuses.  Neither model may be None (ValueError).
+
+    lead_stop = (interval, factor[, min_sims]) (OPT-IN, selfplay.check_lead_stop): BOTH sides end a search once the simulations left are fewer
+    than factor * (the most-visited root child's lead over the second); the interval lies in 1 .. the larger of the two
+    iteration counts.  With sampling off and factor 1 the games are the option-off games move for move, for fewer simulations; each result's
+    sims holds the simulations every search ran.  Neither model may be None (ValueError)."""
     game, size = _game_name(game, size)
     opn = _arena_openings(openings)
     res = self_play_batch(game, (model1, model2), n_games, (model1_mcts_iter, model2_mcts_iter), size=size, seed=seed,
                           first_global_game=first_global_game, device=device, leaf_dtype=leaf_dtype,
                           noise_fn=noise_fn, uniform_fn=uniform_fn, sample_until=20 if sampling else 0, cache_entries=cache_entries,
-                          openings=opn, openings_first_game=openings_first_game, puct=puct, move_temperature=move_temperature, solver=solver)
+                          openings=opn, openings_first_game=openings_first_game, puct=puct, move_temperature=move_temperature, solver=solver,
+                          lead_stop=lead_stop)
     winners = np.array([r.winner for r in res], np.int64)
     return winners, res
 
@@ -141,7 +147,8 @@ def compare_sequential(Game, best_model, contender_model, best_model_mcts_iter, 
 
 
 def compare(game, best_model, contender_model, best_model_mcts_iter, contender_model_mcts_iter, iterations, sampling,
-            early_stopping, size=None, seed=0, device=0, leaf_dtype="float32", openings=None, puct=None, move_temperature=None, solver=None):
+            early_stopping, size=None, seed=0, device=0, leaf_dtype="float32", openings=None, puct=None, move_temperature=None, solver=None,
+            lead_stop=None):
     """test.compare(Game, best_model, contender_model, best_iter, contender_iter, iterations, sampling, early_stopping)
     (test.py:107-140) with all games of a half played at once; a model of None plays vanilla MCTS (main.py:76).
     (compare_sequential is the game-by-game form that reproduces the reference's RNG stream and cache history.)
@@ -151,8 +158,12 @@ def compare(game, best_model, contender_model, best_model_mcts_iter, contender_m
     puct = (c, fpu) (OPT-IN, selfplay.check_puct): both models search under that exploration rate and first-play urgency in both halves.
     move_temperature (OPT-IN, selfplay.check_move_temperature): both models pick their moves by that schedule in both halves, in place of
     what `sampling` would do.
-    solver = True (OPT-IN, selfplay.check_solver): both models search with exact game-end proofs in both halves."""
+    solver = True (OPT-IN, selfplay.check_solver): both models search with exact game-end proofs in both halves.
+    lead_stop = (interval, factor[, min_sims]) (OPT-IN, selfplay.check_lead_stop): both models' searches end under the lead rule in both halves."""
     game, size = _game_name(game, size)
+    if lead_stop is not None:
+        from selfplay import check_lead_stop
+        check_lead_stop(lead_stop, (best_model_mcts_iter, contender_model_mcts_iter), (best_model, contender_model))
     if solver:
         from selfplay import check_solver
         check_solver(solver, (best_model, contender_model), puct=puct)
@@ -170,8 +181,8 @@ def compare(game, best_model, contender_model, best_model_mcts_iter, contender_m
     half = iterations // 2
     w1, _ = compete_batch(game, best_model, contender_model, half, best_model_mcts_iter, contender_model_mcts_iter,
                           sampling, size, seed, 0, device, leaf_dtype, openings=openings, openings_first_game=0, puct=puct,
-                          move_temperature=move_temperature, solver=solver) if half else (np.zeros(0, np.int64), None)
+                          move_temperature=move_temperature, solver=solver, lead_stop=lead_stop) if half else (np.zeros(0, np.int64), None)
     w2, _ = compete_batch(game, contender_model, best_model, iterations - half, contender_model_mcts_iter,
                           best_model_mcts_iter, sampling, size, seed, half, device, leaf_dtype, openings=openings, openings_first_game=0, puct=puct,
-                          move_temperature=move_temperature, solver=solver)
+                          move_temperature=move_temperature, solver=solver, lead_stop=lead_stop)
     return score_like_reference(w1, w2, iterations, early_stopping)

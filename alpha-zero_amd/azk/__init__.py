@@ -51,7 +51,7 @@ SYMBOLS = [
     "azk_debug_fill_solver_status",
     "azk_set_root_noise", "azk_clear_root_noise", "azk_gen_root_noise", "azk_get_root_noise",
     "azk_set_kld_stop", "azk_clear_kld_stop", "azk_kld_checkpoint", "azk_get_search_sims", "azk_get_kld_rate", "azk_get_kld_stats",
-    "azk_async_sims_column",
+    "azk_async_sims_column", "azk_set_lead_stop", "azk_clear_lead_stop", "azk_get_lead", "azk_get_lead_stats",
 ]
 
 
@@ -354,6 +354,7 @@ class Engine:
         self.surprise_weight = None                 # lambda once set_surprise_weighting has switched the option on (0.0 is a live setting)
         self.value_target = None                    # (r, lam) once set_value_target has switched the option on (r = 0.0 is a live setting)
         self.kld_stop = None                        # (interval, min_gain, min_sims) once set_kld_stop has switched the option on
+        self.lead_stop = None                       # (interval, factor, min_sims) once set_lead_stop has switched the option on
         self.cache_entries = int(cache_entries)
         # with the eval cache a step can have pending (cached) leaves to expand although no leaf went to the evaluator
         need = cache_entries or self.K > 1
@@ -717,6 +718,43 @@ class Engine:
         self._chk(self.L.azk_clear_kld_stop(self.h))
         self.kld_stop = None
 
+    def set_lead_stop(self, interval, factor, min_sims=0):
+        """OPT-IN adaptive search budgets, the lead rule (azk_set_lead_stop): from now on a search runs in segments of
+        `interval` simulations and ends at the first checkpoint between two segments at which the most-visited root child leads the second
+        by so much that  left < factor * (N1 - N2)  (not before it has run min_sims new simulations), at a root with a single child, or when
+        its allowance is used up.  At factor 1 the first most-visited child is the full search's.  Driven like set_kld_stop, alone or beside
+        it (one interval for both); the same refusals.  clear_lead_stop switches it off."""
+        self._chk(self.L.azk_set_lead_stop(self.h, int(interval), float(factor), int(min_sims), _stream()))
+        self.lead_stop = (int(interval), float(factor), int(min_sims))
+
+    def clear_lead_stop(self):
+        """The lead rule off (azk_clear_lead_stop): the engine launches what it launched before."""
+        self._chk(self.L.azk_clear_lead_stop(self.h))
+        self.lead_stop = None
+
+    @property
+    def adaptive(self):
+        """Is a search of this engine cut into segments - is either rule of adaptive search budgets set?"""
+        return self.kld_stop is not None or self.lead_stop is not None
+
+    def lead(self):
+        """int32 CUDA tensor [G][3]: N1, N2 and left at each game's last judged lead checkpoint (azk_get_lead; valid until the next call)."""
+        if self.lead_stop is None:
+            raise AzkError("lead: no lead rule is set (set_lead_stop)")
+        if getattr(self, "_lead", None) is None:
+            self._lead = self.torch.zeros((self.G, 3), dtype=self.torch.int32, device=self.device)
+        self._chk(self.L.azk_get_lead(self.h, _p(self._lead), _stream()))
+        return self._lead
+
+    def lead_stats(self):
+        """The five counters since set_lead_stop (azk_get_lead_stats): checkpoints judged, searches ended early, simulations those searches
+        left unrun, forced-move ends, searches that ran their allowance."""
+        if self.lead_stop is None:
+            raise AzkError("lead_stats: no lead rule is set (set_lead_stop)")
+        out = np.zeros(5, np.int64)
+        self._chk(self.L.azk_get_lead_stats(self.h, _np(out), _stream()))
+        return dict(judged=int(out[0]), ended_early=int(out[1]), sims_unrun=int(out[2]), forced=int(out[3]), ran_allowance=int(out[4]))
+
     def kld_checkpoint(self):
         """Judge every game whose segment is complete (azk_kld_checkpoint; host sync): returns how many games were released for another
         segment - 0: every search is over, move."""
@@ -727,8 +765,8 @@ class Engine:
     def search_sims(self):
         """int32 CUDA tensor [G]: the new simulations each game's current or last-judged search has run (azk_get_search_sims; valid until
         the next call)."""
-        if self.kld_stop is None:
-            raise AzkError("search_sims: no adaptive search budget is set (set_kld_stop)")
+        if not self.adaptive:
+            raise AzkError("search_sims: no adaptive search budget is set (set_kld_stop / set_lead_stop)")
         if getattr(self, "_search_sims", None) is None:
             self._search_sims = self.torch.zeros(self.G, dtype=self.torch.int32, device=self.device)
         self._chk(self.L.azk_get_search_sims(self.h, _p(self._search_sims), _stream()))
@@ -846,7 +884,7 @@ class Engine:
         """The same search as `search` - bit-identical trees - with budget stepping: a game runs on inside a launch while its
         simulations need no evaluator, so n_sims simulations take about (share of simulations that miss the cache) * n_sims
         launches, each with a fuller evaluator batch.  Returns the number of launches.
-        With adaptive search budgets set (set_kld_stop) the search runs segment by segment: when every game's segment is complete,
+        With adaptive search budgets set (set_kld_stop, set_lead_stop) the search runs segment by segment: when every game's segment is complete,
         kld_checkpoint judges the games, and the stepping goes on while it released one."""
         self.begin_search_budget(noise, n_sims, per_launch, move_index)
         launches = 0
@@ -867,7 +905,7 @@ class Engine:
                 assert launches <= 2 * n_sims + 8 * segments, "budget stepping does not terminate"
             if self.cache_entries and self.K == 1:
                 self.step_expand_backup(self._no_logits, self._no_values)       # leaves served by the cache in the last launch
-            if self.kld_stop is None or self.kld_checkpoint() == 0:             # every game at a checkpoint: released for another segment, or over
+            if not self.adaptive or self.kld_checkpoint() == 0:             # every game at a checkpoint: released for another segment, or over
                 break
             assert segments <= n_sims, "the checkpoints do not terminate"
         return launches
@@ -895,7 +933,7 @@ class Engine:
                 rec["kl"] = torch.zeros(record_capacity, dtype=torch.float64, device=self.device)
                 rec["coin"] = torch.zeros(record_capacity, dtype=torch.float64, device=self.device)
                 self._chk(self.L.azk_async_surprise_columns(self.h, _p(rec["kl"]), _p(rec["coin"])))
-            if self.kld_stop is not None:                     # ... and its sims column: the new simulations the record's search ran
+            if self.adaptive:                                 # ... and its sims column: the new simulations the record's search ran
                 rec["sims"] = torch.zeros(record_capacity, dtype=torch.int32, device=self.device)
                 self._chk(self.L.azk_async_sims_column(self.h, _p(rec["sims"])))
         self.async_records = rec

@@ -213,6 +213,10 @@ def declare(L, symbols):
     L.azk_get_kld_rate.argtypes = [vp, vp, vp]
     L.azk_get_kld_stats.argtypes = [vp, vp, vp]
     L.azk_async_sims_column.argtypes = [vp, vp]
+    L.azk_set_lead_stop.argtypes = [vp, i32, f64, i32, vp]
+    L.azk_clear_lead_stop.argtypes = [vp]
+    L.azk_get_lead.argtypes = [vp, vp, vp]
+    L.azk_get_lead_stats.argtypes = [vp, vp, vp]
     L.azk_set_eval_symmetry.argtypes = [vp, i32, u64, vp]
     L.azk_get_leaf_symmetry.argtypes = [vp, vp, vp]
     L.azk_eval_symmetry_restore.argtypes = [vp, vp, vp, vp]

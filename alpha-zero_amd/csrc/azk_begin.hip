@@ -452,7 +452,7 @@ __global__ __launch_bounds__(AZK_WAVE) void k_async_restart(RestartPack<CAP, OPE
     async_restart_body<CAP, OPEN>(d, p, recycle, opt<CapDev>(d), opt<OpenDev>(d));
 }
 
-// Adaptive search budgets (azk_set_kld_stop): the searches that have just begun are armed (kld_arm_one), one thread per game -
+// Adaptive search budgets (azk_set_kld_stop, azk_set_lead_stop; DESIGN sections 31 and 32): the searches that have just begun are armed (kld_arm_one), one thread per game -
 // every game (list == nullptr: the lock-step begin, azk_async_begin) or the listed ones (the drain: the games k_async_restart restarted, the
 // games k_reroot_list re-rooted).  It follows the kernel that began the searches on the same stream: sims_done is what that kernel left.
 __global__ void k_kld_arm(Dev d, KldDev kd, const int *list, const int *n_list) {
@@ -467,7 +467,7 @@ __global__ void k_kld_arm(Dev d, KldDev kd, const int *list, const int *n_list) 
 }  // namespace
 
 void azk_launch_kld_arm(azk_engine *e, const int *list, const int *n_list, hipStream_t st) {
-    if (!e->kld_on) return;
+    if (!adaptive_on(e)) return;
     k_kld_arm<<<(unsigned)((e->d.G + 255) / 256), 256, 0, st>>>(e->d, e->kd, list, n_list);
 }
 
@@ -551,7 +551,7 @@ int32_t azk_begin_search(azk_engine *e, const double *noise_dev, void *stream) {
     if (!e) return AZK_ERR_ARG;
     if (gumbel_refuses(e, noise_dev, 0, "azk_begin_search")) return AZK_ERR_STATE;
     if (forced_needs_noise(e, noise_dev, "azk_begin_search")) return AZK_ERR_STATE;
-    if (e->kld_on) { e->err = "azk_begin_search: adaptive search budgets are set (azk_set_kld_stop) - their searches run under budget stepping (azk_begin_search_budget / _capped)"; return AZK_ERR_STATE; }
+    if (adaptive_on(e)) { e->err = "azk_begin_search: adaptive search budgets are set (azk_set_kld_stop / azk_set_lead_stop) - their searches run under budget stepping (azk_begin_search_budget / _capped)"; return AZK_ERR_STATE; }
     if (e->cp.n_fast) { e->err = "azk_begin_search: a playout cap is set - its searches begin with azk_begin_search_capped (budget + move index)"; return AZK_ERR_STATE; }
     e->d.noise = noise_dev; e->d.noise_sel = nullptr;
     if (e->ru.mode == 2) { e->err = "azk_begin_search: top-up tree reuse needs the budget (azk_begin_search_budget)"; return AZK_ERR_STATE; }

@@ -269,29 +269,37 @@ struct RootNoiseDev {
     int *row_key;              // asynchronous engines: [G] the move key the game's row pair last got a row for, -1 = none; null otherwise
 };
 
-// adaptive search budgets (azk_set_kld_stop, opt-in): a search runs in segments of `interval` simulations - sims_done is preset
-// so that budget stepping stops the game after the segment - and at each checkpoint between two segments the game is either released for the
-// next one or, once the KL divergence its root's visit distribution gained per simulation fell below min_gain, moved on the tree as it stands.
-// Its own argument block, passed only to the kernels that exist for it (k_kld_arm in azk_begin.hip; k_kld_checkpoint and the KLD movers
-// k_move_async_kld in azk_moves.hip): every other argument block - and every kernel an engine without the option launches - stays as it was
+// adaptive search budgets (azk_set_kld_stop and azk_set_lead_stop, opt-in; DESIGN sections 31 and 32): a search runs in segments of `interval`
+// simulations - sims_done is preset so that budget stepping stops the game after the segment - and at each checkpoint between two segments the
+// game is either released for the next one or moved on the tree as it stands: once the KL divergence its root's visit distribution gained per
+// simulation fell below min_gain (the KLD rule; min_gain == 0: off), or once the most-visited root child leads the second by more than the
+// simulations left can make up (the lead rule; lead_factor == 0: off).  Either rule or both.
+// Its own argument block, passed only to the kernels that exist for it (k_kld_arm in azk_begin.hip; k_kld_checkpoint and the movers
+// k_move_async_kld in azk_moves_kld.hip): every other argument block - and every kernel an engine without the option launches - stays as it was
 enum { KST_JUDGED = 0, KST_EARLY, KST_UNRUN, KST_ALLOWANCE, KST_N };
+enum { LST_JUDGED = 0, LST_EARLY, LST_UNRUN, LST_FORCED, LST_ALLOWANCE, LST_N };
 struct KldDev {
-    int interval;              // simulations per segment, 1..max_sims
-    int min_sims;              // no search ends early before it has run this many new simulations
-    double min_gain;           // the threshold on KL gained per simulation, finite and > 0
+    int interval;              // simulations per segment, 1..max_sims (one value for both rules)
+    int min_sims;              // KLD rule: no search ends early before it has run this many new simulations
+    double min_gain;           // KLD rule: the threshold on KL gained per simulation, finite and > 0; 0 = the rule is off
     int max_children;          // row length of snap: the board's cells
     int *left;                 // [G] simulations of the search's allowance behind the current segment
     int *run;                  // [G] new simulations the search has run once the current segment is complete (azk_get_search_sims)
     int *ckpt;                 // [G] checkpoints the search has passed; negative once the search is over: ~(that count)
-    int *snap_sum;             // [G] So: sum of the snapshot, 0 = none
-    int *snap;                 // [G][max_children] the root children's N at the last checkpoint, list order
-    double *rate;              // [G] the rate of the game's last judged checkpoint (azk_get_kld_rate)
-    long long *stats;          // [KST_N] checkpoints judged, searches ended early, simulations those left unrun, searches that ran their allowance
+    int *snap_sum;             // KLD rule: [G] So: sum of the snapshot, 0 = none; null while the rule was never set
+    int *snap;                 // KLD rule: [G][max_children] the root children's N at the last checkpoint, list order; null likewise
+    double *rate;              // KLD rule: [G] the rate of the game's last judged checkpoint (azk_get_kld_rate); null likewise
+    long long *stats;          // [KST_N] KLD rule: checkpoints judged, searches ended early, simulations those left unrun, searches that ran their allowance
     int *rec_sims;             // asynchronous record ring: [record_capacity] new simulations of the record's search, or null
+    double lead_factor;        // lead rule: f, finite and > 0; 0 = the rule is off
+    int lead_min_sims;         // lead rule: its own min_sims
+    int *lead_rec;             // lead rule: [G][3] N1, N2 and left at the game's last judged lead checkpoint (azk_get_lead)
+    long long *lead_stats;     // [LST_N] lead rule: checkpoints judged, searches ended early, simulations those left unrun, forced-move ends, searches that ran their allowance
 };
 
 // Arming (one lane; wherever a search begins, behind the begin code's own write of sims_done): the search's allowance T = budget - sims_done
-// is cut into segments; the first one is what budget stepping sees.  A game that is done is not armed.
+// is cut into segments; the first one is what budget stepping sees.  A game that is done is not armed.  (The snapshot sum is the KLD rule's:
+// it exists only while that rule is set.)
 __device__ __forceinline__ void kld_arm_one(const Dev &d, const KldDev &kd, int g) {
     if (d.done[g] != 0) return;
     const int budget = d.budget[0];
@@ -301,7 +309,7 @@ __device__ __forceinline__ void kld_arm_one(const Dev &d, const KldDev &kd, int 
     kd.left[g] = T - seg;
     kd.run[g] = seg;
     kd.ckpt[g] = 0;
-    kd.snap_sum[g] = 0;
+    if (kd.min_gain > 0.0) kd.snap_sum[g] = 0;
 }
 
 struct LdsView {
@@ -539,8 +547,9 @@ struct azk_engine {
     SolverDev sv = {};                   // exact game-end proofs (azk_set_solver); sv_on == false: off, nothing allocated
     bool sv_on = false;
     RootNoiseDev rn = {};                // root noise on the legal moves (azk_set_root_noise); rn.mode == 0: off, nothing allocated
-    KldDev kd = {};                      // adaptive search budgets (azk_set_kld_stop); kld_on == false: off, nothing allocated
-    bool kld_on = false;
+    KldDev kd = {};                      // adaptive search budgets: kld_on - the KLD rule is set (azk_set_kld_stop), lead_on - the lead rule is
+    bool kld_on = false;                 // (azk_set_lead_stop); neither: off, nothing allocated.  adaptive_on(e): either
+    bool lead_on = false;
     bool in_search = false;             // between a search's begin and the move (or new position) that ends it: azk_set_eval_symmetry refuses
 };
 
@@ -592,7 +601,9 @@ AZK_INTERNAL void azk_launch_rows_ahead(azk_engine *e, hipStream_t st);
 // "row exists" test holds), every game's first row.  azk_launch_root_noise_due: the row of every game whose key moved (azk_noise.hip)
 AZK_INTERNAL int32_t azk_root_noise_begin(azk_engine *e, hipStream_t st);
 AZK_INTERNAL void azk_launch_root_noise_due(azk_engine *e, hipStream_t st);
-// adaptive search budgets (azk_set_kld_stop): the searches that have just begun are armed - every game's (list == nullptr) or the *n_list listed
+// adaptive search budgets under either rule?
+static inline bool adaptive_on(const azk_engine *e) { return e->kld_on || e->lead_on; }
+// adaptive search budgets (azk_set_kld_stop, azk_set_lead_stop): the searches that have just begun are armed - every game's (list == nullptr) or the *n_list listed
 // ones'; returns at once while the option is off (azk_begin.hip)
 AZK_INTERNAL void azk_launch_kld_arm(azk_engine *e, const int *list, const int *n_list, hipStream_t st);
 // ... and the asynchronous movers of such an engine, in the place of k_move_async (azk_moves_kld.hip); on the stream, does not wait

@@ -252,7 +252,7 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
         with_flags([&](auto resign) {
             k_move_async<resign.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(d, e->ad, GumbelPack<ReuseDev, resign.value>{e->ru, on<resign.value>(e->rs), on<true>(e->gb)});
         }, e->rs.v_resign != 0.0);
-    else if ((phases & 2) && e->kld_on) azk_launch_move_async_kld(e, st);     // adaptive search budgets: the KLD movers (azk_moves_kld.hip)
+    else if ((phases & 2) && adaptive_on(e)) azk_launch_move_async_kld(e, st);     // adaptive search budgets, either rule: their movers (azk_moves_kld.hip)
     else if (phases & 2)
         with_flags([&](auto reroot, auto cap, auto resign, auto forced, auto surprise, auto temp, auto value) {
             k_move_async<reroot.value, cap.value, resign.value, forced.value, surprise.value, temp.value, value.value><<<d.G, AZK_WAVE, d.lds_bytes, st>>>(
@@ -267,7 +267,7 @@ int32_t azk_async_step(azk_engine *e, const float *logits_dev, const float *valu
 
 int32_t azk_async_set_budget(azk_engine *e, int32_t n_sims, int32_t max_sims_per_launch, void *stream) {
     if (!e || !e->async_on || n_sims < 1 || n_sims > e->cfg.max_sims || max_sims_per_launch < 1) { if (e) e->err = "azk_async_set_budget: bad argument"; return AZK_ERR_ARG; }
-    if (e->kld_on) { e->err = "azk_async_set_budget: adaptive search budgets are set (azk_set_kld_stop) - the running searches' segments are cut against the budget as it stood"; return AZK_ERR_STATE; }
+    if (adaptive_on(e)) { e->err = "azk_async_set_budget: adaptive search budgets are set (azk_set_kld_stop / azk_set_lead_stop) - the running searches' segments are cut against the budget as it stood"; return AZK_ERR_STATE; }
     if (e->gb.m && n_sims != e->gumbel_sims) { e->err = "azk_async_set_budget: a Gumbel root is set - n_sims differs from the n_sims its halving table was built for"; return AZK_ERR_STATE; }
     e->budget_host[0] = n_sims; e->budget_host[1] = max_sims_per_launch;
     return upload_budget(e, (hipStream_t)stream);

@@ -78,60 +78,100 @@ __device__ __forceinline__ double surprise_kl(const Dev &d, const LdsView &L, in
     return part > 0.0 ? part : 0.0;
 }
 
-// Adaptive search budgets (azk_set_kld_stop): the checkpoint of one game (one wave) whose segment is complete - not done,
-// sims_done >= budget, nothing pending; the caller has made that test.  Returns true when the game is RELEASED for another segment (wave-uniform),
-// false when its search is over and the game is to be moved on the tree as it stands.  With n_i the root children's N in list order, S their
-// sum, o_i / So the snapshot of the last checkpoint (So = 0: none), all float64:
+// Adaptive search budgets (azk_set_kld_stop, azk_set_lead_stop; DESIGN sections 31 and 32): the checkpoint of one game (one wave) whose segment
+// is complete - not done, sims_done >= budget, nothing pending; the caller has made that test.  Returns true when the game is RELEASED for
+// another segment (wave-uniform), false when its search is over and the game is to be moved on the tree as it stands.  With n_i the root
+// children's N in list order, S their sum, o_i / So the KLD rule's snapshot of the last checkpoint (So = 0: none):
 //   1  left == 0                          over: the search ran its allowance
-//   2  else if So > 0 and run >= min_sims    gain = sum over i with o_i > 0 of  po_i * log(po_i / pn_i),  po_i = (double)o_i / (double)So,
+//   2L else, lead rule set (lead_factor > 0) and run >= lead_min_sims:
+//                                          nch == 1: over, a forced move.  Otherwise N1 = max n_i, N2 = the second largest counting
+//                                          multiplicity (a tie for the maximum: N2 = N1);  (double)left < lead_factor * (double)(N1 - N2): over,
+//                                          the search ended early with `left` simulations unrun.  Integers but for that one multiply and compare
+//   2K else, KLD rule set (min_gain > 0), So > 0 and run >= min_sims:
+//                                          gain = sum over i with o_i > 0 of  po_i * log(po_i / pn_i),  po_i = (double)o_i / (double)So,
 //                                          pn_i = (double)n_i / (double)S;  rate = gain / (double)(S - So);  rate < min_gain: over, the search
 //                                          ended early with `left` simulations unrun
-//   3  else                               snapshot o = n, So = S;  seg = min(interval, left);  sims_done = budget - seg;  left -= seg;
+//   3  else                               KLD rule: snapshot o = n, So = S;  seg = min(interval, left);  sims_done = budget - seg;  left -= seg;
 //                                          run += seg;  released, nothing else about the game changes
-// Lanes sum their children i, i + 64, ... in list order, then the xor butterfly 32 ... 1: surprise_kl's convention.  Plain vector loads and
-// stores; lane 0 writes the game's words.  A search that is over keeps ckpt negative, so a lock-step checkpoint that meets it again (other
-// games were released) neither counts nor judges it twice.
+// Lanes take their children i, i + 64, ... in list order, then the xor butterfly 32 ... 1: surprise_kl's convention for the sum; for the lead
+// rule each lane keeps a (max, second max) pair and two pairs merge into (the larger max, the largest of the smaller max and both seconds) -
+// the pair's identity is (0, 0), visits are not negative.  Plain vector loads and stores; lane 0 writes the game's words.  With the KLD rule off
+// neither snap, snap_sum nor rate is touched (they do not exist) and no log is executed.  A search that is over keeps ckpt negative, so a
+// lock-step checkpoint that meets it again (other games were released) neither counts nor judges it twice.
 __device__ __forceinline__ bool kld_judge_one(const Dev &d, const KldDev &kd, int g) {
     const int lane = azk_lane();
     const int ck = uniform_i32(kd.ckpt[g]);
     if (ck < 0) return false;                                       // over already
     const int left = uniform_i32(kd.left[g]);
-    unsigned long long *st = (unsigned long long *)kd.stats;
+    const bool kld = kd.min_gain > 0.0, lead = kd.lead_factor > 0.0;
+    unsigned long long *st = (unsigned long long *)kd.stats, *ls = (unsigned long long *)kd.lead_stats;
     if (left == 0) {
-        if (lane == 0) { kd.ckpt[g] = ~(ck + 1); atomicAdd(&st[KST_ALLOWANCE], 1ull); }
+        if (lane == 0) {
+            kd.ckpt[g] = ~(ck + 1);
+            if (kld) atomicAdd(&st[KST_ALLOWANCE], 1ull);
+            if (lead) atomicAdd(&ls[LST_ALLOWANCE], 1ull);
+        }
         return false;
     }
     const size_t base = (size_t)g * d.cap;
     const int fc = uniform_i32(d.H[base].fc), nch = min(uniform_i32(meta_nch(d.H[base].meta)), kd.max_children);
-    const int So = uniform_i32(kd.snap_sum[g]), run = uniform_i32(kd.run[g]);
-    int *snap = kd.snap + (size_t)g * kd.max_children;
-    int S = 0;
-    for (int i = lane; i < nch; i += AZK_WAVE) S += d.H[base + fc + i].N;
-    S = wave_sum_i32(S);
-    if (So > 0 && run >= kd.min_sims) {
-        double part = 0.0;
+    const int run = uniform_i32(kd.run[g]);
+    if (lead && run >= kd.lead_min_sims) {
+        int n1 = 0, n2 = 0;
         for (int i = lane; i < nch; i += AZK_WAVE) {
-            const int o = snap[i], n = d.H[base + fc + i].N;
-            if (o > 0) {
-                const double po = (double)o / (double)So, pn = (double)n / (double)S;
-                part += po * log(po / pn);
-            }
+            const int n = d.H[base + fc + i].N;
+            n2 = max(n2, min(n1, n));
+            n1 = max(n1, n);
         }
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-        const double rate = part / (double)(S - So);
-        const bool early = rate < kd.min_gain;
-        if (lane == 0) {
-            kd.rate[g] = rate;
-            atomicAdd(&st[KST_JUDGED], 1ull);
-            if (early) { kd.ckpt[g] = ~(ck + 1); atomicAdd(&st[KST_EARLY], 1ull); atomicAdd(&st[KST_UNRUN], (unsigned long long)left); }
+        for (int off = 32; off > 0; off >>= 1) {
+            const int o1 = __shfl_xor(n1, off), o2 = __shfl_xor(n2, off);
+            n2 = max(min(n1, o1), max(n2, o2));
+            n1 = max(n1, o1);
         }
-        if (early) return false;
+        const bool forced = nch == 1;
+        const bool early = !forced && (double)left < kd.lead_factor * (double)(n1 - n2);
+        if (lane == 0) {
+            int *rec = kd.lead_rec + (size_t)g * 3;
+            rec[0] = n1; rec[1] = n2; rec[2] = left;
+            atomicAdd(&ls[LST_JUDGED], 1ull);
+            if (forced) atomicAdd(&ls[LST_FORCED], 1ull);
+            if (early) { atomicAdd(&ls[LST_EARLY], 1ull); atomicAdd(&ls[LST_UNRUN], (unsigned long long)left); }
+            if (forced || early) kd.ckpt[g] = ~(ck + 1);
+        }
+        if (forced || early) return false;
     }
-    for (int i = lane; i < nch; i += AZK_WAVE) snap[i] = d.H[base + fc + i].N;
+    int S = 0;
+    if (kld) {
+        const int So = uniform_i32(kd.snap_sum[g]);
+        int *snap = kd.snap + (size_t)g * kd.max_children;
+        for (int i = lane; i < nch; i += AZK_WAVE) S += d.H[base + fc + i].N;
+        S = wave_sum_i32(S);
+        if (So > 0 && run >= kd.min_sims) {
+            double part = 0.0;
+            for (int i = lane; i < nch; i += AZK_WAVE) {
+                const int o = snap[i], n = d.H[base + fc + i].N;
+                if (o > 0) {
+                    const double po = (double)o / (double)So, pn = (double)n / (double)S;
+                    part += po * log(po / pn);
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
+            const double rate = part / (double)(S - So);
+            const bool early = rate < kd.min_gain;
+            if (lane == 0) {
+                kd.rate[g] = rate;
+                atomicAdd(&st[KST_JUDGED], 1ull);
+                if (early) { kd.ckpt[g] = ~(ck + 1); atomicAdd(&st[KST_EARLY], 1ull); atomicAdd(&st[KST_UNRUN], (unsigned long long)left); }
+            }
+            if (early) return false;
+        }
+        for (int i = lane; i < nch; i += AZK_WAVE) snap[i] = d.H[base + fc + i].N;
+    }
     if (lane == 0) {
         const int seg = min(kd.interval, left);
-        kd.snap_sum[g] = S;
+        if (kld) kd.snap_sum[g] = S;
         d.sims_done[g] = d.budget[0] - seg;
         kd.left[g] = left - seg;
         kd.run[g] = run + seg;

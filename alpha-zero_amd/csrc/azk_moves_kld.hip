@@ -1,4 +1,4 @@
-// azk_moves_kld.hip - the kernels of adaptive search budgets (azk_set_kld_stop) that move games: the asynchronous movers of
+// azk_moves_kld.hip - the kernels of adaptive search budgets (azk_set_kld_stop, azk_set_lead_stop; DESIGN sections 31 and 32) that move games: the asynchronous movers of
 // an engine with the option (k_move_async_kld, the k_move_async family once more) and the lock-step checkpoint (k_kld_checkpoint), with the
 // calls that launch them.  A file of its own so that the two halves of the mover family compile side by side: azk_moves.o is what the build
 // waits for.  The device functions are azk_moves_dev.h's; the arming kernel is azk_begin.hip's.  Built with -ffp-contract=off like every
@@ -36,7 +36,7 @@ extern "C" {
 
 int32_t azk_kld_checkpoint(azk_engine *e, int32_t *released_host, void *stream) {
     if (!e || !released_host) return AZK_ERR_ARG;
-    if (!e->kld_on) { e->err = "azk_kld_checkpoint: no adaptive search budget is set (azk_set_kld_stop)"; return AZK_ERR_STATE; }
+    if (!adaptive_on(e)) { e->err = "azk_kld_checkpoint: no adaptive search budget is set (azk_set_kld_stop / azk_set_lead_stop)"; return AZK_ERR_STATE; }
     if (e->async_on) { e->err = "azk_kld_checkpoint: the asynchronous movers judge their games themselves"; return AZK_ERR_STATE; }
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(e, hipMemsetAsync(e->n_leaf_scratch, 0, sizeof(int), st));

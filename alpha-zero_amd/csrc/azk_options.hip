@@ -1,5 +1,5 @@
 // azk_options.hip - the opt-ins' state calls (include/azk.h): set, clear and read playout cap, forced playouts, Gumbel root, resignation,
-// surprise weighting, random openings, root noise on the legal moves, the move temperature, value targets, the solver and adaptive search budgets.  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
+// surprise weighting, random openings, root noise on the legal moves, the move temperature, value targets, the solver and adaptive search budgets (both rules).  No kernel: they check arguments, allocate the option's arrays on first use and fill the argument
 // block (azk_engine_int.h) that azk_opt_pack.h hands to the kernels of azk_begin.hip, azk_moves.hip and azk_emit.hip.
 #include "azk_engine_int.h"
 #include <algorithm>
@@ -102,7 +102,7 @@ int32_t azk_set_gumbel_root(azk_engine *e, int32_t m, int32_t n_sims, double c_v
     if (e->tp_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with a move temperature (azk_set_move_temperature: the Gumbel arg-max is the sample)"; return AZK_ERR_STATE; }
     if (e->vt_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with value targets (azk_set_value_target: the Gumbel movers do not keep the per-ply q)"; return AZK_ERR_STATE; }
     if (e->rn.mode) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with root noise on the legal moves (azk_set_root_noise: its rows are Dirichlet rows)"; return AZK_ERR_STATE; }
-    if (e->kld_on) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with adaptive search budgets (azk_set_kld_stop: the halving table needs a fixed number of simulations)"; return AZK_ERR_STATE; }
+    if (adaptive_on(e)) { e->err = "azk_set_gumbel_root: a Gumbel root does not combine with adaptive search budgets (azk_set_kld_stop, azk_set_lead_stop: the halving table needs a fixed number of simulations)"; return AZK_ERR_STATE; }
     const Dev &d = e->d;
     GumbelDev &gb = e->gb;
     hipStream_t st = (hipStream_t)stream;
@@ -472,7 +472,29 @@ int32_t azk_clear_root_noise(azk_engine *e) {
     return AZK_OK;
 }
 
-// ---- adaptive search budgets ------------------------------------------------------------------------------------------------
+// ---- adaptive search budgets: the KLD rule and the lead rule ------------------------------------------------------------------
+// what both rules keep per game (left, run, the checkpoint count), allocated by whichever is set first and cleared by either setter: no search
+// is armed, a game counts as over (ckpt < 0) until its next search begins.  Both rules' counters are allocated here so that the judge's
+// argument block never holds a null counter pointer; each setter clears its own.
+static int32_t adaptive_common(azk_engine *e, hipStream_t st) {
+    const Dev &d = e->d;
+    KldDev &k = e->kd;
+    if (!k.left) {
+        HIPCHK(e, dalloc(e, &k.left, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &k.run, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &k.ckpt, (size_t)d.G));
+        HIPCHK(e, dalloc(e, &k.stats, (size_t)KST_N));
+        HIPCHK(e, dalloc(e, &k.lead_stats, (size_t)LST_N));
+        HIPCHK(e, hipMemsetAsync(k.stats, 0, sizeof(long long) * KST_N, st));
+        HIPCHK(e, hipMemsetAsync(k.lead_stats, 0, sizeof(long long) * LST_N, st));
+    }
+    HIPCHK(e, hipMemsetAsync(k.left, 0, sizeof(int) * (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(k.run, 0, sizeof(int) * (size_t)d.G, st));
+    HIPCHK(e, hipMemsetAsync(k.ckpt, 0xff, sizeof(int) * (size_t)d.G, st));
+    k.max_children = d.g.rc; k.rec_sims = nullptr;
+    return AZK_OK;
+}
+
 int32_t azk_set_kld_stop(azk_engine *e, int32_t interval, double min_gain, int32_t min_sims, void *stream) {
     if (!e) return AZK_ERR_ARG;
     if (e->async_on) { e->err = "azk_set_kld_stop: set it before azk_async_begin"; return AZK_ERR_STATE; }
@@ -482,27 +504,22 @@ int32_t azk_set_kld_stop(azk_engine *e, int32_t interval, double min_gain, int32
     if (min_sims < 0) { e->err = "azk_set_kld_stop: min_sims must not be negative"; return AZK_ERR_ARG; }
     if (e->d.K > 1) { e->err = "azk_set_kld_stop: adaptive search budgets do not combine with leaves_per_step > 1 (a virtual-loss search has several leaves in flight: no checkpoint finds its tree complete)"; return AZK_ERR_ARG; }
     if (e->gb.m) { e->err = "azk_set_kld_stop: a Gumbel root is set - its halving table needs a fixed number of simulations"; return AZK_ERR_STATE; }
+    if (e->lead_on && interval != e->kd.interval) { e->err = "azk_set_kld_stop: the lead rule is set with another interval (azk_set_lead_stop) - the two rules share one"; return AZK_ERR_STATE; }
     const Dev &d = e->d;
     KldDev &k = e->kd;
     hipStream_t st = (hipStream_t)stream;
-    if (!k.left) {
-        HIPCHK(e, dalloc(e, &k.left, (size_t)d.G));
-        HIPCHK(e, dalloc(e, &k.run, (size_t)d.G));
-        HIPCHK(e, dalloc(e, &k.ckpt, (size_t)d.G));
+    int32_t rc = adaptive_common(e, st);
+    if (rc != AZK_OK) return rc;
+    if (!k.snap) {
         HIPCHK(e, dalloc(e, &k.snap_sum, (size_t)d.G));
         HIPCHK(e, dalloc(e, &k.snap, (size_t)d.G * d.g.rc));
         HIPCHK(e, dalloc(e, &k.rate, (size_t)d.G));
-        HIPCHK(e, dalloc(e, &k.stats, (size_t)KST_N));
     }
-    // no search is armed: a game counts as over (ckpt < 0) until its next search begins
-    HIPCHK(e, hipMemsetAsync(k.left, 0, sizeof(int) * (size_t)d.G, st));
-    HIPCHK(e, hipMemsetAsync(k.run, 0, sizeof(int) * (size_t)d.G, st));
-    HIPCHK(e, hipMemsetAsync(k.ckpt, 0xff, sizeof(int) * (size_t)d.G, st));
     HIPCHK(e, hipMemsetAsync(k.snap_sum, 0, sizeof(int) * (size_t)d.G, st));
     HIPCHK(e, hipMemsetAsync(k.snap, 0, sizeof(int) * (size_t)d.G * d.g.rc, st));
     HIPCHK(e, hipMemsetAsync(k.rate, 0, sizeof(double) * (size_t)d.G, st));
     HIPCHK(e, hipMemsetAsync(k.stats, 0, sizeof(long long) * KST_N, st));
-    k.interval = interval; k.min_gain = min_gain; k.min_sims = min_sims; k.max_children = d.g.rc; k.rec_sims = nullptr;
+    k.interval = interval; k.min_gain = min_gain; k.min_sims = min_sims;
     e->kld_on = true;
     return AZK_OK;
 }
@@ -511,13 +528,62 @@ int32_t azk_clear_kld_stop(azk_engine *e) {
     if (!e) return AZK_ERR_ARG;
     if (e->async_on) { e->err = "azk_clear_kld_stop: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
     if (e->in_search && e->kld_on) { e->err = "azk_clear_kld_stop: a search is under way - clear the option between searches"; return AZK_ERR_STATE; }
-    e->kld_on = false;                                            // off: the engine launches what it launched before
+    e->kld_on = false;                                            // off: the engine launches what it launched before (or, with the lead rule
+    e->kd.min_gain = 0.0;                                         // still set, the judge without its KLD part)
+    return AZK_OK;
+}
+
+// the lead rule: set, clear, read.  The refusals are azk_set_kld_stop's.
+int32_t azk_set_lead_stop(azk_engine *e, int32_t interval, double factor, int32_t min_sims, void *stream) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_set_lead_stop: set it before azk_async_begin"; return AZK_ERR_STATE; }
+    if (e->in_search) { e->err = "azk_set_lead_stop: a search is under way - set the option between searches"; return AZK_ERR_STATE; }
+    if (interval < 1 || interval > e->cfg.max_sims) { e->err = "azk_set_lead_stop: interval must lie in [1, max_sims]"; return AZK_ERR_ARG; }
+    if (!(factor > 0.0) || factor - factor != 0.0) { e->err = "azk_set_lead_stop: factor must be finite and positive"; return AZK_ERR_ARG; }
+    if (min_sims < 0) { e->err = "azk_set_lead_stop: min_sims must not be negative"; return AZK_ERR_ARG; }
+    if (e->d.K > 1) { e->err = "azk_set_lead_stop: adaptive search budgets do not combine with leaves_per_step > 1 (a virtual-loss search has several leaves in flight: no checkpoint finds its tree complete)"; return AZK_ERR_ARG; }
+    if (e->gb.m) { e->err = "azk_set_lead_stop: a Gumbel root is set - its halving table needs a fixed number of simulations"; return AZK_ERR_STATE; }
+    if (e->kld_on && interval != e->kd.interval) { e->err = "azk_set_lead_stop: the KLD rule is set with another interval (azk_set_kld_stop) - the two rules share one"; return AZK_ERR_STATE; }
+    const Dev &d = e->d;
+    KldDev &k = e->kd;
+    hipStream_t st = (hipStream_t)stream;
+    int32_t rc = adaptive_common(e, st);
+    if (rc != AZK_OK) return rc;
+    if (!k.lead_rec) HIPCHK(e, dalloc(e, &k.lead_rec, (size_t)d.G * 3));
+    HIPCHK(e, hipMemsetAsync(k.lead_rec, 0, sizeof(int) * (size_t)d.G * 3, st));
+    HIPCHK(e, hipMemsetAsync(k.lead_stats, 0, sizeof(long long) * LST_N, st));
+    k.interval = interval; k.lead_factor = factor; k.lead_min_sims = min_sims;
+    e->lead_on = true;
+    return AZK_OK;
+}
+
+int32_t azk_clear_lead_stop(azk_engine *e) {
+    if (!e) return AZK_ERR_ARG;
+    if (e->async_on) { e->err = "azk_clear_lead_stop: the asynchronous movers are running (the option is fixed at azk_async_begin)"; return AZK_ERR_STATE; }
+    if (e->in_search && e->lead_on) { e->err = "azk_clear_lead_stop: a search is under way - clear the option between searches"; return AZK_ERR_STATE; }
+    e->lead_on = false;
+    e->kd.lead_factor = 0.0;
+    return AZK_OK;
+}
+
+int32_t azk_get_lead(azk_engine *e, int32_t *lead_dev, void *stream) {
+    if (!e || !lead_dev) return AZK_ERR_ARG;
+    if (!e->lead_on) { e->err = "azk_get_lead: no lead rule is set (azk_set_lead_stop)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(lead_dev, e->kd.lead_rec, sizeof(int) * (size_t)e->d.G * 3, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AZK_OK;
+}
+
+int32_t azk_get_lead_stats(azk_engine *e, int64_t *out5_host, void *stream) {
+    if (!e || !out5_host) return AZK_ERR_ARG;
+    if (!e->lead_on) { e->err = "azk_get_lead_stats: no lead rule is set (azk_set_lead_stop)"; return AZK_ERR_STATE; }
+    HIPCHK(e, hipMemcpyAsync(out5_host, e->kd.lead_stats, sizeof(long long) * LST_N, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     return AZK_OK;
 }
 
 int32_t azk_get_search_sims(azk_engine *e, int32_t *sims_dev, void *stream) {
     if (!e || !sims_dev) return AZK_ERR_ARG;
-    if (!e->kld_on) { e->err = "azk_get_search_sims: no adaptive search budget is set (azk_set_kld_stop)"; return AZK_ERR_STATE; }
+    if (!adaptive_on(e)) { e->err = "azk_get_search_sims: no adaptive search budget is set (azk_set_kld_stop / azk_set_lead_stop)"; return AZK_ERR_STATE; }
     HIPCHK(e, hipMemcpyAsync(sims_dev, e->kd.run, sizeof(int) * (size_t)e->d.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return AZK_OK;
 }
@@ -539,7 +605,7 @@ int32_t azk_get_kld_stats(azk_engine *e, int64_t *out4_host, void *stream) {
 
 int32_t azk_async_sims_column(azk_engine *e, int32_t *rec_sims_dev) {
     if (!e) return AZK_ERR_ARG;
-    if (!e->kld_on) { e->err = "azk_async_sims_column: no adaptive search budget is set (azk_set_kld_stop)"; return AZK_ERR_STATE; }
+    if (!adaptive_on(e)) { e->err = "azk_async_sims_column: no adaptive search budget is set (azk_set_kld_stop / azk_set_lead_stop)"; return AZK_ERR_STATE; }
     if (e->async_on) { e->err = "azk_async_sims_column: call it before azk_async_begin"; return AZK_ERR_STATE; }
     e->kd.rec_sims = rec_sims_dev;
     return AZK_OK;

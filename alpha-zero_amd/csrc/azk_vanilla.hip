@@ -224,7 +224,7 @@ int32_t azk_vanilla_search(azk_engine *e, int32_t n_sims, void *stream) {
     if (!e || n_sims < 0) { if (e) e->err = "azk_vanilla_search: bad argument"; return AZK_ERR_ARG; }
     if (e->puct_on) { e->err = "azk_vanilla_search: configurable PUCT is set (azk_set_puct) - vanilla MCTS selects by UCB1, which the option does not cover"; return AZK_ERR_STATE; }
     if (e->sv_on) { e->err = "azk_vanilla_search: the solver is set (azk_set_solver) - vanilla MCTS keeps no status column"; return AZK_ERR_STATE; }
-    if (e->kld_on) { e->err = "azk_vanilla_search: adaptive search budgets are set (azk_set_kld_stop) - vanilla MCTS runs whole searches inside one launch, without checkpoints"; return AZK_ERR_STATE; }
+    if (adaptive_on(e)) { e->err = "azk_vanilla_search: adaptive search budgets are set (azk_set_kld_stop / azk_set_lead_stop) - vanilla MCTS runs whole searches inside one launch, without checkpoints"; return AZK_ERR_STATE; }
     int32_t rc = vanilla_prepare(e);
     if (rc != AZK_OK) return rc;
     if (n_sims == 0) return AZK_OK;

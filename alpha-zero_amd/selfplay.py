@@ -489,6 +489,41 @@ def check_kld_stop(kld_stop, n_sims, evaluator=True, leaves_per_step=1, gumbel_r
     return interval, min_gain, min_sims
 
 
+def check_lead_stop(lead_stop, n_sims, evaluator=True, leaves_per_step=1, gumbel_root=None, kld_stop=None):
+    """lead_stop = (interval, factor[, min_sims]) -> (int, float, int), or None for off.  OPT-IN adaptive search budgets, the lead rule
+    (include/azk.h azk_set_lead_stop): a search runs in segments of `interval` simulations and ends at the first checkpoint
+    between two segments at which the simulations left are fewer than factor * (the most-visited root child's lead over the second), not before
+    it has run min_sims new simulations; at factor 1 the first most-visited child is the full search's.  n_sims is the engine's max_sims (the
+    largest of a pair); kld_stop is the KLD rule's checked setting where both are given - the two share one interval.  Raises ValueError,
+    before any engine exists, for what the engine refuses too - an interval outside [1, n_sims] or unlike kld_stop's, a factor that is not
+    finite and positive, a negative min_sims, virtual loss, a Gumbel root - and for vanilla MCTS on either side (evaluator None)."""
+    if lead_stop is None:
+        return None
+    try:
+        interval, factor, min_sims = lead_stop if len(lead_stop) == 3 else (lead_stop[0], lead_stop[1], 0) if len(lead_stop) == 2 else (None, None, None)
+        if isinstance(interval, bool) or isinstance(min_sims, bool) or int(interval) != interval or int(min_sims) != min_sims:
+            raise ValueError
+        interval, factor, min_sims = int(interval), float(factor), int(min_sims)
+    except (TypeError, ValueError):
+        raise ValueError(f"lead_stop must be (interval, factor) or (interval, factor, min_sims), not {lead_stop!r}")
+    max_sims = max(n_sims) if isinstance(n_sims, (tuple, list)) else n_sims
+    if not 1 <= interval <= max_sims:
+        raise ValueError(f"lead_stop: interval must lie in [1, n_sims = {max_sims}], not {interval!r}")
+    if not (factor > 0.0 and math.isfinite(factor)):              # (NaN fails the comparison)
+        raise ValueError(f"lead_stop: factor must be finite and positive, not {factor!r}")
+    if min_sims < 0:
+        raise ValueError(f"lead_stop: min_sims must not be negative, not {min_sims!r}")
+    if _is_vanilla(evaluator):
+        raise ValueError("lead_stop: vanilla MCTS (evaluator None) is refused - it runs whole searches inside one launch, without checkpoints")
+    if int(leaves_per_step) > 1:
+        raise ValueError("lead_stop does not combine with leaves_per_step > 1 (a virtual-loss search has several leaves in flight: no checkpoint finds its tree complete)")
+    if gumbel_root is not None:
+        raise ValueError("lead_stop does not combine with gumbel_root (the halving table needs a fixed number of simulations)")
+    if kld_stop is not None and int(kld_stop[0]) != interval:
+        raise ValueError(f"lead_stop and kld_stop share one interval, not {interval!r} and {kld_stop[0]!r}")
+    return interval, factor, min_sims
+
+
 def mask_elements(mask):
     """The elements of an emission mask, ascending."""
     return tuple(s for s in range(8) if (mask >> s) & 1)
@@ -511,7 +546,7 @@ class SelfPlayResult:
         self.opening = []            # ... and the cells they were played on, in order (the players alternate from player 0)
         self.root_status = []        # per ply with solver=True: the root's proven status as the mover sees it (0 unknown, 1 wins, 2 loses, 3 draw)
         self.kl, self.coin = [], []  # per ply with surprise_weight=...: KL(recorded pi || raw prior) and the ply's coin (empty without)
-        self.sims = []               # per ply with kld_stop=...: the new simulations the ply's search ran (empty without)
+        self.sims = []               # per ply with kld_stop=... or lead_stop=...: the new simulations the ply's search ran (empty without)
 
     def as_reference_tuple(self):
         """(boards, actions, policy_distributions, qs, winner) - gomoku.py:164"""
@@ -523,7 +558,8 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
                     max_moves=None, sample_until=None, stats=None, replay=None, cache_entries=0, vanilla_rng=None, cache_shared=False,
                     budget_stepping=False, leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None,
                     eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None,
-                    openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None, root_noise=None, kld_stop=None):
+                    openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None, root_noise=None, kld_stop=None,
+                    lead_stop=None):
     """Play n_games games to the end in one batch.
 
     evaluator(boards[n,F,R,C] CUDA) -> (logits [n,A], values [n] | [n,1]).
@@ -567,7 +603,9 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     check_root_noise): every search's Dirichlet row is drawn over the legal moves of the position it starts from (Engine.gen_root_noise where
     gen_noise is called); `alpha` is then not looked at.  kld_stop = (interval, min_gain[, min_sims]) (OPT-IN, check_kld_stop): every search runs in
     segments and ends when its root's visit distribution stops changing (Engine.search_budget's checkpoints; budget stepping is switched on);
-    SelfPlayResult.sims gets the new simulations each ply's search ran.
+    SelfPlayResult.sims gets the new simulations each ply's search ran.  lead_stop = (interval, factor[, min_sims]) (OPT-IN, check_lead_stop;
+    alone or beside kld_stop, one interval): a search ends once the simulations left are fewer than factor * (the most-visited root child's
+    lead over the second) - at factor 1 and sample_until = 0 the games are the option-off games move for move, for fewer simulations.
     """
     import torch
     rnz = check_root_noise(root_noise, dirichlet, evaluator, gumbel_root, noise_fn)
@@ -591,6 +629,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
     vtg = check_value_target(value_target, evaluator, leaves_per_step, gum)
     slv = check_solver(solver, evaluator, leaves_per_step, fpk, gum, pct, engine.tree_reuse if engine is not None else tree_reuse)
     kls = check_kld_stop(kld_stop, engine.max_sims if engine is not None else n_sims, evaluator, leaves_per_step, gum)
+    lds = check_lead_stop(lead_stop, engine.max_sims if engine is not None else n_sims, evaluator, leaves_per_step, gum, kls)
     _refuse_vanilla_resign(rsg, evaluator)
     if cap is not None and (evaluator is None or (isinstance(evaluator, (tuple, list)) and any(e is None for e in evaluator))):
         raise ValueError("playout_cap caps network searches; vanilla MCTS (evaluator None) has no budget stepping")
@@ -624,12 +663,16 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
         eng.set_root_noise(*rnz)
     elif eng.root_noise is not None:
         eng.clear_root_noise()
+    if eng.kld_stop is not None:                                  # an engine handed in with the option still on (and before the other rule
+        eng.clear_kld_stop()                                      # is set: the two must agree on the interval)
+    if eng.lead_stop is not None:
+        eng.clear_lead_stop()
     if kls is not None:
         eng.set_kld_stop(*kls)
-    elif eng.kld_stop is not None:                                # an engine handed in with the option still on
-        eng.clear_kld_stop()
+    if lds is not None:
+        eng.set_lead_stop(*lds)
     # virtual-loss, top-up and capped engines, and engines with adaptive search budgets, are driven by the simulation budget
-    budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None or eng.kld_stop is not None
+    budget_stepping = budget_stepping or eng.K > 1 or eng.tree_reuse == 2 or eng.playout_cap is not None or eng.adaptive
     assert eng.G == n_games
     G, A = eng.G, eng.action_dim
     eng.reset_games()
@@ -688,7 +731,7 @@ def self_play_batch(game, evaluator, n_games, n_sims, size=None, seed=0, first_g
             eng.search(ev, ns, noise if dirichlet else None)
         full_h = eng.search_full().cpu().numpy() if eng.playout_cap is not None else None
         status_h = eng.solver_status() if eng.solver else None
-        sims_h = eng.search_sims().cpu().numpy() if eng.kld_stop is not None else None
+        sims_h = eng.search_sims().cpu().numpy() if eng.adaptive else None
         pi, q, _ = eng.root_stats()
         if eng.forced_playouts is not None or eng.gumbel_root is not None:
             pi = eng.root_policy_target()                         # what advance records: pruned where the search was a forced one; a Gumbel root's target
@@ -888,6 +931,10 @@ class SelfPlayRunner:
     min_gain of KL divergence per simulation (Engine.kld_checkpoint between the segments, outside the captured graphs).  It turns budget stepping
     on, like top-up.  `record_sims` (int32 [group size], valid inside on_records) holds the new simulations each record's search ran;
     kld_stats() sums the groups' four counters.
+
+    lead_stop = (interval, factor[, min_sims]) (OPT-IN, check_lead_stop; alone or beside kld_stop, which it is driven like): every search ends
+    once the simulations left are fewer than factor * (the most-visited root child's lead over the second).  `record_sims` is filled under
+    either rule; lead_stats() sums the groups' five counters.
     """
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True,
@@ -896,13 +943,15 @@ class SelfPlayRunner:
                  steps_per_graph=32,
                  leaves_per_step=1, tree_reuse=0, playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None,
                  surprise_weight=None, gumbel_root=None, openings=None, openings_seed=None, openings_first_game=None, puct=None,
-                 move_temperature=None, value_target=None, solver=None, root_noise=None, kld_stop=None):
+                 move_temperature=None, value_target=None, solver=None, root_noise=None, kld_stop=None, lead_stop=None):
         import torch
         self.root_noise = check_root_noise(root_noise, dirichlet, evaluator, gumbel_root)
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, leaves_per_step, tree_reuse, playout_cap, forced_playouts,
                                              surprise_weight)
         self.kld_stop = check_kld_stop(kld_stop, n_sims, evaluator, leaves_per_step, self.gumbel_root)
+        self.lead_stop = check_lead_stop(lead_stop, n_sims, evaluator, leaves_per_step, self.gumbel_root, self.kld_stop)
+        self.adaptive = self.kld_stop is not None or self.lead_stop is not None      # searches run in segments: either rule
         self.record_sims = None
         self.solver = check_solver(solver, evaluator, leaves_per_step, forced_playouts, gumbel_root, puct, tree_reuse)
         self.value_target = check_value_target(value_target, evaluator, leaves_per_step, self.gumbel_root)
@@ -926,7 +975,7 @@ class SelfPlayRunner:
         # stops a game at n_sims root visits through the simulation budget, so it turns budget stepping on (eager runner: Engine.search_budget)
         self.tree_reuse = int(tree_reuse)
         self.budget_stepping = (budget_stepping or self.leaves_per_step > 1 or self.tree_reuse == 2 or self.playout_cap is not None
-                                or self.kld_stop is not None) and use_graph
+                                or self.adaptive) and use_graph
         self.per_launch = per_launch
         assert self.leaves_per_step == 1 or use_graph, "virtual-loss mode runs on the graph runner"
         self.launches = 0               # simulation-step launches issued (per game group) since construction
@@ -977,6 +1026,8 @@ class SelfPlayRunner:
                 h.eng.set_root_noise(*self.root_noise)
             if self.kld_stop is not None:
                 h.eng.set_kld_stop(*self.kld_stop)
+            if self.lead_stop is not None:
+                h.eng.set_lead_stop(*self.lead_stop)
             if self.openings is not None:                         # the first games, under the key of their first search (move 0)
                 h.eng.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                                    (first_global_game if openings_first_game is None else openings_first_game) + i * per)
@@ -1003,7 +1054,7 @@ class SelfPlayRunner:
             e = h.eng
             if self.playout_cap is not None:
                 h.h_full.copy_(e.search_full(), non_blocking=True)
-            if self.kld_stop is not None:
+            if self.adaptive:
                 h.h_sims.copy_(e.search_sims(), non_blocking=True)
             pi, q, _ = e.root_stats()
             if self.forced_playouts is not None or self.gumbel_root is not None:
@@ -1033,14 +1084,14 @@ class SelfPlayRunner:
             if self.on_records is not None:
                 self.record_full, self.record_resigned = h.h_full, h.h_resigned
                 self.record_surprise = (h.h_kl, h.h_coin) if self.surprise_weight is not None else None
-                self.record_sims = h.h_sims if self.kld_stop is not None else None
+                self.record_sims = h.h_sims if self.adaptive else None
                 self.on_records(self.move_idx, i * per, h.h_pi, h.h_q, h.h_chosen, h.h_winner, h.h_done)
         self.move_idx += 1
 
     def search(self, noise):
         """Eager stepping (host sync per simulation, n_leaf-sized evaluator batches); optional k_tree event timing."""
         e, kt = self.eng, self.kernel_timer
-        if self.tree_reuse == 2 or self.playout_cap is not None or self.kld_stop is not None:
+        if self.tree_reuse == 2 or self.playout_cap is not None or self.adaptive:
             e.search_budget(self.evaluator, self.n_sims, noise if self.dirichlet else None, self.per_launch, move_index=self.move_idx)
             return
         e.begin_search(noise)
@@ -1171,10 +1222,10 @@ class SelfPlayRunner:
             # no game can finish before its budget's worth of cache misses: a first stretch without looking, then a look (one
             # 4-byte read-back) every few launches
             longest = self.playout_cap[1] if self.playout_cap is not None and self.playout_cap[0] == 0.0 else self.n_sims   # (all searches fast)
-            # adaptive search budgets (kld_stop): the same loop once per segment - when every game's segment is complete and its last leaf
+            # adaptive search budgets (kld_stop, lead_stop): the same loop once per segment - when every game's segment is complete and its last leaf
             # expanded, the groups' checkpoints judge the games (outside the graphs), and the stepping goes on while one was released
-            if self.kld_stop is not None:
-                longest = min(longest, self.kld_stop[0])
+            if self.adaptive:
+                longest = min(longest, (self.kld_stop or self.lead_stop)[0])
             s, first, segments = done, max(done, int(0.36 * longest / self.leaves_per_step)), 1
             while True:
                 while True:
@@ -1188,7 +1239,7 @@ class SelfPlayRunner:
                         break
                     if s > 2 * self.n_sims + 16 * segments:
                         raise RuntimeError("budget stepping does not terminate")
-                if self.kld_stop is None:
+                if not self.adaptive:
                     break
                 self._expand_last_leaves(streams)
                 if sum(h.eng.kld_checkpoint() for h in self.halves) == 0:
@@ -1200,7 +1251,7 @@ class SelfPlayRunner:
                 for st in self.streams:
                     st.wait_stream(cur)
             self.launches += s
-        if self.kld_stop is None:
+        if not self.adaptive:
             self._expand_last_leaves(streams)
 
     def _expand_last_leaves(self, streams):
@@ -1237,6 +1288,16 @@ class SelfPlayRunner:
         out = {}
         for h in self.halves:
             for k, v in h.eng.kld_stats().items():
+                out[k] = out.get(k, 0) + v
+        return out
+
+    def lead_stats(self):
+        """The five counters of Engine.lead_stats summed over the groups (host sync)."""
+        if self.lead_stop is None:
+            raise ValueError("lead_stats: the runner was built without lead_stop=...")
+        out = {}
+        for h in self.halves:
+            for k, v in h.eng.lead_stats().items():
                 out[k] = out.get(k, 0) + v
         return out
 
@@ -1338,19 +1399,24 @@ class AsyncSelfPlayRunner:
     SelfPlayRunner(kld_stop=...), slot for slot - the move kernel judges a game whose segment is complete and either releases it for the next
     segment or moves it, so a game whose root has settled moves without waiting for its allowance.  `record_sims` (int32 numpy, one per record,
     valid inside on_records) holds the new simulations each record's search ran; kld_stats() reads the four counters.  n_sims is fixed for
-    the run (the segments are cut against the budget)."""
+    the run (the segments are cut against the budget).
+
+    lead_stop = (interval, factor[, min_sims]) (OPT-IN, check_lead_stop; alone or beside kld_stop): the games of SelfPlayRunner(lead_stop=...),
+    slot for slot - the same movers judge the lead rule with integer arithmetic only.  `record_sims` is filled under either rule;
+    lead_stats() reads the five counters."""
 
     def __init__(self, game, evaluator, n_games, n_sims, size=None, seed=0, first_global_game=0, dirichlet=True, alpha=0.03, device=0,
                  leaf_dtype="float32", recycle=True, on_records=None, kernel_timer=None, replay=None, cache_entries=0, cache_shared=False,
                  per_launch=2, steps_per_graph=32, record_capacity=None, use_graph=True, young_launch_us=0, tree_reuse=0, reroot=0, arena_nodes=0,
                  playout_cap=None, resign=None, forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None,
                  openings=None, openings_seed=None, openings_first_game=None, puct=None, move_temperature=None, value_target=None, solver=None,
-                 root_noise=None, kld_stop=None):
+                 root_noise=None, kld_stop=None, lead_stop=None):
         import torch
         self.root_noise = check_root_noise(root_noise, dirichlet, evaluator, gumbel_root)
         self.openings = check_openings(openings, game, size, evaluator)
         self.gumbel_root = check_gumbel_root(gumbel_root, n_sims, evaluator, dirichlet, 1, tree_reuse or reroot, playout_cap, forced_playouts, surprise_weight)
         self.kld_stop = check_kld_stop(kld_stop, n_sims, evaluator, 1, self.gumbel_root)
+        self.lead_stop = check_lead_stop(lead_stop, n_sims, evaluator, 1, self.gumbel_root, self.kld_stop)
         self.record_sims = None
         self.solver = check_solver(solver, evaluator, 1, forced_playouts, gumbel_root, puct, tree_reuse or reroot)
         self.value_target = check_value_target(value_target, evaluator, 1, self.gumbel_root)
@@ -1406,6 +1472,8 @@ class AsyncSelfPlayRunner:
             e.set_root_noise(*self.root_noise)
         if self.kld_stop is not None:                             # async_begin arms the first searches, the movers and the drain every later one
             e.set_kld_stop(*self.kld_stop)
+        if self.lead_stop is not None:
+            e.set_lead_stop(*self.lead_stop)
         if self.openings is not None:                             # async_begin opens the first games, the drain's restart every later one
             e.set_openings(self.openings[0], self.openings[1], self.openings[2], seed if openings_seed is None else openings_seed,
                            first_global_game if openings_first_game is None else openings_first_game)
@@ -1572,6 +1640,12 @@ class AsyncSelfPlayRunner:
         if self.kld_stop is None:
             raise ValueError("kld_stats: the runner was built without kld_stop=...")
         return self.eng.kld_stats()
+
+    def lead_stats(self):
+        """The five counters of Engine.lead_stats (host sync)."""
+        if self.lead_stop is None:
+            raise ValueError("lead_stats: the runner was built without lead_stop=...")
+        return self.eng.lead_stats()
 
     def resign_stats(self):
         """[games ended by resignation, never-resign games ended, of those marked, of those whose marked side did not lose] (host sync)."""

@@ -103,7 +103,7 @@ def save_data_to_buffer(Game, buffer, data, full=None, elements=None, copies=Non
 
 def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed=None, batched=True, playout_cap=None, resign=None,
                  forced_playouts=None, eval_symmetry=None, emit_symmetry=None, surprise_weight=None, gumbel_root=None, openings=None, puct=None,
-                 move_temperature=None, value_target=None, solver=None, root_noise=None, kld_stop=None):
+                 move_temperature=None, value_target=None, solver=None, root_noise=None, kld_stop=None, lead_stop=None):
     """train.py:54-83: `iterations` self-play games of Game with `model` into `buffer`; returns [first, second, draw] counts.
     batched=False plays the games one after the other through Game().self_play and save_data_to_buffer exactly as the
     reference does (global np.random stream: a seeded caller gets the reference's buffer); the default plays them as one
@@ -129,7 +129,9 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
     root_noise = ("legal", alpha) | ("total", alpha_total) (OPT-IN, batched only; selfplay.check_root_noise): every search's Dirichlet row is drawn
     over the legal moves of the position it starts from; what is stored does not change shape.  kld_stop = (interval, min_gain[, min_sims])
     (OPT-IN, batched only; selfplay.check_kld_stop): a search ends at the first checkpoint at which its root's visit distribution gained less
-    than min_gain of KL divergence per simulation; what is stored does not change shape."""
+    than min_gain of KL divergence per simulation; what is stored does not change shape.  lead_stop = (interval, factor[, min_sims]) (OPT-IN,
+    batched only; selfplay.check_lead_stop): a search ends once the simulations left are fewer than factor * (the most-visited root child's lead
+    over the second); what is stored does not change shape."""
     from azk import DeviceReplay
     from selfplay import (check_emit_symmetry, check_surprise_weight, check_value_target, mask_elements, self_play_batch, surprise_copies,
                           value_targets)
@@ -139,7 +141,7 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
         for name, value in (("surprise_weight", lam), ("emit_symmetry", emit_symmetry), ("playout_cap", playout_cap), ("resign", resign),
                             ("forced_playouts", forced_playouts), ("gumbel_root", gumbel_root), ("openings", openings), ("puct", puct),
                             ("move_temperature", move_temperature), ("value_target", vtg), ("solver", solver or None), ("root_noise", root_noise),
-                            ("kld_stop", kld_stop),
+                            ("kld_stop", kld_stop), ("lead_stop", lead_stop),
                             ("eval_symmetry", None if eval_symmetry is False else eval_symmetry)):
             if value is not None:
                 raise ValueError(f"collect_data: {name} needs the batched engine (batched=True)")
@@ -158,7 +160,7 @@ def collect_data(Game, model, buffer, iterations, mcts_iter, display=False, seed
                           replay=buffer if on_device else None, playout_cap=playout_cap, resign=resign, forced_playouts=forced_playouts,
                           eval_symmetry=eval_symmetry, emit_symmetry=emit_symmetry, surprise_weight=surprise_weight, gumbel_root=gumbel_root,
                           openings=openings, puct=puct, move_temperature=move_temperature, value_target=value_target, solver=solver,
-                          root_noise=root_noise, kld_stop=kld_stop)
+                          root_noise=root_noise, kld_stop=kld_stop, lead_stop=lead_stop)
     emit = check_emit_symmetry(emit_symmetry, Game.engine_name, Game._size())
     results = [0, 0, 0]
     for r in res:

@@ -850,6 +850,49 @@ int32_t azk_get_kld_rate(azk_engine *e, double *rate_dev, void *stream);
 int32_t azk_get_kld_stats(azk_engine *e, int64_t *out4_host, void *stream);
 int32_t azk_async_sims_column(azk_engine *e, int32_t *rec_sims_dev);
 
+/* ---- adaptive search budgets, the second rule: a search ends once the runner-up cannot catch up (OPT-IN; off, the engine launches exactly the
+ * kernels it launched before).  Smart pruning's stop as Lc0 ships it beside the KLD stopper: the search is over once the most-visited root child
+ * leads the second by more than the simulations that are left.  Segments, arming and the checkpoint's place are the KLD
+ * rule's above, unchanged; the two rules are set apart or together and share the kernels (k_kld_arm, k_kld_checkpoint, k_move_async_kld).
+ *   state      interval I, 1 <= I <= max_sims;  factor f, finite and > 0;  min_sims >= 0.  Per game: left, run (as above) and three int32
+ *              words, N1, N2 and left at the last judged lead checkpoint.
+ *   arming     as above:  T = budget - sims_done;  seg = min(I, T);  sims_done = budget - seg;  left = T - seg;  run = seg.
+ *   checkpoint a game that is not done, with sims_done >= budget and no pending leaf.  n_i = the root children's N, nch their number.
+ *                1  left == 0: the search is over, it ran its allowance.
+ *                2  otherwise, if run >= min_sims (the checkpoint is JUDGED):
+ *                     nch == 1: the search is over - a forced move, counted as such (not as ended early);
+ *                     otherwise N1 = max n_i and N2 = the second largest COUNTING MULTIPLICITY (a tie for the maximum gives N2 = N1; each lane
+ *                     keeps a (max, second) pair over its children i, i + 64, ..., the xor butterfly 32 ... 1 merges two pairs into the larger
+ *                     max and the largest of the smaller max and both seconds; no child index is kept);  lead = N1 - N2;  the search is over,
+ *                     ended early with `left` simulations unrun, iff  (double)left < f * (double)lead  - one float64 multiply and one
+ *                     compare of exactly converted integers, so host and device agree bit for bit and no margin is needed.
+ *                     The three words are written: N1, N2 (0 for a single child), left.
+ *                3  otherwise the game is RELEASED:  seg = min(I, left);  sims_done = budget - seg;  left -= seg;  run += seg.
+ *   hence      a search that is over is moved on the tree as it stands, as under the KLD rule: pi, q, resignation, pruning, surprise kl, the
+ *              temperature table, value records and re-rooting read the root as it is; the tree at every checkpoint is the tree a plain
+ *              search of `run` simulations holds.
+ *   exactness  every simulation adds one visit to exactly one root child.  At f = 1, left < N1 - N2 means that no child can reach N1 in the
+ *              simulations left: the holder of N1 is unique and stays the strict maximum, so the FIRST MOST-VISITED child of the stopped
+ *              search is that of the full search, and greedy play is move for move what it was.  This holds on carried roots: `left` counts
+ *              new simulations, n_i includes carried visits.  (pi, q and a sampled move are those of the shorter search.)
+ *   both rules they share the one interval: azk_set_lead_stop and azk_set_kld_stop refuse (AZK_ERR_STATE) an interval that differs from the
+ *              other rule's.  At a checkpoint the lead rule is judged first, each rule under its own min_sims; the search ends if either
+ *              fires; if neither does the KLD snapshot is taken as above.  With the KLD rule off the judge touches neither the snapshot, its
+ *              sum nor the rate - they are not allocated - and executes no log.
+ * azk_set_lead_stop allocates on first use and clears the three words and the five counters (and left / run / the checkpoint count: no search
+ * is armed); azk_clear_lead_stop switches the rule off.  The refusals are azk_set_kld_stop's: AZK_ERR_ARG for a parameter out of range or an
+ * engine with leaves_per_step > 1; AZK_ERR_STATE with a Gumbel root set (azk_set_gumbel_root refuses in turn), inside a search, after
+ * azk_async_begin, for the interval mismatch, and - while the rule is set - from azk_begin_search, azk_vanilla_search and azk_async_set_budget.
+ * While either rule is set azk_kld_checkpoint, azk_get_search_sims and azk_async_sims_column work as described above; azk_get_kld_rate and
+ * azk_get_kld_stats need the KLD rule.
+ * azk_get_lead: int32 [G][3] into device memory, the three words.  azk_get_lead_stats: out5_host int64 [5] since azk_set_lead_stop -
+ * checkpoints judged, searches ended early, simulations those left unrun, forced-move ends, searches that ran their allowance; waits.  Both
+ * AZK_ERR_STATE while the lead rule is off. */
+int32_t azk_set_lead_stop(azk_engine *e, int32_t interval, double factor, int32_t min_sims, void *stream);
+int32_t azk_clear_lead_stop(azk_engine *e);
+int32_t azk_get_lead(azk_engine *e, int32_t *lead_dev, void *stream);
+int32_t azk_get_lead_stats(azk_engine *e, int64_t *out5_host, void *stream);
+
 /* ---- stateless board-rule kernels over caller boards (float32 [n][F][R][C], the reference's layout) ----
  * game/rows/cols as in azk_config.  These replace the Game statics (games/game.py:4-38):
  *   azk_rules_legal_moves : get_valid_moves - cells in the reference's LIST ORDER (tictactoe.py:82-83,
